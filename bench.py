@@ -10,6 +10,8 @@ configuration the metric is quoted on); SURVEY.md §8(d) defines inputs, byte/fl
 
 Rank 0 prints ONE compact JSON line on stdout (compact_line: < 8 KB, strict JSON, numbers only); the full detail
 object (workload / execution prose, every secondary's fields) goes to stderr and to gpurun_out/bench_detail.json.
+--dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy (dump_outputs), so that two builds
+can be compared output for output on identical inputs.
 """
 import argparse
 import json
@@ -551,6 +553,21 @@ class Workload:
             elapsed = float(tt.item())
         return elapsed, step_ms, float(loss)
 
+    def outputs(self, loss):
+        """What a caller of the step holds after its last call (--dump-outputs): the loss it returned, the trainable
+        parameters of the backbone and the two heads after that step's update (registration order, flattened), and the
+        gradients the step left in their .grad."""
+        params, seen = [], set()
+        for m in (self.model, self.n1, self.n2):
+            for p in m.parameters():
+                if p.requires_grad and id(p) not in seen:
+                    seen.add(id(p))
+                    params.append(p)
+        torch.cuda.synchronize()
+        grads = [p.grad if p.grad is not None else torch.zeros_like(p) for p in params]
+        flat = lambda ts: torch.cat([t.detach().reshape(-1) for t in ts]).cpu().numpy()
+        return {"loss": np.array([loss], dtype=np.float32), "params": flat(params), "grads": flat(grads)}
+
     def diagnostics(self, iters=20):
         """What an N > 1 run needs to be read, measured right after the timed region on every rank:
         `input_ms` - the loader's share of a step: next handle of the shuffled epoch + the refresh of the graph's static
@@ -966,6 +983,8 @@ def forward_only(args, dev, rank, world, do_emit=True):
         for i in range(timed_steps):
             fwd(i, eager=True)
         torch.cuda.synchronize()
+    if getattr(args, "dump_outputs", None) and rank == 0:   # `out`: the last timed pass's (the replay's output cloned)
+        dump_outputs(args.dump_outputs, {"forces" if args.forces else "prediction": out.detach().cpu().numpy()})
     timers, _lib.TIMERS = _lib.TIMERS, None
     if world > 1:
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
@@ -1190,6 +1209,25 @@ def emit(out):
     print(compact_line(out), flush=True)
 
 
+DUMP_LIMIT = 64 << 20   # bytes: everything --dump-outputs writes, together
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy, float64 arrays as float64, all others as float32.  Arrays are
+    written whole while they fit in DUMP_LIMIT together; past it each is cut down to the same share of its elements, a
+    sample drawn with a fixed seed (the same elements in every run)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(a, dtype=np.float64 if np.asarray(a).dtype == np.float64 else np.float32)
+              for k, a in arrays.items()}
+    budget = DUMP_LIMIT - 4096 * len(arrays)   # (.npy headers)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > budget:
+            keep = a.size * budget // total
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def spawn_ranks(n):
     """`bench.py --gpus N` started without torch.distributed.run: N fresh child processes, one per GPU (RANK / LOCAL_RANK
     / WORLD_SIZE / MASTER_* in their environment, rendezvous on 127.0.0.1), each running this script with the same
@@ -1264,7 +1302,13 @@ def main():
                          "position gradient of finetune_md17.py:46, frozen weights, one view")
     ap.add_argument("--model", default="schnet", choices=["schnet", "painn"],
                     help="backbone: schnet = the headline configuration; painn = BASELINE config 5 (secondary line)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what rank 0's last timed step computed as DIR/<name>.npy: the loss, "
+                         "the parameters after the update and the gradients (--forward-only: the prediction, --forces: "
+                         "the forces); the same arguments give the same inputs in every run")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     global CUTOFF
     CUTOFF = args.cutoff
 
@@ -1299,6 +1343,8 @@ def main():
     wl = Workload(dev, rank, world, model=args.model, mols=args.mols, molset=args.molset, cutoff=CUTOFF, api=args.api,
                   graph=not args.no_graph, n_batches=n_batches, dataset_mols=0 if args.precollated else per_rank)
     elapsed, step_ms, final_loss = wl.run(args.warmup, args.steps)
+    if args.dump_outputs and rank == 0:   # (before diagnostics() and the roofline passes touch the gradients)
+        dump_outputs(args.dump_outputs, wl.outputs(final_loss))
     if os.environ.get("GEOSSL_BENCH_RANK_LOSS"):  # tests: every rank's last loss (ranks own different molecules and noise)
         with open(os.path.join(os.environ["GEOSSL_BENCH_RANK_LOSS"], "loss_rank%d.txt" % rank), "w") as fh:
             fh.write(repr(final_loss))

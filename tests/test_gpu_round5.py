@@ -482,19 +482,22 @@ def test_painn_bucket_replays_on_different_edge_lists_bit_for_bit_and_matches_th
         assert rel_err(g[k].cpu(), Pm[k].grad) < TOL_GRAD, k
 
 
-# ------------------------------------------------------------------------------------------- eight ranks, one GPU
-def test_bench_eight_ranks_share_one_gpu(tmp_path):
-    """`python bench.py --gpus 8` as the driver launches it on an 8-GPU node, here with all eight ranks on the one GPU of
-    the box over gloo (no 8-GPU node was ever available to a round): rendezvous on 127.0.0.1, eight different per-rank
-    molecule sets and noise streams (eight different losses), ONE flat all-reduce per step with the 1 / world factor in the
-    Adam launch - the parameters of all eight ranks are bit-identical after three steps - and rank 0's JSON line says
-    n_gpus 8, dp8, world_size_initialised 8."""
+# -------------------------------------------------------------------------------------------- four ranks, one GPU
+RANKS = 4   # with this process: five processes hold the GPU at once
+
+
+def test_bench_four_ranks_share_one_gpu(tmp_path):
+    """`python bench.py --gpus N` as the driver launches it on an N-GPU node, here with four ranks on the one GPU of the
+    box over gloo (no multi-GPU node was ever available to a round): rendezvous on 127.0.0.1, four different per-rank
+    molecule sets and noise streams (four different losses), ONE flat all-reduce per step with the 1 / world factor in the
+    Adam launch - the parameters of all four ranks are bit-identical after three steps - and rank 0's JSON line says
+    n_gpus 4, dp4, world_size_initialised 4."""
     import subprocess
     import sys
     env = dict(os.environ, GEOSSL_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", GEOSSL_BENCH_RANK_LOSS=str(tmp_path))
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(RANKS), "--steps", "3", "--warmup", "1",
            "--no-cpu-baseline", "--mols", "128", "--dataset-mols", "8192"]
     with open(tmp_path / "out.log", "w") as fo, open(tmp_path / "err.log", "w") as fe:
         p = subprocess.Popen(cmd, env=env, stdout=fo, stderr=fe, cwd=REPO)
@@ -509,13 +512,13 @@ def test_bench_eight_ranks_share_one_gpu(tmp_path):
     lines = [ln for ln in out_text.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
     out = json.loads(lines[0])
-    assert out["n_gpus"] == 8 and out["scaling"] == "weak" and out["config"]["parallelism"] == "dp8"
-    assert out["config"]["backend"] == "gloo" and out["config"]["world_size_initialised"] == 8
+    assert out["n_gpus"] == RANKS and out["scaling"] == "weak" and out["config"]["parallelism"] == "dp%d" % RANKS
+    assert out["config"]["backend"] == "gloo" and out["config"]["world_size_initialised"] == RANKS
     assert np.isfinite(out["value"]) and out["value"] > 0
-    assert abs(out["value"] - 8 * 128 * 3 / (out["ms_per_step"] * 3e-3)) < 1e-4 * out["value"]   # (the line's 6 digits)
-    losses = [float(open(tmp_path / ("loss_rank%d.txt" % r)).read()) for r in range(8)]
-    assert all(np.isfinite(v) for v in losses) and len(set(losses)) == 8     # eight molecule sets, eight noise streams
-    params = [open(tmp_path / ("params_rank%d.txt" % r)).read() for r in range(8)]
+    assert abs(out["value"] - RANKS * 128 * 3 / (out["ms_per_step"] * 3e-3)) < 1e-4 * out["value"]   # (the line's 6 digits)
+    losses = [float(open(tmp_path / ("loss_rank%d.txt" % r)).read()) for r in range(RANKS)]
+    assert all(np.isfinite(v) for v in losses) and len(set(losses)) == RANKS  # RANKS molecule sets, RANKS noise streams
+    params = [open(tmp_path / ("params_rank%d.txt" % r)).read() for r in range(RANKS)]
     assert len(set(params)) == 1 and len(params[0]) == 64                    # one all-reduced gradient, one update
 
 
