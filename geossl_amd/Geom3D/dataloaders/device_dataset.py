@@ -19,6 +19,11 @@ step at the reference's batch size).  Here the molecules are uploaded once:
   Anything else that touches ``handle.x`` / ``.positions`` / ``.batch`` / ``.super_edge_index`` /
   ``.radius_edge_index`` gets the collated tensors (built by the same kernel into fresh memory, then cached), so a
   handle is accepted wherever a collated batch is (``do_DDM``, the modules themselves, eager steps).
+* ``DeviceLoader(mask_ratio=r)`` yields MASKED handles: the reference's BFS atom masking (datasets_3D.py:24-67; see
+  ``masking``) over the dataset's bond graph, kept lists drawn on the device (``mask_rng="device"``) or by the
+  reference's own np.random draws on the host (``"numpy"``).  A masked handle carries the kept sizes; its gather is
+  ``geossl_gather_masked_molecules``.  With radius edges the survivor count depends on the draw: collating such a
+  handle takes a count launch and a read-back of B counts before the gather.
 """
 import ctypes as C
 
@@ -27,6 +32,7 @@ import torch
 
 from ... import _lib
 from ..._lib import call, ptr, stream
+from . import masking
 
 _OPTIONS = {"combination": 0, "permutation": 1}
 
@@ -56,10 +62,12 @@ class _Staging:
 
 
 class DeviceDataset:
-    def __init__(self, x, positions, sizes, device, option="combination", radius=None, max_num_neighbors=32):
+    def __init__(self, x, positions, sizes, device, option="combination", radius=None, max_num_neighbors=32,
+                 bond_index=None, bond_counts=None):
         """x [Ntot, C] int64, positions [Ntot, 3] float32 (numpy or tensors; molecule after molecule), sizes [M] atoms
         per molecule.  option: the AtomTupleExtractor enumeration of the batches drawn from it.  radius: also build the
-        per-molecule radius_edge_index (PaiNN) on this geometry."""
+        per-molecule radius_edge_index (PaiNN) on this geometry.  bond_index [2, Etot] (local atom indices, molecule
+        after molecule) with bond_counts [M]: the bond graph (``data.edge_index``) that atom masking walks."""
         if option not in _OPTIONS:
             raise ValueError("option is 'combination' or 'permutation'")
         dev = torch.device(device)
@@ -85,22 +93,82 @@ class DeviceDataset:
         self.pairs = self.sizes * (self.sizes - 1) // 2
         self.radius, self.edges, self.edge_cnt, self.edge_off = None, None, None, None
         self._staging = _Staging()
+        self.bonds, self.bond_off, self.bond_ptr, self.bond_dst = None, None, None, None
+        if (bond_index is None) != (bond_counts is None):
+            raise ValueError("bond_index and bond_counts come together")
+        if bond_index is not None:
+            self._set_bonds(bond_index, bond_counts)
         if radius is not None:
             self._build_edges(float(radius), int(max_num_neighbors))
 
     # ---- construction
     @classmethod
     def from_numpy(cls, d, device, **kw):
-        """From a dict with x, positions, sizes (geossl_amd.synthetic.make_molecules / make_batch)."""
+        """From a dict with x, positions, sizes (geossl_amd.synthetic.make_molecules / make_batch) and, when present,
+        bond_index / bond_counts (synthetic.add_bonds)."""
+        for k in ("bond_index", "bond_counts"):
+            if k not in kw and d.get(k) is not None:
+                kw[k] = d[k]
         return cls(d["x"], d["positions"], d["sizes"], device, **kw)
 
     @classmethod
     def from_data_list(cls, data_list, device, **kw):
         """From the reference's per-molecule records (``Data`` objects with ``x`` and ``positions``,
-        datasets_3D.py:69-80): concatenated once, uploaded once."""
+        datasets_3D.py:69-80, and ``edge_index`` when every record has one): concatenated once, uploaded once."""
         x = torch.cat([torch.as_tensor(d.x) for d in data_list], dim=0)
         pos = torch.cat([torch.as_tensor(d.positions) for d in data_list], dim=0)
+        ei = [getattr(d, "edge_index", None) for d in data_list]
+        if "bond_index" not in kw and data_list and all(e is not None for e in ei):
+            kw["bond_index"] = torch.cat([torch.as_tensor(e).reshape(2, -1) for e in ei], dim=1).numpy()
+            kw["bond_counts"] = [int(torch.as_tensor(e).reshape(2, -1).size(1)) for e in ei]
         return cls(x, pos, [int(d.x.size(0)) for d in data_list], device, **kw)
+
+    def _set_bonds(self, bond_index, bond_counts):
+        """The bond graph: a host copy (the numpy-mode BFS) and a CSR over dataset atoms on the device (successors in
+        edge order, local indices)."""
+        bi = bond_index.cpu().numpy() if torch.is_tensor(bond_index) else np.asarray(bond_index)
+        bi = np.ascontiguousarray(bi.reshape(2, -1).astype(np.int64))
+        cnt = np.asarray(bond_counts, dtype=np.int64)
+        M = len(self)
+        if cnt.shape != (M,) or (M and cnt.min() < 0) or int(cnt.sum()) != bi.shape[1]:
+            raise ValueError("bond_counts has one entry per molecule and sums to the columns of bond_index")
+        if bi.shape[1] >= 2 ** 31:
+            raise ValueError("at most 2^31 - 1 bonds in all")
+        boff = np.zeros(M + 1, dtype=np.int64)
+        np.cumsum(cnt, out=boff[1:])
+        n_of = np.repeat(self.sizes, cnt)
+        if bi.size and (bi.min() < 0 or (bi >= n_of[None, :]).any()):
+            raise ValueError("bond_index holds local atom indices (0 .. n-1 of its molecule)")
+        if (bi[0] == bi[1]).any():
+            raise ValueError("the bond graph has a self-loop")
+        src = np.repeat(self.off[:-1], cnt) + bi[0]          # dataset atom of each bond's source
+        order = np.argsort(src, kind="stable")
+        deg = np.bincount(src, minlength=int(self.off[-1]))
+        rp = np.zeros(int(self.off[-1]) + 1, dtype=np.int32)
+        np.cumsum(deg, out=rp[1:])
+        self.bonds, self.bond_off = bi, boff
+        self.bond_ptr = torch.from_numpy(rp).to(self.device)
+        self.bond_dst = torch.from_numpy(np.ascontiguousarray(bi[1][order].astype(np.int32))).to(self.device)
+        if self.bond_dst.numel() == 0:
+            self.bond_dst = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._succ = {}
+
+    def successors(self, i):
+        """to_networkx successor lists of molecule i (cached)."""
+        s = self._succ.get(i)
+        if s is None:
+            s = self._succ[i] = masking.successors(int(self.sizes[i]), self.bonds[:, self.bond_off[i]:self.bond_off[i + 1]])
+        return s
+
+    def check_masking(self, ratio):
+        """Can this dataset be masked at `ratio`?  Raises ValueError when not."""
+        if self.bonds is None:
+            raise ValueError("atom masking walks the bond graph: build the DeviceDataset with bond_index / bond_counts "
+                             "(or records with edge_index)")
+        if len(self) and int(self.sizes.max()) > masking.MASK_MAX_N:
+            raise ValueError("atom masking takes molecules of at most %d atoms" % masking.MASK_MAX_N)
+        if len(self) and (masking.kept_count(self.sizes, ratio) > self.sizes).any():
+            raise ValueError("mask_ratio %r keeps more atoms than a molecule has" % (ratio,))
 
     def _build_edges(self, radius, max_num_neighbors):
         """radius_graph(positions, r) of every molecule (datasets_3D_Radius.py:120) in two launches over the whole
@@ -155,9 +223,13 @@ class DeviceDataset:
         np.cumsum(hb._sizes, out=mp[1:])
         h[B:2 * B + 1] = mp
         sp = np.zeros(B + 1, dtype=np.int64)
-        np.cumsum(self.pairs[hb.ids] * (1 if self.option == "combination" else 2), out=sp[1:])
+        pairs = self.pairs[hb.ids] if hb._mask is None else hb._sizes * (hb._sizes - 1) // 2
+        np.cumsum(pairs * (1 if self.option == "combination" else 2), out=sp[1:])
         h[2 * B + 1:3 * B + 2] = sp
-        if with_edges:
+        if with_edges and hb._mask is not None:   # (masked: the batch's edge offsets follow the count launch)
+            h[o["e_src_off"]:o["e_src_off"] + B] = self.edge_off[hb.ids]
+            h[o["e_ptr"]:o["e_ptr"] + B + 1] = 0
+        elif with_edges:
             h[o["e_src_off"]:o["e_src_off"] + B] = self.edge_off[hb.ids]
             ep = np.zeros(B + 1, dtype=np.int64)
             np.cumsum(self.edge_cnt[hb.ids], out=ep[1:])
@@ -166,6 +238,40 @@ class DeviceDataset:
         blob.copy_(slot[0][:words], non_blocking=True)
         self._staging.sent(slot)
         return blob, o
+
+    def mask_plan(self, hb, with_edges=False):
+        """A masked handle's side of geossl_gather_masked_molecules on the device (fresh memory): int32 words
+        [mol_id (B int64) | src_n (B) | e_src_cnt (B, with_edges) | keep (N, numpy mode)] -> a filled _lib.Mask whose
+        buffers stay alive with the returned tensor."""
+        B, mk = hb.num_graphs, hb._mask
+        o = {"mol_id": 0, "src_n": 2 * B}
+        words = 3 * B
+        if with_edges:
+            o["e_src_cnt"], words = words, words + B
+        if mk.keep is not None:
+            o["keep"], words = words, words + hb.n_atoms
+        slot = self._staging.take(words)
+        h = slot[0].numpy()
+        h[0:2 * B].view(np.int64)[:] = hb.ids
+        h[o["src_n"]:o["src_n"] + B] = hb._src_n
+        if with_edges:
+            h[o["e_src_cnt"]:o["e_src_cnt"] + B] = self.edge_cnt[hb.ids]
+        if mk.keep is not None:
+            h[o["keep"]:o["keep"] + hb.n_atoms] = mk.keep
+        blob = torch.empty(words, dtype=torch.int32, device=self.device)
+        blob.copy_(slot[0][:words], non_blocking=True)
+        self._staging.sent(slot)
+        base = blob.data_ptr()
+        m = _lib.Mask()
+        m.bond_ptr, m.bond_dst = ptr(self.bond_ptr), ptr(self.bond_dst)
+        m.mol_id, m.src_n = base + 4 * o["mol_id"], base + 4 * o["src_n"]
+        if with_edges:
+            m.e_src_cnt = base + 4 * o["e_src_cnt"]
+        if mk.keep is not None:
+            m.keep_in = base + 4 * o["keep"]
+        m.seed = 0 if mk.seed is None else int(mk.seed)
+        m.max_n = int(hb._src_n.max())
+        return m, blob
 
     def collate(self, hb):
         """The collated batch of a handle as fresh device tensors - what ``BatchAtomTuple.from_data_list`` over these
@@ -188,17 +294,50 @@ class DeviceDataset:
         if S:
             g.sei0, g.sei1 = ptr(sei[0]), ptr(sei[1])
         rei = None
-        if with_edges:
-            E = hb.n_edges
-            rei = torch.empty(2, E, dtype=torch.int64, device=dev)
-            if E:
-                g.e0_src, g.e1_src = ptr(self.edges[0]), ptr(self.edges[1])
-                g.e_src_off, g.e_ptr = base + 4 * o["e_src_off"], base + 4 * o["e_ptr"]
-                g.e0_dst, g.e1_dst = ptr(rei[0]), ptr(rei[1])
-        call("geossl_gather_molecules", C.byref(g), B, stream())
+        if hb._mask is not None:
+            m, mblob = self.mask_plan(hb, with_edges)
+            keep = None
+            if with_edges:
+                rei, keep = self._masked_edges(hb, g, m, blob, o)
+            call("geossl_gather_masked_molecules", C.byref(g), C.byref(m), B, stream())
+            del mblob, keep   # (stream order: a later owner of this memory writes after the launch read it)
+        else:
+            if with_edges:
+                E = hb.n_edges
+                rei = torch.empty(2, E, dtype=torch.int64, device=dev)
+                if E:
+                    g.e0_src, g.e1_src = ptr(self.edges[0]), ptr(self.edges[1])
+                    g.e_src_off, g.e_ptr = base + 4 * o["e_src_off"], base + 4 * o["e_ptr"]
+                    g.e0_dst, g.e1_dst = ptr(rei[0]), ptr(rei[1])
+            call("geossl_gather_molecules", C.byref(g), B, stream())
         out = Batch(x, pos, bvec, sei, rei, B, hb._sizes, self.option)
         prepare_batch(bvec, sei, hb._sizes, lazy=True)
         return out
+
+    def _masked_edges(self, hb, g, m, blob, o):
+        """Radius edges of a masked handle: the count launch (kept lists + survivors per molecule), ONE read-back of
+        the B counts, the batch's edge offsets into `blob`; `g` / `m` are then set up for the gather launch (keep_in =
+        the count launch's kept lists) and the [2, E] edge tensor is returned with the kept lists' buffer."""
+        B, dev, base = hb.num_graphs, self.device, blob.data_ptr()
+        keep = torch.empty(max(hb.n_atoms, 1), dtype=torch.int32, device=dev)
+        cnt = torch.empty(B, dtype=torch.int32, device=dev)
+        g.e0_src, g.e1_src = ptr(self.edges[0]), ptr(self.edges[1])
+        g.e_src_off = base + 4 * o["e_src_off"]
+        m.keep_out, m.e_count = ptr(keep), ptr(cnt)
+        call("geossl_gather_masked_molecules", C.byref(g), C.byref(m), B, stream())
+        counts = cnt.cpu().numpy().astype(np.int64)     # the read-back
+        ep = np.zeros(B + 1, dtype=np.int64)
+        np.cumsum(counts, out=ep[1:])
+        E = int(ep[-1])
+        hb.n_edges = E
+        blob[o["e_ptr"]:o["e_ptr"] + B + 1].copy_(torch.from_numpy(ep.astype(np.int32)))
+        rei = torch.empty(2, E, dtype=torch.int64, device=dev)
+        m.keep_out, m.e_count, m.keep_in = None, None, ptr(keep)
+        if E:
+            g.e_ptr, g.e0_dst, g.e1_dst = base + 4 * o["e_ptr"], ptr(rei[0]), ptr(rei[1])
+        else:
+            g.e0_src = g.e1_src = g.e_src_off = None
+        return rei, keep
 
     def gather_into(self, hb, x_dst, pos_dst, mol_ptr, zero=None):
         """x / positions of the handle's molecules into the static inputs of a per-structure graph (whose index tensors
@@ -219,14 +358,21 @@ class DeviceDataset:
         g.x_dst, g.pos_dst = ptr(x_dst), ptr(pos_dst)
         if zero is not None:
             g.zero, g.zero_count = ptr(zero), zero.numel()
-        call("geossl_gather_molecules", C.byref(g), B, stream())
+        if hb._mask is not None:
+            m, mblob = self.mask_plan(hb)
+            call("geossl_gather_masked_molecules", C.byref(g), C.byref(m), B, stream())
+            del mblob
+        else:
+            call("geossl_gather_molecules", C.byref(g), B, stream())
 
 
 class DatasetBatch:
     """``batch_size`` molecules of a ``DeviceDataset`` by id: what the loader hands to a step.  Host side only - ids,
-    sizes, counts; the collated tensors exist once somebody asks for them."""
+    sizes, counts; the collated tensors exist once somebody asks for them.  `mask` (masking.MaskDraw): a masked batch
+    - its sizes are the kept counts, the original ones are ``_src_n``; the radius edges of a masked batch are counted
+    when it is collated (``n_edges`` is None until then)."""
 
-    def __init__(self, dataset, ids):
+    def __init__(self, dataset, ids, mask=None):
         self._dataset = dataset
         self.ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int64))
         if self.ids.ndim != 1 or not self.ids.size:
@@ -234,14 +380,20 @@ class DatasetBatch:
         if self.ids.min() < 0 or self.ids.max() >= len(dataset):
             raise IndexError("molecule id out of range")
         self._sizes = dataset.sizes[self.ids]            # (numpy: bucket.sizes_array takes it as it is)
+        self._mask = mask
+        if mask is not None:
+            self._src_n = self._sizes
+            self._sizes = masking.kept_count(self._src_n, mask.ratio)
+            if mask.keep is not None and mask.keep.shape != (int(self._sizes.sum()),):
+                raise ValueError("kept lists of a masked batch hold k(n) atoms per molecule")
         self._canonical = dataset.option
         self.device = dataset.device
         self.x_cols = dataset.x_cols
         self.num_graphs = int(self.ids.size)
         self.n_atoms = int(self._sizes.sum())
-        P = int(dataset.pairs[self.ids].sum())
+        P = int(dataset.pairs[self.ids].sum()) if mask is None else int((self._sizes * (self._sizes - 1) // 2).sum())
         self.n_super = P if dataset.option == "combination" else 2 * P
-        self.n_edges = int(dataset.edge_cnt[self.ids].sum()) if dataset.edges is not None else None
+        self.n_edges = int(dataset.edge_cnt[self.ids].sum()) if dataset.edges is not None and mask is None else None
         self._batch = None
 
     def materialize(self):
@@ -278,9 +430,22 @@ class DeviceLoader:
     ``torch.utils.data.RandomSampler`` produces under the same global torch seed (one ``torch.randperm`` per epoch from
     a generator seeded by one draw of the default generator), so a run is reproducible against the reference's loader."""
 
-    def __init__(self, dataset, batch_size=1, shuffle=True, drop_last=False, generator=None):
+    def __init__(self, dataset, batch_size=1, shuffle=True, drop_last=False, generator=None, mask_ratio=0.0,
+                 mask_rng="device"):
+        """mask_ratio > 0: yield masked handles (the reference's ``--GeoSSL_atom_masking_ratio``, datasets_3D.py:77-78).
+        mask_rng "device": the kept atoms are drawn on the GPU from Philox-4x32-10, keyed by one np.random.randint
+        draw per epoch (so np.random.seed(seed) repeats a run) with counter (molecule id, draw index); the rule is in
+        include/geossl_hip.h (geossl_gather_masked_molecules) and DESIGN 2.  "numpy": the reference's own BFS and
+        np.random draws on the host, molecule after molecule in batch order when the handle is yielded (bit-for-bit
+        the masks of a reference run; about as slow as it)."""
         self.dataset, self.batch_size, self.shuffle, self.drop_last = dataset, int(batch_size), shuffle, drop_last
         self.generator = generator
+        self.mask_ratio = masking.check_ratio(mask_ratio)
+        if mask_rng not in masking.MASK_RNGS:
+            raise ValueError("mask_rng is 'device' or 'numpy'")
+        self.mask_rng = mask_rng
+        if self.mask_ratio > 0:
+            dataset.check_masking(self.mask_ratio)
 
     def __len__(self):
         n = len(self.dataset)
@@ -302,5 +467,17 @@ class DeviceLoader:
 
     def __iter__(self):
         order, bs = self.order(), self.batch_size
+        r = self.mask_ratio
+        if r == 0:
+            for k in range(len(self)):
+                yield DatasetBatch(self.dataset, order[k * bs:(k + 1) * bs])
+            return
+        ds = self.dataset
+        seed = int(np.random.randint(0, 2 ** 63 - 1, dtype=np.int64)) if self.mask_rng == "device" else None
         for k in range(len(self)):
-            yield DatasetBatch(self.dataset, order[k * bs:(k + 1) * bs])
+            ids = order[k * bs:(k + 1) * bs]
+            keep = None
+            if seed is None:
+                keep = np.concatenate([masking.reference_bfs(int(ds.sizes[i]), ds.successors(int(i)), r)
+                                       for i in ids]).astype(np.int32)
+            yield DatasetBatch(ds, ids, masking.MaskDraw(r, seed=seed, keep=keep))

@@ -103,6 +103,11 @@ class Gather(C.Structure):
                [("zero_count", i64), ("x_cols", i32), ("option", i32)]
 
 
+class Mask(C.Structure):
+    _fields_ = [(k, vp) for k in ("bond_ptr", "bond_dst", "src_n", "mol_id", "keep_in", "keep_out", "e_src_cnt",
+                                  "e_count")] + [("seed", u64), ("max_n", i32), ("pad_", i32)]
+
+
 P = C.POINTER
 # name -> (restype, argtypes); mirrors include/geossl_hip.h one to one
 PROTOTYPES = {
@@ -232,6 +237,7 @@ PROTOTYPES = {
     "geossl_painn_mix_post_bwd_dyn": (i32, [vp, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp]),
     "geossl_painn_mix_pre_bwd_dyn": (i32, [vp, vp, vp, vp, i64, i32, vp, vp, vp, vp]),
     "geossl_gather_molecules": (i32, [P(Gather), i64, vp]),
+    "geossl_gather_masked_molecules": (i32, [P(Gather), P(Mask), i64, vp]),
 }
 
 _lib = None

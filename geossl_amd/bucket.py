@@ -151,7 +151,8 @@ def eligible(batch, model_3d, normalize=False):
     if lo < 1 or hi > MAX_N or hi < 2:
         return False
     if getattr(batch, "_dataset", None) is not None:   # a handle on a device-resident dataset: gathered by the fill itself
-        return model_3d != "painn" or batch.n_edges is not None
+        # (a masked PaiNN handle: its edge count is drawn - it runs on its collated tensors)
+        return model_3d != "painn" or (batch.n_edges is not None and getattr(batch, "_mask", None) is None)
     if model_3d == "painn":
         rei = getattr(batch, "radius_edge_index", None)
         if (rei is None or not rei.is_cuda or rei.dtype != torch.long or rei.dim() != 2 or rei.size(0) != 2
@@ -423,7 +424,8 @@ class Bucket:
         device, or a handle on a device-resident dataset (Geom3D.dataloaders.DatasetBatch) whose molecules are gathered
         from there.  One pinned upload (everything that is a function of the molecule sizes) + one launch
         (geossl_gather_molecules: atom rows, batch vector, super-edges, pair-slot atoms, incidence lists, radius edges,
-        the cleared buffer) [+ geossl_painn_edge_layout]."""
+        the cleared buffer) [+ geossl_painn_edge_layout].  A masked handle (SchNet only) adds the small upload of its
+        mask and launches geossl_gather_masked_molecules instead: the BFS and the gather are that one launch."""
         global _PARTS
         if _PARTS is None:
             _PARTS = _parts_table()
@@ -510,7 +512,15 @@ class Bucket:
         if zero is not None:
             g.zero, g.zero_count = ptr(zero), zero.numel()
         st_ = stream()
-        call("geossl_gather_molecules", C.byref(g), B, st_)
+        if ds is not None and getattr(batch, "_mask", None) is not None:
+            # a masked handle (DeviceLoader(mask_ratio=...)): the kept atoms are drawn (or read) by the same launch
+            if self.kind == "painn":
+                raise ValueError("a masked PaiNN batch has a drawn edge count: it runs on its collated tensors")
+            m, mblob = ds.mask_plan(batch)
+            call("geossl_gather_masked_molecules", C.byref(g), C.byref(m), B, st_)
+            del mblob
+        else:
+            call("geossl_gather_molecules", C.byref(g), B, st_)
         if self.kind == "painn":
             el = self.el
             try:

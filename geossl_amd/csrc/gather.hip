@@ -35,38 +35,27 @@ __device__ __forceinline__ void pair_of_slot(int p, int n, int& a, int& b) {
   b = p - (g * n - g * (g + 1) / 2) + g + 1;
 }
 
-__global__ __launch_bounds__(GATHER_THREADS) void k_gather_molecules(GeosslGather g, int B) {
+// the blocks behind the molecules clear the float buffer
+__device__ __forceinline__ void clear_zero_block(const GeosslGather& g, int B) {
   const int tid = threadIdx.x;
-  if ((int)blockIdx.x >= B) {  // ---- the blocks behind the molecules: clear the float buffer
-    if (g.zero == nullptr) return;
-    const int64_t nb = (int64_t)gridDim.x - B;
-    const int64_t t0 = ((int64_t)blockIdx.x - B) * GATHER_THREADS + tid, nt = nb * GATHER_THREADS;
-    const int64_t n4 = g.zero_count >> 2;
-    f32x4* z4 = reinterpret_cast<f32x4*>(g.zero);
-    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    if ((reinterpret_cast<uintptr_t>(g.zero) & 15) == 0) {
-      for (int64_t i = t0; i < n4; i += nt) z4[i] = zero4;
-      for (int64_t i = (n4 << 2) + t0; i < g.zero_count; i += nt) g.zero[i] = 0.f;
-    } else {
-      for (int64_t i = t0; i < g.zero_count; i += nt) g.zero[i] = 0.f;
-    }
-    return;
+  if (g.zero == nullptr) return;
+  const int64_t nb = (int64_t)gridDim.x - B;
+  const int64_t t0 = ((int64_t)blockIdx.x - B) * GATHER_THREADS + tid, nt = nb * GATHER_THREADS;
+  const int64_t n4 = g.zero_count >> 2;
+  f32x4* z4 = reinterpret_cast<f32x4*>(g.zero);
+  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+  if ((reinterpret_cast<uintptr_t>(g.zero) & 15) == 0) {
+    for (int64_t i = t0; i < n4; i += nt) z4[i] = zero4;
+    for (int64_t i = (n4 << 2) + t0; i < g.zero_count; i += nt) g.zero[i] = 0.f;
+  } else {
+    for (int64_t i = t0; i < g.zero_count; i += nt) g.zero[i] = 0.f;
   }
-  const int m = blockIdx.x;
-  const int a0 = g.mol_ptr[m], n = g.mol_ptr[m + 1] - a0;
-  const int64_t s0 = g.src_off[m];
-  // ---- atom rows
-  {
-    const int C = g.x_cols;
-    const int64_t* xs = g.x_src + s0 * C;
-    int64_t* xd = g.x_dst + (int64_t)a0 * C;
-    for (int i = tid; i < n * C; i += GATHER_THREADS) xd[i] = xs[i];
-    const float* ps = g.pos_src + s0 * 3;
-    float* pd = g.pos_dst + (int64_t)a0 * 3;
-    for (int i = tid; i < n * 3; i += GATHER_THREADS) pd[i] = ps[i];
-    if (g.batch_dst != nullptr)
-      for (int i = tid; i < n; i += GATHER_THREADS) g.batch_dst[a0 + i] = m;
-  }
+}
+
+// The index structures of molecule m (n atoms from batch row a0 on) that are a function of n alone: pair slots of the
+// two-view batch, super-edges, incidence lists.  Shared by the whole-molecule and the masked gather.
+__device__ __forceinline__ void gather_structures(const GeosslGather& g, int B, int m, int a0, int n) {
+  const int tid = threadIdx.x;
   const int P = n * (n - 1) / 2;
   // ---- pair slots of the two-view batch (geossl_pair_index_fill) and, for "combination", the super-edges
   const bool comb_sei = g.sei0 != nullptr && g.option == 0;
@@ -120,6 +109,30 @@ __global__ __launch_bounds__(GATHER_THREADS) void k_gather_molecules(GeosslGathe
       }
     }
   }
+}
+
+__global__ __launch_bounds__(GATHER_THREADS) void k_gather_molecules(GeosslGather g, int B) {
+  const int tid = threadIdx.x;
+  if ((int)blockIdx.x >= B) {
+    clear_zero_block(g, B);
+    return;
+  }
+  const int m = blockIdx.x;
+  const int a0 = g.mol_ptr[m], n = g.mol_ptr[m + 1] - a0;
+  const int64_t s0 = g.src_off[m];
+  // ---- atom rows
+  {
+    const int C = g.x_cols;
+    const int64_t* xs = g.x_src + s0 * C;
+    int64_t* xd = g.x_dst + (int64_t)a0 * C;
+    for (int i = tid; i < n * C; i += GATHER_THREADS) xd[i] = xs[i];
+    const float* ps = g.pos_src + s0 * 3;
+    float* pd = g.pos_dst + (int64_t)a0 * 3;
+    for (int i = tid; i < n * 3; i += GATHER_THREADS) pd[i] = ps[i];
+    if (g.batch_dst != nullptr)
+      for (int i = tid; i < n; i += GATHER_THREADS) g.batch_dst[a0 + i] = m;
+  }
+  gather_structures(g, B, m, a0, n);
   // ---- radius edges of the molecule: the dataset's node offset replaced by the batch's
   if (g.e0_dst != nullptr) {
     const int d0 = g.e_ptr[m], cnt = g.e_ptr[m + 1] - d0;
@@ -129,6 +142,206 @@ __global__ __launch_bounds__(GATHER_THREADS) void k_gather_molecules(GeosslGathe
       g.e0_dst[d0 + i] = g.e0_src[es + i] + shift;
       g.e1_dst[d0 + i] = g.e1_src[es + i] + shift;
     }
+  }
+}
+
+// ---- masked gather (BFS atom masking of datasets_3D.py:24-67 / datasets_3D_Radius.py:43-87)
+constexpr int MASK_MAX_N = 2048;   // 64 lanes x one 32-bit word of the visited / frontier bitsets
+
+// Philox-4x32-10 (Salmon et al., SC'11), word 0 of the block for counter (c0, c1, 0, 0)
+__device__ __forceinline__ uint32_t philox_w0(uint32_t c0, uint32_t c1, uint64_t seed) {
+  uint32_t c2 = 0, c3 = 0, k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (uint32_t)p1;
+    c3 = (uint32_t)p0;
+    c0 = n0;
+    c2 = n2;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  return c0;
+}
+
+__device__ __forceinline__ int wave_incl_scan(int v) {
+  const int lane = __lane_id();
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int t = __shfl_up(v, d);
+    if (lane >= d) v += t;
+  }
+  return v;
+}
+
+// position of the r-th set bit (0-based) of w
+__device__ __forceinline__ int select_bit(uint32_t w, int r) {
+  int pos = 0;
+#pragma unroll
+  for (int s = 16; s > 0; s >>= 1) {
+    const uint32_t lo = w & ((1u << s) - 1u);
+    const int c = __popc(lo);
+    if (r >= c) {
+      r -= c;
+      w >>= s;
+      pos += s;
+    } else {
+      w = lo;
+    }
+  }
+  return pos;
+}
+
+// the r-th member (ascending) of the set whose lane words are w, incl = inclusive scan of their popcounts; uniform
+__device__ __forceinline__ int wave_pick(uint32_t w, int r, int incl) {
+  const int excl = incl - __popc(w);
+  const uint64_t hit = __ballot(r >= excl && r < incl);
+  const int L = __builtin_ctzll(hit);
+  return __shfl(__lane_id() * 32 + select_bit(w, r - excl), L);
+}
+
+// kept atoms (ascending local indices) of molecule m drawn by wave 0: lane l owns atoms 32 l .. 32 l + 31
+__device__ void bfs_draw(const GeosslMask& mk, int m, int64_t s0, int n, int k, uint32_t* kbits) {
+  const int lane = __lane_id();
+  const int lo = lane * 32;
+  const uint32_t valid = lo >= n ? 0u : (n - lo >= 32 ? ~0u : ((1u << (n - lo)) - 1u));
+  const uint32_t c0 = (uint32_t)mk.mol_id[m];
+  uint32_t vis = 0, fr = 0;
+  int atom = (int)(((uint64_t)philox_w0(c0, 0u, mk.seed) * (uint32_t)n) >> 32);
+  for (int t = 1;; ++t) {
+    if ((atom >> 5) == lane) vis |= 1u << (atom & 31);
+    const int e0 = mk.bond_ptr[s0 + atom], e1 = mk.bond_ptr[s0 + atom + 1];
+    for (int j = e0; j < e1; j += 64) {
+      const int v = j + lane < e1 ? mk.bond_dst[j + lane] : -1;
+      const int cnt = min(64, e1 - j);
+      for (int q = 0; q < cnt; ++q) {
+        const int u = __builtin_amdgcn_readlane(v, q);
+        if ((unsigned)u < (unsigned)n && (u >> 5) == lane) fr |= 1u << (u & 31);
+      }
+    }
+    fr &= ~vis;
+    if (t == k) break;
+    const int fc = wave_incl_scan(__popc(fr));
+    const int ftot = __shfl(fc, 63);
+    const uint32_t w = philox_w0(c0, (uint32_t)t, mk.seed);
+    if (ftot > 0) {
+      atom = wave_pick(fr, (int)(((uint64_t)w * (uint32_t)ftot) >> 32), fc);
+    } else {
+      const uint32_t un = valid & ~vis;
+      atom = wave_pick(un, (int)(((uint64_t)w * (uint32_t)(n - t)) >> 32), wave_incl_scan(__popc(un)));
+    }
+  }
+  kbits[lane] = vis;
+}
+
+__global__ __launch_bounds__(GATHER_THREADS) void k_gather_masked(GeosslGather g, GeosslMask mk, int B) {
+  __shared__ int keep[MASK_MAX_N];
+  __shared__ uint32_t kbits[64];
+  __shared__ int kpre[64];
+  __shared__ int wsum[GATHER_THREADS / 64];
+  const int tid = threadIdx.x;
+  if ((int)blockIdx.x >= B) {
+    clear_zero_block(g, B);
+    return;
+  }
+  const int m = blockIdx.x;
+  const int a0 = g.mol_ptr[m], k = g.mol_ptr[m + 1] - a0;
+  const int n = mk.src_n[m];
+  const int64_t s0 = g.src_off[m];
+  if (n > MASK_MAX_N || k < 1 || k > n) return;   // (uniform over the block)
+  const bool count_only = mk.e_count != nullptr;
+  // ---- the kept bitset
+  if (mk.keep_in != nullptr) {
+    if (tid < 64) kbits[tid] = 0u;
+    __syncthreads();
+    for (int i = tid; i < k; i += GATHER_THREADS) {
+      const int v = mk.keep_in[a0 + i];
+      if ((unsigned)v < (unsigned)n) atomicOr(&kbits[v >> 5], 1u << (v & 31));
+    }
+    __syncthreads();
+  } else {
+    if (tid < 64) bfs_draw(mk, m, s0, n, k, kbits);
+    __syncthreads();
+  }
+  // ---- rank prefix per word and the kept list
+  if (tid < 64) {
+    const uint32_t w = kbits[tid];
+    int pos = wave_incl_scan(__popc(w)) - __popc(w);
+    kpre[tid] = pos;
+    if (mk.keep_in == nullptr)
+      for (uint32_t r = w; r != 0u; r &= r - 1u) keep[pos++] = tid * 32 + __builtin_ctz(r);
+  }
+  if (mk.keep_in != nullptr)
+    for (int i = tid; i < k; i += GATHER_THREADS) {
+      const int v = mk.keep_in[a0 + i];
+      keep[i] = (unsigned)v < (unsigned)n ? v : 0;
+    }
+  __syncthreads();
+  if (mk.keep_out != nullptr)
+    for (int i = tid; i < k; i += GATHER_THREADS) mk.keep_out[a0 + i] = keep[i];
+  if (!count_only) {
+    // ---- atom rows: destination row i <- source row s0 + keep[i]
+    const int C = g.x_cols;
+    const int64_t* xs = g.x_src + s0 * C;
+    int64_t* xd = g.x_dst + (int64_t)a0 * C;
+    for (int i = tid; i < k * C; i += GATHER_THREADS) {
+      const int r = i / C;
+      xd[i] = xs[(int64_t)keep[r] * C + (i - r * C)];
+    }
+    const float* ps = g.pos_src + s0 * 3;
+    float* pd = g.pos_dst + (int64_t)a0 * 3;
+    for (int i = tid; i < k * 3; i += GATHER_THREADS) {
+      const int r = i / 3;
+      pd[i] = ps[(int64_t)keep[r] * 3 + (i - r * 3)];
+    }
+    if (g.batch_dst != nullptr)
+      for (int i = tid; i < k; i += GATHER_THREADS) g.batch_dst[a0 + i] = m;
+    gather_structures(g, B, m, a0, k);
+  }
+  // ---- radius edges: both ends kept, in edge order, renumbered by rank (a block-wide ballot scan)
+  if (count_only ? g.e0_src != nullptr : g.e0_dst != nullptr) {
+    const int64_t es = g.e_src_off[m];
+    const int cnt = mk.e_src_cnt[m];
+    const int d0 = count_only ? 0 : g.e_ptr[m], dcap = count_only ? 0 : g.e_ptr[m + 1] - d0;
+    const int lane = tid & 63, wid = tid >> 6;
+    int base = 0;
+    for (int i0 = 0; i0 < cnt; i0 += GATHER_THREADS) {
+      const int i = i0 + tid;
+      bool keep_e = false;
+      int na = 0, nb = 0;
+      if (i < cnt) {
+        const int64_t u = g.e0_src[es + i] - s0, v = g.e1_src[es + i] - s0;
+        if (u >= 0 && u < n && v >= 0 && v < n) {
+          const uint32_t wu = kbits[u >> 5], wv = kbits[v >> 5];
+          const uint32_t bu = 1u << (u & 31), bv = 1u << (v & 31);
+          if ((wu & bu) && (wv & bv)) {
+            keep_e = true;
+            na = kpre[u >> 5] + __popc(wu & (bu - 1u));
+            nb = kpre[v >> 5] + __popc(wv & (bv - 1u));
+          }
+        }
+      }
+      const uint64_t bal = __ballot(keep_e);
+      if (lane == 0) wsum[wid] = __popcll(bal);
+      __syncthreads();
+      int off = base, tot = 0;
+#pragma unroll
+      for (int w = 0; w < GATHER_THREADS / 64; ++w) {
+        off += w < wid ? wsum[w] : 0;
+        tot += wsum[w];
+      }
+      off += __popcll(bal & ((1ull << lane) - 1ull));
+      if (keep_e && !count_only && off < dcap) {
+        g.e0_dst[d0 + off] = a0 + na;
+        g.e1_dst[d0 + off] = a0 + nb;
+      }
+      base += tot;
+      __syncthreads();   // (wsum is rewritten by the next chunk)
+    }
+    if (count_only && tid == 0) mk.e_count[m] = base;
+  } else if (count_only && tid == 0) {
+    mk.e_count[m] = 0;
   }
 }
 
@@ -156,6 +369,46 @@ extern "C" int geossl_gather_molecules(const GeosslGather* g, int64_t B, hipStre
   }
   if (B + zero_blocks == 0) return 0;
   hipLaunchKernelGGL(k_gather_molecules, dim3((unsigned)(B + zero_blocks)), dim3(GATHER_THREADS), 0, stream, *g, (int)B);
+  GEOSSL_CHECK_LAUNCH();
+  return 0;
+}
+
+
+extern "C" int geossl_gather_masked_molecules(const GeosslGather* g, const GeosslMask* mk, int64_t B, hipStream_t stream) {
+  if (g == nullptr || mk == nullptr || B < 0 || B > (1 << 24)) return (int)hipErrorInvalidValue;
+  if (B == 0) return geossl_gather_molecules(g, 0, stream);   // (nothing to mask: only the buffer to clear)
+  if (mk->max_n < 1 || mk->max_n > MASK_MAX_N || mk->src_n == nullptr || g->src_off == nullptr || g->mol_ptr == nullptr)
+    return (int)hipErrorInvalidValue;
+  if (mk->keep_in == nullptr && (mk->bond_ptr == nullptr || mk->bond_dst == nullptr || mk->mol_id == nullptr))
+    return (int)hipErrorInvalidValue;
+  if (mk->e_count != nullptr) {   // the count launch: kept lists and surviving radius edges only
+    if (mk->keep_out == nullptr) return (int)hipErrorInvalidValue;
+    if (g->e0_src != nullptr && (g->e1_src == nullptr || g->e_src_off == nullptr || mk->e_src_cnt == nullptr))
+      return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_gather_masked, dim3((unsigned)B), dim3(GATHER_THREADS), 0, stream, *g, *mk, (int)B);
+    GEOSSL_CHECK_LAUNCH();
+    return 0;
+  }
+  if (g->x_src == nullptr || g->pos_src == nullptr || g->x_dst == nullptr || g->pos_dst == nullptr || g->x_cols < 1 ||
+      (g->option != 0 && g->option != 1))
+    return (int)hipErrorInvalidValue;
+  if ((g->sei0 != nullptr) != (g->sei1 != nullptr) || (g->pair_i != nullptr) != (g->pair_j != nullptr) ||
+      (g->e0_dst != nullptr) != (g->e1_dst != nullptr))
+    return (int)hipErrorInvalidValue;
+  if ((g->sei0 != nullptr || g->inc_idx != nullptr) && g->se_ptr == nullptr) return (int)hipErrorInvalidValue;
+  if (g->pair_i != nullptr && g->pair_ptr2 == nullptr) return (int)hipErrorInvalidValue;
+  if (g->inc_idx != nullptr && g->inc_ptr == nullptr) return (int)hipErrorInvalidValue;
+  if (g->e0_dst != nullptr && (g->e0_src == nullptr || g->e1_src == nullptr || g->e_src_off == nullptr ||
+                               g->e_ptr == nullptr || mk->e_src_cnt == nullptr))
+    return (int)hipErrorInvalidValue;
+  if (g->zero_count < 0 || (g->zero == nullptr && g->zero_count > 0) || (reinterpret_cast<uintptr_t>(g->zero) & 3))
+    return (int)hipErrorInvalidValue;
+  int zero_blocks = 0;
+  if (g->zero != nullptr && g->zero_count > 0) {
+    const int64_t want = (g->zero_count / 4 + GATHER_THREADS - 1) / GATHER_THREADS;
+    zero_blocks = (int)(want < 1 ? 1 : (want > 256 ? 256 : want));
+  }
+  hipLaunchKernelGGL(k_gather_masked, dim3((unsigned)(B + zero_blocks)), dim3(GATHER_THREADS), 0, stream, *g, *mk, (int)B);
   GEOSSL_CHECK_LAUNCH();
   return 0;
 }

@@ -140,3 +140,38 @@ def draw_noise(batch, seed, num_noise_level=50, sigma=0.3, mu=0.0):
         "noise_level_2": rng.integers(0, num_noise_level, size=B).astype(np.int64),
         "dist_noise_2": rng.normal(size=(S, 1)).astype(np.float32),
     }
+
+
+def add_bonds(mols, cutoff=1.6, seed=0, cut=0.25):
+    """A symmetric bond graph (``data.edge_index`` of the reference's records, what its atom masking walks,
+    Geom3D/datasets/datasets_3D.py:24-45) for the molecules of a make_molecules dict, added to it in place as
+    ``bond_index [2, E]`` (local atom indices, molecule after molecule) and ``bond_counts [M]``: atom pairs closer than
+    `cutoff` A (the growth bonds of 1.4 A among them, so a molecule starts connected), each bond as two directed
+    columns, bonds in random order.  In a fraction `cut` of the molecules with more than two atoms, one random atom
+    loses all its bonds and one more random bond is removed: isolated atoms and several components, the case where the
+    masking BFS restarts from an unvisited atom."""
+    rng = np.random.default_rng(seed)
+    sizes = np.asarray(mols["sizes"], dtype=np.int64)
+    off = np.concatenate([[0], np.cumsum(sizes)])
+    pos = np.asarray(mols["positions"], dtype=np.float64)
+    cols, counts = [], []
+    for m, n in enumerate(sizes.tolist()):
+        p = pos[off[m]:off[m + 1]]
+        d = np.linalg.norm(p[:, None, :] - p[None, :, :], axis=2)
+        i, j = np.nonzero(np.triu(d < cutoff, k=1))
+        if n > 2 and rng.random() < cut:
+            a = rng.integers(0, n)
+            keep = (i != a) & (j != a)
+            i, j = i[keep], j[keep]
+            if i.size:
+                drop = rng.integers(0, i.size)
+                i, j = np.delete(i, drop), np.delete(j, drop)
+        perm = rng.permutation(i.size)
+        i, j = i[perm], j[perm]
+        e = np.empty((2, 2 * i.size), dtype=np.int64)
+        e[0, 0::2], e[1, 0::2], e[0, 1::2], e[1, 1::2] = i, j, j, i
+        cols.append(e)
+        counts.append(e.shape[1])
+    mols["bond_index"] = np.concatenate(cols, axis=1) if cols else np.empty((2, 0), np.int64)
+    mols["bond_counts"] = np.asarray(counts, dtype=np.int64)
+    return mols

@@ -731,6 +731,39 @@ typedef struct GeosslGather {
 } GeosslGather;
 int geossl_gather_molecules(const GeosslGather* g, int64_t B, hipStream_t stream);
 
+/* ---- masked batch assembly: BFS atom masking (Molecule3DDataset.subgraph, Geom3D/datasets/datasets_3D.py:24-67;
+ * MoleculeDataset3DRadius.subgraph, datasets_3D_Radius.py:43-87).  `g` as for geossl_gather_molecules, except that
+ * mol_ptr / se_ptr / pair_ptr2 / inc_ptr / e_ptr describe the MASKED molecules (k kept atoms of molecule m:
+ * k = mol_ptr[m+1] - mol_ptr[m], a function of n alone: int(n (1 - ratio)) + 1) while src_off / e_src_off point at the
+ * whole molecule in the dataset.  Destination row mol_ptr[m] + i reads source row src_off[m] + keep[i]; the structures
+ * that depend on k only are those of a k-atom molecule; a radius edge survives when both its ends are kept, in edge
+ * order, its ends renumbered by their rank among the kept atoms (torch_geometric.utils.subgraph(relabel_nodes=True)).
+ * One block per molecule.  The kept list `keep` (ascending local indices) comes from keep_in, or - keep_in == NULL - is
+ * drawn by the block's first wave: a BFS over the bond graph with Philox-4x32-10, key = (seed low, seed high word),
+ * counter = (mol_id[m], t, 0, 0), word 0; an integer below c is (w * c) >> 32 (64-bit product).  t = 0 picks the start
+ * atom below n; step t = 1 .. k-1 picks, when the frontier (bond successors of the visited atoms, minus the visited) is
+ * empty, the draw(n - t)-th unvisited atom in ascending order, else the draw(|frontier|)-th frontier atom in ascending
+ * order.  With e_count != NULL the launch only decides the kept lists, writes keep_out (required then) and counts the
+ * surviving radius edges of every molecule into e_count - the survivor count depends on the draw, so a gather with
+ * radius edges is a count launch, a read-back of B counts (the caller's e_ptr) and a gather launch with keep_in = the
+ * count launch's keep_out.  Refused (hipErrorInvalidValue): max_n > 2048, bond_ptr / bond_dst NULL when drawing.
+ * Molecules with n > 2048 or k outside [1, n] are skipped; kept atoms of keep_in outside [0, n) read atom 0.          */
+typedef struct GeosslMask {
+  const int32_t* bond_ptr;  /* [Ntot+1] over DATASET atoms: the successors of atom s are bond_dst[bond_ptr[s] ..
+                               bond_ptr[s+1]) (the edge_index of the molecule; no self-loops) */
+  const int32_t* bond_dst;  /* local atom indices 0 .. n-1 */
+  const int32_t* src_n;     /* [B] atoms of each molecule before masking */
+  const int64_t* mol_id;    /* [B] dataset molecule ids (the first counter word of the draw) */
+  const int32_t* keep_in;   /* [mol_ptr[B]] kept atoms, laid out by mol_ptr (NULL: drawn on the device) */
+  int32_t* keep_out;        /* [mol_ptr[B]] the kept lists (NULL: not written) */
+  const int32_t* e_src_cnt; /* [B] radius edges of each molecule in the dataset (with e0_src / e1_src / e_src_off) */
+  int32_t* e_count;         /* [B] non-NULL: the count launch */
+  uint64_t seed;
+  int32_t max_n;            /* largest n of the batch */
+  int32_t pad_;
+} GeosslMask;
+int geossl_gather_masked_molecules(const GeosslGather* g, const GeosslMask* mask, int64_t B, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
