@@ -238,6 +238,11 @@ PROTOTYPES = {
     "geossl_painn_mix_pre_bwd_dyn": (i32, [vp, vp, vp, vp, i64, i32, vp, vp, vp, vp]),
     "geossl_gather_molecules": (i32, [P(Gather), i64, vp]),
     "geossl_gather_masked_molecules": (i32, [P(Gather), P(Mask), i64, vp]),
+    # contrastive heads (csrc/contrastive.hip)
+    "geossl_infonce_fwd": (i32, [vp, vp, i64, i32, f32, vp, vp, vp, vp, vp]),
+    "geossl_infonce_bwd": (i32, [vp, vp, vp, vp, i64, i32, f32, vp, vp, vp, vp]),
+    "geossl_ebm_nce_fwd": (i32, [vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "geossl_ebm_nce_bwd": (i32, [vp, vp, vp, i64, i32, i32, vp, vp, vp, vp]),
 }
 
 _lib = None

@@ -190,9 +190,10 @@ MODULE_SWITCHES = ("GEOSSL_NO_CHAIN", "GEOSSL_NCSN_SPLIT_BWD", "GEOSSL_NCSN_SEPA
 PAINN_SWITCHES = ("GEOSSL_PAINN_NO_CHAIN", "GEOSSL_PAINN_SILU_KERNELS")   # ... for a PaiNN backbone as well
 
 
-def modules_ok(model, n1, n2):
+def modules_ok(model, n1=None, n2=None):
     """The step of these modules can run on a bucket: the F = 128 chain path of SchNet / PaiNN (the chained row kernel is
-    the one that takes a device-side row count) and the paired NCSN heads (two different modules of width 128)."""
+    the one that takes a device-side row count) and the paired NCSN heads (two different modules of width 128).  No heads
+    (n1 = n2 = None): the contrastive steps, whose loss reads the readout of the 2B molecules - exact counts, no capacity."""
     import os
     from .Geom3D.models.painn import PaiNN
     from .Geom3D.models.schnet import SchNet
@@ -212,6 +213,8 @@ def modules_ok(model, n1, n2):
             return False
     else:
         return False
+    if n1 is None and n2 is None:
+        return True
     if not (isinstance(n1, NCSN_version_03) and isinstance(n2, NCSN_version_03)) or n1 is n2 \
             or n1.emb_dim != 128 or n2.emb_dim != 128:
         return False

@@ -453,3 +453,111 @@ def energy_force_loss(pred_energy, actual_energy, dE_dpos, actual_force, energy_
         raise ValueError("actual_force has shape %s, dE_dpos %s" % (tuple(actual_force.shape), tuple(dE_dpos.shape)))
     return _EnergyForceLoss.apply(pred_energy, actual_energy, dE_dpos, actual_force, float(energy_coeff),
                                   float(force_coeff), loss)
+
+
+def two_views(pos, noise, z, dyn=None):
+    """The positions and atom types of the two views of a contrastive step as one 2N-atom batch (pretrain_GeoSSL.py:68-74:
+    [pos ; pos + noise], [z ; z]) in one launch - ddm_views without the super-edge lengths, which these objectives never
+    read.  dyn (bucket.DynDims): N is a capacity, the real count is read on the device; view 1 starts at row dims[N]."""
+    pos, noise = _f32(pos), _f32(noise)
+    N = pos.size(0)
+    assert z.dim() == 1 and z.dtype == torch.long and z.numel() == N
+    pos2 = torch.empty(2 * N, 3, dtype=torch.float32, device=pos.device)
+    z2 = torch.empty(2 * N, dtype=torch.long, device=pos.device)
+    call("geossl_ddm_views_dyn", ptr(pos), ptr(noise), None, None, N, 0, ptr(pos2), None, None, ptr(z),
+         z.stride(0) if N > 0 else 1, ptr(z2), _dyn(dyn, "n_atoms"), None, stream())
+    return pos2, z2
+
+
+def _pair_grads(X, Y, B, F):
+    """dX / dY of a contrastive loss as the two halves of ONE [2B, F] buffer: when X and Y are the halves of a fused
+    two-view readout (pretrain_GeoSSL.split_views) their split's backward joins them without a copy."""
+    d = torch.empty(2 * B, F, dtype=torch.float32, device=X.device)
+    return d[:B], d[B:]
+
+
+class _InfoNCELoss(torch.autograd.Function):
+    """(CE(X Y^T / T, arange B) + CE(Y X^T / T, arange B)) / 2 (pretrain_GeoSSL.py:141-176) on csrc/contrastive.hip:
+    -> (loss fp32 scalar, counts int32 [2] = rows / columns whose first argmax is the diagonal)."""
+
+    @staticmethod
+    def forward(ctx, X, Y, inv_t):
+        X, Y = _f32(X), _f32(Y)
+        B, F = X.shape
+        dev = X.device
+        stats = torch.empty(5 * B, dtype=torch.float32, device=dev)
+        amax = torch.empty(2 * B, dtype=torch.int32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        counts = torch.empty(2, dtype=torch.int32, device=dev)
+        call("geossl_infonce_fwd", ptr(X), ptr(Y), B, F, float(inv_t), ptr(stats), ptr(amax), ptr(loss), ptr(counts),
+             stream())
+        ctx.save_for_backward(X, Y, stats, amax)
+        ctx.inv_t = float(inv_t)
+        ctx.mark_non_differentiable(counts)
+        return loss, counts
+
+    @staticmethod
+    def backward(ctx, gout, _gcounts):
+        X, Y, stats, amax = ctx.saved_tensors
+        B, F = X.shape
+        dX, dY = _pair_grads(X, Y, B, F)
+        g = gout.to(torch.float32).contiguous()
+        call("geossl_infonce_bwd", ptr(X), ptr(Y), ptr(stats), ptr(amax), B, F, ctx.inv_t, ptr(g), ptr(dX), ptr(dY),
+             stream())
+        return dX, dY, None
+
+
+class _EBMNCELoss(torch.autograd.Function):
+    """EBM-NCE (pretrain_GeoSSL.py:103-138) on csrc/contrastive.hip: the positive pair <x_i, y_i> and num_neg negatives
+    <x_i, y_{(i+k) mod B}> through BCEWithLogitsLoss in fp64 -> (loss fp64 scalar, counts int32 [2] = {pos > 0, neg < 0})."""
+
+    @staticmethod
+    def forward(ctx, X, Y, num_neg):
+        X, Y = _f32(X), _f32(Y)
+        B, F = X.shape
+        dev = X.device
+        pred = torch.empty(B, num_neg + 1, dtype=torch.float32, device=dev)
+        terms = torch.empty(B, dtype=torch.float64, device=dev)
+        hits = torch.empty(2 * B, dtype=torch.int32, device=dev)
+        loss = torch.empty((), dtype=torch.float64, device=dev)
+        counts = torch.empty(2, dtype=torch.int32, device=dev)
+        call("geossl_ebm_nce_fwd", ptr(X), ptr(Y), B, F, int(num_neg), ptr(pred), ptr(terms), ptr(hits), ptr(loss),
+             ptr(counts), stream())
+        ctx.save_for_backward(X, Y, pred)
+        ctx.num_neg = int(num_neg)
+        ctx.mark_non_differentiable(counts)
+        return loss, counts
+
+    @staticmethod
+    def backward(ctx, gout, _gcounts):
+        X, Y, pred = ctx.saved_tensors
+        B, F = X.shape
+        dX, dY = _pair_grads(X, Y, B, F)
+        g = gout.to(torch.float64).contiguous()
+        call("geossl_ebm_nce_bwd", ptr(X), ptr(Y), ptr(pred), B, F, ctx.num_neg, ptr(g), ptr(dX), ptr(dY), stream())
+        return dX, dY, None
+
+
+def _check_pair(X, Y):
+    _lib.require_cuda(X, Y)
+    if X.dim() != 2 or X.shape != Y.shape or X.size(0) < 1:
+        raise ValueError("X and Y are [B, F] readouts of the two views with B >= 1, got %s and %s"
+                         % (tuple(X.shape), tuple(Y.shape)))
+
+
+def infonce_loss(X, Y, T):
+    """InfoNCE of two views' readouts (pretrain_GeoSSL.py:141-176, CE_criterion = nn.CrossEntropyLoss()) ->
+    (loss, counts): counts [2] int32 on the device, the reference's acc = (counts[0] / B + counts[1] / B) / 2."""
+    _check_pair(X, Y)
+    return _InfoNCELoss.apply(X, Y, 1.0 / float(T))
+
+
+def ebm_nce_loss(X, Y, num_neg=1):
+    """EBM-NCE of two views' readouts (pretrain_GeoSSL.py:103-138, criterion = nn.BCEWithLogitsLoss()) ->
+    (loss float64, counts): counts [2] int32 on the device, acc = (counts[0] + counts[1]) / (B (1 + num_neg))."""
+    _check_pair(X, Y)
+    num_neg = int(num_neg)
+    if not 1 <= num_neg <= X.size(0):
+        # (cycle_index(B, k) of examples/util.py:19-22 fails for k > B: the reference cannot run such a step either)
+        raise ValueError("num_neg must lie in [1, B] (B = %d), got %d" % (X.size(0), num_neg))
+    return _EBMNCELoss.apply(X, Y, num_neg)

@@ -386,13 +386,16 @@ class StepGraphs:
     ``mode="structure"``: per-structure graphs only, captured at the first sighting (pre-collated, device-resident
     batches that come back every epoch)."""
 
-    def __init__(self, fwd_bwd, model_3d, max_graphs=256, split=None, mode="auto", normalize=False, modules=None):
+    def __init__(self, fwd_bwd, model_3d, max_graphs=256, split=None, mode="auto", normalize=False, modules=None,
+                 noise_keys=None):
         # split = (fwd(batch, noise) -> loss with its autograd graph, bwd(loss)): forward and backward captured as TWO
         # graphs (same pool, same capture stream; replayed in this order) - the forward's loss is then on the device
         # before the backward runs, and the backward can run on a side stream while the host goes on (_AutogradStep)
         self.fwd_bwd, self.model_3d, self.max_graphs, self.split = fwd_bwd, model_3d, max_graphs, split
         self.mode, self.normalize = mode, normalize
-        self.modules = modules  # (backbone, head, head): what bucket.modules_ok looks at
+        self.modules = modules  # (backbone, head, head): what bucket.modules_ok looks at (None: no capacity buckets)
+        # the random draws a step takes as static inputs (the contrastive objectives: the position noise only)
+        self.noise_keys = _NOISE_KEYS if noise_keys is None else tuple(noise_keys)
         self.graphs, self.pool = OrderedDict(), None
         self.enabled = True
         self.captures = 0
@@ -502,7 +505,7 @@ class StepGraphs:
         sb = Batch(batch.x.clone(), batch.positions.clone(), batch.batch, batch.super_edge_index,
                    getattr(batch, "radius_edge_index", None), batch.num_graphs, getattr(batch, "_sizes", None),
                    getattr(batch, "_canonical", None))
-        sn = {k: noise[k].clone() for k in _NOISE_KEYS}
+        sn = {k: noise[k].clone() for k in self.noise_keys}
         g = self._capture(sb, sn)
         if g is not None:
             self.graphs[fp] = g
@@ -540,6 +543,7 @@ class StepGraphs:
               "dist_noise_2": torch.zeros(bkt.S_cap, 1, **f32),
               "noise_level_1": torch.zeros(B, dtype=torch.long, device=dev),
               "noise_level_2": torch.zeros(B, dtype=torch.long, device=dev)}
+        sn = {k: sn[k] for k in self.noise_keys}
         g0 = dict(bucket=bkt, noise=sn, counts=counts)
         self.copy_noise(g0, noise)
         g = self._capture(bkt.batch, sn)
@@ -579,15 +583,20 @@ class StepGraphs:
         gc.disable()
         _OWN_CAPTURE[0] += 1   # (the owner's passes leave the gradient buffer to `refresh` only inside THIS capture)
         try:
+            extra = None   # an owner's forward may return (loss, extra): extra = static outputs beside the loss
             if self.split is None:
                 with torch.cuda.graph(graph, pool=self.pool, capture_error_mode="thread_local"):
                     loss = self.fwd_bwd(sb, sn)
+                if isinstance(loss, tuple):
+                    loss, extra = loss
                 if self.pool is None:
                     self.pool = graph.pool()
             else:
                 cap = torch.cuda.Stream()  # both captures on ONE stream: autograd runs a node's backward where its forward ran
                 with torch.cuda.graph(graph, pool=self.pool, stream=cap, capture_error_mode="thread_local"):
                     live = self.split[0](sb, sn)
+                if isinstance(live, tuple):
+                    live, extra = live
                 if self.pool is None:
                     self.pool = graph.pool()
                 graph_bwd = torch.cuda.CUDAGraph()
@@ -608,7 +617,8 @@ class StepGraphs:
         if timing is not None:
             print("capture timing (ms):", ", ".join("%s %.1f" % (n, 1e3 * (t - timing[i][1])) for i, (n, t) in enumerate(timing[1:])))
         self.captures += 1
-        return dict(graph=graph, graph_bwd=graph_bwd, batch=sb, noise=sn, loss=loss, zero=self.zero_with_refresh)
+        return dict(graph=graph, graph_bwd=graph_bwd, batch=sb, noise=sn, loss=loss, zero=self.zero_with_refresh,
+                    extra=extra)
 
     # ---- per-step refresh of a graph's static inputs
     @staticmethod
@@ -620,14 +630,13 @@ class StepGraphs:
             return g["noise"]
         N, P, S, W = g["counts"]
         sn = g["noise"]
-        return {"pos_noise": sn["pos_noise"][:N], "dist_noise_1": sn["dist_noise_1"][:S],
-                "dist_noise_2": sn["dist_noise_2"][:S], "noise_level_1": sn["noise_level_1"],
-                "noise_level_2": sn["noise_level_2"]}
+        rows = {"pos_noise": N, "dist_noise_1": S, "dist_noise_2": S}   # (the noise levels are per molecule: B is exact)
+        return {k: (v[:rows[k]] if k in rows else v) for k, v in sn.items()}
 
     @staticmethod
     def copy_noise(g, noise):
         into = StepGraphs.noise_views(g)
-        for k in _NOISE_KEYS:
+        for k in into:   # (the graph's own draws: all five of a DDM step)
             into[k].copy_(noise[k].view_as(into[k]))
 
     @staticmethod
@@ -848,14 +857,17 @@ class _AutogradStep:
     land in a flat static buffer (the parameters' .grad point into it only while a step is captured); a step whose
     backward() has not been called when the next step arrives keeps a snapshot of them."""
 
-    def __init__(self, model, n1, n2):
+    def __init__(self, model, n1, n2, objective="DDM"):
         from .NCSN import _head_params
         self.model, self.n1, self.n2 = model, n1, n2
+        # "DDM" (two NCSN heads), or "InfoNCE" / "EBM_NCE": no heads (n1 = n2 = None), the readout is part of the step
+        self.objective = objective
+        heads = [m for m in (n1, n2) if m is not None]
         # the parameters the step reaches (a parameter outside it - an atomref table, PaiNN's output layers - gets no
         # gradient at all, like in the eager path, not a zero one)
         backbone = model._params() if hasattr(model, "_params") else _schnet_step_params(model)
         seen, self.params = set(), []
-        for p in list(backbone) + _head_params(n1) + _head_params(n2):
+        for p in list(backbone) + [q for h in heads for q in _head_params(h)]:
             if id(p) not in seen and p.requires_grad:
                 seen.add(id(p))
                 self.params.append(p)
@@ -876,7 +888,7 @@ class _AutogradStep:
         # where every parameter of the three modules hangs (submodule, name) with its object, address and grad flag:
         # `unchanged()` compares them per call without walking the module trees
         self._where = []
-        for m in (self.model, self.n1, self.n2):
+        for m in [self.model] + heads:
             seen_mod = set()
             for sub in m.modules():
                 if id(sub) in seen_mod:
@@ -910,6 +922,8 @@ class _AutogradStep:
 
     def _fwd(self, batch, noise):
         args, mu, sigma = self._cfg
+        if self.objective != "DDM":   # -> (loss, counts): the counts are a static output of the forward graph
+            return _contrastive_eager(self.objective, args, batch, self.model, mu, sigma, noise, True)
         return _do_ddm_eager(args, batch, self.model, mu, sigma, (self.n1, self.n2), noise, True, True)
 
     def _bwd(self, loss):
@@ -941,6 +955,9 @@ class _AutogradStep:
 
     def _fwd_bwd(self, batch, noise):
         loss = self._fwd(batch, noise)
+        if isinstance(loss, tuple):
+            self._bwd(loss[0])
+            return loss[0].detach(), loss[1]
         self._bwd(loss)
         return loss.detach()
 
@@ -977,18 +994,29 @@ class _AutogradStep:
         return True
 
     def run(self, args, batch, mu, sigma, noise, device_noise):
+        """-> the loss (DDM) / (loss, counts as a host list) (contrastive), or None: run this step eagerly."""
         if getattr(batch, "_dataset", None) is None and (not batch.positions.is_cuda or batch.positions.requires_grad):
             return None
-        key = (args.model_3d, bool(getattr(args, "normalize", False)))
+        contrastive = self.objective != "DDM"
+        normalize = bool(getattr(args, "normalize", False))
+        if contrastive:   # (a graph binds T and num_neg: by-value arguments of its loss launches)
+            cargs = ContrastiveArgs(args.model_3d, normalize, getattr(args, "T", 0.1), getattr(args, "num_neg", 1))
+            key = (self.objective, args.model_3d, normalize, cargs.T, cargs.num_neg)
+        else:
+            key = (args.model_3d, normalize)
         sg = self.graphs.get(key)
         if sg is None:
+            # contrastive steps: capacity buckets with no heads (their row normalisation is over the 2B readout rows, an
+            # exact count: `normalize` does not keep them off buckets), one static draw
             sg = self.graphs[key] = StepGraphs(self._fwd_bwd, args.model_3d, split=(self._fwd, self._bwd),
-                                               mode=getattr(args, "step_graph_mode", "auto"), normalize=key[1],
-                                               modules=(self.model, self.n1, self.n2))
+                                               mode=getattr(args, "step_graph_mode", "auto"),
+                                               normalize=normalize and not contrastive,
+                                               modules=(self.model, self.n1, self.n2),
+                                               noise_keys=("pos_noise",) if contrastive else None)
             sg.zero_with_refresh = self.gflat
         if not sg.enabled:
             return None
-        self._cfg = (Args(args.model_3d, key[1]), mu, sigma)
+        self._cfg = (cargs if contrastive else Args(args.model_3d, normalize), mu, sigma)
         g = sg.lookup(batch)
         if g is None and not sg.capture_now(batch):
             # first sighting of an index structure that only its own graph can serve (sampled tuples, PaiNN edge lists,
@@ -1004,7 +1032,10 @@ class _AutogradStep:
             if t is not None and t["g"] is None and not t.get("used"):
                 t["g"] = self.gflat.clone()  # a step still waiting for its backward() keeps its gradients
         if g is None:
-            drawn = draw_step_noise(batch, self.n1, self.n2, mu, sigma, device_noise, noise)
+            if contrastive:
+                drawn = draw_views_noise(batch, mu, sigma, device_noise, noise)
+            else:
+                drawn = draw_step_noise(batch, self.n1, self.n2, mu, sigma, device_noise, noise)
             g = sg.capture(batch, drawn)
             if g is None:
                 return None
@@ -1013,7 +1044,10 @@ class _AutogradStep:
         else:
             if not sg.refresh(g, batch):
                 return None  # (the bucket refused the batch's tensors: this step as eager launches)
-            draw_step_noise(batch, self.n1, self.n2, mu, sigma, device_noise, noise, into=sg.noise_views(g))
+            if contrastive:
+                draw_views_noise(batch, mu, sigma, device_noise, noise, into=sg.noise_views(g))
+            else:
+                draw_step_noise(batch, self.n1, self.n2, mu, sigma, device_noise, noise, into=sg.noise_views(g))
         g["graph"].replay()            # forward: the loss is on the device when this is done
         loss = g["loss"].clone()
         fwd_done = torch.cuda.Event()
@@ -1042,6 +1076,10 @@ class _AutogradStep:
             st.arm(every=8)
         out = _ReplayedLoss.apply(loss, self, self._ticket, *self.params).as_subclass(_StepLoss)
         out._geossl_step = (self, self._ticket)
+        if contrastive:
+            # the accuracy counts, read once the backward replay is queued: the host waits for the forward only (the
+            # reference's own acc is a host value too, :137 / :170)
+            return out, g["extra"].tolist()
         return out
 
 
@@ -1216,3 +1254,262 @@ class DDMTrainer:
         scale = self.reduce()
         self.opt.step(grad_scale=scale)
         return loss
+
+
+# ---- the contrastive objectives: --GeoSSL_option=InfoNCE / EBM_NCE (pretrain_GeoSSL.py:103-176) -----------------------
+# The reference's do_InfoNCE reads the module global CE_criterion (:165, :345) and ignores its `criterion` argument;
+# do_EBM_NCE applies `criterion` (the loop passes nn.BCEWithLogitsLoss(), :344).  A caller may replace CE_criterion like
+# NCSN_model_01/02; a criterion other than the stock one runs on the eager fallback (_contrastive_with_criterion).
+CE_criterion = torch.nn.CrossEntropyLoss()
+
+CONTRASTIVE_OPTIONS = ("InfoNCE", "EBM_NCE")
+
+
+class ContrastiveArgs:
+    """The fields do_InfoNCE / do_EBM_NCE read from the reference's argparse namespace (examples/config.py:171-172: T
+    0.1, normalize off) plus num_neg, which the reference passes as an argument."""
+
+    def __init__(self, model_3d="schnet", normalize=False, T=0.1, num_neg=1):
+        self.model_3d, self.normalize, self.T, self.num_neg = model_3d, bool(normalize), float(T), int(num_neg)
+
+
+def _stock_ce(c):
+    """nn.CrossEntropyLoss() as the reference builds it (:345): what the InfoNCE kernels compute."""
+    return (type(c) is torch.nn.CrossEntropyLoss and c.weight is None and c.reduction == "mean"
+            and float(c.label_smoothing) == 0.0 and c.ignore_index < 0)
+
+
+def _stock_bce(c):
+    """nn.BCEWithLogitsLoss() as the reference builds it (:344), or None: what the EBM-NCE kernels compute."""
+    return c is None or (type(c) is torch.nn.BCEWithLogitsLoss and c.weight is None and c.pos_weight is None
+                         and c.reduction == "mean")
+
+
+def draw_views_noise(batch, mu, sigma, device_noise, given=None, into=None):
+    """The one random draw of a contrastive step, perturb's (pretrain_GeoSSL.py:72): a host draw copied to the device, or
+    a device draw with device_noise; `given["pos_noise"]` instead of drawing; `into`: written into those tensors."""
+    given = given or {}
+    src = given.get("pos_noise")
+    if into is not None:
+        t_ = into["pos_noise"]
+        if src is not None:
+            t_.copy_(src.view_as(t_))
+        elif device_noise:
+            t_.normal_(mu, sigma)
+        else:
+            _host_normal_into(t_, mu, sigma)
+        return into
+    if src is None:
+        if device_noise:
+            src = torch.empty_like(batch.positions).normal_(mu, sigma)
+        else:
+            src = torch.normal(mu, sigma, size=batch.positions.size()).to(batch.positions.device)
+    return {"pos_noise": src}
+
+
+def _contrastive_views(args, batch, model, mu, sigma, noise, device_noise):
+    """The readouts of both views (:117-118 / :150-156 with perturb, :68-74) -> (X, Y), each [B, F]: the two views as one
+    fused 2B-molecule batch through the backbone (molecules never interact: every row sees the arithmetic of two
+    separate calls), the readout of all 2B molecules, the row normalisation of --normalize, then the split."""
+    if args.model_3d not in ("schnet", "painn"):
+        raise Exception("3D model {} not included.".format(args.model_3d))
+    noise = noise or {}
+    positions = batch.positions
+    x_01 = batch.x[:, 0]
+    pos_noise = draw_views_noise(batch, mu, sigma, device_noise, noise)["pos_noise"]
+    B = batch.num_graphs
+    bucket = getattr(batch, "_bucket", None)
+    if bucket is not None:
+        # the static batch of a capacity bucket: atom rows at the bucket's capacity (real counts in bucket.dyn, view 1 at
+        # row dims[N]); the two-view mol_ptr holds the real offsets of all 2B molecules, so the readout over bucket.lay2
+        # and everything after it (2B rows) see exact counts
+        if args.model_3d != bucket.kind:
+            raise _lib.GeosslHipError("capacity buckets serve the fused step of the backbone they were made for")
+        pos2, x2 = ops.two_views(positions, pos_noise, x_01, dyn=bucket.dyn)
+        if bucket.kind == "schnet":
+            h = model(x2, pos2, bucket.b2, layout=bucket.lay2)
+        else:
+            h = model(x2, pos2, bucket.e2, bucket.b2, layout=bucket.lay2, edge_layout=bucket.el)
+        if getattr(args, "normalize", False):
+            h = ops.row_normalize(h)
+        return split_views(h, B)
+    pos2, x2 = ops.two_views(positions, pos_noise, x_01)
+    if args.model_3d == "schnet":
+        b2, lay2 = _two_view_batch(batch.batch, B)
+        h = model(x2, pos2, b2, layout=lay2)
+    else:
+        b2, e2 = _two_view_edges(batch.batch, batch.radius_edge_index, B)
+        h = model(x2, pos2, e2, b2)
+    if getattr(args, "normalize", False):   # F.normalize(dim=-1) is per row: the 2B rows at once
+        h = ops.row_normalize(h)
+    return split_views(h, B)
+
+
+def _contrastive_eager(objective, args, batch, model, mu, sigma, noise, device_noise):
+    """The step as eager launches -> (loss, counts [2] int32 on the device)."""
+    X, Y = _contrastive_views(args, batch, model, mu, sigma, noise, device_noise)
+    if objective == "InfoNCE":
+        return ops.infonce_loss(X, Y, getattr(args, "T", 0.1))
+    return ops.ebm_nce_loss(X, Y, getattr(args, "num_neg", 1))
+
+
+def contrastive_acc(objective, counts, B, num_neg=1):
+    """The reference's acc from the two counts: InfoNCE (:170-175) a mean of two Python floats, EBM-NCE (:136-137) an
+    fp32 tensor division turned into a Python float."""
+    c0, c1 = int(counts[0]), int(counts[1])
+    if objective == "InfoNCE":
+        return (c0 * 1. / B + c1 * 1. / B) / 2
+    return float(np.float32(c0 + c1) / np.float32(B * (1 + num_neg)))
+
+
+def _contrastive_with_criterion(objective, args, batch, model, criterion, mu, sigma, num_neg, noise, device_noise):
+    """A criterion other than the stock one (weights, pos_weight, label smoothing, another reduction, a subclass): the
+    caller's criterion applied to our backbone's readouts in ATen, exactly as the reference writes the loss.  Correct, not
+    fast: no graph, no loss kernel."""
+    X, Y = _contrastive_views(args, batch, model, mu, sigma, noise, device_noise)
+    B = X.size(0)
+    dev = X.device
+    if objective == "InfoNCE":
+        T = getattr(args, "T", 0.1)
+        labels = torch.arange(B).long().to(dev)
+
+        def cal_loss(A, Bm):
+            logits = torch.div(torch.mm(A, Bm.transpose(1, 0)), T)
+            pred = logits.argmax(dim=1, keepdim=False)
+            return criterion(logits, labels), pred.eq(labels).sum().detach().cpu().item() * 1. / B
+        l1, a1 = cal_loss(X, Y)
+        l2, a2 = cal_loss(Y, X)
+        return (l1 + l2) / 2, (a1 + a2) / 2
+    if not 1 <= num_neg <= B:
+        raise ValueError("num_neg must lie in [1, B] (B = %d), got %d" % (B, num_neg))
+    shift = lambda k: (torch.arange(B) + k) % B   # cycle_index(B, k), examples/util.py:19-22
+    X_neg = X.repeat((num_neg, 1))
+    Y_neg = torch.cat([Y[shift(k + 1).to(dev)] for k in range(num_neg)], dim=0)
+    pred_pos = torch.sum(X * Y, dim=1)
+    pred_neg = torch.sum(X_neg * Y_neg, dim=1)
+    loss_pos = criterion(pred_pos.double(), torch.ones(B).to(dev).double())
+    loss_neg = criterion(pred_neg.double(), torch.zeros(B * num_neg).to(dev).double())
+    loss = (loss_pos + num_neg * loss_neg) / (1 + num_neg)
+    acc = (torch.sum(pred_pos > 0).float() + torch.sum(pred_neg < 0).float()) / (len(pred_pos) + len(pred_neg))
+    return loss, acc.detach().item()
+
+
+def _contrastive_step(model, objective):
+    """The _AutogradStep of (backbone, objective), kept on the backbone module beside the DDM one; rebuilt when a parameter
+    was replaced, moved or frozen since (the graphs bind parameter addresses)."""
+    name = "_geossl_contrastive_step_" + objective
+    eng = model.__dict__.get(name)
+    if eng is None or not eng.unchanged():
+        eng = _AutogradStep(model, None, None, objective=objective)
+        model.__dict__[name] = eng
+    return eng
+
+
+def _do_contrastive(objective, args, batch, model, criterion, mu, sigma, num_neg, noise, device_noise, graph):
+    stock = _stock_ce(CE_criterion) if objective == "InfoNCE" else _stock_bce(criterion)
+    if not stock:
+        crit = CE_criterion if objective == "InfoNCE" else criterion
+        return _contrastive_with_criterion(objective, args, batch, model, crit, mu, sigma, num_neg, noise, device_noise)
+    cargs = ContrastiveArgs(args.model_3d, getattr(args, "normalize", False), getattr(args, "T", 0.1), num_neg)
+    if graph is None:
+        graph = getattr(args, "step_graph", _env("GEOSSL_NO_STEP_GRAPH") is None)
+    if graph and torch.is_grad_enabled() and not torch.cuda.is_current_stream_capturing():
+        cargs.step_graph_mode = getattr(args, "step_graph_mode", "auto")
+        out = _contrastive_step(model, objective).run(cargs, batch, mu, sigma, noise, device_noise)
+        if out is not None:
+            loss, counts = out
+            return loss, contrastive_acc(objective, counts, batch.num_graphs, num_neg)
+    loss, counts = _contrastive_eager(objective, cargs, batch, model, mu, sigma, noise, device_noise)
+    return loss, contrastive_acc(objective, counts.tolist(), batch.num_graphs, num_neg)
+
+
+def do_InfoNCE(args, batch, model, criterion=None, mu=0.0, sigma=0.3, num_neg=1, noise=None, device_noise=False,
+               graph=None):
+    """pretrain_GeoSSL.py:141-176 -> (loss, acc): loss an fp32 scalar tensor, acc a Python float.  `criterion` and
+    `num_neg` are ignored like in the reference (it uses the module global CE_criterion).  noise: optional
+    {"pos_noise": [N, 3]}; device_noise / graph as in do_DDM (graph: HIP graphs of forward + backward, capacity buckets included)."""
+    return _do_contrastive("InfoNCE", args, batch, model, criterion, mu, sigma, num_neg, noise, device_noise, graph)
+
+
+def do_EBM_NCE(args, batch, model, criterion=None, mu=0.0, sigma=0.3, num_neg=1, noise=None, device_noise=False,
+               graph=None):
+    """pretrain_GeoSSL.py:103-138 -> (loss, acc): loss a float64 scalar tensor, acc a Python float.  criterion: None or
+    the reference's nn.BCEWithLogitsLoss() run on the kernels; any other criterion on the eager fallback."""
+    return _do_contrastive("EBM_NCE", args, batch, model, criterion, mu, sigma, int(num_neg), noise, device_noise,
+                           graph)
+
+
+class ContrastiveTrainer:
+    """The body of ``train()`` (pretrain_GeoSSL.py:234-260) for --GeoSSL_option InfoNCE / EBM_NCE: forward of both views,
+    readout, contrastive loss, backward, gradient all-reduce, Adam - all parameters in one flat buffer (one fused Adam
+    launch, one all-reduce), like DDMTrainer.  ``step(batch) -> (loss, counts)``: both device tensors, no host sync
+    (contrastive_acc turns the counts into the reference's acc).  ``use_graph=True``: forward + backward of a batch
+    structure are captured into a HIP graph and replayed (StepGraphs: ragged batches and DeviceLoader handles share one
+    capacity-bucket graph per batch size, gathered into its static inputs on the device; the position noise drawn into
+    them)."""
+
+    def __init__(self, model, option="InfoNCE", lr=5e-4, weight_decay=0.0, mu=0.0, sigma=0.3, T=0.1, num_neg=1,
+                 normalize=False, model_3d="schnet", device_noise=True, use_graph=False, max_graphs=256,
+                 graph_mode="auto"):
+        from .optim import FlatParams, FusedAdam
+        from .parallel import GradAllReduce
+        if option not in CONTRASTIVE_OPTIONS:
+            raise ValueError("option is one of %s" % (CONTRASTIVE_OPTIONS,))
+        self.model, self.option = model, option
+        self.args = ContrastiveArgs(model_3d, normalize, T, num_neg)
+        self.mu, self.sigma = mu, sigma
+        self.device_noise = device_noise
+        self.flat = FlatParams([model])
+        self.opt = FusedAdam(self.flat, lr=lr, weight_decay=weight_decay)
+        self.reduce = GradAllReduce(self.flat.grad)
+        self.use_graph = use_graph
+        # (capacity buckets with no heads; `normalize` is over the 2B readout rows and does not keep a batch off them)
+        self.step_graphs = StepGraphs(self._fwd_bwd, model_3d, max_graphs, mode=graph_mode, modules=(model, None, None),
+                                      noise_keys=("pos_noise",))
+        self.step_graphs.zero_with_refresh = self.flat.grad
+        dev = self.flat.grad.device
+        self._one = torch.ones((), dtype=torch.float64 if option == "EBM_NCE" else torch.float32, device=dev)
+
+    def _fwd_bwd(self, batch, noise):
+        if not own_capture_open():
+            self.flat.zero_grad()  # (a replayed step: cleared with the refresh of the graph's inputs, StepGraphs.refresh)
+        if noise is None:
+            noise = draw_views_noise(batch, self.mu, self.sigma, self.device_noise)
+        loss, counts = _contrastive_eager(self.option, self.args, batch, self.model, self.mu, self.sigma, noise,
+                                          self.device_noise)
+        with _lib.direct_grads():  # every p.grad is a view of self.flat.grad: kernels accumulate into it directly
+            loss.backward(self._one)
+        self.flat.rebind_grads()
+        return loss.detach(), counts
+
+    def _graph_fwd_bwd(self, batch, noise):
+        sg = self.step_graphs
+        g = sg.lookup(batch)
+        if g is None:
+            if not sg.capture_now(batch):  # a structure seen for the first time: eager
+                return self._fwd_bwd(batch, noise)
+            noise = draw_views_noise(batch, self.mu, self.sigma, self.device_noise, noise)
+            g = sg.capture(batch, noise)
+            if g is None:  # capture failed: eager from now on
+                self.use_graph = False
+                return self._fwd_bwd(batch, noise)
+        if not sg.refresh(g, batch, noise):
+            return self._fwd_bwd(batch, noise)
+        if noise is None:   # the step's own draw straight into the graph's static input
+            draw_views_noise(g["batch"], self.mu, self.sigma, self.device_noise, into=g["noise"])
+        g["graph"].replay()
+        return g["loss"].clone(), g["extra"].clone()
+
+    def step(self, batch, noise=None):
+        """One training step -> (loss, counts) on the device."""
+        if self.use_graph and (noise is not None or self.device_noise):
+            loss, counts = self._graph_fwd_bwd(batch, noise)
+        else:
+            loss, counts = self._fwd_bwd(batch, noise)
+        st = self.model.__dict__.get("_geossl_status")
+        if st is not None:  # deferred index check of the backbone (a replayed graph cannot queue the host copy itself)
+            st.poll()
+            st.arm(every=8)
+        scale = self.reduce()
+        self.opt.step(grad_scale=scale)
+        return loss, counts

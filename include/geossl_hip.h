@@ -764,6 +764,27 @@ typedef struct GeosslMask {
 } GeosslMask;
 int geossl_gather_masked_molecules(const GeosslGather* g, const GeosslMask* mask, int64_t B, hipStream_t stream);
 
+/* ---- contrastive heads: pretrain_GeoSSL.py --GeoSSL_option=InfoNCE / EBM_NCE (:103-176) -----------------------------
+ * X, Y [B][F]: the readouts of the two views (row-major fp32).  No atomics: the same inputs give the same bits.
+ * InfoNCE (:141-176), S = X Y^T * inv_t (inv_t = 1 / args.T), loss = (CE(S, arange(B)) + CE(S^T, arange(B))) / 2:
+ *   stats [5B] (out) = {max m of every row [B] and column [B], l = log1p(sum of exp(S - m) over all but the first
+ *   maximum) of every row [B] and column [B], diagonal S_ii [B]}: lse = m + l; amax [2B] (out) first-index argmax of
+ *   every row and column - both the backward's input; loss [1]; counts [2] = {rows with argmax i, columns with argmax
+ *   j} (the reference's acc = (counts[0] / B + counts[1] / B) / 2).
+ *   Backward: G = exp(S - lse_row) + exp(S - lse_col) - 2 I; dX = G Y, dY = G^T X, both * gout[0] * inv_t / (2B). */
+int geossl_infonce_fwd(const float* X, const float* Y, int64_t B, int F, float inv_t, float* stats, int32_t* amax,
+                       float* loss, int32_t* counts, hipStream_t stream);
+int geossl_infonce_bwd(const float* X, const float* Y, const float* stats, const int32_t* amax, int64_t B, int F,
+                       float inv_t, const float* gout, float* dX, float* dY, hipStream_t stream);
+/* EBM-NCE (:103-138, cycle_index examples/util.py:19-22), 1 <= num_neg <= B: pred [B][1 + num_neg] (out, the backward's
+ * input) = <x_i, y_i>, <x_i, y_{(i+k) mod B}> in fp32; BCEWithLogits in fp64: terms [B], hits [2B] workspaces;
+ * loss [1] (double) = (mean softplus(-pos) + num_neg mean softplus(neg)) / (1 + num_neg); counts [2] = {pos > 0, neg < 0}.
+ * Backward with the fp64 upstream gradient gout[0]: dpred cast to fp32, dX / dY gathered from the neighbour rows. */
+int geossl_ebm_nce_fwd(const float* X, const float* Y, int64_t B, int F, int num_neg, float* pred, double* terms,
+                       int32_t* hits, double* loss, int32_t* counts, hipStream_t stream);
+int geossl_ebm_nce_bwd(const float* X, const float* Y, const float* pred, int64_t B, int F, int num_neg,
+                       const double* gout, float* dX, float* dY, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
