@@ -752,7 +752,7 @@ def test_schnet_latent_only_skips_the_readout():
 
 
 # ------------------------------------------------------------------- two-fp16-piece kernels: scales and accuracy
-def _filter_problem(nmol, seed, F=128, G=51, L=2, cutoff=5.0):
+def _filter_problem(nmol, seed, F=128, G=51, L=2, cutoff=5.0, mode="B"):
     """A two-layer filter-network problem on synthetic molecules, through the raw C ABI: returns the tensors the
     backward kernel consumes and an fp64 evaluation of what it must produce (schnet.py:141-145,186-195 differentiated
     w.r.t. the filter weights)."""
@@ -762,7 +762,7 @@ def _filter_problem(nmol, seed, F=128, G=51, L=2, cutoff=5.0):
     from geossl_amd._lib import call, ptr, stream
     from geossl_amd.layout import MolLayout
     from geossl_amd.synthetic import make_batch
-    b = make_batch(nmol, seed=seed, mode="B")
+    b = make_batch(nmol, seed=seed, mode=mode)
     sizes = [int(n) for n in b["sizes"]]
     batch = torch.arange(len(sizes), device=DEV).repeat_interleave(torch.tensor(sizes, device=DEV))
     lay = MolLayout(batch, len(sizes), sizes=sizes)
@@ -783,17 +783,20 @@ def _filter_problem(nmol, seed, F=128, G=51, L=2, cutoff=5.0):
     T = torch.empty(L, P, F, device=DEV)
     call("geossl_cfconv_filter_fwd", ptr(pair_d), ptr(pair_c), P, C.byref(fw), L, F, G, ptr(offset), coeff, ptr(T), ptr(Wf), stream())
 
-    def run(daggs_):
+    def run(daggs_, saved_T=True, outs=None):
+        """saved_T=False: T = NULL, the kernel rebuilds the hidden rows (GEOSSL_FILTER_RECOMPUTE_T); `outs`: the output
+        tensors to write (else zeros)."""
         gin, gout = _lib.FilterGradIn(), _lib.FilterGradOut()
-        outs = [[torch.zeros(F, G, device=DEV), torch.zeros(F, device=DEV), torch.zeros(F, F, device=DEV), torch.zeros(F, device=DEV)]
-                for _ in range(L)]
+        if outs is None:
+            outs = [[torch.zeros(F, G, device=DEV), torch.zeros(F, device=DEV), torch.zeros(F, F, device=DEV),
+                     torch.zeros(F, device=DEV)] for _ in range(L)]
         for l in range(L):
             gin.x[l], gin.dagg[l] = ptr(xs[l]), ptr(daggs_[l])
             gout.dw1[l], gout.db1[l], gout.dw2[l], gout.db2[l] = (ptr(o) for o in outs[l])
         nfl = _lib.load().geossl_cfconv_filter_bwd_workspace_floats(P, L, F, G)
         wsp = torch.empty(nfl, device=DEV)
         call("geossl_cfconv_filter_bwd", ptr(pair_d), ptr(pair_c), ptr(pair_flag), ptr(lay.pair_i), ptr(lay.pair_j), P, N, C.byref(fw),
-             C.byref(gin), L, F, G, ptr(offset), coeff, ptr(T), C.byref(gout), ptr(wsp), 0, stream())
+             C.byref(gin), L, F, G, ptr(offset), coeff, ptr(T) if saved_T else None, C.byref(gout), ptr(wsp), 0, stream())
         torch.cuda.synchronize()
         return outs
 
@@ -813,6 +816,7 @@ def _filter_problem(nmol, seed, F=128, G=51, L=2, cutoff=5.0):
             outs.append([dU.t() @ rbf, dU.sum(0), dO.t() @ tt, dO.sum(0)])
         return outs
 
+    run.inputs = dict(pair_d=pair_d, pair_c=pair_c, pair_flag=pair_flag, ws=ws, xs=xs, offset=offset, coeff=coeff, P=P)
     return lay, daggs, run, ref64
 
 

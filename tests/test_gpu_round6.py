@@ -479,17 +479,44 @@ def test_g15_painn_variants_on_the_hip_path(tag):
     assert seen == sum(1 for k in g if k.startswith("gsum/")) and seen > 8
 
 
+_MU0_SIZES = {"setA": [18] * 1024, "setB": None, "setA2048": [18] * 2048,
+              "ragged": [2, 26, 1, 7, 18, 1, 12, 25, 3, 20, 9, 33, 18, 18, 17, 19] * 64}
+
+
 @pytest.mark.parametrize("R", [20, 8])
 def test_painn_first_interaction_with_mu_null_is_the_general_kernel_bit_for_bit(R):
     """geossl_painn_interaction_fwd_mma with mu = NULL (the first interaction: mu identically zero, painn.py:249) against the
     same call with a tensor of zeros, at the bench size (1024 molecules, every CU holds two blocks): q_out and mu_out
-    identical bit for bit, launch after launch.  The packed-fp32 build of this kernel failed exactly this test (a term of
-    mu_out's y component missing in lanes 48-63 of 5-10 atoms per launch, other atoms every launch)."""
+    identical bit for bit, launch after launch, and within 8 u S of fp64 per element.  The packed-fp32 build of this
+    kernel failed exactly this test (a term of mu_out's y component missing in lanes 48-63 of 5-10 atoms per launch, other
+    atoms every launch)."""
+    _mu_zero_case(R, "setA")
+
+
+@pytest.mark.parametrize("sizes", ["setB", "setA2048", "ragged"])
+@pytest.mark.parametrize("R", [20, 8])
+def test_painn_first_interaction_with_mu_null_at_more_batch_shapes(R, sizes):
+    """The same comparison (general kernel bit for bit, fp64 per element) on 1024 molecules of set B (one block per CU:
+    33-atom molecules), 2048 x 18 atoms (four molecules per persistent block) and a ragged batch of 1024 molecules
+    with 1- to 33-atom molecules."""
+    _mu_zero_case(R, sizes)
+
+
+def _mu_zero_case(R, sizes):
     from geossl_amd import _lib
+    from geossl_amd.synthetic import molecule_sizes
     from test_gpu_round3 import _painn_edge_case
-    c = _painn_edge_case([18] * 1024, seed=3, R=R)
+    import packed_opsel_registry as reg
+    from test_gpu_packed_kernels import U22, assert_occupancy, assert_within, painn_message64
+    sz = _MU0_SIZES[sizes] if _MU0_SIZES[sizes] is not None else [int(n) for n in molecule_sizes(1024, "B")]
+    c = _painn_edge_case(sz, seed=3, R=R)
     lay, el, N, Fd = c["lay"], c["el"], c["N"], 128
     c["mu"].zero_()
+    if sizes in ("setA", "setB"):   # (the registry's launches of k_painn_fwd_mma: 2 waves per SIMD on set A, 1 on set B)
+        lds = reg.painn_mma_lds(lay.max_n)
+        for mz in (0, 1):
+            assert_occupancy(r"k_painn_fwd_mmaILi%dELb%dE" % (R, mz), "R=%d set %s" % (R, sizes[-1]), lds=lds,
+                             grid=reg.painn_mma_grid(lay.B, lds))
     row_edge, grp_atom, _, mol_grp = el.groups("i", lay.mol_ptr)
 
     def run(mu):
@@ -509,6 +536,13 @@ def test_painn_first_interaction_with_mu_null_is_the_general_kernel_bit_for_bit(
         q, mu = run(None)
         assert torch.equal(q, q_ref), rep
         assert int((mu != mu_ref).sum()) == 0, (rep, int((mu != mu_ref).sum()))
+    # and both against fp64 element by element: |got - ref| <= 8 u S, u = 2^-22 (two-piece fp16 filter products), S the
+    # same sums over absolute values - a term missing from one atom's mu_out is far above that bound
+    x64 = {k: c[k].double() for k in ("q", "mu", "xc", "Wf", "bf", "phi", "fcut", "dirv")}
+    q64, mu64, _ = painn_message64(c, **x64)
+    Sq, Smu, _ = painn_message64(c, **{k: v.abs() for k, v in x64.items()})
+    assert_within(q_ref, q64, Sq, 8.0, U22, "q_out")
+    assert_within(mu_ref, mu64, Smu, 8.0, U22, "mu_out")
 
 
 def test_painn_step_with_the_mu_zero_shortcut_is_the_general_step_bit_for_bit(monkeypatch):
