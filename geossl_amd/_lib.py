@@ -243,6 +243,14 @@ PROTOTYPES = {
     "geossl_infonce_bwd": (i32, [vp, vp, vp, vp, i64, i32, f32, vp, vp, vp, vp]),
     "geossl_ebm_nce_fwd": (i32, [vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp]),
     "geossl_ebm_nce_bwd": (i32, [vp, vp, vp, i64, i32, i32, vp, vp, vp, vp]),
+    # distance-prediction head (csrc/distance_head.hip)
+    "geossl_distance_head_width_ok": (i32, [i32]),
+    "geossl_distance_head_fwd_workspace_floats": (i64, [i64]),
+    "geossl_distance_head_bwd_workspace_floats": (i64, [i64, i32]),
+    "geossl_distance_head_fwd": (i32, [vp, i64, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp]),
+    "geossl_distance_head_fwd_dyn": (i32, [vp, i64, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "geossl_distance_head_bwd": (i32, [vp, i64, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
+    "geossl_distance_head_bwd_dyn": (i32, [vp, i64, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]),
 }
 
 _lib = None

@@ -125,8 +125,8 @@ def sizes_array(batch):
     return arr
 
 
-def batch_counts(sizes, option):
-    """(atoms N, pair slots P, super-edges S, aggregation work items W of the two-view batch) of molecules `sizes`."""
+def batch_counts(sizes, option, views=2):
+    """(atoms N, pair slots P, super-edges S, aggregation work items W of the `views`-view batch) of molecules `sizes`."""
     global _PARTS
     if _PARTS is None:
         _PARTS = _parts_table()
@@ -134,7 +134,7 @@ def batch_counts(sizes, option):
     n = sizes if isinstance(sizes, np.ndarray) else np.asarray(sizes, dtype=np.int64)
     P = int((n * (n - 1) // 2).sum())
     S = P if option == "combination" else 2 * P
-    W = work_items_bound(np.concatenate([n, n]), aggregate_by_targets(2 * len(n)))   # (a bound: the list has 8 padded queues)
+    W = work_items_bound(np.concatenate([n] * views), aggregate_by_targets(views * len(n)))   # (a bound: 8 padded queues)
     return int(n.sum()), P, S, W
 
 
@@ -193,7 +193,8 @@ PAINN_SWITCHES = ("GEOSSL_PAINN_NO_CHAIN", "GEOSSL_PAINN_SILU_KERNELS")   # ... 
 def modules_ok(model, n1=None, n2=None):
     """The step of these modules can run on a bucket: the F = 128 chain path of SchNet / PaiNN (the chained row kernel is
     the one that takes a device-side row count) and the paired NCSN heads (two different modules of width 128).  No heads
-    (n1 = n2 = None): the contrastive steps, whose loss reads the readout of the 2B molecules - exact counts, no capacity."""
+    (n1 = n2 = None): the contrastive steps, whose loss reads the readout of the 2B molecules - exact counts, no capacity.
+    One DistancePredictor of width 2 * 128 (n2 = None): the Distance Prediction step on a one-view bucket."""
     import os
     from .Geom3D.models.painn import PaiNN
     from .Geom3D.models.schnet import SchNet
@@ -215,6 +216,9 @@ def modules_ok(model, n1=None, n2=None):
         return False
     if n1 is None and n2 is None:
         return True
+    from .pretrain_DistancePrediction import DistancePredictor, fused_head_ok
+    if isinstance(n1, DistancePredictor) and n2 is None:
+        return fused_head_ok(n1) and n1.predictor.in_features == 2 * 128
     if not (isinstance(n1, NCSN_version_03) and isinstance(n2, NCSN_version_03)) or n1 is n2 \
             or n1.emb_dim != 128 or n2.emb_dim != 128:
         return False
@@ -277,11 +281,12 @@ def edge_capacity(E, B, prev=None, sizes=None):
     return cap if prev is None else max(cap, int(prev))
 
 
-def host_plan(sizes, option):
+def host_plan(sizes, option, views=2):
     """Everything of a batch's index structures that is a function of the molecule sizes alone, as numpy arrays - the part
     of a bucket fill that runs on the host (and is tested without a GPU): counts (N, P, S, W); mol_ptr / pair_ptr of the
     TWO-VIEW batch ([2B + 1], view 1 behind view 0); se_ptr [B + 1]; the aggregation's work list over the 2B molecules
-    (largest first, stable; 27 .. 33-atom molecules as 2 or 4 items, larger ones one item per atom: molecule | part << 24); the divisor of NCSN.py:210-212
+    (largest first, stable; 27 .. 33-atom molecules as 2 or 4 items, larger ones one item per atom: molecule | part << 24;
+    over the B molecules of view 0 only when views = 1); the divisor of NCSN.py:210-212
     (last molecule with a super-edge, + 1); inc_ptr [N + 1] (an atom of an n-atom molecule lies on n - 1 tuples of the
     "combination" enumeration, 2 (n - 1) of "permutation")."""
     global _PARTS
@@ -289,16 +294,15 @@ def host_plan(sizes, option):
         _PARTS = _parts_table()
     n = sizes if isinstance(sizes, np.ndarray) else np.asarray(sizes, dtype=np.int64)
     B = n.shape[0]
-    N, P, S, W = batch_counts(n, option)
+    N, P, S, W = batch_counts(n, option, views)
     mult = 1 if option == "combination" else 2
     mp = np.zeros(B + 1, dtype=np.int64)
     np.cumsum(n, out=mp[1:])
     npair = n * (n - 1) // 2
     pp = np.zeros(B + 1, dtype=np.int64)
     np.cumsum(npair, out=pp[1:])
-    n2 = np.concatenate([n, n])
     from .layout import aggregate_by_targets, aggregate_work_list
-    work = aggregate_work_list(n2, aggregate_by_targets(2 * B))
+    work = aggregate_work_list(np.concatenate([n] * views), aggregate_by_targets(views * B))
     if work.size > W:
         raise ValueError("aggregation work list longer than its bound")   # (work_items_bound: cannot happen)
     has = np.nonzero(npair > 0)[0]
@@ -311,10 +315,18 @@ def host_plan(sizes, option):
 class Bucket:
     """kind "schnet": pair-slot structures of the two-view batch (pointer arrays and work list from the host, pair-slot
     atoms by geossl_pair_index_fill).  kind "painn": the structures of the batch's radius_edge_index for the two-view batch
-    (geossl_painn_edge_layout: one launch on the batch's own edge tensor, outputs at the edge capacity E_cap)."""
+    (geossl_painn_edge_layout: one launch on the batch's own edge tensor, outputs at the edge capacity E_cap).
 
-    def __init__(self, device, B, caps, option, x_cols=2, max_n=SMALL_N, kind="schnet", E_cap=0, n_rbf=20):
+    views = 1 (a step with no second view: Distance Prediction): the backbone's layout `lay2` and the counts in `dims`
+    describe view 0 alone - B molecules, its aggregation work list, its pair slots and edges.  The gather and the PaiNN
+    edge layout still write the two-view structures (view 1 lands in buffer space this step never reads); view 0 comes
+    first in every one of them, so its slices are the one-view structures."""
+
+    def __init__(self, device, B, caps, option, x_cols=2, max_n=SMALL_N, kind="schnet", E_cap=0, n_rbf=20, views=2):
         from .pretrain_GeoSSL import Batch
+        if views not in (1, 2):
+            raise ValueError("a bucket holds one or two views")
+        self.views = int(views)
         self.device, self.B, self.option, self.max_n = device, int(B), option, int(max_n)
         self.kind, self.E_cap = kind, int(E_cap)
         self.N_cap, self.P_cap, self.S_cap, self.W_cap = (int(c) for c in caps[:4])
@@ -355,12 +367,13 @@ class Bucket:
         self.positions = torch.zeros(Nc, 3, dtype=torch.float32, device=device)
         self.batch_vec = torch.zeros(Nc, **i64)
         self.sei = torch.zeros(2, Sc, **i64)
-        self.b2 = torch.zeros(2 * Nc, **i64)   # placeholder for the backbone's `batch` argument (the layout is passed)
-        # ---- two-view molecule layout
+        V = self.views
+        self.b2 = torch.zeros(V * Nc, **i64)   # placeholder for the backbone's `batch` argument (the layout is passed)
+        # ---- molecule layout of the views the backbone sees (the blob's pointer arrays always hold both views)
         lay = _Layout()
-        lay.N, lay.B, lay.P, lay.max_n = 2 * Nc, 2 * B, 2 * Pc, self.max_n
-        lay.mol_ptr = self.blob[o["mol_ptr"]:o["mol_ptr"] + 2 * B + 1]
-        lay.pair_ptr = self.blob[o["pair_ptr"]:o["pair_ptr"] + 2 * B + 1]
+        lay.N, lay.B, lay.P, lay.max_n = V * Nc, V * B, V * Pc, self.max_n
+        lay.mol_ptr = self.blob[o["mol_ptr"]:o["mol_ptr"] + V * B + 1]
+        lay.pair_ptr = self.blob[o["pair_ptr"]:o["pair_ptr"] + V * B + 1]
         lay.device, lay.dyn = device, self.dyn
         lay._batch_version = self.b2._version
         lay.agg_work = None
@@ -372,14 +385,14 @@ class Bucket:
             lay.pair_j = torch.zeros(2 * Pc, **i32)
             lay.agg_work = self.blob[o["work"]:o["work"] + Wc]
             from .layout import aggregate_by_targets
-            lay.agg_targets = aggregate_by_targets(2 * B)
+            lay.agg_targets = aggregate_by_targets(V * B)
         self.lay2 = lay
         # ---- PaiNN: edge structures of the two-view batch
         self.el = None
         if kind == "painn":
             Ec = self.E_cap
             el = _Edges()
-            el.E, el.N, el.B = 2 * Ec, 2 * Nc, 2 * B
+            el.E, el.N, el.B = V * Ec, V * Nc, V * B
             el.idx_i, el.idx_j = torch.zeros(2 * Ec, **i64), torch.zeros(2 * Ec, **i64)
             el.inc = {"i": (torch.zeros(2 * Nc + 1, **i64), torch.zeros(max(2 * Ec, 1), **i32)),
                       "j": (torch.zeros(2 * Nc + 1, **i64), torch.zeros(max(2 * Ec, 1), **i32))}
@@ -436,7 +449,7 @@ class Bucket:
         n = sizes_array(batch)
         if n.shape[0] != B:
             raise ValueError("bucket of %d molecules got a batch of %d" % (B, n.shape[0]))
-        N, P, S, W = counts if counts is not None else batch_counts(n, self.option)
+        N, P, S, W = counts if counts is not None else batch_counts(n, self.option, self.views)
         ds = getattr(batch, "_dataset", None)
         rei, E = None, 0
         if ds is not None:
@@ -461,12 +474,13 @@ class Bucket:
         if slot[1] is not None:
             slot[1].synchronize()   # the upload that last read this staging buffer (three steps ago)
         h = slot[0].numpy()
-        hp = host_plan(n, self.option)
+        hp = host_plan(n, self.option, self.views)
         Wr = hp["work"].size          # (the list's real length: 8 queues; <= the bound W the capacity was checked with)
-        h[0:8] = (N, 2 * N, 2 * P, S, Wr, B, 6 * N, 2 * E)
+        V = self.views
+        h[0:8] = (N, V * N, V * P, S, Wr, B, 3 * V * N, V * E)
         if self.big_caps:
             from .layout import big_atom_list
-            n2 = np.concatenate([n, n])
+            n2 = np.concatenate([n] * V)
             for k, c in enumerate(self.big_caps):
                 idx = big_atom_list(n2, c)
                 h[8 + k] = idx.size

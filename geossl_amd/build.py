@@ -21,7 +21,9 @@ def _sources():
 # results read the HIGH half of src1), and on MI355X that instruction now and then returned a low result of 0 in lanes
 # 48-63 when a second wave shared the SIMD: one term of a sum of four missing, 5-10 atoms of 18 432 per launch, never with
 # one block per CU, never without packed ops (tools/scan_packed_opsel.py).  Same speed either way (140 / 173 us).
-SOURCE_FLAGS = {"painn_mma.hip": ["-fno-slp-vectorize"]}
+# distance_head.hip: the same flag keeps v_pk_fma_f32 op_sel:[0,1,0] out of its projection GEMV (a bandwidth-bound pass
+# that packed fp32 does not speed up).
+SOURCE_FLAGS = {"painn_mma.hip": ["-fno-slp-vectorize"], "distance_head.hip": ["-fno-slp-vectorize"]}
 
 
 def _headers():

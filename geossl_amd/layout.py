@@ -262,6 +262,11 @@ def get_layout(batch):
     return lay
 
 
+class UngroupedSuperEdges(ValueError):
+    """super_edge_index is not grouped by molecule in batch order with both ends in one molecule: the per-molecule
+    bookkeeping and the incidence lists of SuperEdgeLayout cannot be built for it."""
+
+
 class SuperEdgeLayout:
     """Per-batch bookkeeping of ``super_edge_index`` for the DDM head: first super-edge of every
     molecule, the divisor ``max(edge2graph)+1`` of NCSN.py:210-212 (kept on the device), and the
@@ -292,8 +297,8 @@ class SuperEdgeLayout:
         call("geossl_incidence_fill", ptr(self.batch), ptr(self.sei0), ptr(self.sei1), ptr(self.se_ptr), self.N, 3,
              ptr(self.inc_ptr), ptr(self.inc_idx), stream())
         if validate and int(self.stats[1].item()):
-            raise ValueError("super_edge_index must be grouped by molecule in batch order with both ends in "
-                             "the same molecule (collated AtomTupleExtractor output is)")
+            raise UngroupedSuperEdges("super_edge_index must be grouped by molecule in batch order with both ends in "
+                                      "the same molecule (collated AtomTupleExtractor output is)")
         self._versions = (batch._version, sei._version)
         self.dyn = None
 

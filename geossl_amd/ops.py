@@ -561,3 +561,70 @@ def ebm_nce_loss(X, Y, num_neg=1):
         # (cycle_index(B, k) of examples/util.py:19-22 fails for k > B: the reference cannot run such a step either)
         raise ValueError("num_neg must lie in [1, B] (B = %d), got %d" % (X.size(0), num_neg))
     return _EBMNCELoss.apply(X, Y, num_neg)
+
+
+class _DistanceHead(torch.autograd.Function):
+    """L1Loss(Linear(2F, 1)(cat(h_u, h_v)).squeeze(), |pos_u - pos_v|) (examples/pretrain_DistancePrediction.py:15-25,
+    71-77) on csrc/distance_head.hip -> (loss fp32 scalar, pred [S]).  The backward returns dh through autograd; dW / db
+    go through autograd too, or, inside _lib.direct_grads() with dense fp32 .grad buffers, are added into them."""
+
+    @staticmethod
+    def forward(ctx, h, W, b, positions, sei0, sei1, inc_ptr, inc_idx, dyn):
+        h, pos = _f32(h), _f32(positions)
+        N, F = h.shape
+        S = sei0.numel()
+        dev = h.device
+        Wd, bd = W.detach().contiguous().view(-1), b.detach().contiguous().view(-1)
+        lib = _lib.load()
+        proj = torch.empty(max(N, 1), 2, dtype=torch.float32, device=dev)
+        pred = torch.empty(S, dtype=torch.float32, device=dev)
+        sgn = torch.empty(S, dtype=torch.float32, device=dev)
+        ws = torch.empty(int(lib.geossl_distance_head_fwd_workspace_floats(S)), dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        call("geossl_distance_head_fwd_dyn", ptr(h), N, F, ptr(Wd), ptr(bd), ptr(pos), ptr(sei0), ptr(sei1), S,
+             ptr(proj), ptr(pred), ptr(sgn), ptr(ws), ptr(loss), _dyn(dyn, "n_atoms"), _dyn(dyn, "n_super"), stream())
+        ctx.save_for_backward(h, Wd, sei0, sgn, inc_ptr, inc_idx)
+        ctx.params, ctx.dyn = (W, b), dyn
+        ctx.mark_non_differentiable(pred)
+        return loss, pred
+
+    @staticmethod
+    def backward(ctx, gout, _gpred):
+        h, Wd, sei0, sgn, inc_ptr, inc_idx = ctx.saved_tensors
+        W, b = ctx.params
+        N, F = h.shape
+        dev = h.device
+        direct = _lib.direct_grads_enabled((W, b))
+        dW, db = (W.grad, b.grad) if direct else (torch.empty_like(W), torch.empty_like(b))
+        dh = torch.empty_like(h)
+        ws = torch.empty(int(_lib.load().geossl_distance_head_bwd_workspace_floats(N, F)), dtype=torch.float32,
+                         device=dev)
+        g = gout.to(torch.float32).contiguous()
+        call("geossl_distance_head_bwd_dyn", ptr(h), N, F, ptr(Wd), ptr(sei0), sgn.numel(), ptr(sgn), ptr(inc_ptr),
+             ptr(inc_idx), ptr(g), ptr(dh), ptr(dW), ptr(db), ptr(ws), 1 if direct else 0, _dyn(ctx.dyn, "n_atoms"),
+             _dyn(ctx.dyn, "n_super"), stream())
+        if direct:
+            dW = db = None
+        return dh, dW, db, None, None, None, None, None, None
+
+
+def distance_head_width_ok(F):
+    """The node-feature widths the fused distance head serves (a wave holds one row: F = 64 V, V = 1, 2, 4, 8)."""
+    return bool(_lib.load().geossl_distance_head_width_ok(int(F)))
+
+
+def distance_head(h, W, b, positions, super_edge_index, incidence, dyn=None):
+    """The distance-prediction loss of pretrain_DistancePrediction.py:71-77 -> (loss, pred): h [N, F] node features,
+    W [1, 2F] / b [1] the predictor's weight and bias, positions [N, 3] (no gradient), super_edge_index int64 [2, S],
+    incidence = (inc_ptr int64 [N + 1], inc_idx int32 [2S]): every atom's super-edges (as u or v) in ascending order
+    (layout.SuperEdgeLayout).  dyn (bucket.DynDims): N and S are capacities, the real counts are read on the device."""
+    _lib.require_cuda(h, W, b, positions, super_edge_index)
+    F = h.size(1)
+    if h.dim() != 2 or W.numel() != 2 * F or b.numel() != 1 or not distance_head_width_ok(F):
+        raise ValueError("distance_head: h [N, F] with F in (64, 128, 256, 512), W [1, 2F], b [1]; got %s, %s, %s"
+                         % (tuple(h.shape), tuple(W.shape), tuple(b.shape)))
+    if positions.requires_grad:
+        raise ValueError("distance_head: the target distances carry no gradient (positions.requires_grad)")
+    sei = super_edge_index
+    inc_ptr, inc_idx = incidence
+    return _DistanceHead.apply(h, W, b, positions, sei[0].contiguous(), sei[1].contiguous(), inc_ptr, inc_idx, dyn)

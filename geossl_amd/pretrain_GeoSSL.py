@@ -387,7 +387,7 @@ class StepGraphs:
     batches that come back every epoch)."""
 
     def __init__(self, fwd_bwd, model_3d, max_graphs=256, split=None, mode="auto", normalize=False, modules=None,
-                 noise_keys=None):
+                 noise_keys=None, views=2):
         # split = (fwd(batch, noise) -> loss with its autograd graph, bwd(loss)): forward and backward captured as TWO
         # graphs (same pool, same capture stream; replayed in this order) - the forward's loss is then on the device
         # before the backward runs, and the backward can run on a side stream while the host goes on (_AutogradStep)
@@ -396,6 +396,7 @@ class StepGraphs:
         self.modules = modules  # (backbone, head, head): what bucket.modules_ok looks at (None: no capacity buckets)
         # the random draws a step takes as static inputs (the contrastive objectives: the position noise only)
         self.noise_keys = _NOISE_KEYS if noise_keys is None else tuple(noise_keys)
+        self.views = views      # views of the molecules the backbone sees in a bucket (1: the Distance Prediction step)
         self.graphs, self.pool = OrderedDict(), None
         self.enabled = True
         self.captures = 0
@@ -438,7 +439,7 @@ class StepGraphs:
             g = self.graphs.get(key)
             if g is None:
                 return None
-            counts = bk.batch_counts(bk.sizes_array(batch), batch._canonical)
+            counts = bk.batch_counts(bk.sizes_array(batch), batch._canonical, self.views)
             if not g["bucket"].fits(counts, bk.size_range(batch)[1], self._edges(batch)):
                 return None
             g["counts"] = counts
@@ -514,7 +515,7 @@ class StepGraphs:
     def _capture_bucket(self, key, batch, noise):
         from . import bucket as bk
         old = self.graphs.pop(key, None)
-        counts = bk.batch_counts(bk.sizes_array(batch), batch._canonical)
+        counts = bk.batch_counts(bk.sizes_array(batch), batch._canonical, self.views)
         caps = bk.capacities(*counts, B=len(batch._sizes), prev=None if old is None else old["bucket"].caps(),
                              sizes=bk.sizes_array(batch))
         max_n = bk.max_n_class(bk.size_range(batch)[1], None if old is None else old["bucket"].max_n, self.model_3d)
@@ -530,7 +531,7 @@ class StepGraphs:
             bkt = bk.Bucket(dev, len(batch._sizes), caps, batch._canonical,
                             x_cols=batch.x_cols if from_ds else batch.x.size(1), max_n=max_n,
                             n_rbf=getattr(getattr(self.modules[0], "radial_basis", None), "n_rbf", 20),
-                            kind=self.model_3d, E_cap=E_cap)
+                            kind=self.model_3d, E_cap=E_cap, views=self.views)
             bkt.fill(batch, counts)
         except (ValueError, RuntimeError) as e:
             warnings.warn("capacity bucket not usable for this batch (%s); per-structure graphs from now on" % e)
@@ -860,14 +861,16 @@ class _AutogradStep:
     def __init__(self, model, n1, n2, objective="DDM"):
         from .NCSN import _head_params
         self.model, self.n1, self.n2 = model, n1, n2
-        # "DDM" (two NCSN heads), or "InfoNCE" / "EBM_NCE": no heads (n1 = n2 = None), the readout is part of the step
+        # "DDM" (two NCSN heads), "InfoNCE" / "EBM_NCE": no heads (n1 = n2 = None), the readout is part of the step, or
+        # "DistancePrediction": one head, the DistancePredictor (n1; n2 = None)
         self.objective = objective
         heads = [m for m in (n1, n2) if m is not None]
         # the parameters the step reaches (a parameter outside it - an atomref table, PaiNN's output layers - gets no
         # gradient at all, like in the eager path, not a zero one)
         backbone = model._params() if hasattr(model, "_params") else _schnet_step_params(model)
+        head_params = (lambda h: list(h.parameters())) if objective == "DistancePrediction" else _head_params
         seen, self.params = set(), []
-        for p in list(backbone) + [q for h in heads for q in _head_params(h)]:
+        for p in list(backbone) + [q for h in heads for q in head_params(h)]:
             if id(p) not in seen and p.requires_grad:
                 seen.add(id(p))
                 self.params.append(p)
@@ -922,6 +925,9 @@ class _AutogradStep:
 
     def _fwd(self, batch, noise):
         args, mu, sigma = self._cfg
+        if self.objective == "DistancePrediction":
+            from .pretrain_DistancePrediction import distance_step_fused
+            return distance_step_fused(args, batch, self.model, self.n1)
         if self.objective != "DDM":   # -> (loss, counts): the counts are a static output of the forward graph
             return _contrastive_eager(self.objective, args, batch, self.model, mu, sigma, noise, True)
         return _do_ddm_eager(args, batch, self.model, mu, sigma, (self.n1, self.n2), noise, True, True)
@@ -997,11 +1003,14 @@ class _AutogradStep:
         """-> the loss (DDM) / (loss, counts as a host list) (contrastive), or None: run this step eagerly."""
         if getattr(batch, "_dataset", None) is None and (not batch.positions.is_cuda or batch.positions.requires_grad):
             return None
-        contrastive = self.objective != "DDM"
+        contrastive = self.objective in CONTRASTIVE_OPTIONS
+        distance = self.objective == "DistancePrediction"   # (no random draws: the positions as they are)
         normalize = bool(getattr(args, "normalize", False))
         if contrastive:   # (a graph binds T and num_neg: by-value arguments of its loss launches)
             cargs = ContrastiveArgs(args.model_3d, normalize, getattr(args, "T", 0.1), getattr(args, "num_neg", 1))
             key = (self.objective, args.model_3d, normalize, cargs.T, cargs.num_neg)
+        elif distance:   # (the tuple option is part of each StepGraphs key: bucket key / structure fingerprint)
+            key = (self.objective, args.model_3d)
         else:
             key = (args.model_3d, normalize)
         sg = self.graphs.get(key)
@@ -1012,11 +1021,12 @@ class _AutogradStep:
                                                mode=getattr(args, "step_graph_mode", "auto"),
                                                normalize=normalize and not contrastive,
                                                modules=(self.model, self.n1, self.n2),
-                                               noise_keys=("pos_noise",) if contrastive else None)
+                                               noise_keys=("pos_noise",) if contrastive else
+                                               (() if distance else None), views=1 if distance else 2)
             sg.zero_with_refresh = self.gflat
         if not sg.enabled:
             return None
-        self._cfg = (cargs if contrastive else Args(args.model_3d, normalize), mu, sigma)
+        self._cfg = (cargs if contrastive else Args(args.model_3d, normalize and not distance), mu, sigma)
         g = sg.lookup(batch)
         if g is None and not sg.capture_now(batch):
             # first sighting of an index structure that only its own graph can serve (sampled tuples, PaiNN edge lists,
@@ -1032,7 +1042,9 @@ class _AutogradStep:
             if t is not None and t["g"] is None and not t.get("used"):
                 t["g"] = self.gflat.clone()  # a step still waiting for its backward() keeps its gradients
         if g is None:
-            if contrastive:
+            if distance:
+                drawn = {}
+            elif contrastive:
                 drawn = draw_views_noise(batch, mu, sigma, device_noise, noise)
             else:
                 drawn = draw_step_noise(batch, self.n1, self.n2, mu, sigma, device_noise, noise)
@@ -1044,7 +1056,9 @@ class _AutogradStep:
         else:
             if not sg.refresh(g, batch):
                 return None  # (the bucket refused the batch's tensors: this step as eager launches)
-            if contrastive:
+            if distance:
+                pass
+            elif contrastive:
                 draw_views_noise(batch, mu, sigma, device_noise, noise, into=sg.noise_views(g))
             else:
                 draw_step_noise(batch, self.n1, self.n2, mu, sigma, device_noise, noise, into=sg.noise_views(g))

@@ -785,6 +785,38 @@ int geossl_ebm_nce_fwd(const float* X, const float* Y, int64_t B, int F, int num
 int geossl_ebm_nce_bwd(const float* X, const float* Y, const float* pred, int64_t B, int F, int num_neg,
                        const double* gout, float* dX, float* dY, hipStream_t stream);
 
+/* ---- distance-prediction head: examples/pretrain_DistancePrediction.py:15-25,66-79 (csrc/distance_head.hip) ----------
+ * h [N][F] node features (F = 64, 128, 256 or 512: geossl_distance_head_width_ok), W [2F] = predictor.weight = [w_u | w_v],
+ * bias [1], pos [N][3], super-edges (sei0[e], sei1[e]) = (u_e, v_e), e < S.  No atomics: the same inputs give the same bits.
+ * Forward: proj [N][2] (out) = (w_u . h_i, w_v . h_i); pred [S] (out) = (a_{u_e} + b_{v_e}) + bias; target_e =
+ *   sqrtf((dx*dx + dy*dy) + dz*dz) of pos_u - pos_v; sgn [S] (out, the backward's input) = sign(pred_e - target_e) (0 on a
+ *   tie); loss [1] = mean |pred - target| (fp64 sums in a fixed order, NaN for S = 0).  workspace:
+ *   geossl_distance_head_fwd_workspace_floats(S) floats, 8-byte aligned.
+ * Backward with the upstream gradient gout[0]: d pred_e = (gout / S) sgn_e; dA_i / dB_i = the sums of d pred over the
+ *   super-edges with u_e = i / v_e = i in ascending edge order on the atom's incidence list (inc_ptr / inc_idx of
+ *   geossl_incidence_fill with sides = 3); dh [N][F] = dA_i w_u + dB_i w_v; dW [2F] (+)= [sum dA_i h_i | sum dB_i h_i],
+ *   db [1] (+)= sum dA_i, from per-block partials added in block order.  accumulate: dW / db (+)= instead of =.  workspace:
+ *   geossl_distance_head_bwd_workspace_floats(N, F) floats.
+ * `_dyn`: N and S are capacities (grids, workspaces); dyn_N / dyn_S (nullable) point at the real counts - the mean
+ *   divides by the real S, atoms and super-edges past the real counts are neither read nor written. */
+int geossl_distance_head_width_ok(int F);
+int64_t geossl_distance_head_fwd_workspace_floats(int64_t S);
+int64_t geossl_distance_head_bwd_workspace_floats(int64_t N, int F);
+int geossl_distance_head_fwd(const float* h, int64_t N, int F, const float* W, const float* bias, const float* pos,
+                             const int64_t* sei0, const int64_t* sei1, int64_t S, float* proj, float* pred, float* sgn,
+                             float* workspace, float* loss, hipStream_t stream);
+int geossl_distance_head_fwd_dyn(const float* h, int64_t N, int F, const float* W, const float* bias, const float* pos,
+                                 const int64_t* sei0, const int64_t* sei1, int64_t S, float* proj, float* pred,
+                                 float* sgn, float* workspace, float* loss, const int32_t* dyn_N, const int32_t* dyn_S,
+                                 hipStream_t stream);
+int geossl_distance_head_bwd(const float* h, int64_t N, int F, const float* W, const int64_t* sei0, int64_t S,
+                             const float* sgn, const int64_t* inc_ptr, const int32_t* inc_idx, const float* gout,
+                             float* dh, float* dW, float* db, float* workspace, int accumulate, hipStream_t stream);
+int geossl_distance_head_bwd_dyn(const float* h, int64_t N, int F, const float* W, const int64_t* sei0, int64_t S,
+                                 const float* sgn, const int64_t* inc_ptr, const int32_t* inc_idx, const float* gout,
+                                 float* dh, float* dW, float* db, float* workspace, int accumulate,
+                                 const int32_t* dyn_N, const int32_t* dyn_S, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

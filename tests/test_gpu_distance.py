@@ -1,0 +1,373 @@
+"""GPU tests of Distance Prediction pretraining: the head kernels of csrc/distance_head.hip per element against fp64
+on NaN-poisoned outputs (static and `_dyn` forms, both enumerations, a 255-atom molecule), the reference's edge cases
+against ATen, determinism, fixture G18 through do_DistancePrediction, the fallbacks, and the replayed step against the
+eager one and against the reference loop with a stock torch.optim.Adam."""
+import json
+import os
+import types
+
+import numpy as np
+import pytest
+import torch
+
+import distance_twin as tw
+from conftest import load_golden, rel_err
+from helpers import fill_module_, grad_summary, t, unique_named_grads
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+G18 = sorted(f[:-4] for f in os.listdir(os.path.join(REPO, "tests", "golden")) if f.startswith("g18_distance_"))
+U = 2.0 ** -24
+NAN = float("nan")
+
+
+def _inputs(sizes, option, F, seed, ratio=1.0):
+    from geossl_amd.synthetic import make_batch
+    b = make_batch(0, seed=seed, sizes=sizes, option=option)
+    sei = b["super_edge_index"]
+    rng = np.random.default_rng(seed)
+    if ratio < 1:   # a sampled subset, in shuffled order: a molecule's super-edges are not contiguous
+        keep = rng.choice(sei.shape[1], int(sei.shape[1] * ratio), replace=False)
+        sei = sei[:, keep]
+    g = torch.Generator().manual_seed(seed)
+    h = 0.5 * torch.randn(int(np.sum(sizes)), F, generator=g)
+    W = 0.1 * torch.randn(1, 2 * F, generator=g)
+    bias = torch.tensor([0.7])
+    return b, h, W, bias, torch.from_numpy(np.ascontiguousarray(sei))
+
+
+def _incidence(N, sei):
+    """inc_ptr / inc_idx of every atom's super-edges (as u or v) in ascending edge order, built on the host."""
+    S = sei.size(1)
+    ends = torch.cat([sei[0], sei[1]])
+    edge = torch.cat([torch.arange(S), torch.arange(S)])
+    order = torch.argsort(ends * (2 * S + 1) + edge)
+    cnt = torch.bincount(ends, minlength=N)
+    ptr_ = torch.zeros(N + 1, dtype=torch.int64)
+    ptr_[1:] = torch.cumsum(cnt, 0)
+    return ptr_, edge[order].to(torch.int32)
+
+
+class _Dims:
+    def __init__(self, N, S):
+        self.tensor = torch.tensor([N, 0, 0, S], dtype=torch.int32, device=DEV)
+        self.n_atoms, self.n_super = self.tensor.data_ptr(), self.tensor.data_ptr() + 12
+
+
+def _run_raw(h, W, bias, pos, sei, gout, dyn_caps=None):
+    """Forward + backward through the C ABI on NaN-filled outputs.  dyn_caps = (N_cap, S_cap): the `_dyn` forms on
+    buffers at those capacities; the inputs past the real rows are FINITE (atoms at 3.0, super-edges (0, 0)), so a row
+    the kernels wrongly processed would come out finite where the outputs must stay NaN."""
+    from geossl_amd import _lib
+    from geossl_amd._lib import ptr, stream
+    lib = _lib.load()
+    N, F = h.shape
+    S = sei.size(1)
+    Nc, Sc = dyn_caps if dyn_caps else (N, S)
+    pad = lambda a, n: torch.cat([a, torch.full((n - a.size(0),) + tuple(a.shape[1:]), 3.0, dtype=a.dtype)]).to(DEV)
+    hd, posd = pad(h, Nc), pad(pos, Nc)
+    seid = torch.cat([sei, torch.zeros(2, Sc - S, dtype=torch.long)], 1).to(DEV)
+    ip, ii = _incidence(N, sei)
+    ip = torch.cat([ip, ip[-1:].repeat(Nc - N)]).to(DEV)
+    ii = torch.cat([ii, torch.zeros(2 * (Sc - S), dtype=torch.int32)]).to(DEV)
+    Wd, bd = W.to(DEV).contiguous(), bias.to(DEV)
+    dims = _Dims(N, S) if dyn_caps else None
+    dn, ds = (dims.n_atoms, dims.n_super) if dims else (None, None)
+    proj = torch.full((max(Nc, 1), 2), NAN, device=DEV)
+    pred = torch.full((Sc,), NAN, device=DEV)
+    sgn = torch.full((Sc,), NAN, device=DEV)
+    loss = torch.full((), NAN, device=DEV)
+    ws = torch.full((int(lib.geossl_distance_head_fwd_workspace_floats(Sc)),), NAN, device=DEV)
+    st = stream()
+    _lib.call("geossl_distance_head_fwd_dyn", ptr(hd), Nc, F, ptr(Wd), ptr(bd), ptr(posd), ptr(seid[0]), ptr(seid[1]),
+              Sc, ptr(proj), ptr(pred), ptr(sgn), ptr(ws), ptr(loss), dn, ds, st)
+    dh = torch.full((Nc, F), NAN, device=DEV)
+    dW = torch.full((1, 2 * F), NAN, device=DEV)
+    db = torch.full((1,), NAN, device=DEV)
+    ws2 = torch.full((int(lib.geossl_distance_head_bwd_workspace_floats(Nc, F)),), NAN, device=DEV)
+    g = torch.tensor(gout, dtype=torch.float32, device=DEV)
+    _lib.call("geossl_distance_head_bwd_dyn", ptr(hd), Nc, F, ptr(Wd), ptr(seid[0]), Sc, ptr(sgn), ptr(ip), ptr(ii),
+              ptr(g), ptr(dh), ptr(dW), ptr(db), ptr(ws2), 0, dn, ds, st)
+    torch.cuda.synchronize()
+    return dict(proj=proj.cpu(), pred=pred.cpu(), sgn=sgn.cpu(), loss=loss.cpu(), dh=dh.cpu(), dW=dW.cpu(), db=db.cpu())
+
+
+def _check_against_fp64(sizes, option, F, seed, dyn=False, ratio=1.0, gout=1.5):
+    b, h, W, bias, sei = _inputs(sizes, option, F, seed, ratio)
+    pos = torch.from_numpy(b["positions"])
+    N, S = h.size(0), sei.size(1)
+    caps = (N + 37, S + 1000) if dyn else None
+    got = _run_raw(h, W, bias, pos, sei, gout, caps)
+    if dyn:   # rows past the real counts are not written
+        for k, n_ in (("pred", S), ("sgn", S), ("dh", N), ("proj", N)):
+            assert torch.isnan(got[k][n_:]).all(), k
+    got = {k: (v[:N] if k in ("proj", "dh") else v[:S] if k in ("pred", "sgn") else v) for k, v in got.items()}
+    h64, W64, b64 = h.double(), W.double().view(-1), bias.double()
+    wu, wv = W64[:F], W64[F:]
+    a64, bb64 = h64 @ wu, h64 @ wv
+    ah, bh = h64.abs() @ wu.abs(), h64.abs() @ wv.abs()
+    assert ((got["proj"][:, 0].double() - a64).abs() <= F * U * ah + 1e-30).all()
+    assert ((got["proj"][:, 1].double() - bb64).abs() <= F * U * bh + 1e-30).all()
+    u, v = sei[0], sei[1]
+    ref_loss, ref_pred, ref_target = tw.distance_loss(h64, W64, b64, pos, sei)
+    pbound = (F + 2) * U * (ah[u] + bh[v] + b64.abs()) + 4 * U * ref_pred.abs()
+    assert ((got["pred"].double() - ref_pred).abs() <= pbound).all()
+    assert abs(float(got["loss"]) - float(ref_loss)) <= 1e-5 * abs(float(ref_loss))
+    # the sign the kernel took must be the fp64 one wherever the residual is above the rounding of pred and target
+    r = ref_pred - ref_target
+    clear = r.abs() > pbound + 4 * U * ref_target
+    assert torch.equal(got["sgn"][clear].double(), torch.sign(r[clear]))
+    c = float(np.float32(gout) / np.float32(S))
+    dpred = got["sgn"].double() * c
+    dA = torch.zeros(N, dtype=torch.float64).index_add_(0, u, dpred)
+    dB = torch.zeros(N, dtype=torch.float64).index_add_(0, v, dpred)
+    aA = torch.zeros(N, dtype=torch.float64).index_add_(0, u, dpred.abs())
+    aB = torch.zeros(N, dtype=torch.float64).index_add_(0, v, dpred.abs())
+    L = int(torch.bincount(torch.cat([u, v]), minlength=N).max()) + 2
+    ref_dh = dA[:, None] * wu[None] + dB[:, None] * wv[None]
+    bound = L * U * (aA[:, None] * wu.abs()[None] + aB[:, None] * wv.abs()[None]) + 1e-30
+    assert ((got["dh"].double() - ref_dh).abs() <= bound).all()
+    ref_dW = torch.cat([dA @ h64, dB @ h64])
+    wb = (L + N) * U * torch.cat([aA @ h64.abs(), aB @ h64.abs()]) + 1e-30
+    assert ((got["dW"].view(-1).double() - ref_dW).abs() <= wb).all()
+    assert abs(float(got["db"]) - float(dA.sum())) <= (L + N) * U * float(aA.sum()) + 1e-30
+    return got
+
+
+@pytest.mark.parametrize("option", ["permutation", "combination"])
+@pytest.mark.parametrize("F", [64, 128])
+@pytest.mark.parametrize("dyn", [False, True])
+def test_head_kernels_vs_fp64(option, F, dyn):
+    _check_against_fp64([5, 18, 2, 9, 33, 1, 12, 255, 40], option, F, 7 + F, dyn=dyn)
+
+
+def test_head_kernels_sampled_subset_and_wide():
+    _check_against_fp64([18, 30, 7, 2, 25], "permutation", 128, 11, ratio=0.4)
+    _check_against_fp64([18, 30, 7, 2, 25], "combination", 256, 12, dyn=True, ratio=0.5)
+    _check_against_fp64([12] * 64, "permutation", 512, 13)
+
+
+def test_head_kernels_are_deterministic():
+    b, h, W, bias, sei = _inputs([18, 30, 7, 2, 25] * 40, "permutation", 128, 21)
+    pos = torch.from_numpy(b["positions"])
+    runs = [_run_raw(h, W, bias, pos, sei, 1.0) for _ in range(8)]
+    for r in runs[1:]:
+        for k in runs[0]:
+            assert torch.equal(r[k].view(torch.int32), runs[0][k].view(torch.int32)), k
+
+
+def _aten_and_fused(h, pos, sei, W, bias):
+    from geossl_amd import ops
+    from geossl_amd.pretrain_DistancePrediction import DistancePredictor
+    F = h.size(1)
+    dp = DistancePredictor(F).to(DEV)
+    with torch.no_grad():
+        dp.predictor.weight.copy_(W)
+        dp.predictor.bias.copy_(bias)
+    hr = h.to(DEV).requires_grad_()
+    posd, seid = pos.to(DEV), sei.to(DEV)
+    d = torch.sqrt(torch.sum((posd[seid[0]] - posd[seid[1]]) ** 2, dim=1))
+    ref = dp(hr[seid[0]], hr[seid[1]], d)
+    ref.backward()
+    want = (ref.detach(), hr.grad.clone(), dp.predictor.weight.grad.clone(), dp.predictor.bias.grad.clone())
+    dp.zero_grad()
+    hf = h.to(DEV).requires_grad_()
+    ip, ii = _incidence(h.size(0), sei)
+    loss, _ = ops.distance_head(hf, dp.predictor.weight, dp.predictor.bias, posd, seid, (ip.to(DEV), ii.to(DEV)))
+    loss.backward()
+    return want, (loss.detach(), hf.grad, dp.predictor.weight.grad, dp.predictor.bias.grad)
+
+
+def test_edge_cases_match_aten():
+    F = 64
+    g = torch.Generator().manual_seed(5)
+    # S = 0: every molecule has one atom -> NaN loss, zero gradients
+    h = torch.randn(3, F, generator=g)
+    pos = torch.randn(3, 3, generator=g)
+    want, got = _aten_and_fused(h, pos, torch.empty(2, 0, dtype=torch.long), 0.1 * torch.randn(1, 2 * F, generator=g),
+                                torch.tensor([0.3]))
+    assert torch.isnan(want[0]) and torch.isnan(got[0])
+    for a, b in zip(want[1:], got[1:]):
+        assert torch.equal(a, b) and not a.abs().sum()
+    # S = 1: the 0-d prediction against [1]
+    h = torch.randn(2, F, generator=g)
+    want, got = _aten_and_fused(h, torch.randn(2, 3, generator=g), torch.tensor([[0], [1]]),
+                                0.1 * torch.randn(1, 2 * F, generator=g), torch.tensor([0.3]))
+    assert rel_err(got[0], want[0]) < 1e-6
+    for a, b in zip(want[1:], got[1:]):
+        assert rel_err(b, a) < 1e-6
+    # exact tie: atoms one unit apart on an axis, zero weights, bias 1.0 -> pred == target, sgn 0, zero gradients
+    pos = torch.tensor([[0., 0., 0.], [1., 0., 0.], [0., 0., 3.]])
+    want, got = _aten_and_fused(torch.randn(3, F, generator=g), pos, torch.tensor([[0, 1, 2], [1, 0, 0]]),
+                                torch.zeros(1, 2 * F), torch.tensor([1.0]))
+    assert float(want[0]) == float(got[0]) and abs(float(got[0]) - 2.0 / 3.0) < 1e-7   # |0| + |0| + |1 - 3|, over 3
+    assert not got[1].abs().sum() and not want[1].abs().sum()   # zero weights: no gradient reaches h
+    assert rel_err(got[2], want[2]) < 1e-6
+    assert torch.equal(got[3], want[3]) and float(got[3]) == -float(np.float32(1.0) / np.float32(3.0))   # the tie adds 0
+
+
+# ---------------------------------------------------------------------------------------------- the step vs G18
+def _g18_setup(case):
+    from geossl_amd import pretrain_GeoSSL as pg
+    from geossl_amd.Geom3D.models import PaiNN, SchNet
+    from geossl_amd.pretrain_DistancePrediction import DistancePredictor
+    g = load_golden(case)
+    meta, cfg = json.loads(str(g["meta"])), json.loads(str(g["cfg"]))
+    model = fill_module_(SchNet(**cfg) if meta["kind"] == "schnet" else PaiNN(**cfg)).to(DEV)
+    dp = fill_module_(DistancePredictor(meta["emb_dim"])).to(DEV)
+    rei = t(g["radius_edge_index"], DEV) if "radius_edge_index" in g else None
+    batch = pg.Batch(t(g["x"], DEV), t(g["positions"], DEV), t(g["batch"], DEV), t(g["super_edge_index"], DEV),
+                     radius_edge_index=rei, num_graphs=len(g["sizes"]))
+    return g, meta, model, dp, batch, types.SimpleNamespace(model_3d=meta["kind"])
+
+
+def _check_g18(g, model, dp, loss, case):
+    assert rel_err(loss.detach().cpu(), g["loss"]) < 1e-5, case
+    assert rel_err(dp.predictor.weight.grad.cpu(), g["grad_pred_weight"]) < 1e-4, case
+    assert rel_err(dp.predictor.bias.grad.cpu(), g["grad_pred_bias"]) < 1e-4, case
+    grads = unique_named_grads(model)
+    for k in g:
+        if k.startswith("grad/") or k.startswith("gsum/"):
+            got = grads[k.split("/", 1)[1]].cpu()
+            got = grad_summary(got) if k.startswith("gsum/") else got
+            assert rel_err(got, g[k]) < 1e-4 or float(np.abs(g[k]).max()) < 1e-8, (case, k)
+
+
+@pytest.mark.parametrize("case", G18)
+@pytest.mark.parametrize("graph", [False, True])
+def test_g18_end_to_end(case, graph):
+    from geossl_amd.pretrain_DistancePrediction import do_DistancePrediction
+    g, meta, model, dp, batch, args = _g18_setup(case)
+    for _ in range(2 if graph else 1):   # (a structure known by its tensors is captured at its second sighting)
+        model.zero_grad(set_to_none=True)
+        dp.zero_grad(set_to_none=True)
+        loss = do_DistancePrediction(args, batch, model, dp, graph=graph)
+        loss.backward()
+    assert loss.dtype == torch.float32 and loss.dim() == 0
+    _check_g18(g, model, dp, loss, case)
+
+
+def test_fallbacks_match_the_twin():
+    """Width 48 (outside the fused kernels) and a non-default criterion take the ATen head; a sampled (ratio < 1)
+    batch takes the fused head on its own incidence lists."""
+    from geossl_amd.Geom3D.models import SchNet
+    from geossl_amd import pretrain_GeoSSL as pg
+    from geossl_amd.pretrain_DistancePrediction import DistancePredictor, do_DistancePrediction, fused_head_ok
+    g = load_golden("g18_distance_schnet_reduced_ratio")
+    for F in (48, 64):
+        cfg = dict(hidden_channels=F, num_filters=F, num_interactions=2, num_gaussians=8, cutoff=5.0, node_class=9)
+        model = fill_module_(SchNet(**cfg)).to(DEV)
+        dp = fill_module_(DistancePredictor(F)).to(DEV)
+        assert fused_head_ok(dp) == (F == 64)
+        batch = pg.Batch(t(g["x"], DEV), t(g["positions"], DEV), t(g["batch"], DEV), t(g["super_edge_index"], DEV),
+                         num_graphs=len(g["sizes"]))
+        loss = do_DistancePrediction(types.SimpleNamespace(model_3d="schnet"), batch, model, dp)
+        _, h = model(batch.x[:, 0], batch.positions, batch.batch, return_latent=True)
+        ref, _, _ = tw.distance_loss(h.detach().cpu(), dp.predictor.weight.detach().cpu(),
+                                     dp.predictor.bias.detach().cpu(), batch.positions.cpu(), batch.super_edge_index.cpu())
+        assert rel_err(loss.detach().cpu(), ref) < 1e-5, F
+    dp.criterion = torch.nn.L1Loss(reduction="sum")
+    assert not fused_head_ok(dp)
+
+
+# ---------------------------------------------------------------------------------------------- graph paths
+def _ragged_batches(n, B, seed, option="permutation"):
+    from geossl_amd import pretrain_GeoSSL as pg
+    from geossl_amd.synthetic import collate_subset, make_batch
+    pool = make_batch(4 * B, seed=seed, mode="B", option=option)
+    rng = np.random.default_rng(seed)
+    return [pg.Batch.from_numpy(collate_subset(pool, rng.permutation(4 * B)[:B], option=option), DEV) for _ in range(n)]
+
+
+def test_trainer_bucket_replay_matches_reference_loop():
+    """10 steps of DistancePredictionTrainer on shuffled ragged batches (no size sequence repeats) replay ONE one-view
+    capacity-bucket graph, and match the reference loop on eager launches with a stock torch.optim.Adam step by step."""
+    from geossl_amd.Geom3D.models import SchNet
+    from geossl_amd.pretrain_DistancePrediction import (DistancePredictionTrainer, DistancePredictor,
+                                                        do_DistancePrediction)
+    cfg = dict(hidden_channels=128, num_filters=128, num_interactions=6, num_gaussians=51, cutoff=10.0, node_class=9)
+    batches = _ragged_batches(10, 16, 5)
+    assert len({tuple(b._sizes) for b in batches}) == 10
+    m1, d1 = fill_module_(SchNet(**cfg)).to(DEV), fill_module_(DistancePredictor(128)).to(DEV)
+    m2, d2 = fill_module_(SchNet(**cfg)).to(DEV), fill_module_(DistancePredictor(128)).to(DEV)
+    opt = torch.optim.Adam([{"params": m1.parameters(), "lr": 1e-4}, {"params": d1.parameters(), "lr": 1e-4}],
+                           lr=1e-4)
+    tr = DistancePredictionTrainer(m2, d2, lr=1e-4, use_graph=True)
+    args = types.SimpleNamespace(model_3d="schnet")
+    for k, b in enumerate(batches):
+        loss = do_DistancePrediction(args, b, m1, d1, graph=False)
+        opt.zero_grad()
+        loss.backward()
+        opt.step()
+        l2 = tr.step(b)
+        assert rel_err(l2.cpu(), loss.detach().cpu()) < 1e-4, k
+    assert rel_err(d2.predictor.weight.detach().cpu(), d1.predictor.weight.detach().cpu()) < 1e-4
+    assert rel_err(m2.lin2.weight.detach().cpu(), m1.lin2.weight.detach().cpu()) < 1e-4
+    # one graph for the batch size (a batch that outgrows the first bucket's capacity replaces it by a larger one)
+    assert len(tr.step_graphs) == 1 and 1 <= tr.step_graphs.captures <= 2
+    (key, g), = tr.step_graphs.graphs.items()
+    assert key[0] == "bucket" and g["bucket"].views == 1
+
+
+def _grads(model, dp):
+    return [p.grad.clone() for p in list(model.parameters()) + list(dp.parameters()) if p.grad is not None]
+
+
+def _replay_vs_eager(model, dp, kind, batches):
+    from geossl_amd.pretrain_DistancePrediction import do_DistancePrediction
+    args = types.SimpleNamespace(model_3d=kind)
+    for k, b in enumerate(batches):
+        out = []
+        for graph in (False, True):
+            model.zero_grad(set_to_none=True)
+            dp.zero_grad(set_to_none=True)
+            loss = do_DistancePrediction(args, b, model, dp, graph=graph)
+            loss.backward()
+            out.append((loss.detach().clone(), _grads(model, dp)))
+        assert rel_err(out[1][0].cpu(), out[0][0].cpu()) < 1e-6, (kind, k)
+        assert len(out[1][1]) == len(out[0][1])
+        for a, c in zip(out[1][1], out[0][1]):
+            assert rel_err(a, c) < 1e-5, (kind, k)
+    eng = model.__dict__["_geossl_distance_step"]
+    (sg,) = eng.graphs.values()
+    return sg
+
+
+@pytest.mark.parametrize("kind", ["schnet", "painn"])
+def test_bucket_replay_matches_eager_on_ragged_batches(kind):
+    """The reference loop's path (do_DistancePrediction -> _AutogradStep): shuffled ragged batches replay one one-view
+    bucket graph, loss and every gradient as the eager launches give them."""
+    from geossl_amd.Geom3D.models import PaiNN, SchNet
+    from geossl_amd.pretrain_DistancePrediction import DistancePredictor
+    model = (fill_module_(SchNet(hidden_channels=128, num_filters=128, num_interactions=6, num_gaussians=51,
+                                 cutoff=10.0, node_class=9)) if kind == "schnet" else
+             fill_module_(PaiNN(n_atom_basis=128, n_interactions=3, n_rbf=20, cutoff=5.0, max_z=9, n_out=1,
+                               readout="add"))).to(DEV)
+    dp = fill_module_(DistancePredictor(128)).to(DEV)
+    batches = _ragged_batches(4, 24, 17)
+    if kind == "painn":
+        from geossl_amd import ops
+        for b in batches:
+            b.radius_edge_index = ops.radius_graph(b.positions, 5.0, b.batch)
+    sg = _replay_vs_eager(model, dp, kind, batches)
+    assert len(sg) == 1 and next(iter(sg.graphs))[0] == "bucket"
+
+
+@pytest.mark.parametrize("kind", ["schnet", "painn"])
+def test_bucket_replay_matches_eager_on_device_loader(kind):
+    """DeviceLoader handles (gathered into the bucket on the device) replay one one-view bucket graph per batch size."""
+    from geossl_amd.Geom3D.dataloaders import DeviceDataset, DeviceLoader
+    from geossl_amd.Geom3D.models import PaiNN, SchNet
+    from geossl_amd.pretrain_DistancePrediction import DistancePredictor
+    from geossl_amd.synthetic import make_molecules
+    ds = DeviceDataset.from_numpy(make_molecules(200, seed=3, mode="C"), DEV, option="permutation",
+                                  **({"radius": 5.0} if kind == "painn" else {}))
+    loader = DeviceLoader(ds, batch_size=32, shuffle=True, drop_last=True, generator=torch.Generator().manual_seed(2))
+    model = (fill_module_(SchNet(hidden_channels=128, num_filters=128, num_interactions=6, num_gaussians=51,
+                                 cutoff=10.0, node_class=9)) if kind == "schnet" else
+             fill_module_(PaiNN(n_atom_basis=128, n_interactions=3, n_rbf=20, cutoff=5.0, max_z=9, n_out=1,
+                               readout="add"))).to(DEV)
+    dp = fill_module_(DistancePredictor(128)).to(DEV)
+    sg = _replay_vs_eager(model, dp, kind, [hb for _, hb in zip(range(4), loader)])
+    assert len(sg) == 1 and next(iter(sg.graphs))[0] == "bucket"
