@@ -251,6 +251,17 @@ PROTOTYPES = {
     "geossl_distance_head_fwd_dyn": (i32, [vp, i64, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
     "geossl_distance_head_bwd": (i32, [vp, i64, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
     "geossl_distance_head_bwd_dyn": (i32, [vp, i64, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]),
+    # charge-prediction mask and head (csrc/charge_head.hip)
+    "geossl_charge_mask_count": (i64, [i64, f64]),
+    "geossl_charge_mask": (i32, [vp, i32, i64, f64, i32, vp, vp, vp, vp, vp, vp]),
+    "geossl_charge_mask_dyn": (i32, [vp, i32, i64, f64, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "geossl_charge_head_width_ok": (i32, [i32, i32]),
+    "geossl_charge_head_fwd_workspace_floats": (i64, [i64]),
+    "geossl_charge_head_bwd_workspace_floats": (i64, [i64, i32, i32]),
+    "geossl_charge_head_fwd": (i32, [vp, i64, i32, vp, vp, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp]),
+    "geossl_charge_head_fwd_dyn": (i32, [vp, i64, i32, vp, vp, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+    "geossl_charge_head_bwd": (i32, [vp, i64, i32, vp, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
+    "geossl_charge_head_bwd_dyn": (i32, [vp, i64, i32, vp, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]),
 }
 
 _lib = None

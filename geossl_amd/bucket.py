@@ -194,7 +194,8 @@ def modules_ok(model, n1=None, n2=None):
     """The step of these modules can run on a bucket: the F = 128 chain path of SchNet / PaiNN (the chained row kernel is
     the one that takes a device-side row count) and the paired NCSN heads (two different modules of width 128).  No heads
     (n1 = n2 = None): the contrastive steps, whose loss reads the readout of the 2B molecules - exact counts, no capacity.
-    One DistancePredictor of width 2 * 128 (n2 = None): the Distance Prediction step on a one-view bucket."""
+    One DistancePredictor of width 2 * 128 / ChargePredictor of width 128 (n2 = None): the Distance / Charge Prediction
+    steps on a one-view bucket."""
     import os
     from .Geom3D.models.painn import PaiNN
     from .Geom3D.models.schnet import SchNet
@@ -219,6 +220,9 @@ def modules_ok(model, n1=None, n2=None):
     from .pretrain_DistancePrediction import DistancePredictor, fused_head_ok
     if isinstance(n1, DistancePredictor) and n2 is None:
         return fused_head_ok(n1) and n1.predictor.in_features == 2 * 128
+    from .pretrain_ChargePrediction import ChargePredictor, fused_head_ok as charge_head_ok
+    if isinstance(n1, ChargePredictor) and n2 is None:
+        return charge_head_ok(n1) and n1.predictor.in_features == 128
     if not (isinstance(n1, NCSN_version_03) and isinstance(n2, NCSN_version_03)) or n1 is n2 \
             or n1.emb_dim != 128 or n2.emb_dim != 128:
         return False

@@ -23,7 +23,9 @@ def _sources():
 # one block per CU, never without packed ops (tools/scan_packed_opsel.py).  Same speed either way (140 / 173 us).
 # distance_head.hip: the same flag keeps v_pk_fma_f32 op_sel:[0,1,0] out of its projection GEMV (a bandwidth-bound pass
 # that packed fp32 does not speed up).
-SOURCE_FLAGS = {"painn_mma.hip": ["-fno-slp-vectorize"], "distance_head.hip": ["-fno-slp-vectorize"]}
+# charge_head.hip: likewise (its row dot products and weight-gradient columns are small fp32 loops).
+SOURCE_FLAGS = {"painn_mma.hip": ["-fno-slp-vectorize"], "distance_head.hip": ["-fno-slp-vectorize"],
+                "charge_head.hip": ["-fno-slp-vectorize"]}
 
 
 def _headers():

@@ -628,3 +628,100 @@ def distance_head(h, W, b, positions, super_edge_index, incidence, dyn=None):
     sei = super_edge_index
     inc_ptr, inc_idx = incidence
     return _DistanceHead.apply(h, W, b, positions, sei[0].contiguous(), sei[1].contiguous(), inc_ptr, inc_idx, dyn)
+
+
+def charge_mask_count(N, ratio):
+    """k of the Charge Prediction mask: Python's int(N * ratio), computed by the library (the device uses the same rule)."""
+    return int(_lib.load().geossl_charge_mask_count(int(N), float(ratio)))
+
+
+def charge_mask(x, ratio, C, seed=None, given=None, dyn=None):
+    """The masked-atom draw of pretrain_ChargePrediction.py:62-66 on the device -> (idx int64 [K], labels int64 [K],
+    k int32 [1]).  x: int64 [N, cols] atom features, column 0 overwritten in place with the token C - 1 on the masked
+    rows.  seed (int64 [1] on the device, advanced by the launch): a device draw (Philox, ascending list); given (int64
+    [>= k]): a host-drawn list used as it is.  dyn (bucket.DynDims): N is a capacity, the real count is read on the device
+    (K = N then; the real k is k[0]); else K = int(N * ratio)."""
+    _lib.require_cuda(x, seed, given)
+    if x.dtype != torch.long or x.dim() != 2 or not x.is_contiguous():
+        raise ValueError("charge_mask: x must be a contiguous int64 [N, cols] tensor")
+    if (seed is None) == (given is None):
+        raise ValueError("charge_mask: exactly one of seed / given")
+    if not 0.0 <= float(ratio) <= 1.0:
+        raise ValueError("charge_mask: ratio must lie in [0, 1]")
+    N = x.size(0)
+    K = N if dyn is not None else charge_mask_count(N, ratio)
+    if given is not None and (given.dtype != torch.long or not given.is_contiguous() or given.numel() < K
+                              and dyn is None):
+        raise ValueError("charge_mask: given must be a contiguous int64 list of at least k entries")
+    dev = x.device
+    if given is not None and given.numel() == 0:   # (k = 0: a list with no entries still selects the host-list form)
+        given = torch.zeros(1, dtype=torch.long, device=dev)
+    idx = torch.empty(max(K, 1), dtype=torch.long, device=dev)
+    labels = torch.empty(max(K, 1), dtype=torch.long, device=dev)
+    k = torch.empty(1, dtype=torch.int32, device=dev)
+    call("geossl_charge_mask_dyn", ptr(x), x.size(1), N, float(ratio), int(C), ptr(seed), ptr(given), ptr(idx),
+         ptr(labels), ptr(k), _dyn(dyn, "n_atoms"), stream())
+    return idx[:K], labels[:K], k
+
+
+class _ChargeHead(torch.autograd.Function):
+    """CrossEntropyLoss(Linear(F, C)(h[idx]), labels) (examples/pretrain_ChargePrediction.py:15-25,81) on
+    csrc/charge_head.hip -> loss (fp32 scalar).  The backward returns dh [N, F] (zero off the masked rows) through
+    autograd; dW / db go through autograd too, or, inside _lib.direct_grads() with dense fp32 .grad buffers, are added
+    into them."""
+
+    @staticmethod
+    def forward(ctx, h, W, b, idx, labels, k, status, dyn):
+        h = _f32(h)
+        N, F = h.shape
+        C = W.size(0)
+        K = idx.numel()
+        dev = h.device
+        Wd, bd = W.detach().contiguous(), b.detach().contiguous()
+        lib = _lib.load()
+        prob = torch.empty(max(K, 1), C, dtype=torch.float32, device=dev)
+        ws = torch.empty(int(lib.geossl_charge_head_fwd_workspace_floats(K)), dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        call("geossl_charge_head_fwd_dyn", ptr(h), N, F, ptr(Wd), ptr(bd), C, ptr(idx), ptr(labels), K, ptr(k),
+             ptr(prob), ptr(ws), ptr(loss), ptr(status), _dyn(dyn, "n_atoms"), stream())
+        ctx.save_for_backward(h, Wd, idx, labels, k, prob)
+        ctx.params, ctx.dyn = (W, b), dyn
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        h, Wd, idx, labels, k, prob = ctx.saved_tensors
+        W, b = ctx.params
+        N, F = h.shape
+        C, K = Wd.size(0), idx.numel()
+        direct = _lib.direct_grads_enabled((W, b))
+        dW, db = (W.grad, b.grad) if direct else (torch.empty_like(W), torch.empty_like(b))
+        dh = torch.empty_like(h)
+        ws = torch.empty(max(int(_lib.load().geossl_charge_head_bwd_workspace_floats(K, F, C)), 1), dtype=torch.float32,
+                         device=h.device)
+        g = gout.to(torch.float32).contiguous()
+        call("geossl_charge_head_bwd_dyn", ptr(h), N, F, ptr(Wd), C, ptr(idx), ptr(labels), K, ptr(k), ptr(prob),
+             ptr(g), ptr(dh), ptr(dW), ptr(db), ptr(ws), 1 if direct else 0, _dyn(ctx.dyn, "n_atoms"), stream())
+        if direct:
+            dW = db = None
+        return dh, dW, db, None, None, None, None, None
+
+
+def charge_head_width_ok(F, C):
+    """The widths the fused charge head serves: F = 64, 128, 256 or 512 (a wave holds one row) and 2 <= C <= 16."""
+    return bool(_lib.load().geossl_charge_head_width_ok(int(F), int(C)))
+
+
+def charge_head(h, W, b, idx, labels, k, status, dyn=None):
+    """The Charge Prediction loss of pretrain_ChargePrediction.py:81 -> loss: h [N, F] node features, W [C, F] / b [C]
+    the predictor's Linear, idx / labels int64 [K] the masked atoms and their original types with k (int32 [1] on the
+    device) real rows (charge_mask), status: an int32 word that a row out of range flags (the backbone's
+    _lib.StatusWord).  dyn (bucket.DynDims): N is a capacity, the real atom count is read on the device."""
+    _lib.require_cuda(h, W, b, idx, labels, k, status)
+    if (h.dim() != 2 or W.dim() != 2 or W.size(1) != h.size(1) or b.numel() != W.size(0)
+            or not charge_head_width_ok(h.size(1), W.size(0))):
+        raise ValueError("charge_head: h [N, F] with F in (64, 128, 256, 512), W [C, F] with 2 <= C <= 16, b [C]; "
+                         "got %s, %s, %s" % (tuple(h.shape), tuple(W.shape), tuple(b.shape)))
+    if idx.numel() != labels.numel() or idx.numel() > h.size(0):
+        raise ValueError("charge_head: idx and labels hold the same K <= N rows")
+    return _ChargeHead.apply(h, W, b, idx, labels, k, status, dyn)

@@ -396,7 +396,8 @@ class StepGraphs:
         self.modules = modules  # (backbone, head, head): what bucket.modules_ok looks at (None: no capacity buckets)
         # the random draws a step takes as static inputs (the contrastive objectives: the position noise only)
         self.noise_keys = _NOISE_KEYS if noise_keys is None else tuple(noise_keys)
-        self.views = views      # views of the molecules the backbone sees in a bucket (1: the Distance Prediction step)
+        # views of the molecules the backbone sees in a bucket (1: the Distance / Charge Prediction steps)
+        self.views = views
         self.graphs, self.pool = OrderedDict(), None
         self.enabled = True
         self.captures = 0
@@ -543,7 +544,10 @@ class StepGraphs:
         sn = {"pos_noise": torch.zeros(bkt.N_cap, 3, **f32), "dist_noise_1": torch.zeros(bkt.S_cap, 1, **f32),
               "dist_noise_2": torch.zeros(bkt.S_cap, 1, **f32),
               "noise_level_1": torch.zeros(B, dtype=torch.long, device=dev),
-              "noise_level_2": torch.zeros(B, dtype=torch.long, device=dev)}
+              "noise_level_2": torch.zeros(B, dtype=torch.long, device=dev),
+              # Charge Prediction's mask input: the device draw's seed, or the host-drawn list (k <= N entries)
+              "mask_seed": torch.zeros(1, dtype=torch.long, device=dev),
+              "mask_idx": torch.zeros(max(bkt.N_cap, 1), dtype=torch.long, device=dev)}
         sn = {k: sn[k] for k in self.noise_keys}
         g0 = dict(bucket=bkt, noise=sn, counts=counts)
         self.copy_noise(g0, noise)
@@ -631,14 +635,18 @@ class StepGraphs:
             return g["noise"]
         N, P, S, W = g["counts"]
         sn = g["noise"]
-        rows = {"pos_noise": N, "dist_noise_1": S, "dist_noise_2": S}   # (the noise levels are per molecule: B is exact)
+        # (the noise levels are per molecule: B is exact; a mask list holds k <= N entries, copy_noise writes k)
+        rows = {"pos_noise": N, "dist_noise_1": S, "dist_noise_2": S, "mask_idx": N}
         return {k: (v[:rows[k]] if k in rows else v) for k, v in sn.items()}
 
     @staticmethod
     def copy_noise(g, noise):
         into = StepGraphs.noise_views(g)
         for k in into:   # (the graph's own draws: all five of a DDM step)
-            into[k].copy_(noise[k].view_as(into[k]))
+            dst = into[k]
+            if k == "mask_idx":   # (the leading k entries: the kernel reads as many as the batch's k)
+                dst = dst[:noise[k].numel()]
+            dst.copy_(noise[k].view_as(dst))
 
     @staticmethod
     def refresh(g, batch, noise=None):
@@ -862,13 +870,14 @@ class _AutogradStep:
         from .NCSN import _head_params
         self.model, self.n1, self.n2 = model, n1, n2
         # "DDM" (two NCSN heads), "InfoNCE" / "EBM_NCE": no heads (n1 = n2 = None), the readout is part of the step, or
-        # "DistancePrediction": one head, the DistancePredictor (n1; n2 = None)
+        # "DistancePrediction" / "ChargePrediction": one head, the DistancePredictor / ChargePredictor (n1; n2 = None)
         self.objective = objective
         heads = [m for m in (n1, n2) if m is not None]
         # the parameters the step reaches (a parameter outside it - an atomref table, PaiNN's output layers - gets no
         # gradient at all, like in the eager path, not a zero one)
         backbone = model._params() if hasattr(model, "_params") else _schnet_step_params(model)
-        head_params = (lambda h: list(h.parameters())) if objective == "DistancePrediction" else _head_params
+        head_params = ((lambda h: list(h.parameters())) if objective in ("DistancePrediction", "ChargePrediction")
+                       else _head_params)
         seen, self.params = set(), []
         for p in list(backbone) + [q for h in heads for q in head_params(h)]:
             if id(p) not in seen and p.requires_grad:
@@ -902,6 +911,9 @@ class _AutogradStep:
                         self._where.append((sub._parameters, name, p, p.data_ptr(), p.requires_grad))
         self.graphs = {}   # (model_3d, normalize) -> StepGraphs
         self._cfg = None
+        # ChargePrediction: (masked atoms, k) of the step `run` just replayed, the graph's static outputs (the caller takes
+        # them at once and clears this)
+        self.extra = None
         self._side = torch.cuda.Stream(device=dev)   # the backward graphs replay here
         self._bwd_done = None                        # event behind the last backward replay
         self._ticket = None                          # the step whose gradients are in gflat: {"serial", "event", "g"}
@@ -928,6 +940,9 @@ class _AutogradStep:
         if self.objective == "DistancePrediction":
             from .pretrain_DistancePrediction import distance_step_fused
             return distance_step_fused(args, batch, self.model, self.n1)
+        if self.objective == "ChargePrediction":   # -> (loss, (masked atoms, k)): static outputs of the forward graph
+            from .pretrain_ChargePrediction import charge_step_fused
+            return charge_step_fused(args, batch, self.model, self.n1, noise)
         if self.objective != "DDM":   # -> (loss, counts): the counts are a static output of the forward graph
             return _contrastive_eager(self.objective, args, batch, self.model, mu, sigma, noise, True)
         return _do_ddm_eager(args, batch, self.model, mu, sigma, (self.n1, self.n2), noise, True, True)
@@ -1005,12 +1020,16 @@ class _AutogradStep:
             return None
         contrastive = self.objective in CONTRASTIVE_OPTIONS
         distance = self.objective == "DistancePrediction"   # (no random draws: the positions as they are)
+        # (the mask is the one draw: `noise` = {"mask_seed"} (device draw; a graph advances its own seed) or {"mask_idx"})
+        charge = self.objective == "ChargePrediction"
         normalize = bool(getattr(args, "normalize", False))
         if contrastive:   # (a graph binds T and num_neg: by-value arguments of its loss launches)
             cargs = ContrastiveArgs(args.model_3d, normalize, getattr(args, "T", 0.1), getattr(args, "num_neg", 1))
             key = (self.objective, args.model_3d, normalize, cargs.T, cargs.num_neg)
         elif distance:   # (the tuple option is part of each StepGraphs key: bucket key / structure fingerprint)
             key = (self.objective, args.model_3d)
+        elif charge:     # (a graph binds the ratio: a by-value argument of its mask launch)
+            key = (self.objective, args.model_3d, float(args.charge_masking_ratio), args.mask_rng)
         else:
             key = (args.model_3d, normalize)
         sg = self.graphs.get(key)
@@ -1022,11 +1041,14 @@ class _AutogradStep:
                                                normalize=normalize and not contrastive,
                                                modules=(self.model, self.n1, self.n2),
                                                noise_keys=("pos_noise",) if contrastive else
-                                               (() if distance else None), views=1 if distance else 2)
+                                               (() if distance else
+                                                (("mask_idx" if args.mask_rng == "numpy" else "mask_seed",) if charge
+                                                 else None)), views=1 if distance or charge else 2)
             sg.zero_with_refresh = self.gflat
         if not sg.enabled:
             return None
-        self._cfg = (cargs if contrastive else Args(args.model_3d, normalize and not distance), mu, sigma)
+        self._cfg = (cargs if contrastive else args if charge else Args(args.model_3d, normalize and not distance), mu,
+                     sigma)
         g = sg.lookup(batch)
         if g is None and not sg.capture_now(batch):
             # first sighting of an index structure that only its own graph can serve (sampled tuples, PaiNN edge lists,
@@ -1044,6 +1066,8 @@ class _AutogradStep:
         if g is None:
             if distance:
                 drawn = {}
+            elif charge:
+                drawn = noise
             elif contrastive:
                 drawn = draw_views_noise(batch, mu, sigma, device_noise, noise)
             else:
@@ -1058,6 +1082,9 @@ class _AutogradStep:
                 return None  # (the bucket refused the batch's tensors: this step as eager launches)
             if distance:
                 pass
+            elif charge:
+                if args.mask_rng == "numpy":   # (this step's host draw into the graph's static list)
+                    sg.copy_noise(g, noise)
             elif contrastive:
                 draw_views_noise(batch, mu, sigma, device_noise, noise, into=sg.noise_views(g))
             else:
@@ -1094,6 +1121,8 @@ class _AutogradStep:
             # the accuracy counts, read once the backward replay is queued: the host waits for the forward only (the
             # reference's own acc is a host value too, :137 / :170)
             return out, g["extra"].tolist()
+        if charge:
+            self.extra = g["extra"]
         return out
 
 

@@ -817,6 +817,52 @@ int geossl_distance_head_bwd_dyn(const float* h, int64_t N, int F, const float* 
                                  float* dh, float* dW, float* db, float* workspace, int accumulate,
                                  const int32_t* dyn_N, const int32_t* dyn_S, hipStream_t stream);
 
+/* ---- charge prediction: examples/pretrain_ChargePrediction.py:15-25,61-81 (csrc/charge_head.hip) ---------------------
+ * Mask draw and apply (geossl_charge_mask[_dyn], one block): x [N][x_cols] int64 atom features (column 0: the type);
+ * k (out, [1]) = trunc((double)N * ratio) - Python's int(M * ratio), geossl_charge_mask_count(N, ratio) on the host.
+ * Exactly one of seed / given is non-NULL:
+ *   seed: the k atoms are drawn on the device.  Atom i gets the 64-bit key (w0 << 32) | w1 of Philox-4x32-10 with
+ *     key = (seed[0] low, seed[0] high word), counter = (i, 0, 0, 0); the k atoms with the smallest (key, i) are taken
+ *     (a uniform k-subset: a radix select over the keys, equal keys by ascending i), written to idx [k] in ascending
+ *     atom order; then seed[0] += 1 (a replayed graph draws a fresh mask, the same seed value the same mask).
+ *   given: idx [k] = given[0 .. k) as it is (a host draw, np.random.choice(M, k, replace=False)).
+ * labels [k] (out) = x[idx[j]][0] before any write (-1 for an index outside [0, N)); then x[idx[j]][0] = C - 1 (the
+ * mask token) for every listed atom.  2 <= C <= 16, 0 <= ratio <= 1.
+ * Head (geossl_charge_head_*): h [N][F] node features (F = 64, 128, 256 or 512 and 2 <= C <= 16:
+ * geossl_charge_head_width_ok), W [C][F], bias [C], idx / labels [K] with k = k_dev[0] (NULL: k = K) real rows.
+ * Forward: logits_j = h[idx_j] W^T + bias, a max-subtracted log-softmax in fp32; prob [K][C] (out) = softmax rows;
+ *   loss [1] = mean_j (lse_j - logit_j[labels_j]) (fp64 sums in a fixed order; NaN for k = 0).  A row with idx outside
+ *   [0, N) or a label outside [0, C) reads nothing, adds NaN, gets a zero prob row and sets bit 0 of status[0].
+ *   workspace: geossl_charge_head_fwd_workspace_floats(K) floats, 8-byte aligned.
+ * Backward with the upstream gradient gout[0]: d_j = (prob_j - onehot(labels_j)) (gout / k); dh [N][F] (out) = 0 on
+ *   every row, d_j W on the rows idx_j (indices are distinct); dW [C][F] / db [C] (+)= sum_j d_j^T h[idx_j] / sum_j d_j
+ *   from per-block partials added in block order.  accumulate: dW / db (+)= instead of =.  k = 0: all zero.
+ *   workspace: geossl_charge_head_bwd_workspace_floats(K, F, C) floats.
+ * `_dyn`: N is a capacity and dyn_N (nullable) points at the real atom count; with k_dev, K is a capacity too.  Rows
+ *   past the real counts are neither read nor written.  No atomics beyond integer counts: the same bits every launch. */
+int64_t geossl_charge_mask_count(int64_t N, double ratio);
+int geossl_charge_mask(int64_t* x, int x_cols, int64_t N, double ratio, int C, int64_t* seed, const int64_t* given,
+                       int64_t* idx, int64_t* labels, int32_t* k, hipStream_t stream);
+int geossl_charge_mask_dyn(int64_t* x, int x_cols, int64_t N, double ratio, int C, int64_t* seed, const int64_t* given,
+                           int64_t* idx, int64_t* labels, int32_t* k, const int32_t* dyn_N, hipStream_t stream);
+int geossl_charge_head_width_ok(int F, int C);
+int64_t geossl_charge_head_fwd_workspace_floats(int64_t K);
+int64_t geossl_charge_head_bwd_workspace_floats(int64_t K, int F, int C);
+int geossl_charge_head_fwd(const float* h, int64_t N, int F, const float* W, const float* bias, int C,
+                           const int64_t* idx, const int64_t* labels, int64_t K, const int32_t* k_dev, float* prob,
+                           float* workspace, float* loss, int32_t* status, hipStream_t stream);
+int geossl_charge_head_fwd_dyn(const float* h, int64_t N, int F, const float* W, const float* bias, int C,
+                               const int64_t* idx, const int64_t* labels, int64_t K, const int32_t* k_dev, float* prob,
+                               float* workspace, float* loss, int32_t* status, const int32_t* dyn_N,
+                               hipStream_t stream);
+int geossl_charge_head_bwd(const float* h, int64_t N, int F, const float* W, int C, const int64_t* idx,
+                           const int64_t* labels, int64_t K, const int32_t* k_dev, const float* prob, const float* gout,
+                           float* dh, float* dW, float* db, float* workspace, int accumulate, hipStream_t stream);
+int geossl_charge_head_bwd_dyn(const float* h, int64_t N, int F, const float* W, int C, const int64_t* idx,
+                               const int64_t* labels, int64_t K, const int32_t* k_dev, const float* prob,
+                               const float* gout, float* dh, float* dW, float* db, float* workspace, int accumulate,
+                               const int32_t* dyn_N, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
