@@ -7,6 +7,12 @@ configuration the metric is quoted on); SURVEY.md §8(d) defines inputs, byte/fl
     python bench.py --gpus 1 --steps 100 --warmup 20
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+    python bench.py --full --gpus 1 --steps 100 --warmup 20
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: what the headline needs and
+nothing else.  --full adds everything else the benchmark measures or checks, after the timed steps: the secondary
+configurations (1 GPU, headline configuration), the CPU oracle's baseline and the parity of the HIP step against it, the
+eager per-kernel passes behind `roofline` / `kernel_ms`, and the loader / all-reduce diagnostics of `multi_gpu`.
 
 Rank 0 prints ONE compact JSON line on stdout (compact_line: < 8 KB, strict JSON, numbers only); the full detail
 object (workload / execution prose, every secondary's fields) goes to stderr and to gpurun_out/bench_detail.json.
@@ -711,7 +717,7 @@ class Workload:
 
 
 def secondary_line(dev, rank, world, steps, warmup, **kw):
-    """A secondary configuration timed inside the default run, so that it is observed by the driver: value, ms/step."""
+    """A secondary configuration timed inside a --full run, so that it is observed by the driver: value, ms/step."""
     n_batches = kw.pop("n_batches", 1)
     env = kw.pop("env", None) or {}
     want_roof = kw.pop("roofline", False)
@@ -750,7 +756,7 @@ def secondary_line(dev, rank, world, steps, warmup, **kw):
     return out
 
 
-# The secondary configurations of the default run: name -> (timed steps, warm-up steps, Workload arguments).  `distinct`
+# The secondary configurations of a --full run: name -> (timed steps, warm-up steps, Workload arguments).  `distinct`
 # lines are fresh random draws of molecules in random order (a shuffled loader, pretrain_GeoSSL.py:301), each batch visited
 # once, nothing primed - the captures fall into the timed region; their twins visit a few pre-collated batches in a fixed
 # order, primed (ragged sets: the first 16 draws of the distinct line's own pool - four batches of 128 molecules differ
@@ -827,9 +833,9 @@ def run_secondary(name, dev, rank, world):
 
 
 def forward_only_line(dev, rank, world):
-    """BASELINE configs[1] as a secondary of the default run (so that the driver observes it): value, ms/step, roofline."""
+    """BASELINE configs[1] as a secondary of a --full run (so that the driver observes it): value, ms/step, roofline."""
     args = types_namespace(mols=1024, molset="A", max_batches=8, warmup=10, steps=40, forces=False, no_cpu_baseline=True,
-                           no_graph=False)
+                           no_graph=False, full=True)
     try:
         out = forward_only(args, dev, rank, world, do_emit=False)
     except Exception as e:
@@ -841,7 +847,7 @@ def forward_only_line(dev, rank, world):
 
 def force_training_line(dev, backbone, mols=256, steps=40, warmup=6, use_graph=True):
     """A train-on-forces step (examples/finetune_md17.py:30-54: energy head, dE/dpos with create_graph, loss on energy and
-    force, backward through the force, optimiser) on the library's pieces - a secondary of the default run, so that the
+    force, backward through the force, optimiser) on the library's pieces - a secondary of a --full run, so that the
     driver sees the second-order route (the library's own tape, geossl_amd/tape.py), replayed as ONE
     captured HIP graph per batch structure (geossl_amd.graphed.ForceTrainer; use_graph=False: ~1000 eager launches)."""
     try:
@@ -900,7 +906,7 @@ def rccl_single_rank_line(mols=1024, steps=40, warmup=10):
                    GEOSSL_DIST_BACKEND="nccl")
         env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
-               "--mols", str(mols), "--no-secondary", "--no-cpu-baseline", "--no-roofline"]
+               "--mols", str(mols), "--full", "--no-secondary", "--no-cpu-baseline", "--no-roofline"]   # (allreduce_ms)
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=120, cwd=REPO)
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
         if r.returncode != 0 or not lines:
@@ -972,9 +978,10 @@ def forward_only(args, dev, rank, world, do_emit=True):
     elapsed = time.perf_counter() - t0
     timed_steps = args.steps
     if graphed is not None:
+        out = out.clone()
+    if graphed is not None and args.full:
         # a replay has no host-side launch boundaries to bracket: the entry points are timed over eager passes of the same
         # workload right after the timed region (rocprofv3 sees the replayed kernels and agrees, profiles/)
-        out = out.clone()
         timed_steps = min(args.steps, 10)
         for i in range(2):
             fwd(i, eager=True)
@@ -993,7 +1000,7 @@ def forward_only(args, dev, rank, world, do_emit=True):
     if rank != 0:
         return
     roof = None
-    evs = timers.get("geossl_cfconv_filter_fwd") or []
+    evs = (timers or {}).get("geossl_cfconv_filter_fwd") or []
     if evs:
         # the dominant kernel of a forward pass: the continuous-filter network of one view (no T store at inference)
         ms = float(np.mean([a.elapsed_time(b) for a, b in evs]))
@@ -1020,7 +1027,7 @@ def forward_only(args, dev, rank, world, do_emit=True):
                 "peak_note": "executed 16-bit MFMA flops (3 per fp32 product, one filter evaluation per undirected pair slot, "
                              "G padded to 64) over the 2.5 PFLOP/s dense peak"}
     cpu = None
-    if world == 1 and not args.no_cpu_baseline and not args.forces:
+    if world == 1 and args.full and not args.no_cpu_baseline and not args.forces:
         cpu = cpu_baseline_forward(seed=1000)
     result = {
         "metric": ("molecules/s/GPU SchNet energy + forces (QM9-sized, bs=1024) [SURVEY 8(f) N3]" if args.forces
@@ -1281,10 +1288,15 @@ def main():
     ap.add_argument("--precollated", action="store_true",
                     help="the form of rounds 1-5: pre-collated device-resident batches visited in a fixed order (no loader "
                          "in the timed region)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true", help="skip the eager per-kernel timing passes behind `roofline`")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beyond the headline: the secondary "
+                         "configurations, the CPU baseline and the parity against the oracle, the eager per-kernel passes "
+                         "behind `roofline` / `kernel_ms`, the loader and all-reduce diagnostics (about a minute more)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity")
+    ap.add_argument("--no-roofline", action="store_true",
+                    help="with --full: skip the eager per-kernel timing passes behind `roofline`")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary configurations the default 1-GPU run times after the headline")
+                    help="with --full: skip the secondary configurations a 1-GPU run of the headline times after it")
     ap.add_argument("--max-batches", type=int, default=97, help="distinct pre-collated batches per GPU (config 3: 97)")
     ap.add_argument("--cutoff", type=float, default=5.0,
                     help="SchNet radius: 5 A = BASELINE's bench configuration, 10 A = the reference's default (config.py:114)")
@@ -1353,12 +1365,13 @@ def main():
             torch.cuda.synchronize()
             with open(os.path.join(os.environ["GEOSSL_BENCH_RANK_LOSS"], "params_rank%d.txt" % rank), "w") as fh:
                 fh.write(hashlib.sha256(wl.trainer.flat.flat.detach().cpu().numpy().tobytes()).hexdigest())
-    diag = wl.diagnostics()      # (collective inside: every rank)
+    diag = wl.diagnostics() if args.full else {}     # (collective inside: every rank)
     if wl.rank_ms is not None:
         diag["rank_ms_per_step"] = {"min": min(wl.rank_ms), "max": max(wl.rank_ms)}
     roof, kern, calls_per_step, shape = None, {}, None, None
-    if rank == 0:
-        roof, kern, calls_per_step, shape = dominant_roofline(wl, 0 if args.no_roofline else min(args.steps, 10))
+    if rank == 0:   # (0 eager steps: only the batch's shape and the algorithmic model, for `step_roofline`)
+        prof_steps = min(args.steps, 10) if args.full and not args.no_roofline else 0
+        roof, kern, calls_per_step, shape = dominant_roofline(wl, prof_steps)
 
     if rank == 0:
         N, E, S, step_bytes, step_flops = (shape[k] for k in ("N", "E", "S", "step_bytes", "step_flops"))
@@ -1394,9 +1407,9 @@ def main():
         }
         headline = (args.model == "schnet" and args.mols == 1024 and args.molset == "A" and args.api == "trainer"
                     and CUTOFF == 5.0 and not args.no_graph and not args.precollated)
-        if world == 1 and headline and not args.no_secondary:
-            # Secondary configurations, timed here so that the driver observes them (20 steps each, a few seconds in all):
-            # the reference's own loop and batch size, ragged molecules, the second backbone.
+        if world == 1 and headline and args.full and not args.no_secondary:
+            # Secondary configurations, timed here so that the driver observes them (about a minute in all): the
+            # reference's own loop and batch size, ragged molecules, the second backbone.
             del wl
             torch.cuda.empty_cache()
             sec = {}
@@ -1418,8 +1431,8 @@ def main():
             if "value" in ref:
                 ref["vs_trainer"] = ref["value"] / value
             out["secondary"] = sec
-        out["cpu_baseline"] = None  # timed on rank 0 at N=1 only
-        if world == 1 and not args.no_cpu_baseline:
+        out["cpu_baseline"] = None  # timed on rank 0 at N=1 only (--full)
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(seed=1000) if args.model == "schnet" else cpu_baseline_painn(seed=1000)
             first = out["cpu_baseline"].pop("_first", None)
             if first is not None and CUTOFF == 5.0:

@@ -184,12 +184,12 @@ def test_bench_two_ranks_share_one_gpu(tmp_path):
     """`python bench.py --gpus 2` with no launcher around it - the command shape the driver uses: the parent (which never
     touches the GPU) starts two fresh ranks itself; they run bench.py's N > 1 branch (init_distributed, per-rank
     molecules and noise streams, barrier + max-over-ranks timing, all-reduce + Adam, the JSON line of rank 0) on the one
-    GPU of the box over gloo."""
+    GPU of the box over gloo; --full for the diagnostics of `multi_gpu`."""
     env = dict(os.environ, GEOSSL_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", GEOSSL_BENCH_RANK_LOSS=str(tmp_path))
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline", "--mols", "256", "--dataset-mols", "8192"]
+           "--full", "--no-cpu-baseline", "--mols", "256", "--dataset-mols", "8192"]
     with open(tmp_path / "out.log", "w") as fo, open(tmp_path / "err.log", "w") as fe:
         p = subprocess.Popen(cmd, env=env, stdout=fo, stderr=fe, cwd=REPO)
         try:

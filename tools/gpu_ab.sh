@@ -4,8 +4,8 @@ old=$1; shift
 out=gpurun_out/ab; mkdir -p $out
 [ -x scratch/split_probe ] && scratch/split_probe > $out/split_probe.txt 2>&1
 for i in 1 2; do
-  GEOSSL_HIP_LIB=$PWD/$old python bench.py --no-cpu-baseline --no-secondary "$@" | tail -1 > $out/old_$i.json
-  python bench.py --no-cpu-baseline --no-secondary "$@" | tail -1 > $out/new_$i.json
+  GEOSSL_HIP_LIB=$PWD/$old python bench.py --full --no-cpu-baseline --no-secondary "$@" | tail -1 > $out/old_$i.json
+  python bench.py --full --no-cpu-baseline --no-secondary "$@" | tail -1 > $out/new_$i.json
 done
 python - <<'PY'
 import json,glob

@@ -17,7 +17,7 @@ python tools/pmc_sq.py $(ls $out/sqp/sq_counter_collection.csv $out/sqp/*/sq_cou
   "painn/ddm-step/mols=1024/set=A/cutoff=5, tools/prof_step_painn.py 4 (eager steps)" "$head" k_painn > profiles/r03_pmc_sq_painn_${tag}.txt 2>> $out/sqp.log
 for extra in "--model painn --max-batches 8:painn" "--set B --max-batches 24:setB" "--cutoff 10:cutoff10" "--forward-only:forward_only" "--forces:forces" "--api reference:reference_api" "--mols 128:mols128" "--api reference --mols 128:reference_api_mols128"; do
   flags=${extra%%:*}; name=${extra##*:}
-  python bench.py $flags --steps 50 --warmup 10 --no-secondary 2>> $out/bench.err | tail -1 > profiles/r03_bench_${name}_${tag}.json
+  python bench.py $flags --full --steps 50 --warmup 10 --no-secondary 2>> $out/bench.err | tail -1 > profiles/r03_bench_${name}_${tag}.json
 done
 ls -la profiles | grep r03; tail -3 $out/refresh.log
 # only gpurun_out/ travels back from the GPU box: the profile files written above go there as well

@@ -39,8 +39,8 @@ tl painn_setC_mols128 --model painn --mols 128 --set C
 rocprofv3 --kernel-trace -d $out/trace_painn -o t -- python3 bench.py --model painn --steps 10 --warmup 3 --no-cpu-baseline > /dev/null 2>&1
 { echo "# rocprofv3 --kernel-trace -- python3 bench.py --model painn --steps 10 --warmup 3 --no-cpu-baseline, summarised by tools/rocpd_stats.py @ $head"
   python tools/rocpd_stats.py "$(ls $out/trace_painn/*.db $out/trace_painn/*/*.db 2>/dev/null | head -1)" 40; } > profiles/r05_bench_painn_${tag}_kernel_stats.txt
-python bench.py --model painn 2>/dev/null | tail -1 > profiles/r05_bench_painn_${tag}.json
-python bench.py --forward-only 2>/dev/null | tail -1 > profiles/r05_bench_forward_only_${tag}.json
+python bench.py --full --model painn 2>/dev/null | tail -1 > profiles/r05_bench_painn_${tag}.json
+python bench.py --full --forward-only 2>/dev/null | tail -1 > profiles/r05_bench_forward_only_${tag}.json
 # train-on-forces steps: which kernels are not the library's (second order on the tape)
 bash tools/gpu_force_train_trace.sh $head 256 6 > /dev/null 2>&1
 cut -c1-200 gpurun_out/force_train_non_library_kernels.txt > profiles/r05_force_train_non_library_kernels.txt

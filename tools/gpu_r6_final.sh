@@ -53,9 +53,9 @@ for bb in schnet painn; do
     python tools/rocpd_stats.py $(ls $out/ft_$bb/*.db $out/ft_$bb/*/*.db 2>/dev/null | head -1) 30 | cut -c1-150; } > profiles/${R}_force_train_${bb}_${tag}_kernel_stats.txt
 done
 # ---- bench lines (compact line + detail)
-python bench.py > profiles/${R}_bench_${tag}.json 2> $out/bench.err; cp gpurun_out/bench_detail.json profiles/${R}_bench_${tag}_detail.json
-python bench.py --model painn --no-secondary > profiles/${R}_bench_painn_${tag}.json 2> $out/bench_painn.err
-python bench.py --forward-only > profiles/${R}_bench_forward_only_${tag}.json 2> $out/bench_fwd.err
+python bench.py --full > profiles/${R}_bench_${tag}.json 2> $out/bench.err; cp "$(dirname $out)"/bench_detail.json profiles/${R}_bench_${tag}_detail.json
+python bench.py --full --model painn --no-secondary > profiles/${R}_bench_painn_${tag}.json 2> $out/bench_painn.err
+python bench.py --full --forward-only > profiles/${R}_bench_forward_only_${tag}.json 2> $out/bench_fwd.err
 # ---- long runs on shuffled epochs over the device-resident dataset (memory, RSS and step time flat; captures)
 { python tools/soak.py 3000 128 trainer painn C dataset 2>&1 | tail -11; python tools/soak.py 3000 128 trainer schnet C dataset 2>&1 | tail -11;
   python tools/soak.py 3000 128 reference schnet B dataset 2>&1 | tail -11; } > profiles/${R}_soak_${tag}.txt

@@ -4,7 +4,7 @@ out=gpurun_out/variants; mkdir -p $out; rm -f $out/*.json
 for i in 1 2; do
   for lib in "$@"; do
     if [ "$lib" = "-" ]; then name=intree; unset GEOSSL_HIP_LIB; else name=$(basename $lib .so); export GEOSSL_HIP_LIB=$PWD/$lib; fi
-    python bench.py --no-cpu-baseline --no-secondary --steps 60 --warmup 15 $BENCH_ARGS | tail -1 > $out/${name}_$i.json
+    python bench.py --full --no-cpu-baseline --no-secondary --steps 60 --warmup 15 $BENCH_ARGS | tail -1 > $out/${name}_$i.json
   done
 done
 unset GEOSSL_HIP_LIB
