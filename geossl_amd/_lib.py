@@ -262,6 +262,13 @@ PROTOTYPES = {
     "geossl_charge_head_fwd_dyn": (i32, [vp, i64, i32, vp, vp, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
     "geossl_charge_head_bwd": (i32, [vp, i64, i32, vp, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
     "geossl_charge_head_bwd_dyn": (i32, [vp, i64, i32, vp, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]),
+    # 3D InfoGraph discriminator head (csrc/infograph_head.hip)
+    "geossl_infograph_width_ok": (i32, [i32]),
+    "geossl_infograph_fwd_workspace_floats": (i64, [i64]),
+    "geossl_infograph_fwd": (i32, [vp, i64, i32, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "geossl_infograph_fwd_dyn": (i32, [vp, i64, i32, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "geossl_infograph_bwd": (i32, [vp, i64, i32, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "geossl_infograph_bwd_dyn": (i32, [vp, i64, i32, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
 }
 
 _lib = None

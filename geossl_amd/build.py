@@ -24,8 +24,9 @@ def _sources():
 # distance_head.hip: the same flag keeps v_pk_fma_f32 op_sel:[0,1,0] out of its projection GEMV (a bandwidth-bound pass
 # that packed fp32 does not speed up).
 # charge_head.hip: likewise (its row dot products and weight-gradient columns are small fp32 loops).
+# infograph_head.hip: likewise (per-lane dot products and fp32 fma chains over the features).
 SOURCE_FLAGS = {"painn_mma.hip": ["-fno-slp-vectorize"], "distance_head.hip": ["-fno-slp-vectorize"],
-                "charge_head.hip": ["-fno-slp-vectorize"]}
+                "charge_head.hip": ["-fno-slp-vectorize"], "infograph_head.hip": ["-fno-slp-vectorize"]}
 
 
 def _headers():

@@ -725,3 +725,108 @@ def charge_head(h, W, b, idx, labels, k, status, dyn=None):
     if idx.numel() != labels.numel() or idx.numel() > h.size(0):
         raise ValueError("charge_head: idx and labels hold the same K <= N rows")
     return _ChargeHead.apply(h, W, b, idx, labels, k, status, dyn)
+
+
+INFOGRAPH_READOUTS = {"add": 0, "sum": 0, "mean": 1}
+
+
+def _infograph_wgrad(s, dh, dW, accumulate):
+    """dW = s^T dh (linear_wgrad: A = s [B, F], B = dh [B, F]); F = 256 as four 128-column blocks of one launch."""
+    B, F = s.shape
+    if F <= 128:
+        linear_wgrad([(s, dh, dW, None)], B, F, F, accumulate=accumulate)
+        return
+    c = 128
+    probs = [(s[:, i:i + c], dh[:, j:j + c], dW[i:i + c, j:j + c], None) for i in range(0, F, c) for j in range(0, F, c)]
+    linear_wgrad(probs, B, c, c, accumulate=accumulate, lda=F, ldb=F, ldw=F)
+
+
+class _InfoGraphHead(torch.autograd.Function):
+    """The 3D InfoGraph loss (examples/pretrain_3DInfoGraph.py:56-76) on csrc/infograph_head.hip -> (loss fp32 scalar,
+    counts int32 [2] = #(pos > 0), #(neg < 0)).  m None: the readout of x over `layout` is part of the head (readout "add" /
+    "mean"); else m [B, F] is the caller's readout and gets its own gradient.  The backward returns dx (with the readout's
+    backward in it) and dm through autograd; dW goes through autograd too, or, inside _lib.direct_grads() with a dense
+    fp32 .grad, is added into it."""
+
+    @staticmethod
+    def forward(ctx, x, W, m, layout, readout, dyn):
+        x = _f32(x)
+        N, F = x.shape
+        B = int(layout.B)
+        dev = x.device
+        Wd = W.detach().contiguous()
+        mode = 2 if m is not None else INFOGRAPH_READOUTS[readout]
+        md = _f32(m) if m is not None else None
+        f32 = dict(dtype=torch.float32, device=dev)
+        s, h = torch.empty(B, F, **f32), torch.empty(B, F, **f32)
+        scores = torch.empty(2, N, **f32)
+        ws = torch.empty(int(_lib.load().geossl_infograph_fwd_workspace_floats(B)), **f32)
+        loss = torch.empty((), **f32)
+        counts = torch.empty(2, dtype=torch.int32, device=dev)
+        call("geossl_infograph_fwd_dyn", ptr(x), N, F, ptr(Wd), ptr(layout.mol_ptr), B, mode, ptr(md), ptr(s), ptr(h),
+             ptr(scores), ptr(ws), ptr(loss), ptr(counts), _dyn(dyn, "n_atoms"), stream())
+        ctx.save_for_backward(x, Wd, s, h, scores)
+        ctx.lay, ctx.mode, ctx.dyn, ctx.W = layout, mode, dyn, W
+        ctx.mark_non_differentiable(counts)
+        ctx.set_materialize_grads(False)   # (no zero-filled gradient of the counts: the backward is kernels only)
+        return loss, counts
+
+    @staticmethod
+    def backward(ctx, gout, _gcounts):
+        if gout is None:
+            return None, None, None, None, None, None
+        x, Wd, s, h, scores = ctx.saved_tensors
+        N, F = x.shape
+        B = s.size(0)
+        W = ctx.W
+        dx = torch.empty_like(x)
+        dm = torch.empty(B, F, dtype=torch.float32, device=x.device) if ctx.mode == 2 else None
+        dh = torch.empty(B, F, dtype=torch.float32, device=x.device)
+        g = gout.to(torch.float32).contiguous()
+        call("geossl_infograph_bwd_dyn", ptr(x), N, F, ptr(Wd), ptr(ctx.lay.mol_ptr), B, ctx.mode, ptr(s), ptr(h),
+             ptr(scores), ptr(g), ptr(dx), ptr(dm), ptr(dh), _dyn(ctx.dyn, "n_atoms"), stream())
+        direct = W.requires_grad and _lib.direct_grads_enabled((W,))
+        dW = None
+        if direct:
+            _infograph_wgrad(s, dh, W.grad, True)
+        elif ctx.needs_input_grad[1]:
+            dW = torch.empty_like(Wd)
+            _infograph_wgrad(s, dh, dW, False)
+        return dx, dW, dm, None, None, None
+
+
+def infograph_width_ok(F):
+    """The widths the fused InfoGraph head serves: F = 64, 128 or 256."""
+    return bool(_lib.load().geossl_infograph_width_ok(int(F)))
+
+
+def _check_infograph(x, W, layout):
+    _lib.require_cuda(x, W, layout.mol_ptr)
+    if x.dim() != 2 or W.dim() != 2 or tuple(W.shape) != (x.size(1), x.size(1)) or not infograph_width_ok(x.size(1)):
+        raise ValueError("infograph: node_repr [N, F] with F in (64, 128, 256) and W [F, F]; got %s, %s"
+                         % (tuple(x.shape), tuple(W.shape)))
+    if int(layout.B) < 1:
+        raise ValueError("infograph: at least one molecule")
+
+
+def infograph_head(h, W, layout, readout, dyn=None):
+    """3D InfoGraph with the readout inside the head (pretrain_3DInfoGraph.py:56-76 after the backbone's
+    return_latent=True call) -> (loss, counts): h [N, F] node features of atoms sorted by molecule, W [F, F] the
+    Discriminator's weight, layout: the batch's MolLayout (mol_ptr, B), readout "mean" / "add" ("sum"), the backbone's.
+    counts [2] int32 on the device: acc = (counts[0] + counts[1]) / (2 N).  dyn (bucket.DynDims): N is a capacity, the
+    real atom count is read on the device."""
+    _check_infograph(h, W, layout)
+    if readout not in INFOGRAPH_READOUTS:
+        raise ValueError("infograph_head: readout is 'mean', 'add' or 'sum', got %r" % (readout,))
+    return _InfoGraphHead.apply(h, W, None, layout, readout, dyn)
+
+
+def infograph_loss(node_repr, molecule_repr, W, layout):
+    """3D InfoGraph on a readout the caller brings (do_InfoGraph's arguments) -> (loss, counts); the gradient reaches
+    node_repr and molecule_repr [B, F] both."""
+    _check_infograph(node_repr, W, layout)
+    _lib.require_cuda(molecule_repr)
+    if molecule_repr.dim() != 2 or tuple(molecule_repr.shape) != (int(layout.B), node_repr.size(1)):
+        raise ValueError("infograph_loss: molecule_repr [B, F] with B = %d, got %s"
+                         % (int(layout.B), tuple(molecule_repr.shape)))
+    return _InfoGraphHead.apply(node_repr, W, molecule_repr, layout, None, None)

@@ -870,14 +870,15 @@ class _AutogradStep:
         from .NCSN import _head_params
         self.model, self.n1, self.n2 = model, n1, n2
         # "DDM" (two NCSN heads), "InfoNCE" / "EBM_NCE": no heads (n1 = n2 = None), the readout is part of the step, or
-        # "DistancePrediction" / "ChargePrediction": one head, the DistancePredictor / ChargePredictor (n1; n2 = None)
+        # "DistancePrediction" / "ChargePrediction": one head, the DistancePredictor / ChargePredictor (n1; n2 = None), or
+        # "InfoGraph": the Discriminator (n1; n2 = None), the readout is part of its head
         self.objective = objective
         heads = [m for m in (n1, n2) if m is not None]
         # the parameters the step reaches (a parameter outside it - an atomref table, PaiNN's output layers - gets no
         # gradient at all, like in the eager path, not a zero one)
         backbone = model._params() if hasattr(model, "_params") else _schnet_step_params(model)
-        head_params = ((lambda h: list(h.parameters())) if objective in ("DistancePrediction", "ChargePrediction")
-                       else _head_params)
+        head_params = ((lambda h: list(h.parameters()))
+                       if objective in ("DistancePrediction", "ChargePrediction", "InfoGraph") else _head_params)
         seen, self.params = set(), []
         for p in list(backbone) + [q for h in heads for q in head_params(h)]:
             if id(p) not in seen and p.requires_grad:
@@ -943,6 +944,9 @@ class _AutogradStep:
         if self.objective == "ChargePrediction":   # -> (loss, (masked atoms, k)): static outputs of the forward graph
             from .pretrain_ChargePrediction import charge_step_fused
             return charge_step_fused(args, batch, self.model, self.n1, noise)
+        if self.objective == "InfoGraph":   # -> (loss, counts): the counts are a static output of the forward graph
+            from .pretrain_3DInfoGraph import infograph_step_fused
+            return infograph_step_fused(args, batch, self.model, self.n1)
         if self.objective != "DDM":   # -> (loss, counts): the counts are a static output of the forward graph
             return _contrastive_eager(self.objective, args, batch, self.model, mu, sigma, noise, True)
         return _do_ddm_eager(args, batch, self.model, mu, sigma, (self.n1, self.n2), noise, True, True)
@@ -1015,18 +1019,19 @@ class _AutogradStep:
         return True
 
     def run(self, args, batch, mu, sigma, noise, device_noise):
-        """-> the loss (DDM) / (loss, counts as a host list) (contrastive), or None: run this step eagerly."""
+        """-> the loss (DDM) / (loss, counts as a host list) (contrastive, InfoGraph), or None: run this step eagerly."""
         if getattr(batch, "_dataset", None) is None and (not batch.positions.is_cuda or batch.positions.requires_grad):
             return None
         contrastive = self.objective in CONTRASTIVE_OPTIONS
         distance = self.objective == "DistancePrediction"   # (no random draws: the positions as they are)
         # (the mask is the one draw: `noise` = {"mask_seed"} (device draw; a graph advances its own seed) or {"mask_idx"})
         charge = self.objective == "ChargePrediction"
+        infograph = self.objective == "InfoGraph"   # (no random draws either)
         normalize = bool(getattr(args, "normalize", False))
         if contrastive:   # (a graph binds T and num_neg: by-value arguments of its loss launches)
             cargs = ContrastiveArgs(args.model_3d, normalize, getattr(args, "T", 0.1), getattr(args, "num_neg", 1))
             key = (self.objective, args.model_3d, normalize, cargs.T, cargs.num_neg)
-        elif distance:   # (the tuple option is part of each StepGraphs key: bucket key / structure fingerprint)
+        elif distance or infograph:   # (the tuple option is part of each StepGraphs key: bucket key / fingerprint)
             key = (self.objective, args.model_3d)
         elif charge:     # (a graph binds the ratio: a by-value argument of its mask launch)
             key = (self.objective, args.model_3d, float(args.charge_masking_ratio), args.mask_rng)
@@ -1041,14 +1046,14 @@ class _AutogradStep:
                                                normalize=normalize and not contrastive,
                                                modules=(self.model, self.n1, self.n2),
                                                noise_keys=("pos_noise",) if contrastive else
-                                               (() if distance else
+                                               (() if distance or infograph else
                                                 (("mask_idx" if args.mask_rng == "numpy" else "mask_seed",) if charge
-                                                 else None)), views=1 if distance or charge else 2)
+                                                 else None)), views=1 if distance or charge or infograph else 2)
             sg.zero_with_refresh = self.gflat
         if not sg.enabled:
             return None
-        self._cfg = (cargs if contrastive else args if charge else Args(args.model_3d, normalize and not distance), mu,
-                     sigma)
+        self._cfg = (cargs if contrastive else args if charge else
+                     Args(args.model_3d, normalize and not (distance or infograph)), mu, sigma)
         g = sg.lookup(batch)
         if g is None and not sg.capture_now(batch):
             # first sighting of an index structure that only its own graph can serve (sampled tuples, PaiNN edge lists,
@@ -1064,7 +1069,7 @@ class _AutogradStep:
             if t is not None and t["g"] is None and not t.get("used"):
                 t["g"] = self.gflat.clone()  # a step still waiting for its backward() keeps its gradients
         if g is None:
-            if distance:
+            if distance or infograph:
                 drawn = {}
             elif charge:
                 drawn = noise
@@ -1080,7 +1085,7 @@ class _AutogradStep:
         else:
             if not sg.refresh(g, batch):
                 return None  # (the bucket refused the batch's tensors: this step as eager launches)
-            if distance:
+            if distance or infograph:
                 pass
             elif charge:
                 if args.mask_rng == "numpy":   # (this step's host draw into the graph's static list)
@@ -1117,9 +1122,9 @@ class _AutogradStep:
             st.arm(every=8)
         out = _ReplayedLoss.apply(loss, self, self._ticket, *self.params).as_subclass(_StepLoss)
         out._geossl_step = (self, self._ticket)
-        if contrastive:
+        if contrastive or infograph:
             # the accuracy counts, read once the backward replay is queued: the host waits for the forward only (the
-            # reference's own acc is a host value too, :137 / :170)
+            # reference's own acc is a host value too, :137 / :170; pretrain_3DInfoGraph.py:72-74)
             return out, g["extra"].tolist()
         if charge:
             self.extra = g["extra"]

@@ -863,6 +863,38 @@ int geossl_charge_head_bwd_dyn(const float* h, int64_t N, int F, const float* W,
                                const float* gout, float* dh, float* dW, float* db, float* workspace, int accumulate,
                                const int32_t* dyn_N, hipStream_t stream);
 
+/* ---- 3D InfoGraph: examples/pretrain_3DInfoGraph.py:19-31,56-76 (csrc/infograph_head.hip) ---------------------------
+ * x [N][F] node features (F = 64, 128 or 256: geossl_infograph_width_ok), W [F][F] the Discriminator's weight,
+ * mol_ptr [B + 1] int32 offsets of the B >= 1 molecules (atoms sorted by molecule).  readout: 0 "add", 1 "mean"
+ * (sum / max(n_b, 1), the arithmetic of geossl_segment_reduce_fwd) of the rows of x, or 2: the caller's m_in [B][F]
+ * (m_in non-NULL exactly for 2).
+ * Forward: s [B][F] (out) = sigmoid(m), h [B][F] (out) = s W; scores [2][N] (out): pos_i = <x_i, h_b> at [i],
+ *   neg_i = <x_i, h_{(b+1) mod B}> at [N + i] for atom i of molecule b; loss [1] = mean_i softplus(-pos_i) +
+ *   mean_i softplus(neg_i) (BCEWithLogits against 1 and 0; fp64 sums in a fixed order, stored as fp32; no atoms: NaN);
+ *   counts [2] int32 = #(pos_i > 0), #(neg_i < 0).  workspace: geossl_infograph_fwd_workspace_floats(B) floats, 8-byte
+ *   aligned.
+ * Backward with the upstream gradient gout[0] and c = gout[0] / N: g_pos_i = (sigmoid(pos_i) - 1) c,
+ *   g_neg_i = sigmoid(neg_i) c; dh [B][F] (out) = sum_{i in b} g_pos_i x_i + sum_{i in (b-1) mod B} g_neg_i x_i;
+ *   dm_b = (dh_b W^T) s_b (1 - s_b); dx [N][F] (out) = g_pos_i h_b + g_neg_i h_{(b+1) mod B} plus the readout's backward
+ *   dm_b (/ max(n_b, 1) for "mean"), or, for readout 2, dm [B][F] (out; non-NULL exactly for 2) and no readout term.
+ *   dW = s^T dh is left to the caller (geossl_linear_wgrad).
+ * `_dyn`: N is a capacity (the row stride of scores) and dyn_N (nullable) points at the real atom count; mol_ptr holds
+ *   the real offsets.  Rows past the real count are neither read nor written.  No atomics: the same bits every launch. */
+int geossl_infograph_width_ok(int F);
+int64_t geossl_infograph_fwd_workspace_floats(int64_t B);
+int geossl_infograph_fwd(const float* x, int64_t N, int F, const float* W, const int32_t* mol_ptr, int64_t B,
+                         int readout, const float* m_in, float* s, float* h, float* scores, float* workspace,
+                         float* loss, int32_t* counts, hipStream_t stream);
+int geossl_infograph_fwd_dyn(const float* x, int64_t N, int F, const float* W, const int32_t* mol_ptr, int64_t B,
+                             int readout, const float* m_in, float* s, float* h, float* scores, float* workspace,
+                             float* loss, int32_t* counts, const int32_t* dyn_N, hipStream_t stream);
+int geossl_infograph_bwd(const float* x, int64_t N, int F, const float* W, const int32_t* mol_ptr, int64_t B,
+                         int readout, const float* s, const float* h, const float* scores, const float* gout,
+                         float* dx, float* dm, float* dh, hipStream_t stream);
+int geossl_infograph_bwd_dyn(const float* x, int64_t N, int F, const float* W, const int32_t* mol_ptr, int64_t B,
+                             int readout, const float* s, const float* h, const float* scores, const float* gout,
+                             float* dx, float* dm, float* dh, const int32_t* dyn_N, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
