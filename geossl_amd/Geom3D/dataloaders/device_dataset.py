@@ -63,11 +63,12 @@ class _Staging:
 
 class DeviceDataset:
     def __init__(self, x, positions, sizes, device, option="combination", radius=None, max_num_neighbors=32,
-                 bond_index=None, bond_counts=None):
+                 bond_index=None, bond_counts=None, y=None):
         """x [Ntot, C] int64, positions [Ntot, 3] float32 (numpy or tensors; molecule after molecule), sizes [M] atoms
         per molecule.  option: the AtomTupleExtractor enumeration of the batches drawn from it.  radius: also build the
         per-molecule radius_edge_index (PaiNN) on this geometry.  bond_index [2, Etot] (local atom indices, molecule
-        after molecule) with bond_counts [M]: the bond graph (``data.edge_index``) that atom masking walks."""
+        after molecule) with bond_counts [M]: the bond graph (``data.edge_index``) that atom masking walks.  y [M, T]
+        (or [M]): per-molecule targets, kept in device memory as float32 (the Supervised / fine-tuning steps)."""
         if option not in _OPTIONS:
             raise ValueError("option is 'combination' or 'permutation'")
         dev = torch.device(device)
@@ -100,6 +101,19 @@ class DeviceDataset:
             self._set_bonds(bond_index, bond_counts)
         if radius is not None:
             self._build_edges(float(radius), int(max_num_neighbors))
+        self.y, self._mol_off = None, None
+        if y is not None:
+            self.y = as_t(y, torch.float32)
+            if self.y.dim() == 1:
+                self.y = self.y.reshape(-1, 1)
+            if self.y.dim() != 2 or self.y.size(0) != M:
+                raise ValueError("y holds one row of targets per molecule: [%d, T], got %s" % (M, tuple(self.y.shape)))
+
+    def mol_off(self):
+        """The atom offsets of the molecules [M + 1] as an int64 device tensor (uploaded once, on first use)."""
+        if self._mol_off is None:
+            self._mol_off = torch.from_numpy(self.off).to(self.device)
+        return self._mol_off
 
     # ---- construction
     @classmethod
@@ -114,8 +128,12 @@ class DeviceDataset:
     @classmethod
     def from_data_list(cls, data_list, device, **kw):
         """From the reference's per-molecule records (``Data`` objects with ``x`` and ``positions``,
-        datasets_3D.py:69-80, and ``edge_index`` when every record has one): concatenated once, uploaded once."""
+        datasets_3D.py:69-80, ``edge_index`` when every record has one, and ``y`` - a row of targets per molecule, the
+        Molecule3D ``data.y`` - when every record has one): concatenated once, uploaded once."""
         x = torch.cat([torch.as_tensor(d.x) for d in data_list], dim=0)
+        ys = [getattr(d, "y", None) for d in data_list]
+        if "y" not in kw and data_list and all(y_ is not None for y_ in ys):
+            kw["y"] = torch.stack([torch.as_tensor(y_, dtype=torch.float32).reshape(-1) for y_ in ys], dim=0)
         pos = torch.cat([torch.as_tensor(d.positions) for d in data_list], dim=0)
         ei = [getattr(d, "edge_index", None) for d in data_list]
         if "bond_index" not in kw and data_list and all(e is not None for e in ei):
@@ -406,6 +424,19 @@ class DatasetBatch:
     batch = property(lambda self: self.materialize().batch)
     super_edge_index = property(lambda self: self.materialize().super_edge_index)
     radius_edge_index = property(lambda self: self.materialize().radius_edge_index)
+
+    @property
+    def y(self):
+        """The targets as the reference's collation holds them: the molecules' rows concatenated along dim 0 ([B * T];
+        ``batch.y.view(B, -1)[:, task_id]`` is a column).  None for a dataset without targets."""
+        ds = self._dataset
+        if ds.y is None:
+            return None
+        got = self.__dict__.get("_y")
+        if got is None:
+            ids = torch.from_numpy(self.ids).to(ds.device, non_blocking=False)
+            got = self.__dict__["_y"] = ds.y.index_select(0, ids).reshape(-1)
+        return got
 
     def to(self, device, **kw):
         """``batch.to(device)`` of the reference's loop (pretrain_GeoSSL.py:248): the molecules are there already."""

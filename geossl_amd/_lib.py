@@ -269,6 +269,20 @@ PROTOTYPES = {
     "geossl_infograph_fwd_dyn": (i32, [vp, i64, i32, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "geossl_infograph_bwd": (i32, [vp, i64, i32, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
     "geossl_infograph_bwd_dyn": (i32, [vp, i64, i32, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    # Supervised property head (csrc/property_head.hip)
+    "geossl_property_width_ok": (i32, [i32]),
+    "geossl_property_workspace_floats": (i64, [i64]),
+    "geossl_property_fwd": (i32, [vp, i64, i32, vp, i64, i32, i32, vp, vp, vp, vp, vp, i64, vp, i32, vp, vp, vp, vp, vp,
+                                  vp]),
+    "geossl_property_fwd_dyn": (i32, [vp, i64, i32, vp, i64, i32, i32, vp, vp, vp, vp, vp, i64, vp, i32, vp, vp, vp, vp,
+                                      vp, vp, vp]),
+    "geossl_property_predict": (i32, [vp, i64, i32, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "geossl_property_predict_dyn": (i32, [vp, i64, i32, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "geossl_property_bwd": (i32, [i64, i32, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp, i32, vp, vp, vp, vp, vp,
+                                  vp, i32, vp]),
+    "geossl_property_bwd_dyn": (i32, [i64, i32, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp, i32, vp, vp, vp, vp,
+                                      vp, vp, i32, vp, vp]),
+    "geossl_property_targets": (i32, [vp, i64, i32, i32, vp, vp, i64, vp, vp]),
 }
 
 _lib = None

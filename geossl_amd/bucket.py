@@ -194,9 +194,9 @@ def modules_ok(model, n1=None, n2=None):
     """The step of these modules can run on a bucket: the F = 128 chain path of SchNet / PaiNN (the chained row kernel is
     the one that takes a device-side row count) and the paired NCSN heads (two different modules of width 128).  No heads
     (n1 = n2 = None): the contrastive steps, whose loss reads the readout of the 2B molecules - exact counts, no capacity.
-    One DistancePredictor of width 2 * 128 / ChargePredictor of width 128 / Discriminator of width 128 (n2 = None): the
-    Distance / Charge Prediction and 3D InfoGraph steps on a one-view bucket (InfoGraph's readout reads view 0's B real
-    molecule offsets: exact counts)."""
+    One DistancePredictor of width 2 * 128 / ChargePredictor of width 128 / Discriminator of width 128 / property head of
+    width 128 (n2 = None): the Distance / Charge Prediction, 3D InfoGraph and Supervised steps on a one-view bucket
+    (InfoGraph's and the property head's readouts read view 0's B real molecule offsets: exact counts)."""
     import os
     from .Geom3D.models.painn import PaiNN
     from .Geom3D.models.schnet import SchNet
@@ -227,6 +227,9 @@ def modules_ok(model, n1=None, n2=None):
     from .pretrain_3DInfoGraph import Discriminator, fused_head_ok as infograph_head_ok, readout_of
     if isinstance(n1, Discriminator) and n2 is None:
         return infograph_head_ok(n1) and n1.weight.size(0) == 128 and readout_of(model) is not None
+    from .pretrain_Supervised import head_width, readout_of as property_readout_of
+    if isinstance(n1, (torch.nn.Linear, torch.nn.Sequential)) and n2 is None:
+        return head_width(n1) == 128 and property_readout_of(model) is not None
     if not (isinstance(n1, NCSN_version_03) and isinstance(n2, NCSN_version_03)) or n1 is n2 \
             or n1.emb_dim != 128 or n2.emb_dim != 128:
         return False

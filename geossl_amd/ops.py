@@ -830,3 +830,156 @@ def infograph_loss(node_repr, molecule_repr, W, layout):
         raise ValueError("infograph_loss: molecule_repr [B, F] with B = %d, got %s"
                          % (int(layout.B), tuple(molecule_repr.shape)))
     return _InfoGraphHead.apply(node_repr, W, molecule_repr, layout, None, None)
+
+
+PROPERTY_READOUTS = {"add": 0, "sum": 0, "mean": 1}
+PROPERTY_LOSSES = {"mae": 0, "mse": 1}
+
+
+def _property_w1_grad(dz, m, dW1, db1, accumulate):
+    """dW1 = dz^T m, db1 = column sums of dz (linear_wgrad: A = dz [B, F/2], B = m [B, F]); F = 256 as two 128-column
+    problems of one launch."""
+    B, K = dz.shape
+    F = m.size(1)
+    if F <= 128:
+        linear_wgrad([(dz, m, dW1, db1)], B, K, F, accumulate=accumulate)
+        return
+    c = 128
+    probs = [(dz, m[:, j:j + c], dW1[:, j:j + c], db1 if j == 0 else None) for j in range(0, F, c)]
+    linear_wgrad(probs, B, K, c, accumulate=accumulate, lda=K, ldb=F, ldw=F)
+
+
+class _PropertyHead(torch.autograd.Function):
+    """The Supervised step after the backbone (pretrain_Supervised.py:89-101) on csrc/property_head.hip -> (loss fp32
+    scalar, pred [B] fp32, non-differentiable).  params: (w, b) of Linear(F, 1), or (W1, b1, w2, b2) of the default
+    create_output_layers().  The backward returns dh (the readout's backward in it) and the head's gradients through
+    autograd, or, inside _lib.direct_grads() with dense fp32 .grad tensors, adds the head's gradients into them."""
+
+    @staticmethod
+    def forward(ctx, h, y, stats, layout, readout, loss_kind, dyn, *params):
+        h = _f32(h)
+        N, F = h.shape
+        B = int(layout.B)
+        dev = h.device
+        mlp = len(params) == 4
+        ps = [p.detach().contiguous() for p in params]
+        W1, b1 = ps[0], ps[1]
+        W2, b2 = (ps[2], ps[3]) if mlp else (None, None)
+        f32 = dict(dtype=torch.float32, device=dev)
+        m = torch.empty(B, F, **f32)
+        z = torch.empty(B, F // 2, **f32) if mlp else None
+        pred = torch.empty(B, **f32)
+        ws = torch.empty(int(_lib.load().geossl_property_workspace_floats(B)), **f32)
+        loss = torch.empty((), **f32)
+        call("geossl_property_fwd_dyn", ptr(h), N, F, ptr(layout.mol_ptr), B, PROPERTY_READOUTS[readout],
+             1 if mlp else 0, ptr(W1), ptr(b1), ptr(W2), ptr(b2), ptr(y), y.stride(0), ptr(stats),
+             PROPERTY_LOSSES[loss_kind], ptr(m), ptr(z), ptr(pred), ptr(ws), ptr(loss), _dyn(dyn, "n_atoms"), stream())
+        ctx.save_for_backward(m, z, pred, y, stats, W1, W2)
+        ctx.lay, ctx.readout, ctx.loss_kind, ctx.dyn, ctx.params, ctx.N = layout, readout, loss_kind, dyn, params, N
+        ctx.mark_non_differentiable(pred)
+        ctx.set_materialize_grads(False)
+        return loss, pred
+
+    @staticmethod
+    def backward(ctx, gout, _gpred):
+        params = ctx.params
+        none = (None,) * (7 + len(params))
+        if gout is None:
+            return none
+        m, z, pred, y, stats, W1, W2 = ctx.saved_tensors
+        B, F = m.shape
+        mlp = len(params) == 4
+        dev = m.device
+        dh = torch.empty(ctx.N, F, dtype=torch.float32, device=dev)
+        dz = torch.empty(B, F // 2, dtype=torch.float32, device=dev) if mlp else None
+        ws = torch.empty(int(_lib.load().geossl_property_workspace_floats(B)), dtype=torch.float32, device=dev)
+        g = gout.to(torch.float32).contiguous()
+        live = [p for p in params if p.requires_grad]
+        direct = bool(live) and _lib.direct_grads_enabled(live)
+        grads = [None] * len(params)
+        for i, p in enumerate(params):
+            if direct:
+                grads[i] = p.grad if p.requires_grad else None
+            elif ctx.needs_input_grad[7 + i]:
+                grads[i] = torch.empty_like(p, dtype=torch.float32)
+        # the vector gradients of the launch: (w, b) of head 0, (w2, b2) of head 1
+        vw, vb = (grads[2], grads[3]) if mlp else (grads[0], grads[1])
+        call("geossl_property_bwd_dyn", ctx.N, F, ptr(ctx.lay.mol_ptr), B, PROPERTY_READOUTS[ctx.readout],
+             1 if mlp else 0, ptr(W1), ptr(W2), ptr(m), ptr(z), ptr(pred), ptr(y), y.stride(0), ptr(stats),
+             PROPERTY_LOSSES[ctx.loss_kind], ptr(g), ptr(dh), ptr(dz), ptr(vw), ptr(vb), ptr(ws), 1 if direct else 0,
+             _dyn(ctx.dyn, "n_atoms"), stream())
+        if mlp and (grads[0] is not None or grads[1] is not None):
+            dW1 = grads[0] if grads[0] is not None else torch.empty_like(W1)
+            _property_w1_grad(dz, m, dW1, grads[1], direct)
+        if direct:
+            grads = [None] * len(params)
+        return (dh, None, None, None, None, None, None) + tuple(grads)
+
+
+def property_width_ok(F):
+    """The widths the fused property head serves: F = 64, 128 or 256."""
+    return bool(_lib.load().geossl_property_width_ok(int(F)))
+
+
+def _check_property(h, layout, readout, params):
+    _lib.require_cuda(h, layout.mol_ptr, *params)
+    F = h.size(1) if h.dim() == 2 else -1
+    if h.dim() != 2 or not property_width_ok(F):
+        raise ValueError("property head: h [N, F] with F in (64, 128, 256), got %s" % (tuple(h.shape),))
+    shapes = [tuple(p.shape) for p in params]
+    if shapes not in ([(1, F), (1,)], [(F // 2, F), (F // 2,), (1, F // 2), (1,)]):
+        raise ValueError("property head: Linear(F, 1) or Dense(F, F/2) + Dense(F/2, 1) parameters, got %s" % (shapes,))
+    if readout not in PROPERTY_READOUTS:
+        raise ValueError("property head: readout is 'mean', 'add' or 'sum', got %r" % (readout,))
+    if int(layout.B) < 1:
+        raise ValueError("property head: at least one molecule")
+
+
+def _property_stats(stats, device):
+    if not torch.is_tensor(stats):
+        stats = torch.tensor([float(stats[0]), float(stats[1])], dtype=torch.float32).to(device)
+    if stats.dtype != torch.float32 or stats.numel() != 2 or not stats.is_cuda or not stats.is_contiguous():
+        raise ValueError("property head: stats is (mean, std), or a float32 [2] device tensor")
+    return stats
+
+
+def property_head(h, params, layout, readout, y, stats, loss="mae", dyn=None):
+    """The Supervised loss with the readout inside the head -> (loss, pred): h [N, F] per-atom latent of atoms sorted by
+    molecule (the backbone's latent_only output), params (w, b) of Linear(F, 1) or (W1, b1, w2, b2) of PaiNN's default
+    create_output_layers(), layout: the batch's MolLayout, readout "mean" / "add" ("sum"), y [B] the target column (any
+    stride), stats (mean, std) - a float32 [2] device tensor is read at launch time, so a replayed graph sees new values;
+    loss "mae" (L1) or "mse".  pred [B] is the normalised prediction.  dyn (bucket.DynDims): N is a capacity, the real
+    atom count is read on the device."""
+    _check_property(h, layout, readout, params)
+    if loss not in PROPERTY_LOSSES:
+        raise ValueError("property head: loss is 'mae' or 'mse', got %r" % (loss,))
+    B = int(layout.B)
+    _lib.require_cuda(y)
+    if y.dim() != 1 or y.numel() != B or y.dtype != torch.float32 or y.stride(0) < 1:
+        raise ValueError("property head: y is a float32 [B] column, B = %d, got %s" % (B, tuple(y.shape)))
+    stats = _property_stats(stats, h.device)
+    return _PropertyHead.apply(h, y, stats, layout, readout, loss, dyn, *params)
+
+
+def property_predict(h, params, layout, readout, stats, dyn=None):
+    """eval() of finetune_qm9.py:290-374 after the backbone: pred * std + mean [B] (no autograd)."""
+    _check_property(h, layout, readout, params)
+    stats = _property_stats(stats, h.device)
+    h = _f32(h.detach())
+    N, F = h.shape
+    B = int(layout.B)
+    ps = [p.detach().contiguous() for p in params]
+    mlp = len(ps) == 4
+    pred = torch.empty(B, dtype=torch.float32, device=h.device)
+    call("geossl_property_predict_dyn", ptr(h), N, F, ptr(layout.mol_ptr), B, PROPERTY_READOUTS[readout], 1 if mlp else 0,
+         ptr(ps[0]), ptr(ps[1]), ptr(ps[2] if mlp else None), ptr(ps[3] if mlp else None), ptr(stats), ptr(pred),
+         _dyn(dyn, "n_atoms"), stream())
+    return pred
+
+
+def property_targets(y, task_id, mol_off, src_off, B, out):
+    """out [B] = y[m, task_id] of the dataset molecules whose first atoms are src_off [B] (int32, device): y [M, T]
+    float32, mol_off [M + 1] int64 on the device."""
+    call("geossl_property_targets", ptr(y), y.size(0), y.size(1), int(task_id), ptr(mol_off), src_off, int(B), ptr(out),
+         stream())
+    return out

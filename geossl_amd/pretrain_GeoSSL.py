@@ -547,7 +547,9 @@ class StepGraphs:
               "noise_level_2": torch.zeros(B, dtype=torch.long, device=dev),
               # Charge Prediction's mask input: the device draw's seed, or the host-drawn list (k <= N entries)
               "mask_seed": torch.zeros(1, dtype=torch.long, device=dev),
-              "mask_idx": torch.zeros(max(bkt.N_cap, 1), dtype=torch.long, device=dev)}
+              "mask_idx": torch.zeros(max(bkt.N_cap, 1), dtype=torch.long, device=dev),
+              # the Supervised step's target column (B exact)
+              "target": torch.zeros(B, **f32)}
         sn = {k: sn[k] for k in self.noise_keys}
         g0 = dict(bucket=bkt, noise=sn, counts=counts)
         self.copy_noise(g0, noise)
@@ -871,14 +873,16 @@ class _AutogradStep:
         self.model, self.n1, self.n2 = model, n1, n2
         # "DDM" (two NCSN heads), "InfoNCE" / "EBM_NCE": no heads (n1 = n2 = None), the readout is part of the step, or
         # "DistancePrediction" / "ChargePrediction": one head, the DistancePredictor / ChargePredictor (n1; n2 = None), or
-        # "InfoGraph": the Discriminator (n1; n2 = None), the readout is part of its head
+        # "InfoGraph": the Discriminator (n1; n2 = None), the readout is part of its head, or
+        # "Supervised": graph_pred_linear (n1; n2 = None), the readout is part of its head
         self.objective = objective
         heads = [m for m in (n1, n2) if m is not None]
         # the parameters the step reaches (a parameter outside it - an atomref table, PaiNN's output layers - gets no
         # gradient at all, like in the eager path, not a zero one)
         backbone = model._params() if hasattr(model, "_params") else _schnet_step_params(model)
         head_params = ((lambda h: list(h.parameters()))
-                       if objective in ("DistancePrediction", "ChargePrediction", "InfoGraph") else _head_params)
+                       if objective in ("DistancePrediction", "ChargePrediction", "InfoGraph", "Supervised")
+                       else _head_params)
         seen, self.params = set(), []
         for p in list(backbone) + [q for h in heads for q in head_params(h)]:
             if id(p) not in seen and p.requires_grad:
@@ -947,6 +951,9 @@ class _AutogradStep:
         if self.objective == "InfoGraph":   # -> (loss, counts): the counts are a static output of the forward graph
             from .pretrain_3DInfoGraph import infograph_step_fused
             return infograph_step_fused(args, batch, self.model, self.n1)
+        if self.objective == "Supervised":   # (the target column is the graph's static input "target")
+            from .pretrain_Supervised import supervised_step_fused
+            return supervised_step_fused(args, batch, self.model, self.n1, noise["target"], args.stats, args.loss)[0]
         if self.objective != "DDM":   # -> (loss, counts): the counts are a static output of the forward graph
             return _contrastive_eager(self.objective, args, batch, self.model, mu, sigma, noise, True)
         return _do_ddm_eager(args, batch, self.model, mu, sigma, (self.n1, self.n2), noise, True, True)
@@ -1027,6 +1034,8 @@ class _AutogradStep:
         # (the mask is the one draw: `noise` = {"mask_seed"} (device draw; a graph advances its own seed) or {"mask_idx"})
         charge = self.objective == "ChargePrediction"
         infograph = self.objective == "InfoGraph"   # (no random draws either)
+        # (no draws: the batch's target column is the one per-step input beside the molecules)
+        supervised = self.objective == "Supervised"
         normalize = bool(getattr(args, "normalize", False))
         if contrastive:   # (a graph binds T and num_neg: by-value arguments of its loss launches)
             cargs = ContrastiveArgs(args.model_3d, normalize, getattr(args, "T", 0.1), getattr(args, "num_neg", 1))
@@ -1035,6 +1044,8 @@ class _AutogradStep:
             key = (self.objective, args.model_3d)
         elif charge:     # (a graph binds the ratio: a by-value argument of its mask launch)
             key = (self.objective, args.model_3d, float(args.charge_masking_ratio), args.mask_rng)
+        elif supervised:   # (a graph binds the loss kind; the task column is chosen when the targets are written)
+            key = (self.objective, args.model_3d, args.loss, args.task_id)
         else:
             key = (args.model_3d, normalize)
         sg = self.graphs.get(key)
@@ -1048,11 +1059,12 @@ class _AutogradStep:
                                                noise_keys=("pos_noise",) if contrastive else
                                                (() if distance or infograph else
                                                 (("mask_idx" if args.mask_rng == "numpy" else "mask_seed",) if charge
-                                                 else None)), views=1 if distance or charge or infograph else 2)
+                                                 else (("target",) if supervised else None))),
+                                               views=1 if distance or charge or infograph or supervised else 2)
             sg.zero_with_refresh = self.gflat
         if not sg.enabled:
             return None
-        self._cfg = (cargs if contrastive else args if charge else
+        self._cfg = (cargs if contrastive else args if charge or supervised else
                      Args(args.model_3d, normalize and not (distance or infograph)), mu, sigma)
         g = sg.lookup(batch)
         if g is None and not sg.capture_now(batch):
@@ -1073,6 +1085,9 @@ class _AutogradStep:
                 drawn = {}
             elif charge:
                 drawn = noise
+            elif supervised:
+                from .pretrain_Supervised import target_column
+                drawn = {"target": target_column(batch, args.task_id)}
             elif contrastive:
                 drawn = draw_views_noise(batch, mu, sigma, device_noise, noise)
             else:
@@ -1090,6 +1105,9 @@ class _AutogradStep:
             elif charge:
                 if args.mask_rng == "numpy":   # (this step's host draw into the graph's static list)
                     sg.copy_noise(g, noise)
+            elif supervised:
+                from .pretrain_Supervised import write_targets
+                write_targets(g, batch, args.task_id)
             elif contrastive:
                 draw_views_noise(batch, mu, sigma, device_noise, noise, into=sg.noise_views(g))
             else:

@@ -895,6 +895,53 @@ int geossl_infograph_bwd_dyn(const float* x, int64_t N, int F, const float* W, c
                              int readout, const float* s, const float* h, const float* scores, const float* gout,
                              float* dx, float* dm, float* dh, const int32_t* dyn_N, hipStream_t stream);
 
+/* ---- Supervised property head: examples/pretrain_Supervised.py:79-104, finetune_qm9.py:163-384 (csrc/property_head.hip)
+ * h [N][F] per-atom latent (F = 64, 128 or 256: geossl_property_width_ok), mol_ptr [B + 1] int32 offsets of the B >= 1
+ * molecules (atoms sorted by molecule).  readout: 0 "add", 1 "mean" (sum / max(n_b, 1), the arithmetic of
+ * geossl_segment_reduce_fwd).  head 0: Linear(F, 1), W1 = w [F], b1 = b [1], W2 = b2 = NULL; head 1: Dense(F, F/2, silu)
+ * then Dense(F/2, 1), W1 [F/2][F], b1 [F/2], W2 = w2 [F/2], b2 [1].  stats [2] = (mean, std) in device memory.
+ * y: target of molecule b at y[b * y_stride].  loss_kind: 0 L1, 1 MSE.
+ * Forward: m [B][F] (out) = readout; z [B][F/2] (out, head 1) = pre-activation; pred [B] (out); t_b = (y_b - mean) / std
+ *   (fp32, two roundings); loss [1] = mean_b |pred_b - t_b| or mean_b (pred_b - t_b)^2 (fp64 sum in a fixed order,
+ *   stored as fp32).  workspace: geossl_property_workspace_floats(B) floats, 8-byte aligned.
+ * Predict: pred [B] (out) = pred_b * std + mean (eval()); no loss, no m / z.
+ * Backward with gout[0]: dpred_b = sign(pred_b - t_b) gout / B (sign(0) = 0) or (2 / B) (pred_b - t_b) gout;
+ *   dh [N][F] (out) = dm_b (/ max(n_b, 1) for "mean") on every atom of b, dm_b = dpred_b w (head 0) or
+ *   dz_b W1 with dz [B][F/2] (out, head 1) = dpred_b w2 silu'(z_b);  dw / db (nullable; head 0: dL/dw [F], dL/db [1];
+ *   head 1: dL/dw2 [F/2], dL/db2 [1]) written, or added to with accumulate = 1.  Head 1's dW1 = dz^T m and db1 are left to
+ *   the caller (geossl_linear_wgrad).
+ * `_dyn`: N is a capacity and dyn_N (nullable) points at the real atom count; mol_ptr holds the real offsets.  No atom
+ *   row at or past the real count is read or written.  No atomics: the same bits every launch.
+ * geossl_property_targets: out[b] = y[m * T + task_id] for the dataset molecule m whose first atom is src_off[b]
+ *   (mol_off [M + 1] int64, strictly increasing; NaN when no molecule starts there). */
+int geossl_property_width_ok(int F);
+int64_t geossl_property_workspace_floats(int64_t B);
+int geossl_property_fwd(const float* h, int64_t N, int F, const int32_t* mol_ptr, int64_t B, int readout, int head,
+                        const float* W1, const float* b1, const float* W2, const float* b2, const float* y,
+                        int64_t y_stride, const float* stats, int loss_kind, float* m, float* z, float* pred,
+                        float* workspace, float* loss, hipStream_t stream);
+int geossl_property_fwd_dyn(const float* h, int64_t N, int F, const int32_t* mol_ptr, int64_t B, int readout, int head,
+                            const float* W1, const float* b1, const float* W2, const float* b2, const float* y,
+                            int64_t y_stride, const float* stats, int loss_kind, float* m, float* z, float* pred,
+                            float* workspace, float* loss, const int32_t* dyn_N, hipStream_t stream);
+int geossl_property_predict(const float* h, int64_t N, int F, const int32_t* mol_ptr, int64_t B, int readout, int head,
+                            const float* W1, const float* b1, const float* W2, const float* b2, const float* stats,
+                            float* pred, hipStream_t stream);
+int geossl_property_predict_dyn(const float* h, int64_t N, int F, const int32_t* mol_ptr, int64_t B, int readout,
+                                int head, const float* W1, const float* b1, const float* W2, const float* b2,
+                                const float* stats, float* pred, const int32_t* dyn_N, hipStream_t stream);
+int geossl_property_bwd(int64_t N, int F, const int32_t* mol_ptr, int64_t B, int readout, int head, const float* W1,
+                        const float* W2, const float* m, const float* z, const float* pred, const float* y,
+                        int64_t y_stride, const float* stats, int loss_kind, const float* gout, float* dh, float* dz,
+                        float* dw, float* db, float* workspace, int accumulate, hipStream_t stream);
+int geossl_property_bwd_dyn(int64_t N, int F, const int32_t* mol_ptr, int64_t B, int readout, int head, const float* W1,
+                            const float* W2, const float* m, const float* z, const float* pred, const float* y,
+                            int64_t y_stride, const float* stats, int loss_kind, const float* gout, float* dh, float* dz,
+                            float* dw, float* db, float* workspace, int accumulate, const int32_t* dyn_N,
+                            hipStream_t stream);
+int geossl_property_targets(const float* y, int64_t M, int T, int task_id, const int64_t* mol_off,
+                            const int32_t* src_off, int64_t B, float* out, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
