@@ -29,7 +29,8 @@ class GraphedForward:
 
     def _eager(self, x, positions, batch_vec):
         with torch.no_grad():
-            return self.model(x[:, 0], positions, batch_vec, return_latent=self.return_latent)
+            z = x if x.dim() == 1 else x[:, 0]   # (1-D x: a batch of DatasetMD17 / finetune_md17.py's format)
+            return self.model(z, positions, batch_vec, return_latent=self.return_latent)
 
     def __call__(self, batch):
         from . import bucket as bk
@@ -53,6 +54,8 @@ class GraphedForward:
         else:
             self.graphs.move_to_end(fp)
             sx, sp, dx, dp = batch.x, batch.positions, g["x"], g["pos"]
+            if sx.shape != dx.shape:   # (1-D against 2-D x: the fingerprint holds no x; byte copies would overrun)
+                return self._eager(batch.x, batch.positions, batch.batch)
             if sx.is_contiguous() and sp.is_contiguous() and sx.dtype == dx.dtype and sp.dtype == dp.dtype:
                 call("geossl_copy2", ptr(dx), ptr(sx), dx.numel() * dx.element_size(), ptr(dp), ptr(sp),
                      dp.numel() * dp.element_size(), stream())
@@ -142,7 +145,7 @@ class ForceTrainer:
         if self.model_3d == "painn":
             rep = self.model(x, pos, rei, batch_vec)
         else:
-            rep = self.model(x[:, 0], pos, batch_vec)
+            rep = self.model(x if x.dim() == 1 else x[:, 0], pos, batch_vec)   # (MD17 batches: 1-D x, datasets_MD17.py:61)
         energy = self.head(rep).squeeze(1)                                                              # :36-44
         dE = torch.autograd.grad(energy, pos, grad_outputs=ones, create_graph=True, retain_graph=True)[0]   # :46
         loss = ops.energy_force_loss(energy, y_e, dE, y_f, self.coeff[0], self.coeff[1], self.loss_kind)    # :46-51
@@ -230,6 +233,8 @@ class ForceTrainer:
                     self._seen.popitem(last=False)
             else:
                 self.graphs.move_to_end(key)
+            if g is not None and g["x"].shape != batch.x.shape:   # (1-D against 2-D x: the key holds no x)
+                g = None
         if g is None:
             ones = torch.ones(batch.num_graphs, dtype=torch.float32, device=batch.positions.device)
             loss = self._body(batch.x, batch.positions, batch.batch, getattr(batch, "radius_edge_index", None),

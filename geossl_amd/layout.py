@@ -13,6 +13,10 @@ from .switches import env as _env
 from . import _lib
 from ._lib import call, ptr, stream
 
+# largest molecule the one-block-per-molecule aggregation (geossl_cfconv_aggregate: 2 n F floats of LDS, at most 160 KB)
+# takes at every width up to F = 128; larger ones need the work list of the by-target kernels
+AGG_LDS_MAX_N = 128
+
 
 class MolLayout:
     """mol_ptr / pair-slot enumeration of a sorted ``batch`` vector.
@@ -72,9 +76,16 @@ class MolLayout:
         # by descending size, the 21..33-atom ones as 2 or 4 work items (one group of target atoms each)
         # (molecules above 33 atoms - Molecule3D with hydrogens - as 16 items each: lists of target atoms, no size class)
         self.agg_work, self.agg_targets = None, False
-        if sizes is not None and 20 < self.max_n <= 255 and B < (1 << 24) and not _env("GEOSSL_AGG_NO_SPLIT"):
+        # (without host sizes, molecules above AGG_LDS_MAX_N atoms still need the list: the one-block-per-molecule kernel
+        # keeps a molecule's rows in LDS, 2 n F floats - past ~150 atoms at F = 128 it cannot launch.  Their sizes are read
+        # back once, for such batches only; the stream was drained for max_n above already.)
+        work_sizes = sizes
+        if sizes is None and AGG_LDS_MAX_N < self.max_n <= 255:
+            work_sizes = (self.mol_ptr[1:] - self.mol_ptr[:-1]).tolist()
+        if work_sizes is not None and 20 < self.max_n <= 255 and B < (1 << 24) and not _env("GEOSSL_AGG_NO_SPLIT"):
             self.agg_targets = aggregate_by_targets(B)
-            self.agg_work = torch.from_numpy(aggregate_work_list(np.asarray(sizes, dtype=np.int64), self.agg_targets)).to(dev)
+            self.agg_work = torch.from_numpy(aggregate_work_list(np.asarray(work_sizes, dtype=np.int64),
+                                                                 self.agg_targets)).to(dev)
         self.device = dev
         self._batch_version = batch._version
         self._sizes_host = sizes

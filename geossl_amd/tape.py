@@ -224,6 +224,9 @@ class _LazyV(V):
     def t(self):
         if self._t is None:
             self.pending.flush()
+            if self._t is None:   # a part of a sum, or a sum taken over by a larger one: the batch formed no value for it
+                raise RuntimeError("deferred weight gradient read after it was summed into another one: it holds no value "
+                                   "of its own (read the sum)")
         return self._t
 
     @t.setter
@@ -264,7 +267,8 @@ class _TnNode(_LazyV):
 
 class _SumNode(_LazyV):
     """The sum of deferred products with one shape (contributions to one weight): formed by the batched launches
-    themselves - the k-th part of every sum goes into round k, which accumulates onto round k - 1."""
+    themselves - the k-th part of every sum goes into round k, which accumulates onto round k - 1.  Only the last sum
+    of a chain of `total`s gets a tensor: its parts and the smaller sums it took over (`parts` None) raise when read."""
     __slots__ = ("parts",)
 
 
@@ -292,7 +296,7 @@ class _Deferred:
     def total(self, x, y):
         """x + y for two deferred values of one shape, without a launch of its own; None if that is not possible."""
         ok = lambda v: isinstance(v, (_TnNode, _SumNode)) and v._t is None and v.pending is self and \
-            (not isinstance(v, _TnNode) or v.target is None)
+            (v.target is None if isinstance(v, _TnNode) else v.parts is not None)
         if not (ok(x) and ok(y)) or x.shape != y.shape:
             return None
         parts = [p for v in (x, y) for p in (v.parts if isinstance(v, _SumNode) else [v])]
@@ -302,6 +306,9 @@ class _Deferred:
         s.parts = parts
         for p in parts:
             p.target = s
+        for v in (x, y):
+            if isinstance(v, _SumNode):
+                v.parts = None   # (taken over by s: no tensor of its own, never a part of another sum)
         return s
 
     def flush(self):
@@ -337,10 +344,8 @@ class _Deferred:
             for tgt, out in outs.values():
                 M, N = tgt.shape
                 res = out if (Mp == M and Np == N) else raw_block(out, 0, M, 0, N, M, N)
-                tgt._t = res
+                tgt._t = res   # (the parts of a sum keep no tensor: reading one raises, see _LazyV.t)
                 if isinstance(tgt, _SumNode):
-                    for p_ in tgt.parts:
-                        p_._t = res   # (a part read on its own after the sum was formed: not on the tape's paths)
                     tgt.parts = None
             for n in ns:
                 if n.bias is not None and n.bias._t is not None and n.bias._t.size(1) != n.bias.shape[1]:

@@ -40,10 +40,10 @@ def segment_reduce(src, index, reduce):
     """torch_scatter.scatter(src, index, dim=0, reduce) as used at schnet.py:115 / painn.py:266:
     dim_size = index.max()+1, mean = sum / clamp(count, 1) (third-party; parity unpinned)."""
     size = int(index.max()) + 1
-    out = torch.zeros((size,) + tuple(src.shape[1:]), dtype=src.dtype).index_add(0, index, src)
+    out = torch.zeros((size,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device).index_add(0, index, src)
     if reduce in ("add", "sum"):
         return out
-    cnt = torch.zeros(size, dtype=src.dtype).index_add(0, index, torch.ones_like(index, dtype=src.dtype))
+    cnt = torch.zeros(size, dtype=src.dtype, device=src.device).index_add(0, index, torch.ones_like(index, dtype=src.dtype))
     return out / cnt.clamp(min=1).view(-1, *([1] * (src.dim() - 1)))
 
 
@@ -206,7 +206,7 @@ def painn_forward(P, x, positions, radius_edge_index, batch, n_atom_basis, n_int
     filter_list = [filters] * n_interactions if shared_filters else torch.split(filters, 3 * F_, dim=-1)  # :242-245
     emb = P["embedding.weight"]
     q = F.embedding(z, emb, padding_idx=0)[:, None]  # :247
-    mu = torch.zeros((q.shape[0], 3, q.shape[2]), dtype=q.dtype)  # :249
+    mu = torch.zeros((q.shape[0], 3, q.shape[2]), dtype=q.dtype, device=q.device)  # :249
     for i in range(n_interactions):  # :251-253
         blk = 0 if shared_interactions else i
         p = "interactions.%d.interatomic_context_net." % blk
@@ -215,9 +215,9 @@ def painn_forward(P, x, positions, radius_edge_index, batch, n_atom_basis, n_int
         muj = mu[idx_j]  # :55
         xx = filter_list[i] * xj  # :56
         dq, dmuR, dmumu = torch.split(xx, F_, dim=-1)  # :58
-        dq = torch.zeros((n_atoms,) + tuple(dq.shape[1:]), dtype=dq.dtype).index_add(0, idx_i, dq)  # :59
+        dq = torch.zeros((n_atoms,) + tuple(dq.shape[1:]), dtype=dq.dtype, device=dq.device).index_add(0, idx_i, dq)  # :59
         dmu = dmuR * dir_ij[..., None] + dmumu * muj  # :60
-        dmu = torch.zeros((n_atoms,) + tuple(dmu.shape[1:]), dtype=dmu.dtype).index_add(0, idx_i, dmu)  # :61
+        dmu = torch.zeros((n_atoms,) + tuple(dmu.shape[1:]), dtype=dmu.dtype, device=dmu.device).index_add(0, idx_i, dmu)  # :61
         q = q + dq  # :63
         mu = mu + dmu  # :64
         m = "mixing.%d." % blk
