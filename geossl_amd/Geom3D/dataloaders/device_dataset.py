@@ -19,6 +19,11 @@ step at the reference's batch size).  Here the molecules are uploaded once:
   Anything else that touches ``handle.x`` / ``.positions`` / ``.batch`` / ``.super_edge_index`` /
   ``.radius_edge_index`` gets the collated tensors (built by the same kernel into fresh memory, then cached), so a
   handle is accepted wherever a collated batch is (``do_DDM``, the modules themselves, eager steps).
+* ``DeviceDataset(..., triples=, triple_counts=[, triple_angle=])`` (or ``dataset.sample_triples(ratio)``): a dataset for
+  angle prediction on atom triples (examples/pretrain_TorsionAnglePrediction.py).  The sampled triples of every molecule
+  (local atom indices) and their angles live in device memory, the per-molecule offsets on the host; a handle of such a
+  dataset shows ``super_edge_index [3, T]`` / ``super_edge_angle [T]`` - the triples, not the pair tuples - written by
+  ``geossl_gather_triples`` (csrc/torsion_head.hip), bit for bit what ``BatchAtomTriple.from_data_list`` gives.
 * ``DeviceLoader(mask_ratio=r)`` yields MASKED handles: the reference's BFS atom masking (datasets_3D.py:24-67; see
   ``masking``) over the dataset's bond graph, kept lists drawn on the device (``mask_rng="device"``) or by the
   reference's own np.random draws on the host (``"numpy"``).  A masked handle carries the kept sizes; its gather is
@@ -63,12 +68,15 @@ class _Staging:
 
 class DeviceDataset:
     def __init__(self, x, positions, sizes, device, option="combination", radius=None, max_num_neighbors=32,
-                 bond_index=None, bond_counts=None, y=None):
+                 bond_index=None, bond_counts=None, y=None, triples=None, triple_counts=None, triple_angle=None):
         """x [Ntot, C] int64, positions [Ntot, 3] float32 (numpy or tensors; molecule after molecule), sizes [M] atoms
         per molecule.  option: the AtomTupleExtractor enumeration of the batches drawn from it.  radius: also build the
         per-molecule radius_edge_index (PaiNN) on this geometry.  bond_index [2, Etot] (local atom indices, molecule
         after molecule) with bond_counts [M]: the bond graph (``data.edge_index``) that atom masking walks.  y [M, T]
-        (or [M]): per-molecule targets, kept in device memory as float32 (the Supervised / fine-tuning steps)."""
+        (or [M]): per-molecule targets, kept in device memory as float32 (the Supervised / fine-tuning steps).
+        triples [3, Ttot] int (local atom indices, molecule after molecule) with triple_counts [M]: the atom triples of
+        angle prediction (AtomTripleExtractor output per molecule); triple_angle [Ttot] float32 their targets, or None:
+        computed once on the device by ops.triple_angles (this library's definition: the angle at the middle atom)."""
         if option not in _OPTIONS:
             raise ValueError("option is 'combination' or 'permutation'")
         dev = torch.device(device)
@@ -101,6 +109,11 @@ class DeviceDataset:
             self._set_bonds(bond_index, bond_counts)
         if radius is not None:
             self._build_edges(float(radius), int(max_num_neighbors))
+        self.triples, self.triple_angle, self.triple_cnt, self.triple_off = None, None, None, None
+        if (triples is None) != (triple_counts is None) or (triple_angle is not None and triples is None):
+            raise ValueError("triples and triple_counts come together (triple_angle only with them)")
+        if triples is not None:
+            self._set_triples(triples, triple_counts, triple_angle)
         self.y, self._mol_off = None, None
         if y is not None:
             self.y = as_t(y, torch.float32)
@@ -170,6 +183,50 @@ class DeviceDataset:
         if self.bond_dst.numel() == 0:
             self.bond_dst = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._succ = {}
+
+    def _set_triples(self, triples, triple_counts, triple_angle):
+        """The triple lists: int32 [3, Ttot] local atom indices and float32 [Ttot] angles on the device, per-molecule
+        offsets on the host (like the edge offsets)."""
+        tr = triples.cpu().numpy() if torch.is_tensor(triples) else np.asarray(triples)
+        tr = np.ascontiguousarray(tr.reshape(3, -1).astype(np.int64))
+        cnt = np.asarray(triple_counts, dtype=np.int64)
+        M = len(self)
+        if cnt.shape != (M,) or (M and cnt.min() < 0) or int(cnt.sum()) != tr.shape[1]:
+            raise ValueError("triple_counts has one entry per molecule and sums to the columns of triples")
+        if tr.shape[1] >= 2 ** 31:
+            raise ValueError("at most 2^31 - 1 triples in all")
+        if tr.size and (tr.min() < 0 or (tr >= np.repeat(self.sizes, cnt)[None, :]).any()):
+            raise ValueError("triples holds local atom indices (0 .. n-1 of its molecule)")
+        self.triple_cnt = cnt
+        self.triple_off = np.zeros(M + 1, dtype=np.int64)
+        np.cumsum(cnt, out=self.triple_off[1:])
+        Tt = tr.shape[1]
+        dev = self.device
+        self.triples = torch.zeros(3, max(Tt, 1), dtype=torch.int32, device=dev)
+        self.triples[:, :Tt] = torch.from_numpy(tr.astype(np.int32)).to(dev)
+        if triple_angle is not None:
+            ang = (triple_angle if torch.is_tensor(triple_angle)
+                   else torch.from_numpy(np.ascontiguousarray(np.asarray(triple_angle, dtype=np.float32))))
+            ang = ang.to(dev, torch.float32).reshape(-1)
+            if ang.numel() != Tt:
+                raise ValueError("triple_angle holds one angle per triple")
+        else:   # the angle at the middle atom, on the dataset's own geometry (dataset atom ids = local + atom offset)
+            from ...ops import triple_angles
+            glob = torch.from_numpy(tr + np.repeat(self.off[:-1], cnt)[None, :]).to(dev)
+            ang = triple_angles(self.positions, glob)
+        self.triple_angle = torch.zeros(max(Tt, 1), dtype=torch.float32, device=dev)
+        self.triple_angle[:Tt] = ang
+
+    def sample_triples(self, ratio):
+        """Draw the dataset's triples with AtomTripleExtractor(ratio), molecule after molecule on the global np.random
+        stream (what the reference's per-molecule transform does over the same molecules), angles by ops.triple_angles.
+        Host work, once.  -> self"""
+        from .dataloaders_AtomTriple import AtomTripleExtractor
+        ext = AtomTripleExtractor(ratio)
+        parts = [ext.triples(int(n)) for n in self.sizes]
+        tr = np.concatenate(parts, axis=1) if parts else np.empty((3, 0), dtype=np.int64)
+        self._set_triples(tr, [p_.shape[1] for p_ in parts], None)
+        return self
 
     def successors(self, i):
         """to_networkx successor lists of molecule i (cached)."""
@@ -297,7 +354,7 @@ class DeviceDataset:
         from ...pretrain_GeoSSL import Batch
         from ...layout import prepare_batch
         B, dev = hb.num_graphs, self.device
-        N, S = hb.n_atoms, hb.n_super
+        N, S = hb.n_atoms, (0 if self.triples is not None else hb.n_super)   # (a triple dataset enumerates no pair tuples)
         with_edges = self.edges is not None
         blob, o = self.upload_plan(hb, with_edges)
         x = torch.empty(N, self.x_cols, dtype=torch.int64, device=dev)
@@ -328,8 +385,33 @@ class DeviceDataset:
                     g.e_src_off, g.e_ptr = base + 4 * o["e_src_off"], base + 4 * o["e_ptr"]
                     g.e0_dst, g.e1_dst = ptr(rei[0]), ptr(rei[1])
             call("geossl_gather_molecules", C.byref(g), B, stream())
+        if self.triples is not None:   # a triple dataset: the handle shows its triples and their angles
+            return self._collate_triples(hb, x, pos, bvec, rei, blob, o)
         out = Batch(x, pos, bvec, sei, rei, B, hb._sizes, self.option)
         prepare_batch(bvec, sei, hb._sizes, lazy=True)
+        return out
+
+    def _collate_triples(self, hb, x, pos, bvec, rei, blob, o):
+        from ...pretrain_GeoSSL import TripleBatch
+        from ...layout import prepare_batch
+        B, T, dev = hb.num_graphs, hb.n_triples, self.device
+        tri = torch.empty(3, T, dtype=torch.int64, device=dev)
+        ang = torch.empty(T, dtype=torch.float32, device=dev)
+        if T:
+            slot = self._staging.take(2 * B + 1)
+            h = slot[0].numpy()
+            h[0:B] = self.triple_off[hb.ids]
+            h[B] = 0
+            np.cumsum(self.triple_cnt[hb.ids], out=h[B + 1:2 * B + 1])
+            tb = torch.empty(2 * B + 1, dtype=torch.int32, device=dev)
+            tb.copy_(slot[0][:2 * B + 1], non_blocking=True)
+            self._staging.sent(slot)
+            base = tb.data_ptr()
+            call("geossl_gather_triples", ptr(self.triples), self.triples.size(1), ptr(self.triple_angle), base,
+                 base + 4 * B, blob.data_ptr() + 4 * o["mol_ptr"], B, ptr(tri[0]), ptr(tri[1]), ptr(tri[2]), ptr(ang),
+                 stream())
+        out = TripleBatch(x, pos, bvec, tri, ang, rei, B, hb._sizes)
+        prepare_batch(bvec, tri, hb._sizes, lazy=True)
         return out
 
     def _masked_edges(self, hb, g, m, blob, o):
@@ -404,7 +486,12 @@ class DatasetBatch:
             self._sizes = masking.kept_count(self._src_n, mask.ratio)
             if mask.keep is not None and mask.keep.shape != (int(self._sizes.sum()),):
                 raise ValueError("kept lists of a masked batch hold k(n) atoms per molecule")
-        self._canonical = dataset.option
+        # a triple dataset: the handle's super_edge_index are its sampled triples - nothing the sizes determine
+        self._triples = getattr(dataset, "triples", None) is not None
+        self._canonical = None if self._triples else dataset.option
+        if self._triples and mask is not None:
+            raise ValueError("atom masking of a triple dataset is not supported (its triples name atoms by index)")
+        self.n_triples = int(dataset.triple_cnt[self.ids].sum()) if self._triples else 0
         self.device = dataset.device
         self.x_cols = dataset.x_cols
         self.num_graphs = int(self.ids.size)
@@ -424,6 +511,7 @@ class DatasetBatch:
     batch = property(lambda self: self.materialize().batch)
     super_edge_index = property(lambda self: self.materialize().super_edge_index)
     radius_edge_index = property(lambda self: self.materialize().radius_edge_index)
+    super_edge_angle = property(lambda self: self.materialize().super_edge_angle if self._triples else None)
 
     @property
     def y(self):
@@ -449,6 +537,8 @@ class DatasetBatch:
     def fingerprint(self):
         """pretrain_GeoSSL.structure_fingerprint of the collated batch, from the host sizes alone."""
         fp = self.__dict__.get("_fp")
+        if fp is None and self._triples:   # (sampled triples: only the same molecules share index tensors)
+            fp = self.__dict__["_fp"] = ("triples", id(self._dataset), self.ids.tobytes())
         if fp is None:
             fp = self.__dict__["_fp"] = ("sizes", self._canonical, self.n_atoms, self.n_super,
                                          np.asarray(self._sizes, dtype=np.int32).tobytes())
@@ -476,6 +566,9 @@ class DeviceLoader:
             raise ValueError("mask_rng is 'device' or 'numpy'")
         self.mask_rng = mask_rng
         if self.mask_ratio > 0:
+            if getattr(dataset, "triples", None) is not None:
+                raise ValueError("mask_ratio > 0 with a triple dataset is not supported: the sampled triples name atoms "
+                                 "by index, and masking renumbers them")
             dataset.check_masking(self.mask_ratio)
 
     def __len__(self):

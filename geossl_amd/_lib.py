@@ -283,6 +283,17 @@ PROTOTYPES = {
     "geossl_property_bwd_dyn": (i32, [i64, i32, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp, i32, vp, vp, vp, vp,
                                       vp, vp, i32, vp, vp]),
     "geossl_property_targets": (i32, [vp, i64, i32, i32, vp, vp, i64, vp, vp]),
+    # angle-prediction head on atom triples, the angle producer and the triple gather (csrc/torsion_head.hip)
+    "geossl_torsion_head_width_ok": (i32, [i32]),
+    "geossl_torsion_head_fwd_workspace_floats": (i64, [i64]),
+    "geossl_torsion_head_bwd_workspace_floats": (i64, [i64, i32]),
+    "geossl_torsion_head_fwd": (i32, [vp, i64, i32, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp]),
+    "geossl_torsion_head_fwd_dyn": (i32, [vp, i64, i32, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "geossl_torsion_head_bwd": (i32, [vp, i64, i32, vp, vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, i32, vp]),
+    "geossl_torsion_head_bwd_dyn": (i32, [vp, i64, i32, vp, vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, i32, vp, vp,
+                                          vp]),
+    "geossl_triple_angles": (i32, [vp, i64, vp, vp, vp, i64, vp, vp]),
+    "geossl_gather_triples": (i32, [vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp]),
 }
 
 _lib = None

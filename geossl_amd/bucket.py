@@ -33,7 +33,7 @@ MAX_N = 255         # largest molecule a bucket takes (the limit of the aggregat
 SMALL_N = 33        # ... and the largest one of the register-form aggregation's size classes: buckets whose molecules
                     # all fit it keep the flat pair-geometry kernel and the ragged layer loop
 MAX_N_CLASSES = (SMALL_N, 64, 128, MAX_N)   # a bucket's bound on the molecule size (LDS of the radius-graph kernel)
-D_N, D_N2, D_P2, D_S, D_W, D_B, D_N6, D_E2, D_BIG0, D_BIG1 = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9   # words of `dims`
+D_N, D_N2, D_P2, D_S, D_W, D_B, D_N6, D_E2, D_BIG0, D_BIG1, D_T = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10   # words of `dims`
 DIMS_WORDS = 16
 PAINN_MAX_N_CLASSES = (22, 33, 44, 64, 96, 128, MAX_N)   # PaiNN: the bound sizes the LDS of its per-molecule kernels
 
@@ -52,6 +52,7 @@ class DynDims:
         self.n_atoms2x3 = base + 4 * D_N6   # PaiNN: rows of the vector features viewed as [3 N2, F]
         self.n_edges2 = base + 4 * D_E2     # PaiNN: edges of the two-view batch
         self.n_big = (base + 4 * D_BIG0, base + 4 * D_BIG1)   # PaiNN: atoms of the molecules above the two stage caps
+        self.n_triples = base + 4 * D_T     # atom triples of the batch (a "triples" bucket: angle prediction)
 
 
 class _Layout:
@@ -125,15 +126,33 @@ def sizes_array(batch):
     return arr
 
 
+TRIPLES = "triples"   # the "tuple option" of a bucket whose step reads atom triples and no pair tuples (angle prediction)
+
+
+def option_of(batch):
+    """What a bucket for this batch enumerates: the AtomTupleExtractor option of a canonical pair enumeration, "triples"
+    for a collated AtomTripleExtractor batch (or a handle of a triple dataset) - its list is per-step DATA of the bucket,
+    not a function of the sizes - or None."""
+    return TRIPLES if getattr(batch, "_triples", False) else getattr(batch, "_canonical", None)
+
+
+def n_triples(batch):
+    """Triples of a triple batch (a handle knows them on the host; a collated batch by its tensor's shape)."""
+    if getattr(batch, "_dataset", None) is not None:
+        return int(batch.n_triples)
+    return int(batch.super_edge_index.size(1))
+
+
 def batch_counts(sizes, option, views=2):
-    """(atoms N, pair slots P, super-edges S, aggregation work items W of the `views`-view batch) of molecules `sizes`."""
+    """(atoms N, pair slots P, super-edges S, aggregation work items W of the `views`-view batch) of molecules `sizes`.
+    option "triples": no pair tuples (S = 0)."""
     global _PARTS
     if _PARTS is None:
         _PARTS = _parts_table()
     from .layout import aggregate_by_targets, work_items_bound
     n = sizes if isinstance(sizes, np.ndarray) else np.asarray(sizes, dtype=np.int64)
     P = int((n * (n - 1) // 2).sum())
-    S = P if option == "combination" else 2 * P
+    S = P if option == "combination" else (0 if option == TRIPLES else 2 * P)
     W = work_items_bound(np.concatenate([n] * views), aggregate_by_targets(views * len(n)))   # (a bound: 8 padded queues)
     return int(n.sum()), P, S, W
 
@@ -143,9 +162,9 @@ def eligible(batch, model_3d, normalize=False):
     with a pair), super_edge_index the extractor's full enumeration - every index tensor of the SchNet step is then a
     function of the sizes; PaiNN: also a collated radius_edge_index on the device (its structures are rebuilt on the
     device per step, geossl_painn_edge_layout)."""
-    sizes, canon = getattr(batch, "_sizes", None), getattr(batch, "_canonical", None)
-    if (model_3d not in ("schnet", "painn") or normalize or sizes is None or canon not in ("combination", "permutation")
-            or not len(sizes)):
+    sizes, canon = getattr(batch, "_sizes", None), option_of(batch)
+    if (model_3d not in ("schnet", "painn") or normalize or sizes is None
+            or canon not in ("combination", "permutation", TRIPLES) or not len(sizes)):
         return False
     lo, hi = size_range(batch)
     if lo < 1 or hi > MAX_N or hi < 2:
@@ -161,11 +180,32 @@ def eligible(batch, model_3d, normalize=False):
     return tensors_ok(batch)
 
 
+def triple_tensors_ok(batch):
+    """`tensors_ok` for a collated triple batch: int64 super_edge_index [3, T] and float32 super_edge_angle [T] without
+    a gradient, contiguous along what `Bucket.fill` copies; x / positions / batch as the molecule sizes give them."""
+    x, pos, bv, sei = batch.x, batch.positions, batch.batch, batch.super_edge_index
+    ang = getattr(batch, "super_edge_angle", None)
+    if ang is None or not torch.is_tensor(sei):
+        return False
+    n = sizes_array(batch)
+    N = int(n.sum())
+    return (pos.is_cuda and pos.dtype == torch.float32 and pos.dim() == 2 and pos.size(1) == 3 and pos.is_contiguous()
+            and pos.size(0) == N
+            and x.is_cuda and x.dtype == torch.long and x.dim() == 2 and x.is_contiguous() and x.size(0) == N
+            and bv.is_cuda and bv.dtype == torch.long and bv.dim() == 1 and bv.is_contiguous() and bv.numel() == N
+            and sei.is_cuda and sei.dtype == torch.long and sei.dim() == 2 and sei.size(0) == 3
+            and (sei.size(1) == 0 or sei.stride(1) == 1)
+            and ang.is_cuda and ang.dtype == torch.float32 and ang.dim() == 1 and ang.numel() == sei.size(1)
+            and ang.is_contiguous() and not ang.requires_grad)
+
+
 def tensors_ok(batch):
     """The batch's tensors are what `Bucket.fill` copies by byte count: int64 x [N, c] / batch [N] / super_edge_index
     [2, S], float32 positions [N, 3], all contiguous along what is copied, with N and S the counts the molecule sizes
     give (an int32 x, or a super_edge_index altered after the extractor marked it canonical, would make the copy read past
     the source).  Checked once per (batch object, tensor versions)."""
+    if option_of(batch) == TRIPLES:
+        return triple_tensors_ok(batch)
     x, pos, bv, sei = batch.x, batch.positions, batch.batch, batch.super_edge_index
     from .pretrain_GeoSSL import _tensor_uid   # (lifetime-unique stamps: id() of a freed tensor is handed out again)
     tag = tuple((_tensor_uid(t_), t_._version) for t_ in (x, pos, bv, sei))
@@ -196,7 +236,8 @@ def modules_ok(model, n1=None, n2=None):
     (n1 = n2 = None): the contrastive steps, whose loss reads the readout of the 2B molecules - exact counts, no capacity.
     One DistancePredictor of width 2 * 128 / ChargePredictor of width 128 / Discriminator of width 128 / property head of
     width 128 (n2 = None): the Distance / Charge Prediction, 3D InfoGraph and Supervised steps on a one-view bucket
-    (InfoGraph's and the property head's readouts read view 0's B real molecule offsets: exact counts)."""
+    (InfoGraph's and the property head's readouts read view 0's B real molecule offsets: exact counts); one
+    TorsionAnglePredictor of width 3 * 128: the angle-prediction step on a one-view "triples" bucket."""
     import os
     from .Geom3D.models.painn import PaiNN
     from .Geom3D.models.schnet import SchNet
@@ -221,6 +262,9 @@ def modules_ok(model, n1=None, n2=None):
     from .pretrain_DistancePrediction import DistancePredictor, fused_head_ok
     if isinstance(n1, DistancePredictor) and n2 is None:
         return fused_head_ok(n1) and n1.predictor.in_features == 2 * 128
+    from .pretrain_TorsionAnglePrediction import TorsionAnglePredictor, fused_head_ok as torsion_head_ok
+    if isinstance(n1, TorsionAnglePredictor) and n2 is None:
+        return torsion_head_ok(n1) and n1.predictor.in_features == 3 * 128
     from .pretrain_ChargePrediction import ChargePredictor, fused_head_ok as charge_head_ok
     if isinstance(n1, ChargePredictor) and n2 is None:
         return charge_head_ok(n1) and n1.predictor.in_features == 128
@@ -284,6 +328,13 @@ def capacities(N, P, S, W, B, prev=None, sizes=None):
     return tuple(out)
 
 
+def triple_capacity(T, B, prev=None):
+    """Capacity for the sampled triples of a batch with T of them: the per-molecule count goes with n^3, so its batch sums
+    spread far more than the atoms' - half as much again (twice after a bucket was outgrown), never below a block's 1024."""
+    cap = _round_up(max(T, 1) * (2.0 if prev is not None else 1.5) + 1024, 1024)
+    return cap if prev is None else max(cap, int(prev))
+
+
 def edge_capacity(E, B, prev=None, sizes=None):
     """Capacity for the edges of a PaiNN batch (one view) with E edges, with the slack of `capacities` for pair-slot-like
     counts (the edges of a molecule lie between its atoms and its pair slots)."""
@@ -306,7 +357,7 @@ def host_plan(sizes, option, views=2):
     n = sizes if isinstance(sizes, np.ndarray) else np.asarray(sizes, dtype=np.int64)
     B = n.shape[0]
     N, P, S, W = batch_counts(n, option, views)
-    mult = 1 if option == "combination" else 2
+    mult = 1 if option == "combination" else (0 if option == TRIPLES else 2)
     mp = np.zeros(B + 1, dtype=np.int64)
     np.cumsum(n, out=mp[1:])
     npair = n * (n - 1) // 2
@@ -333,13 +384,19 @@ class Bucket:
     edge layout still write the two-view structures (view 1 lands in buffer space this step never reads); view 0 comes
     first in every one of them, so its slices are the one-view structures."""
 
-    def __init__(self, device, B, caps, option, x_cols=2, max_n=SMALL_N, kind="schnet", E_cap=0, n_rbf=20, views=2):
-        from .pretrain_GeoSSL import Batch
+    def __init__(self, device, B, caps, option, x_cols=2, max_n=SMALL_N, kind="schnet", E_cap=0, n_rbf=20, views=2,
+                 T_cap=0):
+        from .pretrain_GeoSSL import Batch, TripleBatch
         if views not in (1, 2):
             raise ValueError("a bucket holds one or two views")
         self.views = int(views)
         self.device, self.B, self.option, self.max_n = device, int(B), option, int(max_n)
         self.kind, self.E_cap = kind, int(E_cap)
+        # option "triples" (one view; angle prediction): the step reads no pair tuples - no super-edges and no incidence
+        # lists are enumerated - but a sampled list of atom triples with a float payload, static inputs at T_cap
+        self.T_cap = int(T_cap) if option == TRIPLES else 0
+        if option == TRIPLES and views != 1:
+            raise ValueError("a triples bucket holds one view")
         self.N_cap, self.P_cap, self.S_cap, self.W_cap = (int(c) for c in caps[:4])
         B, Nc, Pc, Sc, Wc = self.B, self.N_cap, self.P_cap, self.S_cap, self.W_cap
         i32 = dict(dtype=torch.int32, device=device)
@@ -366,7 +423,10 @@ class Bucket:
         o["src_off"] = o["big1"] + (2 * Nc if len(self.big_caps) > 1 else 0)
         o["e_src_off"] = o["src_off"] + B
         o["e_ptr"] = o["e_src_off"] + (B if kind == "painn" else 0)
-        self.words = o["e_ptr"] + (B + 1 if kind == "painn" else 0)
+        # a triples bucket filled from a dataset: where its molecules' triples start there, and their offsets in the batch
+        o["t_src_off"] = o["e_ptr"] + (B + 1 if kind == "painn" else 0)
+        o["t_ptr"] = o["t_src_off"] + (B if option == TRIPLES else 0)
+        self.words = o["t_ptr"] + (B + 1 if option == TRIPLES else 0)
         self.off = o
         self.blob = torch.zeros(self.words, **i32)
         self.dims = self.blob[0:DIMS_WORDS]
@@ -433,17 +493,23 @@ class Bucket:
         sel._versions = (self.batch_vec._version, self.sei._version)
         self.sel = sel
         # ---- the batch object the captured step sees
-        self.batch = Batch(self.x, self.positions, self.batch_vec, self.sei, None, B, None, option)
+        if option == TRIPLES:
+            self.triples = torch.zeros(3, max(self.T_cap, 1), **i64)
+            self.triple_angle = torch.zeros(max(self.T_cap, 1), dtype=torch.float32, device=device)
+            self.batch = TripleBatch(self.x, self.positions, self.batch_vec, self.triples, self.triple_angle, None, B, None)
+        else:
+            self.batch = Batch(self.x, self.positions, self.batch_vec, self.sei, None, B, None, option)
         self.batch._bucket = self
         self.real = None  # (N, P, S, W) of the batch last filled in
 
     def caps(self):
         return (self.N_cap, self.P_cap, self.S_cap, self.W_cap)
 
-    def fits(self, counts, hi=None, E=None):
-        """counts = (N, P, S, W) of a batch; hi: its largest molecule; E: its edges (PaiNN)."""
+    def fits(self, counts, hi=None, E=None, T=None):
+        """counts = (N, P, S, W) of a batch; hi: its largest molecule; E: its edges (PaiNN); T: its triples."""
         return (all(c <= cap for c, cap in zip(counts, self.caps())) and (hi is None or hi <= self.max_n)
-                and (E is None or self.kind != "painn" or E <= self.E_cap))
+                and (E is None or self.kind != "painn" or E <= self.E_cap)
+                and (T is None or self.option != TRIPLES or T <= self.T_cap))
 
     def fill(self, batch, counts=None, zero=None):
         """The batch's atom types, positions, index tensors and derived structures into the static buffers; `zero`: a
@@ -463,8 +529,13 @@ class Bucket:
         N, P, S, W = counts if counts is not None else batch_counts(n, self.option, self.views)
         ds = getattr(batch, "_dataset", None)
         rei, E = None, 0
+        triples = self.option == TRIPLES
+        if option_of(batch) != self.option:
+            raise ValueError("batch and bucket disagree on the tuple option")
+        T = n_triples(batch) if triples else None
         if ds is not None:
-            if ds.option != self.option or ds.x_cols != self.x.size(1) or ds.device != self.x.device:
+            if ((not triples and ds.option != self.option) or ds.x_cols != self.x.size(1)
+                    or ds.device != self.x.device):
                 raise ValueError("dataset and bucket disagree (tuple option, x columns or device)")
             if self.kind == "painn":
                 if batch.n_edges is None:
@@ -476,7 +547,7 @@ class Bucket:
                     or rei.stride(1) != 1):
                 raise ValueError("PaiNN bucket fill expects a collated int64 radius_edge_index [2, E] on the device")
             E = int(rei.size(1))
-        if not self.fits((N, P, S, W), int(n.max()), E) or P < 1:
+        if not self.fits((N, P, S, W), int(n.max()), E, T) or P < 1:
             raise ValueError("batch exceeds the bucket's capacity")
         if ds is None and (not tensors_ok(batch) or batch.x.size(1) != self.x.size(1)):
             raise ValueError("bucket fill expects contiguous collated int64 / float32 tensors of the sizes' shapes")
@@ -489,6 +560,13 @@ class Bucket:
         Wr = hp["work"].size          # (the list's real length: 8 queues; <= the bound W the capacity was checked with)
         V = self.views
         h[0:8] = (N, V * N, V * P, S, Wr, B, 3 * V * N, V * E)
+        if triples:
+            h[D_T] = T
+            if ds is not None:
+                h[o["t_src_off"]:o["t_src_off"] + B] = ds.triple_off[batch.ids]
+                tp = h[o["t_ptr"]:o["t_ptr"] + B + 1]
+                tp[0] = 0
+                np.cumsum(ds.triple_cnt[batch.ids], out=tp[1:])
         if self.big_caps:
             from .layout import big_atom_list
             n2 = np.concatenate([n] * V)
@@ -521,14 +599,16 @@ class Bucket:
         g.option, g.x_cols = (0 if self.option == "combination" else 1), self.x.size(1)
         g.mol_ptr, g.se_ptr = base + 4 * o["mol_ptr"], base + 4 * o["se_ptr"]
         g.x_dst, g.pos_dst, g.batch_dst = ptr(self.x), ptr(self.positions), ptr(self.batch_vec)
-        g.sei0, g.sei1 = ptr(self.sei[0]), ptr(self.sei[1])
+        if not triples:
+            g.sei0, g.sei1 = ptr(self.sei[0]), ptr(self.sei[1])
         if ds is not None:
             g.x_src, g.pos_src, g.src_off = ptr(ds.x), ptr(ds.positions), base + 4 * o["src_off"]
         else:   # a collated batch: its molecules start where the bucket's do (the extractor's enumeration is generated)
             g.x_src, g.pos_src, g.src_off = ptr(batch.x), ptr(batch.positions), g.mol_ptr
         if self.kind == "schnet":
             g.pair_ptr2, g.pair_i, g.pair_j = base + 4 * o["pair_ptr"], ptr(lay.pair_i), ptr(lay.pair_j)
-        g.inc_ptr, g.inc_idx = ptr(sel.inc_ptr), ptr(sel.inc_idx)
+        if not triples:
+            g.inc_ptr, g.inc_idx = ptr(sel.inc_ptr), ptr(sel.inc_idx)
         if ds is not None and self.kind == "painn":
             if self.rei is None:
                 self.rei = torch.zeros(2, max(self.E_cap, 1), dtype=torch.int64, device=self.device)
@@ -549,6 +629,15 @@ class Bucket:
             del mblob
         else:
             call("geossl_gather_molecules", C.byref(g), B, st_)
+        if triples and ds is not None:
+            # the molecules' sampled triples (node offset added) and their angles: one launch
+            if T:
+                call("geossl_gather_triples", ptr(ds.triples), ds.triples.size(1), ptr(ds.triple_angle),
+                     base + 4 * o["t_src_off"], base + 4 * o["t_ptr"], g.mol_ptr, B, ptr(self.triples[0]),
+                     ptr(self.triples[1]), ptr(self.triples[2]), ptr(self.triple_angle), st_)
+        elif triples and T:   # a collated batch: one copy each
+            self.triples[:, :T].copy_(batch.super_edge_index)
+            self.triple_angle[:T].copy_(batch.super_edge_angle)
         if self.kind == "painn":
             el = self.el
             try:

@@ -630,6 +630,96 @@ def distance_head(h, W, b, positions, super_edge_index, incidence, dyn=None):
     return _DistanceHead.apply(h, W, b, positions, sei[0].contiguous(), sei[1].contiguous(), inc_ptr, inc_idx, dyn)
 
 
+class _TorsionHead(torch.autograd.Function):
+    """MSELoss(Linear(3F, 1)(cat(h_u, h_v, h_w)).squeeze(), super_edge_angle) (examples/pretrain_TorsionAnglePrediction.py:
+    16-27, 73-78) on csrc/torsion_head.hip -> (loss fp32 scalar, pred [T]).  The backward returns dh through autograd;
+    dW / db go through autograd too, or, inside _lib.direct_grads() with dense fp32 .grad buffers, are added into them."""
+
+    @staticmethod
+    def forward(ctx, h, W, b, tri0, tri1, tri2, angle, mol_ptr, dyn):
+        h = _f32(h)
+        N, F = h.shape
+        T = tri0.numel()
+        dev = h.device
+        Wd, bd = W.detach().contiguous().view(-1), b.detach().contiguous().view(-1)
+        lib = _lib.load()
+        proj = torch.empty(max(N, 1), 3, dtype=torch.float32, device=dev)
+        pred = torch.empty(T, dtype=torch.float32, device=dev)
+        res = torch.empty(T, dtype=torch.float32, device=dev)
+        ws = torch.empty(int(lib.geossl_torsion_head_fwd_workspace_floats(T)), dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        call("geossl_torsion_head_fwd_dyn", ptr(h), N, F, ptr(Wd), ptr(bd), ptr(tri0), ptr(tri1), ptr(tri2), ptr(angle), T,
+             ptr(proj), ptr(pred), ptr(res), ptr(ws), ptr(loss), _dyn(dyn, "n_atoms"), _dyn(dyn, "n_triples"), stream())
+        ctx.save_for_backward(h, Wd, tri0, tri1, tri2, res, mol_ptr)
+        ctx.params, ctx.dyn = (W, b), dyn
+        ctx.mark_non_differentiable(pred)
+        return loss, pred
+
+    @staticmethod
+    def backward(ctx, gout, _gpred):
+        h, Wd, tri0, tri1, tri2, res, mol_ptr = ctx.saved_tensors
+        W, b = ctx.params
+        N, F = h.shape
+        direct = _lib.direct_grads_enabled((W, b))
+        dW, db = (W.grad, b.grad) if direct else (torch.empty_like(W), torch.empty_like(b))
+        dh = torch.empty_like(h)
+        ws = torch.empty(int(_lib.load().geossl_torsion_head_bwd_workspace_floats(N, F)), dtype=torch.float32,
+                         device=h.device)
+        g = gout.to(torch.float32).contiguous()
+        call("geossl_torsion_head_bwd_dyn", ptr(h), N, F, ptr(Wd), ptr(tri0), ptr(tri1), ptr(tri2), res.numel(), ptr(res),
+             ptr(mol_ptr), mol_ptr.numel() - 1, ptr(g), ptr(dh), ptr(dW), ptr(db), ptr(ws), 1 if direct else 0,
+             _dyn(ctx.dyn, "n_atoms"), _dyn(ctx.dyn, "n_triples"), stream())
+        if direct:
+            dW = db = None
+        return dh, dW, db, None, None, None, None, None, None
+
+
+def torsion_head_width_ok(F):
+    """The node-feature widths the fused angle head serves (a wave holds one row: F = 64 V, V = 1, 2, 4, 8)."""
+    return bool(_lib.load().geossl_torsion_head_width_ok(int(F)))
+
+
+def torsion_head(h, W, b, triples, angle, mol_ptr, dyn=None):
+    """The angle-prediction loss of pretrain_TorsionAnglePrediction.py:73-78 -> (loss, pred): h [N, F] node features,
+    W [1, 3F] / b [1] the predictor's weight and bias, triples int64 [3, T] (batch atom ids, grouped by molecule in batch
+    order: collated AtomTripleExtractor output), angle float32 [T] the targets (no gradient), mol_ptr int32 [B + 1] the
+    atom offsets of the molecules (layout.MolLayout.mol_ptr): the backward scans a molecule's run of triples per atom.
+    dyn (bucket.DynDims): N and T are capacities, the real counts are read on the device."""
+    _lib.require_cuda(h, W, b, triples, angle, mol_ptr)
+    F = h.size(1)
+    if h.dim() != 2 or W.numel() != 3 * F or b.numel() != 1 or not torsion_head_width_ok(F):
+        raise ValueError("torsion_head: h [N, F] with F in (64, 128, 256, 512), W [1, 3F], b [1]; got %s, %s, %s"
+                         % (tuple(h.shape), tuple(W.shape), tuple(b.shape)))
+    if triples.dtype != torch.long or triples.dim() != 2 or triples.size(0) != 3:
+        raise ValueError("torsion_head: triples must be int64 [3, T]")
+    T = triples.size(1)
+    if angle.dtype != torch.float32 or angle.numel() != T or angle.requires_grad:
+        raise ValueError("torsion_head: angle is a float32 [T] target without a gradient")
+    if mol_ptr.dtype != torch.int32 or mol_ptr.dim() != 1 or (h.size(0) > 0 and mol_ptr.numel() < 2):
+        raise ValueError("torsion_head: mol_ptr is int32 [B + 1]")
+    return _TorsionHead.apply(h, W, b, triples[0].contiguous(), triples[1].contiguous(), triples[2].contiguous(),
+                              angle.contiguous().view(-1), mol_ptr.contiguous(), dyn)
+
+
+def triple_angles(positions, super_edge_index):
+    """The angle (radians, [0, pi]) at the MIDDLE atom of every triple (u, v, w) of super_edge_index int64 [3, T]:
+    atan2(|a x b|, a . b) with a = pos_u - pos_v, b = pos_w - pos_v; 0 when a or b is zero -> float32 [T]
+    (geossl_triple_angles).  This is THIS LIBRARY'S definition of ``super_edge_angle``, not the reference's: the reference
+    tree does not contain the code that fills that attribute (MoleculeDataset3DTorsionAngle is missing), so nothing pins
+    it; the training step takes the target from the batch and never computes it."""
+    _lib.require_cuda(positions, super_edge_index)
+    pos = _f32(positions)
+    sei = super_edge_index
+    if pos.dim() != 2 or pos.size(1) != 3 or sei.dtype != torch.long or sei.dim() != 2 or sei.size(0) != 3:
+        raise ValueError("triple_angles: positions float32 [N, 3], super_edge_index int64 [3, T]")
+    T = sei.size(1)
+    out = torch.empty(T, dtype=torch.float32, device=pos.device)
+    if T:
+        call("geossl_triple_angles", ptr(pos), pos.size(0), ptr(sei[0].contiguous()), ptr(sei[1].contiguous()),
+             ptr(sei[2].contiguous()), T, ptr(out), stream())
+    return out
+
+
 def charge_mask_count(N, ratio):
     """k of the Charge Prediction mask: Python's int(N * ratio), computed by the library (the device uses the same rule)."""
     return int(_lib.load().geossl_charge_mask_count(int(N), float(ratio)))

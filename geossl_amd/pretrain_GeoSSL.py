@@ -273,6 +273,45 @@ class Batch:
                      mv(self.radius_edge_index), self._num_graphs, self._sizes, self._canonical)
 
 
+class TripleBatch(Batch):
+    """Device-resident collated batch of atom TRIPLES with the attributes the loop of
+    examples/pretrain_TorsionAnglePrediction.py:64-78 reads (BatchAtomTriple, dataloaders_AtomTriple.py:34-72):
+    ``super_edge_index`` is int64 [3, T] (grouped by molecule in batch order) and ``super_edge_angle`` float32 [T] its
+    targets.  The list is sampled: never a function of the sizes (``_canonical`` stays None)."""
+
+    _triples = True
+
+    def __init__(self, x, positions, batch, super_edge_index, super_edge_angle, radius_edge_index=None, num_graphs=None,
+                 sizes=None):
+        super().__init__(x, positions, batch, super_edge_index, radius_edge_index, num_graphs, sizes, None)
+        self.super_edge_angle = super_edge_angle
+
+    @classmethod
+    def from_numpy(cls, d, device):
+        """From a dict with x, positions, batch, super_edge_index [3, T], super_edge_angle [T], sizes [, radius_edge_index]
+        (collated on the host: triples grouped by molecule in batch order)."""
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+        rei = t(d["radius_edge_index"]) if "radius_edge_index" in d else None
+        sizes = d.get("sizes")
+        out = cls(t(d["x"]), t(d["positions"]), t(d["batch"]), t(np.asarray(d["super_edge_index"]).reshape(3, -1)),
+                  t(np.asarray(d["super_edge_angle"], dtype=np.float32).reshape(-1)), rei,
+                  None if sizes is None else int(len(sizes)), sizes)
+        if sizes is not None:
+            from .layout import prepare_batch
+            prepare_batch(out.batch, out.super_edge_index, sizes, lazy=True)
+        return out
+
+    def to(self, device):
+        dev = torch.device(device)
+        if all(a is None or (a.device == dev or (dev.index is None and a.device.type == dev.type))
+               for a in (self.x, self.positions, self.batch, self.super_edge_index, self.super_edge_angle,
+                         self.radius_edge_index)):
+            return self
+        mv = lambda a: None if a is None else a.to(device)
+        return TripleBatch(mv(self.x), mv(self.positions), mv(self.batch), mv(self.super_edge_index),
+                           mv(self.super_edge_angle), mv(self.radius_edge_index), self._num_graphs, self._sizes)
+
+
 _PAIR_CACHE = {}
 
 
@@ -333,6 +372,8 @@ def structure_fingerprint(batch, model_3d="schnet"):
     tag = lambda t_: None if t_ is None else (_tensor_uid(t_), t_._version, tuple(t_.shape))
     rei = getattr(batch, "radius_edge_index", None) if model_3d == "painn" else None
     tags = (tag(batch.batch), tag(batch.super_edge_index), tag(rei))
+    if getattr(batch, "_triples", False):   # (a triple batch: its targets are bound by a per-structure graph too)
+        tags += (tag(batch.super_edge_angle),)
     cached = batch.__dict__.get("_geossl_fp")
     if cached is not None and cached[0] == tags:
         return cached[1]
@@ -421,7 +462,7 @@ class StepGraphs:
                 or (self.model_3d != "painn" and bk.is_uniform(batch))   # (PaiNN: the edge list differs batch by batch anyway)
                 or self.modules is None or not self._modules_ok()):
             return None
-        return ("bucket", len(batch._sizes), batch._canonical)
+        return ("bucket", len(batch._sizes), bk.option_of(batch))
 
     def _modules_ok(self):
         """bucket.modules_ok of this engine's modules, remembered per state of the switches it reads (the modules of a
@@ -440,8 +481,9 @@ class StepGraphs:
             g = self.graphs.get(key)
             if g is None:
                 return None
-            counts = bk.batch_counts(bk.sizes_array(batch), batch._canonical, self.views)
-            if not g["bucket"].fits(counts, bk.size_range(batch)[1], self._edges(batch)):
+            counts = bk.batch_counts(bk.sizes_array(batch), key[2], self.views)
+            if not g["bucket"].fits(counts, bk.size_range(batch)[1], self._edges(batch),
+                                    bk.n_triples(batch) if key[2] == bk.TRIPLES else None):
                 return None
             g["counts"] = counts
             self.graphs.move_to_end(key)
@@ -504,9 +546,14 @@ class StepGraphs:
             key = None  # the bucket could not be captured: this batch's own structure
         fp = structure_fingerprint(batch, self.model_3d)
         self._evict()
-        sb = Batch(batch.x.clone(), batch.positions.clone(), batch.batch, batch.super_edge_index,
-                   getattr(batch, "radius_edge_index", None), batch.num_graphs, getattr(batch, "_sizes", None),
-                   getattr(batch, "_canonical", None))
+        if getattr(batch, "_triples", False):   # (triples and targets bound as they are, like the other index tensors)
+            sb = TripleBatch(batch.x.clone(), batch.positions.clone(), batch.batch, batch.super_edge_index,
+                             batch.super_edge_angle, getattr(batch, "radius_edge_index", None), batch.num_graphs,
+                             getattr(batch, "_sizes", None))
+        else:
+            sb = Batch(batch.x.clone(), batch.positions.clone(), batch.batch, batch.super_edge_index,
+                       getattr(batch, "radius_edge_index", None), batch.num_graphs, getattr(batch, "_sizes", None),
+                       getattr(batch, "_canonical", None))
         sn = {k: noise[k].clone() for k in self.noise_keys}
         g = self._capture(sb, sn)
         if g is not None:
@@ -516,7 +563,8 @@ class StepGraphs:
     def _capture_bucket(self, key, batch, noise):
         from . import bucket as bk
         old = self.graphs.pop(key, None)
-        counts = bk.batch_counts(bk.sizes_array(batch), batch._canonical, self.views)
+        option = key[2]
+        counts = bk.batch_counts(bk.sizes_array(batch), option, self.views)
         caps = bk.capacities(*counts, B=len(batch._sizes), prev=None if old is None else old["bucket"].caps(),
                              sizes=bk.sizes_array(batch))
         max_n = bk.max_n_class(bk.size_range(batch)[1], None if old is None else old["bucket"].max_n, self.model_3d)
@@ -524,15 +572,18 @@ class StepGraphs:
         if self.model_3d == "painn":
             E_cap = bk.edge_capacity(self._edges(batch), len(batch._sizes), None if old is None else old["bucket"].E_cap,
                                      sizes=bk.sizes_array(batch))
+        T_cap = 0
+        if option == bk.TRIPLES:
+            T_cap = bk.triple_capacity(bk.n_triples(batch), len(batch._sizes), None if old is None else old["bucket"].T_cap)
         del old  # (its graph and static buffers go before the larger ones are made)
         self._evict()
         from_ds = getattr(batch, "_dataset", None) is not None
         dev = batch.device if from_ds else batch.positions.device
         try:
-            bkt = bk.Bucket(dev, len(batch._sizes), caps, batch._canonical,
+            bkt = bk.Bucket(dev, len(batch._sizes), caps, option,
                             x_cols=batch.x_cols if from_ds else batch.x.size(1), max_n=max_n,
                             n_rbf=getattr(getattr(self.modules[0], "radial_basis", None), "n_rbf", 20),
-                            kind=self.model_3d, E_cap=E_cap, views=self.views)
+                            kind=self.model_3d, E_cap=E_cap, views=self.views, T_cap=T_cap)
             bkt.fill(batch, counts)
         except (ValueError, RuntimeError) as e:
             warnings.warn("capacity bucket not usable for this batch (%s); per-structure graphs from now on" % e)
@@ -874,14 +925,16 @@ class _AutogradStep:
         # "DDM" (two NCSN heads), "InfoNCE" / "EBM_NCE": no heads (n1 = n2 = None), the readout is part of the step, or
         # "DistancePrediction" / "ChargePrediction": one head, the DistancePredictor / ChargePredictor (n1; n2 = None), or
         # "InfoGraph": the Discriminator (n1; n2 = None), the readout is part of its head, or
-        # "Supervised": graph_pred_linear (n1; n2 = None), the readout is part of its head
+        # "Supervised": graph_pred_linear (n1; n2 = None), the readout is part of its head, or
+        # "TorsionAnglePrediction": the TorsionAnglePredictor (n1; n2 = None)
         self.objective = objective
         heads = [m for m in (n1, n2) if m is not None]
         # the parameters the step reaches (a parameter outside it - an atomref table, PaiNN's output layers - gets no
         # gradient at all, like in the eager path, not a zero one)
         backbone = model._params() if hasattr(model, "_params") else _schnet_step_params(model)
         head_params = ((lambda h: list(h.parameters()))
-                       if objective in ("DistancePrediction", "ChargePrediction", "InfoGraph", "Supervised")
+                       if objective in ("DistancePrediction", "ChargePrediction", "InfoGraph", "Supervised",
+                                        "TorsionAnglePrediction")
                        else _head_params)
         seen, self.params = set(), []
         for p in list(backbone) + [q for h in heads for q in head_params(h)]:
@@ -945,6 +998,9 @@ class _AutogradStep:
         if self.objective == "DistancePrediction":
             from .pretrain_DistancePrediction import distance_step_fused
             return distance_step_fused(args, batch, self.model, self.n1)
+        if self.objective == "TorsionAnglePrediction":
+            from .pretrain_TorsionAnglePrediction import torsion_step_fused
+            return torsion_step_fused(args, batch, self.model, self.n1)
         if self.objective == "ChargePrediction":   # -> (loss, (masked atoms, k)): static outputs of the forward graph
             from .pretrain_ChargePrediction import charge_step_fused
             return charge_step_fused(args, batch, self.model, self.n1, noise)
@@ -1030,7 +1086,9 @@ class _AutogradStep:
         if getattr(batch, "_dataset", None) is None and (not batch.positions.is_cuda or batch.positions.requires_grad):
             return None
         contrastive = self.objective in CONTRASTIVE_OPTIONS
-        distance = self.objective == "DistancePrediction"   # (no random draws: the positions as they are)
+        # (no random draws: the positions as they are; angle prediction: triples and targets are the batch's own, static
+        # inputs of a "triples" bucket that its fill refreshes)
+        distance = self.objective in ("DistancePrediction", "TorsionAnglePrediction")
         # (the mask is the one draw: `noise` = {"mask_seed"} (device draw; a graph advances its own seed) or {"mask_idx"})
         charge = self.objective == "ChargePrediction"
         infograph = self.objective == "InfoGraph"   # (no random draws either)

@@ -942,6 +942,55 @@ int geossl_property_bwd_dyn(int64_t N, int F, const int32_t* mol_ptr, int64_t B,
 int geossl_property_targets(const float* y, int64_t M, int T, int task_id, const int64_t* mol_off,
                             const int32_t* src_off, int64_t B, float* out, hipStream_t stream);
 
+/* ---- angle prediction on atom triples: examples/pretrain_TorsionAnglePrediction.py:16-27,64-78 (csrc/torsion_head.hip)
+ * h [N][F] node features (F = 64, 128, 256 or 512: geossl_torsion_head_width_ok), W [3F] = predictor.weight =
+ * [w_u | w_v | w_w], bias [1], triples (tri0[t], tri1[t], tri2[t]) = (u_t, v_t, w_t), t < T (batch atom ids), angle [T] the
+ * targets (batch.super_edge_angle).  No atomics: the same inputs give the same bits.
+ * Forward: proj [N][3] (out) = (w_u . h_i, w_v . h_i, w_w . h_i); pred [T] (out) = ((a_u + b_v) + c_w) + bias; res [T]
+ *   (out, the backward's input) = pred - angle; loss [1] = mean res^2 (fp64 sums in a fixed order, NaN for T = 0).  A
+ *   triple with an atom outside [0, N) reads nothing: pred = res = NaN.  workspace:
+ *   geossl_torsion_head_fwd_workspace_floats(T) floats, 8-byte aligned.
+ * Backward with the upstream gradient gout[0]: d pred_t = (2 gout / T) res_t; dA_i / dB_i / dC_i = the sums of d pred over
+ *   the triples with u_t = i / v_t = i / w_t = i in ascending triple order; dh [N][F] = dA_i w_u + dB_i w_v + dC_i w_w;
+ *   dW [3F] (+)= [sum dA_i h_i | sum dB_i h_i | sum dC_i h_i], db [1] (+)= sum dA_i, from per-block partials added in block
+ *   order.  accumulate: dW / db (+)= instead of =.  The triples must be grouped by molecule in batch order with their three
+ *   atoms in one molecule (collated AtomTripleExtractor output is): mol_ptr [B + 1] int32 are the atom offsets of the
+ *   B >= 1 molecules, and molecule m's triples are the run whose u lies in [mol_ptr[m], mol_ptr[m + 1]) (one block per
+ *   molecule scans it; a triple that breaks the grouping is dropped from the sums).  workspace:
+ *   geossl_torsion_head_bwd_workspace_floats(N, F) floats.
+ * `_dyn`: N and T are capacities (grids, workspaces); dyn_N / dyn_T (nullable) point at the real counts - the mean divides
+ *   by the real T, atoms and triples past the real counts are neither read nor written; mol_ptr holds the real offsets.
+ * geossl_triple_angles: angle [T] (out) = the angle at the MIDDLE atom of each triple, atan2f(|a x b|, a . b) with
+ *   a = pos_u - pos_v, b = pos_w - pos_v, in [0, pi], 0 when a or b is zero (NaN for an atom outside [0, N)).  This is
+ *   this library's definition of super_edge_angle: the reference tree holds no code that fills it.
+ * geossl_gather_triples (one block per molecule m of the batch, B of them): columns [t_ptr[m], t_ptr[m + 1]) of
+ *   tri0 / tri1 / tri2 = columns [t_src_off[m], ...) of the dataset's tri_src [3][stride] (int32, local atom indices)
+ *   + mol_ptr[m] (dataloaders_AtomTriple.py:58-59); angle_dst likewise from angle_src. */
+int geossl_torsion_head_width_ok(int F);
+int64_t geossl_torsion_head_fwd_workspace_floats(int64_t T);
+int64_t geossl_torsion_head_bwd_workspace_floats(int64_t N, int F);
+int geossl_torsion_head_fwd(const float* h, int64_t N, int F, const float* W, const float* bias, const int64_t* tri0,
+                            const int64_t* tri1, const int64_t* tri2, const float* angle, int64_t T, float* proj,
+                            float* pred, float* res, float* workspace, float* loss, hipStream_t stream);
+int geossl_torsion_head_fwd_dyn(const float* h, int64_t N, int F, const float* W, const float* bias, const int64_t* tri0,
+                                const int64_t* tri1, const int64_t* tri2, const float* angle, int64_t T, float* proj,
+                                float* pred, float* res, float* workspace, float* loss, const int32_t* dyn_N,
+                                const int32_t* dyn_T, hipStream_t stream);
+int geossl_torsion_head_bwd(const float* h, int64_t N, int F, const float* W, const int64_t* tri0, const int64_t* tri1,
+                            const int64_t* tri2, int64_t T, const float* res, const int32_t* mol_ptr, int64_t B,
+                            const float* gout, float* dh, float* dW, float* db, float* workspace, int accumulate,
+                            hipStream_t stream);
+int geossl_torsion_head_bwd_dyn(const float* h, int64_t N, int F, const float* W, const int64_t* tri0,
+                                const int64_t* tri1, const int64_t* tri2, int64_t T, const float* res,
+                                const int32_t* mol_ptr, int64_t B, const float* gout, float* dh, float* dW, float* db,
+                                float* workspace, int accumulate, const int32_t* dyn_N, const int32_t* dyn_T,
+                                hipStream_t stream);
+int geossl_triple_angles(const float* pos, int64_t N, const int64_t* tri0, const int64_t* tri1, const int64_t* tri2,
+                         int64_t T, float* angle, hipStream_t stream);
+int geossl_gather_triples(const int32_t* tri_src, int64_t stride, const float* angle_src, const int32_t* t_src_off,
+                          const int32_t* t_ptr, const int32_t* mol_ptr, int64_t B, int64_t* tri0, int64_t* tri1,
+                          int64_t* tri2, float* angle_dst, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

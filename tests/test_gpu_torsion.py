@@ -1,0 +1,515 @@
+"""GPU tests of angle prediction on atom triples: the head kernels of csrc/torsion_head.hip per element against fp64 on
+NaN-poisoned outputs (static and `_dyn` forms, full and sampled lists, a 255-atom molecule and a 33-atom one at ratio 1),
+the angle kernel against the fp64 twin, the reference's edge cases against ATen, determinism, fixture G23 through
+do_TorsionAnglePrediction, the fallbacks, and the replayed step against the eager one and against the reference loop
+with a stock torch.optim.Adam."""
+import json
+import os
+import types
+
+import numpy as np
+import pytest
+import torch
+
+import torsion_twin as tw
+from conftest import load_golden, rel_err
+from helpers import fill_module_, grad_summary, t, unique_named_grads
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+G23 = sorted(f[:-4] for f in os.listdir(os.path.join(REPO, "tests", "golden")) if f.startswith("g23_torsion_"))
+U = 2.0 ** -24
+NAN = float("nan")
+
+
+def _triples(sizes, ratio, seed):
+    """AtomTripleExtractor per molecule under np.random.seed(seed), collated with node offsets -> int64 [3, T]."""
+    from geossl_amd.Geom3D.dataloaders import AtomTripleExtractor
+    np.random.seed(seed)
+    ext = AtomTripleExtractor(ratio)
+    parts, off = [], 0
+    for n in sizes:
+        parts.append(ext.triples(int(n)) + off)
+        off += int(n)
+    return torch.from_numpy(np.ascontiguousarray(np.concatenate(parts, axis=1)))
+
+
+def _inputs(sizes, F, seed, ratio=1.0):
+    from geossl_amd.synthetic import make_batch
+    b = make_batch(0, seed=seed, sizes=sizes)
+    tri = _triples(sizes, ratio, seed)
+    g = torch.Generator().manual_seed(seed)
+    h = 0.5 * torch.randn(int(np.sum(sizes)), F, generator=g)
+    W = 0.1 * torch.randn(1, 3 * F, generator=g)
+    bias = torch.tensor([0.7])
+    angle = tw.triple_angles(torch.from_numpy(b["positions"]), tri).float()
+    mol_ptr = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32))
+    return h, W, bias, tri, angle, mol_ptr
+
+
+class _Dims:
+    def __init__(self, N, T):
+        from geossl_amd.bucket import D_N, D_T, DIMS_WORDS
+        w = [0] * DIMS_WORDS
+        w[D_N], w[D_T] = N, T
+        self.tensor = torch.tensor(w, dtype=torch.int32, device=DEV)
+        self.n_atoms, self.n_triples = self.tensor.data_ptr() + 4 * D_N, self.tensor.data_ptr() + 4 * D_T
+
+
+def _run_raw(h, W, bias, tri, angle, mol_ptr, gout, dyn_caps=None):
+    """Forward + backward through the C ABI on NaN-filled outputs.  dyn_caps = (N_cap, T_cap): the `_dyn` forms on
+    buffers at those capacities; the inputs past the real rows are FINITE (atoms at 3.0, triples (0, 0, 0) with angle 3.0),
+    so a row the kernels wrongly processed would come out finite where the outputs must stay NaN."""
+    from geossl_amd import _lib
+    from geossl_amd._lib import ptr, stream
+    lib = _lib.load()
+    N, F = h.shape
+    T = tri.size(1)
+    Nc, Tc = dyn_caps if dyn_caps else (N, T)
+    pad = lambda a, n: torch.cat([a, torch.full((n - a.size(0),) + tuple(a.shape[1:]), 3.0, dtype=a.dtype)]).to(DEV)
+    hd, angd = pad(h, Nc), pad(angle, Tc)
+    trid = torch.cat([tri, torch.zeros(3, Tc - T, dtype=torch.long)], 1).contiguous().to(DEV)
+    Wd, bd, mp = W.to(DEV).contiguous(), bias.to(DEV), mol_ptr.to(DEV)
+    dims = _Dims(N, T) if dyn_caps else None
+    dn, dt = (dims.n_atoms, dims.n_triples) if dims else (None, None)
+    proj = torch.full((max(Nc, 1), 3), NAN, device=DEV)
+    pred = torch.full((Tc,), NAN, device=DEV)
+    res = torch.full((Tc,), NAN, device=DEV)
+    loss = torch.full((), NAN, device=DEV)
+    ws = torch.full((int(lib.geossl_torsion_head_fwd_workspace_floats(Tc)),), NAN, device=DEV)
+    st = stream()
+    _lib.call("geossl_torsion_head_fwd_dyn", ptr(hd), Nc, F, ptr(Wd), ptr(bd), ptr(trid[0]), ptr(trid[1]), ptr(trid[2]),
+              ptr(angd), Tc, ptr(proj), ptr(pred), ptr(res), ptr(ws), ptr(loss), dn, dt, st)
+    dh = torch.full((Nc, F), NAN, device=DEV)
+    dW = torch.full((1, 3 * F), NAN, device=DEV)
+    db = torch.full((1,), NAN, device=DEV)
+    ws2 = torch.full((int(lib.geossl_torsion_head_bwd_workspace_floats(Nc, F)),), NAN, device=DEV)
+    g = torch.tensor(gout, dtype=torch.float32, device=DEV)
+    _lib.call("geossl_torsion_head_bwd_dyn", ptr(hd), Nc, F, ptr(Wd), ptr(trid[0]), ptr(trid[1]), ptr(trid[2]), Tc,
+              ptr(res), ptr(mp), mp.numel() - 1, ptr(g), ptr(dh), ptr(dW), ptr(db), ptr(ws2), 0, dn, dt, st)
+    torch.cuda.synchronize()
+    return dict(proj=proj.cpu(), pred=pred.cpu(), res=res.cpu(), loss=loss.cpu(), dh=dh.cpu(), dW=dW.cpu(), db=db.cpu())
+
+
+def _check_against_fp64(sizes, F, seed, dyn=False, ratio=1.0, gout=1.5):
+    """Every element of every output against float64, bounds from fp32 rounding with U = 2^-24 (no element excluded: MSE
+    has no sign ties).  The backward is checked from the kernel's own res."""
+    h, W, bias, tri, angle, mol_ptr = _inputs(sizes, F, seed, ratio)
+    N, T = h.size(0), tri.size(1)
+    caps = (N + 37, T + 1000) if dyn else None
+    got = _run_raw(h, W, bias, tri, angle, mol_ptr, gout, caps)
+    if dyn:   # rows past the real counts are not written
+        for k, n_ in (("pred", T), ("res", T), ("dh", N), ("proj", N)):
+            assert torch.isnan(got[k][n_:]).all(), k
+    got = {k: (v[:N] if k in ("proj", "dh") else v[:T] if k in ("pred", "res") else v) for k, v in got.items()}
+    for k, v in got.items():
+        assert torch.isfinite(v).all(), k
+    h64, W64, b64 = h.double(), W.double().view(-1), bias.double()
+    ws_ = (W64[:F], W64[F:2 * F], W64[2 * F:])
+    for s in range(3):
+        assert ((got["proj"][:, s].double() - h64 @ ws_[s]).abs() <= F * U * (h64.abs() @ ws_[s].abs()) + 1e-30).all(), s
+    ah = [h64.abs() @ w_.abs() for w_ in ws_]
+    u, v, w = tri[0], tri[1], tri[2]
+    ref_loss, ref_pred = tw.torsion_loss(h64, W64, b64, tri, angle)
+    pbound = (F + 3) * U * (ah[0][u] + ah[1][v] + ah[2][w] + b64.abs()) + 4 * U * ref_pred.abs()
+    assert ((got["pred"].double() - ref_pred).abs() <= pbound).all()
+    ref_res = ref_pred - angle.double()
+    assert ((got["res"].double() - ref_res).abs() <= pbound + U * ref_res.abs()).all()
+    assert abs(float(got["loss"]) - float(ref_loss)) <= 1e-5 * abs(float(ref_loss))
+    c = float(np.float32(2.0) * np.float32(gout) / np.float32(T))
+    dpred = got["res"].double() * c
+    roles = (u, v, w)
+    d = [torch.zeros(N, dtype=torch.float64).index_add_(0, r, dpred) for r in roles]
+    a = [torch.zeros(N, dtype=torch.float64).index_add_(0, r, dpred.abs()) for r in roles]
+    L = max(int(torch.bincount(r, minlength=N).max()) for r in roles) + 2
+    ref_dh = sum(d[s][:, None] * ws_[s][None] for s in range(3))
+    bound = L * U * sum(a[s][:, None] * ws_[s].abs()[None] for s in range(3)) + 1e-30
+    assert ((got["dh"].double() - ref_dh).abs() <= bound).all()
+    ref_dW = torch.cat([d[s] @ h64 for s in range(3)])
+    wb = (L + N) * U * torch.cat([a[s] @ h64.abs() for s in range(3)]) + 1e-30
+    assert ((got["dW"].view(-1).double() - ref_dW).abs() <= wb).all()
+    assert abs(float(got["db"]) - float(d[0].sum())) <= (L + N) * U * float(a[0].sum()) + 1e-30
+    return got
+
+
+@pytest.mark.parametrize("F", [64, 128])
+@pytest.mark.parametrize("dyn", [False, True])
+def test_head_kernels_vs_fp64(F, dyn):
+    _check_against_fp64([5, 18, 2, 9, 12, 1, 3], F, 7 + F, dyn=dyn)                 # ratio 1, molecules without a triple
+    _check_against_fp64([18, 30, 7, 2, 25], F, 9 + F, dyn=dyn, ratio=0.3)           # a sampled subset
+
+
+@pytest.mark.parametrize("dyn", [False, True])
+def test_head_kernels_large_molecules(dyn):
+    got = _check_against_fp64([12, 255, 1, 40], 128, 31, dyn=dyn, ratio=1e-3)       # 16 386 triples of one molecule
+    assert got["pred"].numel() == 1 + 16386 + 0 + 59
+    got = _check_against_fp64([4, 33, 2], 64, 32, dyn=dyn)                          # 32 736 triples: the chunked scan
+    assert got["pred"].numel() == 24 + 32736
+
+
+def test_head_kernels_are_deterministic():
+    h, W, bias, tri, angle, mol_ptr = _inputs([18, 30, 7, 2, 25] * 20, 128, 21, ratio=0.05)
+    runs = [_run_raw(h, W, bias, tri, angle, mol_ptr, 1.0) for _ in range(2)]
+    for k in runs[0]:
+        assert torch.equal(runs[1][k].view(torch.int32), runs[0][k].view(torch.int32)), k
+
+
+# ---------------------------------------------------------------------------------------------- the angle kernel
+def _angle_check(pos, tri):
+    from geossl_amd import ops
+    got = ops.triple_angles(pos.to(DEV), tri.to(DEV)).cpu()
+    want = tw.triple_angles(pos, tri)
+    assert got.dtype == torch.float32 and got.shape == (tri.size(1),)
+    err = (got.double() - want).abs()
+    worst = int(err.argmax()) if err.numel() else 0
+    print("triple_angles: worst error %.3g rad (%.1f U) at triple %s" % (
+        float(err.max()) if err.numel() else 0.0, float(err.max()) / U if err.numel() else 0.0,
+        tri[:, worst].tolist() if err.numel() else None))
+    assert (err <= 64 * U).all()
+    assert (got >= 0).all() and (got <= np.float32(np.pi)).all()
+    return got
+
+
+def test_triple_angles_vs_fp64():
+    """Absolute error <= 64 U rad: a, b carry relative error U per component; cross and dot each <= 8 U |a||b| after that;
+    d atan2(y, x) <= (|x| |dy| + |y| |dx|) / (x^2 + y^2) <= 8 sqrt(2) U; the square root is correctly rounded; atan2f at
+    the OpenCL full-profile bound of 6 ulp is <= 24 U for results up to pi; sum < 48 U, rounded up to 64 U."""
+    from geossl_amd.synthetic import make_batch
+    for case in G23:
+        g = load_golden(case)
+        got = _angle_check(torch.from_numpy(g["positions"]), torch.from_numpy(g["super_edge_index"]))
+        assert float((got.double() - torch.from_numpy(g["super_edge_angle"]).double()).abs().max()) <= 66 * U   # (+ the fixture's rounding to float32)
+    pos = torch.from_numpy(make_batch(0, seed=41, sizes=[255])["positions"])
+    rng = np.random.default_rng(41)
+    tri = np.stack([rng.permutation(255)[:3] for _ in range(10000)], axis=1)
+    _angle_check(pos, torch.from_numpy(tri))
+    # exact cases: collinear (pi and 0), a right angle, a repeated atom
+    pos = torch.tensor([[0., 0., 0.], [1., 0., 0.], [2., 0., 0.], [1., 2., 0.], [-3., 5., 0.25]])
+    tri = torch.tensor([[0, 1, 0, 1, 1, 4, 2], [1, 0, 1, 1, 3, 4, 4], [2, 2, 3, 3, 3, 4, 2]])
+    got = _angle_check(pos, tri)
+    assert abs(float(got[0]) - np.pi) <= 64 * U and abs(float(got[1])) <= 64 * U
+    assert abs(float(got[2]) - np.pi / 2) <= 64 * U
+    assert float(got[3]) == 0.0 and float(got[4]) == 0.0 and float(got[5]) == 0.0   # u = v, v = w, u = v = w: a zero arm
+    assert abs(float(got[6])) <= 64 * U                                               # u = w: the same arm twice
+
+
+# ---------------------------------------------------------------------------------------------- edge cases vs ATen
+def _aten_and_fused(h, tri, angle, sizes, W, bias):
+    from geossl_amd import ops
+    from geossl_amd.pretrain_TorsionAnglePrediction import TorsionAnglePredictor
+    F = h.size(1)
+    tp = TorsionAnglePredictor(F).to(DEV)
+    with torch.no_grad():
+        tp.predictor.weight.copy_(W)
+        tp.predictor.bias.copy_(bias)
+    hr = h.to(DEV).requires_grad_()
+    trid, angd = tri.to(DEV), angle.to(DEV)
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")   # (T = 1: the reference's 0-d prediction against a [1] target)
+        ref = tp(hr[trid[0]], hr[trid[1]], hr[trid[2]], angd)
+    ref.backward()
+    want = (ref.detach(), hr.grad.clone(), tp.predictor.weight.grad.clone(), tp.predictor.bias.grad.clone())
+    tp.zero_grad()
+    hf = h.to(DEV).requires_grad_()
+    mp = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)).to(DEV)
+    loss, _ = ops.torsion_head(hf, tp.predictor.weight, tp.predictor.bias, trid, angd, mp)
+    loss.backward()
+    return want, (loss.detach(), hf.grad, tp.predictor.weight.grad, tp.predictor.bias.grad)
+
+
+def test_edge_cases_match_aten():
+    F = 64
+    g = torch.Generator().manual_seed(5)
+    mk = lambda n: (torch.randn(n, F, generator=g), 0.1 * torch.randn(1, 3 * F, generator=g), torch.tensor([0.3]))
+    # T = 0: NaN loss, all-zero gradients
+    h, W, bias = mk(5)
+    want, got = _aten_and_fused(h, torch.empty(3, 0, dtype=torch.long), torch.empty(0), [2, 3], W, bias)
+    assert torch.isnan(want[0]) and torch.isnan(got[0])
+    for a, b in zip(want[1:], got[1:]):
+        assert torch.equal(a, b) and not a.abs().sum()
+    # T = 1: the 0-d prediction against [1]
+    h, W, bias = mk(4)
+    want, got = _aten_and_fused(h, torch.tensor([[2], [0], [3]]), torch.tensor([1.25]), [4], W, bias)
+    assert rel_err(got[0], want[0]) < 1e-6
+    for a, b in zip(want[1:], got[1:]):
+        assert rel_err(b, a) < 1e-6
+    # the first and the last molecule have no triple
+    sizes = [2, 5, 1, 4, 2]
+    h, W, bias = mk(sum(sizes))
+    tri = _triples(sizes, 1, 3)
+    assert int(tri.min()) == 2 and int(tri.max()) == 11
+    want, got = _aten_and_fused(h, tri, torch.rand(tri.size(1), generator=g) * 3.0, sizes, W, bias)
+    assert rel_err(got[0], want[0]) < 1e-6
+    for a, b in zip(want[1:], got[1:]):
+        assert rel_err(b, a) < 1e-5
+    assert not got[1][:2].abs().sum() and not got[1][12:].abs().sum()
+
+
+# ---------------------------------------------------------------------------------------------- the step vs G23
+def _g23_setup(case):
+    from geossl_amd import pretrain_GeoSSL as pg
+    from geossl_amd.Geom3D.models import PaiNN, SchNet
+    from geossl_amd.pretrain_TorsionAnglePrediction import TorsionAnglePredictor
+    g = load_golden(case)
+    meta, cfg = json.loads(str(g["meta"])), json.loads(str(g["cfg"]))
+    model = fill_module_(SchNet(**cfg) if meta["kind"] == "schnet" else PaiNN(**cfg)).to(DEV)
+    tp = fill_module_(TorsionAnglePredictor(meta["emb_dim"])).to(DEV)
+    batch = pg.TripleBatch.from_numpy(g, DEV)
+    return g, meta, model, tp, batch, types.SimpleNamespace(model_3d=meta["kind"])
+
+
+def _check_g23(g, model, tp, loss, case):
+    assert rel_err(loss.detach().cpu(), g["loss"]) < 1e-5, case
+    assert rel_err(tp.predictor.weight.grad.cpu(), g["grad_pred_weight"]) < 1e-4, case
+    assert rel_err(tp.predictor.bias.grad.cpu(), g["grad_pred_bias"]) < 1e-4, case
+    grads = unique_named_grads(model)
+    for k in g:
+        if k.startswith("grad/") or k.startswith("gsum/"):
+            got = grads[k.split("/", 1)[1]].cpu()
+            got = grad_summary(got) if k.startswith("gsum/") else got
+            assert rel_err(got, g[k]) < 1e-4 or float(np.abs(g[k]).max()) < 1e-8, (case, k)
+
+
+@pytest.mark.parametrize("case", G23)
+@pytest.mark.parametrize("graph", [False, True])
+def test_g23_end_to_end(case, graph):
+    from geossl_amd.pretrain_TorsionAnglePrediction import do_TorsionAnglePrediction
+    g, meta, model, tp, batch, args = _g23_setup(case)
+    for _ in range(2 if graph else 1):   # (a structure known by its tensors is captured at its second sighting)
+        model.zero_grad(set_to_none=True)
+        tp.zero_grad(set_to_none=True)
+        loss = do_TorsionAnglePrediction(args, batch, model, tp, graph=graph)
+        loss.backward()
+    assert loss.dtype == torch.float32 and loss.dim() == 0
+    _check_g23(g, model, tp, loss, case)
+
+
+def test_fallbacks_match_the_twin(monkeypatch):
+    """Width 48, MSELoss(reduction="sum"), a subclass, float64 angles and shuffled (ungrouped) triples take the ATen head
+    and match the twin; the grouped float32 batch at width 64 takes the fused one."""
+    from geossl_amd import ops, pretrain_GeoSSL as pg
+    from geossl_amd.Geom3D.models import SchNet
+    from geossl_amd.pretrain_TorsionAnglePrediction import (TorsionAnglePredictor, do_TorsionAnglePrediction,
+                                                            fused_head_ok)
+    g = load_golden("g23_torsion_schnet_reduced_r001")
+    calls = []
+    real = ops.torsion_head
+    monkeypatch.setattr(ops, "torsion_head", lambda *a, **k: (calls.append(1), real(*a, **k))[1])
+    args = types.SimpleNamespace(model_3d="schnet")
+
+    def run(F, batch, tp=None, reduction="mean"):
+        cfg = dict(hidden_channels=F, num_filters=F, num_interactions=2, num_gaussians=8, cutoff=5.0, node_class=9)
+        model = fill_module_(SchNet(**cfg)).to(DEV)
+        tp = tp or fill_module_(TorsionAnglePredictor(F)).to(DEV)
+        del calls[:]
+        loss = do_TorsionAnglePrediction(args, batch, model, tp, graph=False)
+        _, h = model(batch.x[:, 0], batch.positions, batch.batch, return_latent=True)
+        ref, pred = tw.torsion_loss(h.detach().cpu(), tp.predictor.weight.detach().cpu(), tp.predictor.bias.detach().cpu(),
+                                    batch.super_edge_index.cpu(), batch.super_edge_angle.cpu())
+        if reduction == "sum":
+            ref = ref * pred.numel()
+        assert rel_err(loss.detach().cpu(), ref) < 1e-5
+        return len(calls), tp
+
+    mk = lambda tri, ang: pg.TripleBatch(t(g["x"], DEV), t(g["positions"], DEV), t(g["batch"], DEV), tri, ang,
+                                         num_graphs=len(g["sizes"]))
+    tri, ang = t(g["super_edge_index"], DEV), t(g["super_edge_angle"], DEV)
+    n, tp = run(64, mk(tri, ang))
+    assert n == 1 and fused_head_ok(tp)
+    n, tp = run(48, mk(tri, ang))
+    assert n == 0 and not fused_head_ok(tp)
+    tp = fill_module_(TorsionAnglePredictor(64)).to(DEV)
+    tp.criterion = torch.nn.MSELoss(reduction="sum")
+    assert not fused_head_ok(tp)
+    assert run(64, mk(tri, ang), tp, "sum")[0] == 0
+
+    class Sub(TorsionAnglePredictor):
+        pass
+    tp = fill_module_(Sub(64)).to(DEV)
+    assert not fused_head_ok(tp) and run(64, mk(tri, ang), tp)[0] == 0
+    n, tp = run(64, mk(tri, ang.double()))
+    assert n == 0 and fused_head_ok(tp)
+    perm = torch.randperm(tri.size(1), generator=torch.Generator().manual_seed(1)).to(DEV)
+    n, tp = run(64, mk(tri[:, perm].contiguous(), ang[perm].contiguous()))
+    assert n == 0 and fused_head_ok(tp)
+
+
+# ---------------------------------------------------------------------------------------------- graph paths
+def _triple_batch(d, ratio, seed):
+    """The collated numpy batch `d` (synthetic.make_batch layout) with AtomTripleExtractor(ratio) triples and the twin's
+    angles (rounded to float32) as a device TripleBatch."""
+    from geossl_amd import pretrain_GeoSSL as pg
+    tri = _triples(d["sizes"], ratio, seed)
+    ang = tw.triple_angles(torch.from_numpy(d["positions"]), tri).float()
+    dd = dict(x=d["x"], positions=d["positions"], batch=d["batch"], sizes=d["sizes"], super_edge_index=tri.numpy(),
+              super_edge_angle=ang.numpy())
+    return pg.TripleBatch.from_numpy(dd, DEV)
+
+
+def _ragged_batches(n, B, seed, ratio=0.01, ratios=None):
+    from geossl_amd.synthetic import collate_subset, make_batch
+    pool = make_batch(4 * B, seed=seed, mode="B")
+    rng = np.random.default_rng(seed)
+    return [_triple_batch(collate_subset(pool, rng.permutation(4 * B)[:B]), ratios[k] if ratios else ratio, seed + k)
+            for k in range(n)]
+
+
+def test_trainer_bucket_replay_matches_reference_loop():
+    """10 steps of TorsionAnglePredictionTrainer on shuffled ragged batches (no size sequence repeats, T differs) replay
+    ONE one-view capacity-bucket graph, and match the reference loop on eager launches with a stock torch.optim.Adam
+    step by step."""
+    from geossl_amd.Geom3D.models import SchNet
+    from geossl_amd.pretrain_TorsionAnglePrediction import (TorsionAnglePredictionTrainer, TorsionAnglePredictor,
+                                                            do_TorsionAnglePrediction)
+    cfg = dict(hidden_channels=128, num_filters=128, num_interactions=6, num_gaussians=51, cutoff=10.0, node_class=9)
+    batches = _ragged_batches(10, 16, 5)
+    assert len({tuple(b._sizes) for b in batches}) == 10
+    assert len({int(b.super_edge_index.size(1)) for b in batches}) > 5
+    m1, d1 = fill_module_(SchNet(**cfg)).to(DEV), fill_module_(TorsionAnglePredictor(128)).to(DEV)
+    m2, d2 = fill_module_(SchNet(**cfg)).to(DEV), fill_module_(TorsionAnglePredictor(128)).to(DEV)
+    opt = torch.optim.Adam([{"params": m1.parameters(), "lr": 1e-4}, {"params": d1.parameters(), "lr": 1e-4}],
+                           lr=1e-4)
+    tr = TorsionAnglePredictionTrainer(m2, d2, lr=1e-4, use_graph=True)
+    args = types.SimpleNamespace(model_3d="schnet")
+    for k, b in enumerate(batches):
+        loss = do_TorsionAnglePrediction(args, b, m1, d1, graph=False)
+        opt.zero_grad()
+        loss.backward()
+        opt.step()
+        l2 = tr.step(b)
+        assert rel_err(l2.cpu(), loss.detach().cpu()) < 1e-4, k
+    assert rel_err(d2.predictor.weight.detach().cpu(), d1.predictor.weight.detach().cpu()) < 1e-4
+    assert rel_err(m2.lin2.weight.detach().cpu(), m1.lin2.weight.detach().cpu()) < 1e-4
+    # one graph for the batch size (a batch that outgrows the first bucket's capacity replaces it by a larger one)
+    assert len(tr.step_graphs) == 1 and 1 <= tr.step_graphs.captures <= 2
+    (key, g), = tr.step_graphs.graphs.items()
+    assert key[0] == "bucket" and g["bucket"].views == 1
+
+
+def _grads(model, tp):
+    return [p.grad.clone() for p in list(model.parameters()) + list(tp.parameters()) if p.grad is not None]
+
+
+def _replay_vs_eager(model, tp, kind, batches):
+    from geossl_amd.pretrain_TorsionAnglePrediction import do_TorsionAnglePrediction
+    args = types.SimpleNamespace(model_3d=kind)
+    for k, b in enumerate(batches):
+        out = []
+        for graph in (False, True):
+            model.zero_grad(set_to_none=True)
+            tp.zero_grad(set_to_none=True)
+            loss = do_TorsionAnglePrediction(args, b, model, tp, graph=graph)
+            loss.backward()
+            out.append((loss.detach().clone(), _grads(model, tp)))
+        assert rel_err(out[1][0].cpu(), out[0][0].cpu()) < 1e-6, (kind, k)
+        assert len(out[1][1]) == len(out[0][1])
+        for a, c in zip(out[1][1], out[0][1]):
+            assert rel_err(a, c) < 1e-5, (kind, k)
+    eng = model.__dict__["_geossl_torsion_step"]
+    (sg,) = eng.graphs.values()
+    return sg
+
+
+def _models(kind):
+    from geossl_amd.Geom3D.models import PaiNN, SchNet
+    from geossl_amd.pretrain_TorsionAnglePrediction import TorsionAnglePredictor
+    model = (fill_module_(SchNet(hidden_channels=128, num_filters=128, num_interactions=6, num_gaussians=51,
+                                 cutoff=10.0, node_class=9)) if kind == "schnet" else
+             fill_module_(PaiNN(n_atom_basis=128, n_interactions=3, n_rbf=20, cutoff=5.0, max_z=9, n_out=1,
+                               readout="add"))).to(DEV)
+    return model, fill_module_(TorsionAnglePredictor(128)).to(DEV)
+
+
+@pytest.mark.parametrize("kind", ["schnet", "painn"])
+def test_bucket_replay_matches_eager_on_ragged_batches(kind):
+    """The reference loop's path (do_TorsionAnglePrediction -> _AutogradStep): shuffled ragged batches replay one one-view
+    bucket graph, loss and every gradient as the eager launches give them."""
+    model, tp = _models(kind)
+    batches = _ragged_batches(4, 24, 17)
+    if kind == "painn":
+        from geossl_amd import ops
+        for b in batches:
+            b.radius_edge_index = ops.radius_graph(b.positions, 5.0, b.batch)
+    sg = _replay_vs_eager(model, tp, kind, batches)
+    assert len(sg) == 1 and next(iter(sg.graphs))[0] == "bucket" and sg.captures == 1
+
+
+def test_reference_loader_flow_replays_one_bucket_graph():
+    """The reference's own flow: AtomTripleExtractor as the per-molecule transform, DataLoaderAtomTriple's collation,
+    batch.to(device), then the loop body - ragged batches replay one bucket graph and match the eager launches."""
+    from geossl_amd.Geom3D.dataloaders import AtomTripleExtractor, BatchAtomTriple, Data, DataLoaderAtomTriple
+    from geossl_amd.synthetic import make_molecules
+    mols = make_molecules(64, seed=23, mode="B")
+    off = np.concatenate([[0], np.cumsum(mols["sizes"])])
+    np.random.seed(23)
+    ext = AtomTripleExtractor(0.01)
+    recs = []
+    for m in range(64):
+        d = ext(Data(x=torch.from_numpy(mols["x"][off[m]:off[m + 1]]),
+                     positions=torch.from_numpy(mols["positions"][off[m]:off[m + 1]])))
+        d.super_edge_angle = tw.triple_angles(d.positions, d.super_edge_index).float()
+        recs.append(d)
+    batches = [b.to(DEV) for b in DataLoaderAtomTriple(recs, batch_size=16, shuffle=False)]
+    assert len(batches) == 4 and all(isinstance(b, BatchAtomTriple) and b.super_edge_index.is_cuda for b in batches)
+    model, tp = _models("schnet")
+    sg = _replay_vs_eager(model, tp, "schnet", batches)
+    assert len(sg) == 1 and next(iter(sg.graphs))[0] == "bucket" and sg.captures == 1
+
+
+def test_bucket_recaptures_when_the_triples_outgrow_it():
+    """A batch whose T exceeds the first bucket's triple capacity is served by a larger bucket and still matches eager."""
+    model, tp = _models("schnet")
+    batches = _ragged_batches(4, 24, 19, ratios=[0.002, 0.002, 0.2, 0.002])
+    T = [int(b.super_edge_index.size(1)) for b in batches]
+    sg = _replay_vs_eager(model, tp, "schnet", batches[:2])
+    (g,) = sg.graphs.values()
+    assert T[2] > g["bucket"].T_cap >= max(T[:2]) and sg.captures == 1
+    sg = _replay_vs_eager(model, tp, "schnet", batches[2:])
+    (g,) = sg.graphs.values()
+    assert len(sg) == 1 and sg.captures == 2 and g["bucket"].T_cap >= T[2]
+
+
+@pytest.mark.parametrize("kind", ["schnet", "painn"])
+def test_bucket_replay_matches_eager_on_device_loader(kind):
+    """DeviceLoader handles of a triple dataset (molecules and triples gathered into the bucket on the device) replay one
+    one-view bucket graph per batch size; a handle's triples and angles are bit for bit what host collation gives."""
+    from geossl_amd import ops
+    from geossl_amd.Geom3D.dataloaders import BatchAtomTriple, Data, DeviceDataset, DeviceLoader
+    from geossl_amd.synthetic import make_molecules
+    mols = make_molecules(200, seed=3, mode="C")
+    np.random.seed(8)
+    ds = DeviceDataset.from_numpy(mols, DEV, **({"radius": 5.0} if kind == "painn" else {})).sample_triples(2e-3)
+    assert ds.triples is not None and int(ds.triple_cnt.sum()) > 200 and (ds.triple_cnt == 0).any()
+    # the dataset's angles are the angle kernel's on the dataset's geometry
+    off = np.concatenate([[0], np.cumsum(mols["sizes"])])
+    glob = ds.triples[:, :int(ds.triple_cnt.sum())].long() + torch.from_numpy(
+        np.repeat(off[:-1], ds.triple_cnt)).to(DEV)[None]
+    assert torch.equal(ds.triple_angle[:glob.size(1)], ops.triple_angles(ds.positions, glob))
+    loader = DeviceLoader(ds, batch_size=32, shuffle=True, drop_last=True, generator=torch.Generator().manual_seed(2))
+    handles = [hb for _, hb in zip(range(4), loader)]
+    for hb in handles[:2]:   # host collation of the same molecules
+        recs = []
+        for i in hb.ids:
+            a0, t0, tc = int(off[i]), int(ds.triple_off[i]), int(ds.triple_cnt[i])
+            recs.append(Data(x=torch.from_numpy(mols["x"][a0:off[i + 1]]),
+                             positions=torch.from_numpy(mols["positions"][a0:off[i + 1]]),
+                             super_edge_index=ds.triples[:, t0:t0 + tc].long().cpu(),
+                             super_edge_angle=ds.triple_angle[t0:t0 + tc].cpu()))
+        want = BatchAtomTriple.from_data_list(recs)
+        assert hb.super_edge_index.dtype == torch.long and tuple(hb.super_edge_index.shape) == (3, hb.n_triples)
+        assert torch.equal(hb.super_edge_index.cpu(), want.super_edge_index)
+        assert hb.super_edge_angle.dtype == torch.float32
+        assert torch.equal(hb.super_edge_angle.cpu(), want.super_edge_angle)
+        assert torch.equal(hb.x.cpu(), want.x) and torch.equal(hb.batch.cpu(), want.batch)
+    with pytest.raises(ValueError):
+        DeviceLoader(ds, batch_size=32, mask_ratio=0.15)
+    model, tp = _models(kind)
+    sg = _replay_vs_eager(model, tp, kind, handles)
+    assert len(sg) == 1 and next(iter(sg.graphs))[0] == "bucket"
+    (g,) = sg.graphs.values()
+    # the bucket's static triples are the handle's own (refreshed by geossl_gather_triples)
+    hb, bkt = handles[-1], g["bucket"]
+    assert torch.equal(bkt.triples[:, :hb.n_triples], hb.super_edge_index)
+    assert torch.equal(bkt.triple_angle[:hb.n_triples], hb.super_edge_angle)
