@@ -16,7 +16,9 @@ import math
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
+from . import ops
+from .pretrain_GeoSSL import Args
+from .step import Objective, StepTrainer, backbone_forward, backbone_latent, engine_for, with_counts
 from .switches import env as _env
 
 
@@ -122,51 +124,24 @@ def do_InfoGraph(node_repr, molecule_repr, batch, criterion, infograph_discrimin
     return _infograph_aten(node_repr, molecule_repr, batch, criterion, disc)
 
 
-def _latent(args, batch, model):
-    """:94-99 -> node_repr [N, F] (the readout is the head's)."""
-    x = batch.x[:, 0]
-    if args.model_3d == "schnet":
-        _, h = model(x, batch.positions, batch.batch, return_latent=True, latent_only=True)
-    elif args.model_3d == "painn":
-        _, h = model(x, batch.positions, batch.radius_edge_index, batch.batch, return_latent=True, latent_only=True)
-    else:
-        raise Exception("3D model {} not included.".format(args.model_3d))
-    return h
-
-
 def infograph_step_fused(args, batch, model, discriminator):
     """The step as eager launches: the backbone's latent, then the fused head with the backbone's readout in it ->
-    (loss fp32 scalar, counts int32 [2] on the device)."""
-    W = discriminator.weight
+    (loss fp32 scalar, counts int32 [2] on the device).  (A one-view capacity bucket: lay.mol_ptr holds the B real
+    offsets of view 0, so the readout and the scores see exact molecules.)"""
     readout = readout_of(model)
-    bucket = getattr(batch, "_bucket", None)
-    if bucket is not None:
-        # the static batch of a one-view capacity bucket (geossl_amd/bucket.py): capacity-sized atom rows, the real atom
-        # count in bucket.dyn; lay2.mol_ptr holds the B real offsets of view 0, so the readout and the scores see exact
-        # molecules
-        if args.model_3d != bucket.kind or bucket.views != 1:
-            raise _lib.GeosslHipError("the 3D InfoGraph step needs a one-view bucket of its own backbone")
-        x = batch.x[:, 0]
-        if bucket.kind == "schnet":
-            _, h = model(x, batch.positions, bucket.b2, return_latent=True, latent_only=True, layout=bucket.lay2)
-        else:
-            _, h = model(x, batch.positions, bucket.e2, bucket.b2, return_latent=True, latent_only=True,
-                         layout=bucket.lay2, edge_layout=bucket.el)
-        return ops.infograph_head(h, W, bucket.lay2, readout, dyn=bucket.dyn)
-    from .layout import get_layout
-    h = _latent(args, batch, model)
-    return ops.infograph_head(h, W, get_layout(batch.batch), readout)
+    h, lay, dyn = backbone_latent(args.model_3d, batch, model, what="3D InfoGraph", layout=True)
+    return ops.infograph_head(h, discriminator.weight, lay, readout, dyn=dyn)
+
+
+# (no random draws; forward -> (loss, counts): the counts are a static output of the forward graph)
+INFOGRAPH = Objective("InfoGraph",
+                      lambda eng, args, mu, sigma, batch, noise: infograph_step_fused(args, batch, eng.model, eng.n1),
+                      result=with_counts)
 
 
 def infograph_step_aten(args, batch, model, discriminator, criterion):
     """:92-108 on our backbone with the caller's criterion: the backbone's own readout, then do_InfoGraph."""
-    if args.model_3d == "schnet":
-        molecule_repr, node_repr = model(batch.x[:, 0], batch.positions, batch.batch, return_latent=True)
-    elif args.model_3d == "painn":
-        molecule_repr, node_repr = model(batch.x[:, 0], batch.positions, batch.radius_edge_index, batch.batch,
-                                         return_latent=True)
-    else:
-        raise Exception("3D model {} not included.".format(args.model_3d))
+    molecule_repr, node_repr = backbone_forward(args, batch, model, True)
     return do_InfoGraph(node_repr, molecule_repr, batch, criterion, discriminator)
 
 
@@ -180,17 +155,6 @@ def _fused_batch_ok(batch):
 
 def _n_atoms(batch):
     return batch.n_atoms if getattr(batch, "_dataset", None) is not None else int(batch.batch.numel())
-
-
-def _infograph_step(model, discriminator):
-    """The _AutogradStep of (backbone, discriminator), kept on the backbone module; rebuilt when a parameter was
-    replaced, moved or frozen since (the graphs bind parameter addresses)."""
-    from .pretrain_GeoSSL import _AutogradStep
-    eng = model.__dict__.get("_geossl_infograph_step")
-    if eng is None or eng.n1 is not discriminator or not eng.unchanged():
-        eng = _AutogradStep(model, discriminator, None, objective="InfoGraph")
-        model.__dict__["_geossl_infograph_step"] = eng
-    return eng
 
 
 def do_3DInfoGraph(args, batch, model, discriminator, criterion=None, graph=None):
@@ -210,10 +174,9 @@ def do_3DInfoGraph(args, batch, model, discriminator, criterion=None, graph=None
         graph = getattr(args, "step_graph", _env("GEOSSL_NO_STEP_GRAPH") is None)
     N = _n_atoms(batch)
     if graph and torch.is_grad_enabled() and not torch.cuda.is_current_stream_capturing():
-        from .pretrain_GeoSSL import Args
         a = Args(args.model_3d)
         a.step_graph_mode = getattr(args, "step_graph_mode", "auto")
-        got = _infograph_step(model, discriminator).run(a, batch, 0.0, 0.0, None, False)
+        got = engine_for(model, "_geossl_infograph_step", INFOGRAPH, discriminator).run(a, batch, 0.0, 0.0, None, False)
         if got is not None:
             loss, counts = got
             return loss, infograph_acc(counts, N)
@@ -221,7 +184,7 @@ def do_3DInfoGraph(args, batch, model, discriminator, criterion=None, graph=None
     return loss, infograph_acc(counts.tolist(), N)
 
 
-class InfoGraphTrainer:
+class InfoGraphTrainer(StepTrainer):
     """The body of ``train()`` (examples/pretrain_3DInfoGraph.py:79-125): backbone latent, fused InfoGraph head with the
     readout in it, backward, gradient all-reduce, Adam - backbone and discriminator in one flat buffer (one fused Adam
     launch at one learning rate: both of the reference's groups run at lr * gnn_3d_lr_scale), no host sync inside
@@ -232,56 +195,15 @@ class InfoGraphTrainer:
 
     def __init__(self, model, discriminator, lr=5e-4, weight_decay=0.0, model_3d="schnet", use_graph=False,
                  max_graphs=256, graph_mode="auto"):
-        from .optim import FlatParams, FusedAdam
-        from .parallel import GradAllReduce
-        from .pretrain_GeoSSL import Args, StepGraphs
         if not fused_head_ok(discriminator) or readout_of(model) is None:
             raise ValueError("InfoGraphTrainer needs the reference Discriminator at a width of the fused head (64, 128 or "
                              "256) on the GPU and a backbone with an unscaled mean / add readout; use do_3DInfoGraph for "
                              "anything else")
-        self.model, self.discriminator = model, discriminator
+        self.discriminator = discriminator
         self.args = Args(model_3d)
-        self.flat = FlatParams([model, discriminator])
-        self.opt = FusedAdam(self.flat, lr=lr, weight_decay=weight_decay)
-        self.reduce = GradAllReduce(self.flat.grad)
-        self.use_graph = use_graph
-        self.step_graphs = StepGraphs(self._fwd_bwd, model_3d, max_graphs, mode=graph_mode,
-                                      modules=(model, discriminator, None), noise_keys=(), views=1)
-        self.step_graphs.zero_with_refresh = self.flat.grad
-        self._one = torch.ones((), dtype=torch.float32, device=self.flat.grad.device)
+        super().__init__([model, discriminator], model_3d, lr, weight_decay, use_graph, max_graphs, graph_mode)
 
-    def _fwd_bwd(self, batch, noise=None):
-        from .pretrain_GeoSSL import own_capture_open
-        if not own_capture_open():
-            self.flat.zero_grad()  # (a replayed step: cleared with the refresh of the graph's inputs, StepGraphs.refresh)
-        loss, counts = infograph_step_fused(self.args, batch, self.model, self.discriminator)
-        with _lib.direct_grads():  # every p.grad is a view of self.flat.grad: kernels accumulate into it directly
-            loss.backward(self._one)
-        self.flat.rebind_grads()
-        return loss.detach(), counts
+    with_extra = True   # step(batch) -> (loss, counts)
 
-    def _graph_fwd_bwd(self, batch):
-        sg = self.step_graphs
-        g = sg.lookup(batch)
-        if g is None:
-            if not sg.capture_now(batch):  # a structure seen for the first time: eager
-                return self._fwd_bwd(batch)
-            g = sg.capture(batch, {})
-            if g is None:  # capture failed: eager from now on
-                self.use_graph = False
-                return self._fwd_bwd(batch)
-        if not sg.refresh(g, batch):
-            return self._fwd_bwd(batch)
-        g["graph"].replay()
-        return g["loss"].clone(), g["extra"].clone()
-
-    def step(self, batch):
-        """One training step -> (loss, counts) on the device."""
-        loss, counts = self._graph_fwd_bwd(batch) if self.use_graph else self._fwd_bwd(batch)
-        st = self.model.__dict__.get("_geossl_status")
-        if st is not None:  # deferred index check of the backbone (a replayed graph cannot queue the host copy itself)
-            st.poll()
-            st.arm(every=8)
-        scale = self.reduce()
-        self.opt.step(grad_scale=scale)
-        return loss, counts
+    def _forward(self, batch, noise):
+        return infograph_step_fused(self.args, batch, self.model, self.discriminator)

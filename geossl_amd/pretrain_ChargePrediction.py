@@ -20,6 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
+from .step import Objective, StepTrainer, backbone_forward, backbone_latent, engine_for
 from .switches import env as _env
 
 node_class = 9   # examples/pretrain_ChargePrediction.py:106 (the mask token is node_class - 1)
@@ -102,17 +103,6 @@ def draw_mask(rng, batch, ratio):
     return {"mask_seed": device_seed(dev)}
 
 
-def _latent(args, batch, model, x0):
-    """:70-75 on the masked types x0 -> node_repr [N, F] (the readout is not evaluated: the step never reads it)."""
-    if args.model_3d == "schnet":
-        _, h = model(x0, batch.positions, batch.batch, return_latent=True, latent_only=True)
-    elif args.model_3d == "painn":
-        _, h = model(x0, batch.positions, batch.radius_edge_index, batch.batch, return_latent=True, latent_only=True)
-    else:
-        raise Exception("3D model {} not included.".format(args.model_3d))
-    return h
-
-
 def _status(model, h):
     """The backbone's deferred status word (_lib.StatusWord, made by its first forward), which a label out of range
     flags too."""
@@ -127,24 +117,11 @@ def charge_step_fused(args, batch, model, charge_predictor, mask):
     C = lin.out_features
     ratio = float(args.charge_masking_ratio)
     seed, given = mask.get("mask_seed"), mask.get("mask_idx")
-    bucket = getattr(batch, "_bucket", None)
-    if bucket is not None:
-        # the static batch of a one-view capacity bucket (geossl_amd/bucket.py): capacity-sized tensors, the real atom
-        # count in bucket.dyn; the fill has written x before this launch
-        if args.model_3d != bucket.kind or bucket.views != 1:
-            raise _lib.GeosslHipError("the Charge Prediction step needs a one-view bucket of its own backbone")
-        idx, labels, k = ops.charge_mask(batch.x, ratio, C, seed=seed, given=given, dyn=bucket.dyn)
-        x0 = batch.x[:, 0]
-        if bucket.kind == "schnet":
-            _, h = model(x0, batch.positions, bucket.b2, return_latent=True, latent_only=True, layout=bucket.lay2)
-        else:
-            _, h = model(x0, batch.positions, bucket.e2, bucket.b2, return_latent=True, latent_only=True,
-                         layout=bucket.lay2, edge_layout=bucket.el)
-        loss = ops.charge_head(h, lin.weight, lin.bias, idx, labels, k, _status(model, h), dyn=bucket.dyn)
-        return loss, (idx, k)
-    idx, labels, k = ops.charge_mask(batch.x, ratio, C, seed=seed, given=given)
-    h = _latent(args, batch, model, batch.x[:, 0])
-    return ops.charge_head(h, lin.weight, lin.bias, idx, labels, k, _status(model, h)), (idx, k)
+    # (a one-view capacity bucket: the real atom count in bucket.dyn; its fill has written x before this launch)
+    dyn = getattr(getattr(batch, "_bucket", None), "dyn", None)
+    idx, labels, k = ops.charge_mask(batch.x, ratio, C, seed=seed, given=given, dyn=dyn)
+    h, _, dyn = backbone_latent(args.model_3d, batch, model, x=batch.x[:, 0], what="Charge Prediction")
+    return ops.charge_head(h, lin.weight, lin.bias, idx, labels, k, _status(model, h), dyn=dyn), (idx, k)
 
 
 def charge_step_aten(args, batch, model, charge_predictor):
@@ -161,12 +138,7 @@ def charge_step_aten(args, batch, model, charge_predictor):
         masked_index = np.random.choice(M, mask_count(M, ratio), replace=False)
         charge[masked_index] = mask_token(charge_predictor)
         charge_actual_masked = charge_actual[masked_index]
-    if args.model_3d == "schnet":
-        _, node_repr = model(charge, batch.positions, batch.batch, return_latent=True)
-    elif args.model_3d == "painn":
-        _, node_repr = model(charge, batch.positions, batch.radius_edge_index, batch.batch, return_latent=True)
-    else:
-        raise Exception("3D model {} not included.".format(args.model_3d))
+    _, node_repr = backbone_forward(args, batch, model, True, x=charge)
     return charge_predictor(node_repr[masked_index], charge_actual_masked)
 
 
@@ -178,17 +150,6 @@ def _fused_batch_ok(batch):
             and x.is_contiguous() and pos.is_cuda and not pos.requires_grad and pos.dtype == torch.float32)
 
 
-def _charge_step(model, charge_predictor):
-    """The _AutogradStep of (backbone, predictor), kept on the backbone module; rebuilt when a parameter was replaced,
-    moved or frozen since (the graphs bind parameter addresses)."""
-    from .pretrain_GeoSSL import _AutogradStep
-    eng = model.__dict__.get("_geossl_charge_step")
-    if eng is None or eng.n1 is not charge_predictor or not eng.unchanged():
-        eng = _AutogradStep(model, charge_predictor, None, objective="ChargePrediction")
-        model.__dict__["_geossl_charge_step"] = eng
-    return eng
-
-
 class ChargeArgs:
     """The fields of the reference's argparse namespace the step reads."""
 
@@ -197,6 +158,27 @@ class ChargeArgs:
         self.charge_masking_ratio = float(charge_masking_ratio)
         self.mask_rng = mask_rng
         self.normalize = False
+
+
+def _write_mask(eng, args, sg, g, batch, mu, sigma, noise, device_noise):
+    if args.mask_rng == "numpy":   # (this step's host draw into the graph's static list; a device graph advances its seed)
+        sg.copy_noise(g, noise)
+
+
+def _keep_extra(eng, out, g):
+    eng.extra = g["extra"]   # (masked atoms, k) of the step just replayed: do_ChargePrediction takes them at once
+    return out
+
+
+# the mask is the one draw: `noise` = {"mask_seed"} (device draw) or {"mask_idx"} (host draw); a graph binds the ratio, a
+# by-value argument of its mask launch; forward -> (loss, (masked atoms, k)): static outputs of the forward graph
+CHARGE = Objective(
+    "ChargePrediction",
+    lambda eng, args, mu, sigma, batch, noise: charge_step_fused(args, batch, eng.model, eng.n1, noise),
+    graph_key=lambda args: ("ChargePrediction", args.model_3d, float(args.charge_masking_ratio), args.mask_rng),
+    noise_keys=lambda args: ("mask_idx" if args.mask_rng == "numpy" else "mask_seed",),
+    capture_inputs=lambda eng, args, batch, mu, sigma, noise, device_noise: noise,
+    write_inputs=_write_mask, result=_keep_extra)
 
 
 def do_ChargePrediction(args, batch, model, charge_predictor, graph=None):
@@ -227,7 +209,7 @@ def do_ChargePrediction(args, batch, model, charge_predictor, graph=None):
             and (handle or hasattr(batch, "super_edge_index"))):
         a = ChargeArgs(args.model_3d, ratio, rng)
         a.step_graph_mode = getattr(args, "step_graph_mode", "auto")
-        eng = _charge_step(model, charge_predictor)
+        eng = engine_for(model, "_geossl_charge_step", CHARGE, charge_predictor)
         loss = eng.run(a, batch, 0.0, 0.0, mask, False)
         if loss is not None:
             # (the graph's static outputs live in its memory pool: no reference to them may outlive this call, or a
@@ -240,7 +222,7 @@ def do_ChargePrediction(args, batch, model, charge_predictor, graph=None):
     return charge_step_fused(args, batch, model, charge_predictor, mask)[0]
 
 
-class ChargePredictionTrainer:
+class ChargePredictionTrainer(StepTrainer):
     """The body of ``train()`` (examples/pretrain_ChargePrediction.py:49-86): mask, backbone latent, fused charge head,
     backward, gradient all-reduce, Adam - backbone and predictor in one flat buffer (one fused Adam launch at one
     learning rate: the reference's gnn_3d_lr_scale is 1 by default), no host sync inside ``step``.
@@ -253,32 +235,23 @@ class ChargePredictionTrainer:
 
     def __init__(self, model, charge_predictor, lr=5e-4, weight_decay=0.0, model_3d="schnet", use_graph=False,
                  charge_masking_ratio=0.3, mask_rng="device", seed=None, max_graphs=256, graph_mode="auto"):
-        from .optim import FlatParams, FusedAdam
-        from .parallel import GradAllReduce
-        from .pretrain_GeoSSL import StepGraphs
         if not fused_head_ok(charge_predictor):
             raise ValueError("ChargePredictionTrainer needs the reference predictor at a width of the fused head "
                              "(F in 64, 128, 256, 512; 2 <= C <= 16) on the GPU; use do_ChargePrediction for anything "
                              "else")
         if mask_rng not in MASK_RNGS:
             raise ValueError("mask_rng is 'numpy' or 'device'")
-        self.model, self.predictor = model, charge_predictor
+        self.predictor = charge_predictor
         self.args = ChargeArgs(model_3d, charge_masking_ratio, mask_rng)
-        self.flat = FlatParams([model, charge_predictor])
-        self.opt = FusedAdam(self.flat, lr=lr, weight_decay=weight_decay)
-        self.reduce = GradAllReduce(self.flat.grad)
-        self.use_graph = use_graph
-        dev = self.flat.grad.device
         self._seeds = None
         if mask_rng == "device" and seed is not None:
             # successive seeds of this trainer: splitmix64 of (seed, n) - one for the eager buffer, one per capture
             self._seeds = [int(seed), 0]
         self.key = "mask_seed" if mask_rng == "device" else "mask_idx"
-        self.step_graphs = StepGraphs(self._fwd_bwd, model_3d, max_graphs, mode=graph_mode,
-                                      modules=(model, charge_predictor, None), noise_keys=(self.key,), views=1)
-        self.step_graphs.zero_with_refresh = self.flat.grad
-        self.seed = self._new_seed(dev) if mask_rng == "device" else None   # the eager steps' seed, advanced per draw
-        self._one = torch.ones((), dtype=torch.float32, device=dev)
+        super().__init__([model, charge_predictor], model_3d, lr, weight_decay, use_graph, max_graphs, graph_mode,
+                         noise_keys=(self.key,))
+        # the eager steps' seed, advanced per draw
+        self.seed = self._new_seed(self.flat.grad.device) if mask_rng == "device" else None
 
     def _new_seed(self, dev):
         if self._seeds is None:
@@ -291,49 +264,24 @@ class ChargePredictionTrainer:
         x ^= x >> 31
         return torch.tensor([x - (1 << 64) if x >= 1 << 63 else x], dtype=torch.long).to(dev)
 
-    def _fwd_bwd(self, batch, mask):
-        from .pretrain_GeoSSL import own_capture_open
-        if not own_capture_open():
-            self.flat.zero_grad()  # (a replayed step: cleared with the refresh of the graph's inputs, StepGraphs.refresh)
-        loss, extra = charge_step_fused(self.args, batch, self.model, self.predictor, mask)
-        with _lib.direct_grads():  # every p.grad is a view of self.flat.grad: kernels accumulate into it directly
-            loss.backward(self._one)
-        self.flat.rebind_grads()
-        return loss.detach(), extra
+    def _forward(self, batch, mask):
+        return charge_step_fused(self.args, batch, self.model, self.predictor, mask)
 
     def _mask(self, batch, fresh=False):
         if self.key == "mask_idx":
             return draw_mask("numpy", batch, self.args.charge_masking_ratio)
         return {"mask_seed": self._new_seed(batch_device(batch)) if fresh else self.seed}
 
-    def _graph_fwd_bwd(self, batch):
-        sg = self.step_graphs
-        g = sg.lookup(batch)
-        if g is None:
-            if not sg.capture_now(batch):  # a structure seen for the first time: eager
-                return self._fwd_bwd(batch, self._mask(batch))[0]
-            mask = self._mask(batch, fresh=True)
-            g = sg.capture(batch, mask)
-            if g is None:  # capture failed: eager from now on
-                self.use_graph = False
-                return self._fwd_bwd(batch, self._mask(batch))[0]
-            if not sg.refresh(g, batch, mask):
-                return self._fwd_bwd(batch, self._mask(batch))[0]
-        else:
-            # device masks: nothing to upload (the graph's seed advances on the device); numpy: this step's draw
-            mask = self._mask(batch) if self.key == "mask_idx" else None
-            if not sg.refresh(g, batch, mask):
-                return self._fwd_bwd(batch, self._mask(batch))[0]
-        g["graph"].replay()
-        return g["loss"].clone()
+    def _eager(self, batch, noise=None):
+        return self._fwd_bwd(batch, self._mask(batch))[0]
 
-    def step(self, batch):
-        """One training step -> the loss on the device."""
-        loss = self._graph_fwd_bwd(batch) if self.use_graph else self._fwd_bwd(batch, self._mask(batch))[0]
-        st = self.model.__dict__.get("_geossl_status")
-        if st is not None:  # deferred index check of the backbone and the labels
-            st.poll()
-            st.arm(every=8)
-        scale = self.reduce()
-        self.opt.step(grad_scale=scale)
-        return loss
+    def _capture_inputs(self, batch, noise):
+        return self._mask(batch, fresh=True)
+
+    def _write_inputs(self, g, batch, mask):
+        # a capture's own mask; then device masks: nothing to upload (the graph's seed advances on the device); numpy:
+        # this step's draw
+        if mask is None and self.key == "mask_idx":
+            mask = self._mask(batch)
+        if mask is not None:
+            self.step_graphs.copy_noise(g, mask)

@@ -24,6 +24,7 @@ from .switches import env as _env
 from . import _lib, ops
 from ._lib import call, ptr, stream
 from .layout import MolLayout
+from .step import Objective, StepTrainer, _OWN_CAPTURE, engine_for, latent, own_capture_open, with_counts  # noqa: F401
 
 NCSN_model_01 = None
 NCSN_model_02 = None
@@ -147,7 +148,8 @@ def do_DDM(args, batch, model, criterion=None, mu=0.0, sigma=0.3, num_neg=1, NCS
     if graph is None:
         graph = getattr(args, "step_graph", _env("GEOSSL_NO_STEP_GRAPH") is None)
     if graph and torch.is_grad_enabled() and not torch.cuda.is_current_stream_capturing() and fuse_views:
-        loss = _autograd_step(model, n1, n2).run(args, batch, mu, sigma, noise, device_noise)
+        eng = engine_for(model, "_geossl_autograd_step", DDM, n1, n2)
+        loss = eng.run(args, batch, mu, sigma, noise, device_noise)
         if loss is not None:
             return loss, 0
     return _do_ddm_eager(args, batch, model, mu, sigma, (n1, n2), noise, fuse_views, device_noise), 0
@@ -175,10 +177,9 @@ def _do_ddm_eager(args, batch, model, mu, sigma, heads, noise, fuse_views, devic
         pos2, distance_01, distance_02, x2 = ops.ddm_views(positions, pos_noise, super_edge_index[0], super_edge_index[1],
                                                            z=x_01, dyn=bucket.dyn)
         if bucket.kind == "schnet":
-            _, h = model(x2, pos2, bucket.b2, return_latent=True, layout=bucket.lay2, latent_only=True)
+            h = latent(model, "schnet", x2, pos2, bucket.b2, layout=bucket.lay2)
         else:
-            _, h = model(x2, pos2, bucket.e2, bucket.b2, return_latent=True, latent_only=True, layout=bucket.lay2,
-                         edge_layout=bucket.el)
+            h = latent(model, "painn", x2, pos2, bucket.b2, bucket.e2, layout=bucket.lay2, edge_layout=bucket.el)
         from .NCSN import ddm_heads_loss
         return ddm_heads_loss(n1, n2, batch, h, distance_02, None, distance_01,
                               noise_level_1=noise.get("noise_level_1"), distance_noise_1=noise.get("dist_noise_1"),
@@ -199,10 +200,10 @@ def _do_ddm_eager(args, batch, model, mu, sigma, heads, noise, fuse_views, devic
         if args.model_3d == "schnet":
             b2, lay2 = _two_view_batch(batch.batch, batch.num_graphs)
             # the readout is dead compute in this step (`_` at pretrain_GeoSSL.py:187): not evaluated
-            _, h = model(x2, pos2, b2, return_latent=True, layout=lay2, latent_only=True)
+            h = latent(model, "schnet", x2, pos2, b2, layout=lay2)
         else:
             b2, e2 = _two_view_edges(batch.batch, batch.radius_edge_index, batch.num_graphs)
-            _, h = model(x2, pos2, e2, b2, return_latent=True, latent_only=True)
+            h = latent(model, "painn", x2, pos2, b2, e2)
         molecule_3D_repr_01, molecule_3D_repr_02 = split_views(h, N)
     else:
         x_02, positions_02 = perturb(x_01, positions, mu, sigma, noise=noise.get("pos_noise"), device_noise=device_noise)
@@ -396,14 +397,6 @@ class Args:
 
 
 _NOISE_KEYS = ("pos_noise", "noise_level_1", "dist_noise_1", "noise_level_2", "dist_noise_2")
-_OWN_CAPTURE = [0]  # > 0 while StepGraphs._capture has a capture open
-
-
-def own_capture_open():
-    """True while a StepGraphs capture of this module is recording on the current stream: the one situation in which the
-    step's passes leave clearing the gradient buffer to StepGraphs.refresh.  A caller that captures the step in a CUDA
-    graph of ITS OWN gets the fill recorded into that graph like any other launch."""
-    return _OWN_CAPTURE[0] > 0 and torch.cuda.is_current_stream_capturing()
 
 
 class StepGraphs:
@@ -919,25 +912,18 @@ class _AutogradStep:
     land in a flat static buffer (the parameters' .grad point into it only while a step is captured); a step whose
     backward() has not been called when the next step arrives keeps a snapshot of them."""
 
-    def __init__(self, model, n1, n2, objective="DDM"):
-        from .NCSN import _head_params
+    def __init__(self, model, n1, n2, objective=None):
         self.model, self.n1, self.n2 = model, n1, n2
-        # "DDM" (two NCSN heads), "InfoNCE" / "EBM_NCE": no heads (n1 = n2 = None), the readout is part of the step, or
-        # "DistancePrediction" / "ChargePrediction": one head, the DistancePredictor / ChargePredictor (n1; n2 = None), or
-        # "InfoGraph": the Discriminator (n1; n2 = None), the readout is part of its head, or
-        # "Supervised": graph_pred_linear (n1; n2 = None), the readout is part of its head, or
-        # "TorsionAnglePrediction": the TorsionAnglePredictor (n1; n2 = None)
-        self.objective = objective
+        # the step.Objective of this engine (default: DDM) says everything that differs between objectives: the heads'
+        # parameters, the graphs' key and per-step static inputs, the forward, and what `run` returns.  The heads are
+        # the objective's own: two NCSN heads (DDM), none (n1 = n2 = None: the contrastive steps), or one (n1).
+        self.objective = objective = DDM if objective is None else objective
         heads = [m for m in (n1, n2) if m is not None]
         # the parameters the step reaches (a parameter outside it - an atomref table, PaiNN's output layers - gets no
         # gradient at all, like in the eager path, not a zero one)
         backbone = model._params() if hasattr(model, "_params") else _schnet_step_params(model)
-        head_params = ((lambda h: list(h.parameters()))
-                       if objective in ("DistancePrediction", "ChargePrediction", "InfoGraph", "Supervised",
-                                        "TorsionAnglePrediction")
-                       else _head_params)
         seen, self.params = set(), []
-        for p in list(backbone) + [q for h in heads for q in head_params(h)]:
+        for p in list(backbone) + [q for h in heads for q in objective.head_params(h)]:
             if id(p) not in seen and p.requires_grad:
                 seen.add(id(p))
                 self.params.append(p)
@@ -967,10 +953,10 @@ class _AutogradStep:
                 for name, p in sub._parameters.items():
                     if p is not None:
                         self._where.append((sub._parameters, name, p, p.data_ptr(), p.requires_grad))
-        self.graphs = {}   # (model_3d, normalize) -> StepGraphs
+        self.graphs = {}   # objective.graph_key(args) -> StepGraphs
         self._cfg = None
-        # ChargePrediction: (masked atoms, k) of the step `run` just replayed, the graph's static outputs (the caller takes
-        # them at once and clears this)
+        # static outputs of the graph `run` just replayed, for an objective whose `result` leaves them here (the caller
+        # takes them at once and clears this)
         self.extra = None
         self._side = torch.cuda.Stream(device=dev)   # the backward graphs replay here
         self._bwd_done = None                        # event behind the last backward replay
@@ -995,24 +981,7 @@ class _AutogradStep:
 
     def _fwd(self, batch, noise):
         args, mu, sigma = self._cfg
-        if self.objective == "DistancePrediction":
-            from .pretrain_DistancePrediction import distance_step_fused
-            return distance_step_fused(args, batch, self.model, self.n1)
-        if self.objective == "TorsionAnglePrediction":
-            from .pretrain_TorsionAnglePrediction import torsion_step_fused
-            return torsion_step_fused(args, batch, self.model, self.n1)
-        if self.objective == "ChargePrediction":   # -> (loss, (masked atoms, k)): static outputs of the forward graph
-            from .pretrain_ChargePrediction import charge_step_fused
-            return charge_step_fused(args, batch, self.model, self.n1, noise)
-        if self.objective == "InfoGraph":   # -> (loss, counts): the counts are a static output of the forward graph
-            from .pretrain_3DInfoGraph import infograph_step_fused
-            return infograph_step_fused(args, batch, self.model, self.n1)
-        if self.objective == "Supervised":   # (the target column is the graph's static input "target")
-            from .pretrain_Supervised import supervised_step_fused
-            return supervised_step_fused(args, batch, self.model, self.n1, noise["target"], args.stats, args.loss)[0]
-        if self.objective != "DDM":   # -> (loss, counts): the counts are a static output of the forward graph
-            return _contrastive_eager(self.objective, args, batch, self.model, mu, sigma, noise, True)
-        return _do_ddm_eager(args, batch, self.model, mu, sigma, (self.n1, self.n2), noise, True, True)
+        return self.objective.forward(self, args, mu, sigma, batch, noise)
 
     def _bwd(self, loss):
         held = [p.grad for p in self.params]
@@ -1082,48 +1051,22 @@ class _AutogradStep:
         return True
 
     def run(self, args, batch, mu, sigma, noise, device_noise):
-        """-> the loss (DDM) / (loss, counts as a host list) (contrastive, InfoGraph), or None: run this step eagerly."""
+        """-> `objective.result` of the replayed step (the loss, or the loss and more), or None: run this step eagerly."""
         if getattr(batch, "_dataset", None) is None and (not batch.positions.is_cuda or batch.positions.requires_grad):
             return None
-        contrastive = self.objective in CONTRASTIVE_OPTIONS
-        # (no random draws: the positions as they are; angle prediction: triples and targets are the batch's own, static
-        # inputs of a "triples" bucket that its fill refreshes)
-        distance = self.objective in ("DistancePrediction", "TorsionAnglePrediction")
-        # (the mask is the one draw: `noise` = {"mask_seed"} (device draw; a graph advances its own seed) or {"mask_idx"})
-        charge = self.objective == "ChargePrediction"
-        infograph = self.objective == "InfoGraph"   # (no random draws either)
-        # (no draws: the batch's target column is the one per-step input beside the molecules)
-        supervised = self.objective == "Supervised"
-        normalize = bool(getattr(args, "normalize", False))
-        if contrastive:   # (a graph binds T and num_neg: by-value arguments of its loss launches)
-            cargs = ContrastiveArgs(args.model_3d, normalize, getattr(args, "T", 0.1), getattr(args, "num_neg", 1))
-            key = (self.objective, args.model_3d, normalize, cargs.T, cargs.num_neg)
-        elif distance or infograph:   # (the tuple option is part of each StepGraphs key: bucket key / fingerprint)
-            key = (self.objective, args.model_3d)
-        elif charge:     # (a graph binds the ratio: a by-value argument of its mask launch)
-            key = (self.objective, args.model_3d, float(args.charge_masking_ratio), args.mask_rng)
-        elif supervised:   # (a graph binds the loss kind; the task column is chosen when the targets are written)
-            key = (self.objective, args.model_3d, args.loss, args.task_id)
-        else:
-            key = (args.model_3d, normalize)
+        obj = self.objective
+        key = obj.graph_key(args)   # (whatever a graph binds by value is part of it)
         sg = self.graphs.get(key)
         if sg is None:
-            # contrastive steps: capacity buckets with no heads (their row normalisation is over the 2B readout rows, an
-            # exact count: `normalize` does not keep them off buckets), one static draw
             sg = self.graphs[key] = StepGraphs(self._fwd_bwd, args.model_3d, split=(self._fwd, self._bwd),
                                                mode=getattr(args, "step_graph_mode", "auto"),
-                                               normalize=normalize and not contrastive,
+                                               normalize=obj.normalize and bool(getattr(args, "normalize", False)),
                                                modules=(self.model, self.n1, self.n2),
-                                               noise_keys=("pos_noise",) if contrastive else
-                                               (() if distance or infograph else
-                                                (("mask_idx" if args.mask_rng == "numpy" else "mask_seed",) if charge
-                                                 else (("target",) if supervised else None))),
-                                               views=1 if distance or charge or infograph or supervised else 2)
+                                               noise_keys=obj.noise_keys(args), views=obj.views)
             sg.zero_with_refresh = self.gflat
         if not sg.enabled:
             return None
-        self._cfg = (cargs if contrastive else args if charge or supervised else
-                     Args(args.model_3d, normalize and not (distance or infograph)), mu, sigma)
+        self._cfg = (obj.step_args(args), mu, sigma)
         g = sg.lookup(batch)
         if g is None and not sg.capture_now(batch):
             # first sighting of an index structure that only its own graph can serve (sampled tuples, PaiNN edge lists,
@@ -1139,17 +1082,7 @@ class _AutogradStep:
             if t is not None and t["g"] is None and not t.get("used"):
                 t["g"] = self.gflat.clone()  # a step still waiting for its backward() keeps its gradients
         if g is None:
-            if distance or infograph:
-                drawn = {}
-            elif charge:
-                drawn = noise
-            elif supervised:
-                from .pretrain_Supervised import target_column
-                drawn = {"target": target_column(batch, args.task_id)}
-            elif contrastive:
-                drawn = draw_views_noise(batch, mu, sigma, device_noise, noise)
-            else:
-                drawn = draw_step_noise(batch, self.n1, self.n2, mu, sigma, device_noise, noise)
+            drawn = obj.capture_inputs(self, args, batch, mu, sigma, noise, device_noise)
             g = sg.capture(batch, drawn)
             if g is None:
                 return None
@@ -1158,18 +1091,8 @@ class _AutogradStep:
         else:
             if not sg.refresh(g, batch):
                 return None  # (the bucket refused the batch's tensors: this step as eager launches)
-            if distance or infograph:
-                pass
-            elif charge:
-                if args.mask_rng == "numpy":   # (this step's host draw into the graph's static list)
-                    sg.copy_noise(g, noise)
-            elif supervised:
-                from .pretrain_Supervised import write_targets
-                write_targets(g, batch, args.task_id)
-            elif contrastive:
-                draw_views_noise(batch, mu, sigma, device_noise, noise, into=sg.noise_views(g))
-            else:
-                draw_step_noise(batch, self.n1, self.n2, mu, sigma, device_noise, noise, into=sg.noise_views(g))
+            if obj.write_inputs is not None:
+                obj.write_inputs(self, args, sg, g, batch, mu, sigma, noise, device_noise)
         g["graph"].replay()            # forward: the loss is on the device when this is done
         loss = g["loss"].clone()
         fwd_done = torch.cuda.Event()
@@ -1198,13 +1121,7 @@ class _AutogradStep:
             st.arm(every=8)
         out = _ReplayedLoss.apply(loss, self, self._ticket, *self.params).as_subclass(_StepLoss)
         out._geossl_step = (self, self._ticket)
-        if contrastive or infograph:
-            # the accuracy counts, read once the backward replay is queued: the host waits for the forward only (the
-            # reference's own acc is a host value too, :137 / :170; pretrain_3DInfoGraph.py:72-74)
-            return out, g["extra"].tolist()
-        if charge:
-            self.extra = g["extra"]
-        return out
+        return obj.result(self, out, g)
 
 
 _MT_PENDING = []   # tickets of this process whose autograd thread switch is still to be put back
@@ -1259,17 +1176,28 @@ def _schnet_step_params(model):
     return _core_params(model)
 
 
-def _autograd_step(model, n1, n2):
-    """The _AutogradStep of a (backbone, head, head) triple, kept on the backbone module; rebuilt when a parameter was
-    replaced, moved or frozen since (the graphs bind parameter addresses)."""
-    eng = model.__dict__.get("_geossl_autograd_step")
-    if eng is None or eng.n1 is not n1 or eng.n2 is not n2 or not eng.unchanged():
-        eng = _AutogradStep(model, n1, n2)
-        model.__dict__["_geossl_autograd_step"] = eng
-    return eng
+def _ddm_forward(engine, args, mu, sigma, batch, noise):
+    return _do_ddm_eager(args, batch, engine.model, mu, sigma, (engine.n1, engine.n2), noise, True, True)
 
 
-class DDMTrainer:
+def _ddm_head_params(head):
+    from .NCSN import _head_params
+    return _head_params(head)
+
+
+# the five draws of a step are the static inputs of its graphs: made for a capture, drawn into them before a replay
+DDM = Objective(
+    "DDM", _ddm_forward, views=2, normalize=True, head_params=_ddm_head_params,
+    graph_key=lambda args: (args.model_3d, bool(getattr(args, "normalize", False))),
+    noise_keys=lambda args: _NOISE_KEYS,
+    step_args=lambda args: Args(args.model_3d, bool(getattr(args, "normalize", False))),
+    capture_inputs=lambda eng, args, batch, mu, sigma, noise, device_noise:
+        draw_step_noise(batch, eng.n1, eng.n2, mu, sigma, device_noise, noise),
+    write_inputs=lambda eng, args, sg, g, batch, mu, sigma, noise, device_noise:
+        draw_step_noise(batch, eng.n1, eng.n2, mu, sigma, device_noise, noise, into=sg.noise_views(g)))
+
+
+class DDMTrainer(StepTrainer):
     """The body of ``train()`` (pretrain_GeoSSL.py:234-260) for the DDM option: forward of both
     views + both heads, backward, gradient all-reduce, Adam — flat parameter buffer, no host sync
     inside ``step`` (the reference's per-step ``loss.item()`` at :255 is logging, call
@@ -1285,41 +1213,32 @@ class DDMTrainer:
 
     def __init__(self, model, ncsn_01, ncsn_02, lr=5e-4, weight_decay=0.0, mu=0.0, sigma=0.3, model_3d="schnet",
                  device_noise=True, use_graph=False, overlap_heads=True, max_graphs=256, graph_mode="auto"):
-        from .optim import FlatParams, FusedAdam
-        from .parallel import GradAllReduce
-        self.model, self.n1, self.n2 = model, ncsn_01, ncsn_02
+        self.n1, self.n2 = ncsn_01, ncsn_02
         self.args = Args(model_3d)
         self.mu, self.sigma = mu, sigma
         self.device_noise = device_noise
-        self.flat = FlatParams([model, ncsn_01, ncsn_02])
-        self.opt = FusedAdam(self.flat, lr=lr, weight_decay=weight_decay)
-        self.reduce = GradAllReduce(self.flat.grad)
-        self.use_graph = use_graph
         # two-pass NCSN backward only (GEOSSL_NCSN_SPLIT_BWD): its weight-gradient kernels on a side stream, concurrent
         # with the backbone's backward; the default one-pass backward has nothing to overlap
         self.overlap_heads = overlap_heads
-        # graph_mode "auto": ragged SchNet batches share one capacity-bucket graph per batch size, equal-sized molecules
-        # one graph per size, anything else one per structure from its second sighting on; "structure": one graph per
-        # structure fingerprint, captured at first sight (StepGraphs)
-        self.step_graphs = StepGraphs(self._fwd_bwd, model_3d, max_graphs, mode=graph_mode,
-                                      modules=(model, ncsn_01, ncsn_02))
-        self.step_graphs.zero_with_refresh = self.flat.grad
         self._zero_outside = True
-        self._one = torch.ones((), dtype=torch.float32, device=self.flat.grad.device)
         self._side = None
+        super().__init__([model, ncsn_01, ncsn_02], model_3d, lr, weight_decay, use_graph, max_graphs, graph_mode,
+                         noise_keys=None, views=2)
 
     @property
     def _graphs(self):
         return self.step_graphs.graphs
 
     def _fwd_bwd(self, batch, noise):
-        from . import NCSN as _ncsn
         if not (self._zero_outside and own_capture_open()):
             self.flat.zero_grad()  # (a replayed step: cleared with the refresh of the graph's inputs, StepGraphs.refresh)
         if noise is None and self.device_noise:
             noise = self._draw_noise(batch)  # the trainer's own stream, eager launches or replayed graph alike
-        loss = _do_ddm_eager(self.args, batch, self.model, self.mu, self.sigma, (self.n1, self.n2), noise, True,
-                             self.device_noise)
+        return self._backward(_do_ddm_eager(self.args, batch, self.model, self.mu, self.sigma, (self.n1, self.n2), noise,
+                                            True, self.device_noise))
+
+    def _backward(self, loss):
+        from . import NCSN as _ncsn
         if self._side is None and self.overlap_heads:
             self._side = torch.cuda.Stream()
         _ncsn.set_side_stream(self._side)  # head weight gradients overlap the backbone's backward
@@ -1334,27 +1253,14 @@ class DDMTrainer:
 
     _NOISE_KEYS = _NOISE_KEYS
 
-    def _graph_fwd_bwd(self, batch, noise):
-        sg = self.step_graphs
-        g = sg.lookup(batch)
-        own_noise = noise is None
-        if g is None:
-            if not sg.capture_now(batch):  # a structure only its own graph can serve, seen for the first time: eager
-                return self._fwd_bwd(batch, noise)
-            if own_noise:
-                noise = self._draw_noise(batch)  # this step's draws (the capture needs tensors to clone)
-            g = sg.capture(batch, noise)
-            if g is None:  # capture failed: eager from now on
-                self.use_graph = False
-                return self._fwd_bwd(batch, noise)
-            own_noise = False  # already drawn: copied below like a caller's
-        if not sg.refresh(g, batch, None if own_noise else noise):
-            return self._fwd_bwd(batch, noise)  # (the bucket refused the batch's tensors: this step as eager launches)
-        if own_noise:  # the step's own draws go straight into the graph's static inputs (no staging copies)
+    def _capture_inputs(self, batch, noise):
+        return self._draw_noise(batch) if noise is None else noise  # (the capture needs tensors to clone)
+
+    def _write_inputs(self, g, batch, noise):
+        if noise is None:  # the step's own draws go straight into the graph's static inputs (no staging copies)
             self._draw_noise(g["batch"], into=g["noise"])  # (g["batch"]: a bucket's draws cover its capacity)
-        g["graph"].replay()
-        # (a clone: the static scalar is overwritten by the next replay, and freed with its graph when that is dropped)
-        return g["loss"].clone()
+        else:
+            StepGraphs.copy_noise(g, noise)
 
     def _draw_noise(self, batch, into=None):
         """The five random draws of a step on the device (perturb: pretrain_GeoSSL.py:72; the heads: NCSN.py:190,194),
@@ -1368,16 +1274,8 @@ class DDMTrainer:
         batch's own fingerprint."""
         if self.use_graph and ((noise is None and self.device_noise)
                                or (noise is not None and all(k in noise for k in _NOISE_KEYS))):
-            loss = self._graph_fwd_bwd(batch, noise)
-        else:
-            loss = self._fwd_bwd(batch, noise)
-        st = self.model.__dict__.get("_geossl_status")
-        if st is not None:  # deferred index check of the backbone (a replayed graph cannot queue the host copy itself)
-            st.poll()
-            st.arm(every=8)  # an out-of-range atom type surfaces up to eight steps late
-        scale = self.reduce()
-        self.opt.step(grad_scale=scale)
-        return loss
+            return self._finish(self._graph_fwd_bwd(batch, noise))
+        return self._finish(self._fwd_bwd(batch, noise))
 
 
 # ---- the contrastive objectives: --GeoSSL_option=InfoNCE / EBM_NCE (pretrain_GeoSSL.py:103-176) -----------------------
@@ -1518,18 +1416,34 @@ def _contrastive_with_criterion(objective, args, batch, model, criterion, mu, si
     return loss, acc.detach().item()
 
 
-def _contrastive_step(model, objective):
-    """The _AutogradStep of (backbone, objective), kept on the backbone module beside the DDM one; rebuilt when a parameter
-    was replaced, moved or frozen since (the graphs bind parameter addresses)."""
-    name = "_geossl_contrastive_step_" + objective
-    eng = model.__dict__.get(name)
-    if eng is None or not eng.unchanged():
-        eng = _AutogradStep(model, None, None, objective=objective)
-        model.__dict__[name] = eng
-    return eng
+def _contrastive_objective(option):
+    """The step.Objective of one contrastive option: no heads (the readout is part of the step), two views, capacity
+    buckets whatever `normalize` says (the row normalisation is over the 2B readout rows, an exact count), one static
+    draw; a graph binds T and num_neg (by-value arguments of its loss launches); -> (loss, counts)."""
+    def cargs(args):
+        return ContrastiveArgs(args.model_3d, getattr(args, "normalize", False), getattr(args, "T", 0.1),
+                               getattr(args, "num_neg", 1))
+
+    def key(args):
+        return (option, args.model_3d, bool(getattr(args, "normalize", False)), float(getattr(args, "T", 0.1)),
+                int(getattr(args, "num_neg", 1)))
+
+    return Objective(
+        option, lambda eng, args, mu, sigma, batch, noise:
+            _contrastive_eager(option, args, batch, eng.model, mu, sigma, noise, True),
+        views=2, graph_key=key, noise_keys=lambda args: ("pos_noise",), step_args=cargs,
+        capture_inputs=lambda eng, args, batch, mu, sigma, noise, device_noise:
+            draw_views_noise(batch, mu, sigma, device_noise, noise),
+        write_inputs=lambda eng, args, sg, g, batch, mu, sigma, noise, device_noise:
+            draw_views_noise(batch, mu, sigma, device_noise, noise, into=sg.noise_views(g)),
+        result=with_counts)
 
 
-def _do_contrastive(objective, args, batch, model, criterion, mu, sigma, num_neg, noise, device_noise, graph):
+INFONCE, EBM_NCE = (_contrastive_objective(o) for o in CONTRASTIVE_OPTIONS)
+
+
+def _do_contrastive(obj, args, batch, model, criterion, mu, sigma, num_neg, noise, device_noise, graph):
+    objective = obj.name
     stock = _stock_ce(CE_criterion) if objective == "InfoNCE" else _stock_bce(criterion)
     if not stock:
         crit = CE_criterion if objective == "InfoNCE" else criterion
@@ -1539,7 +1453,8 @@ def _do_contrastive(objective, args, batch, model, criterion, mu, sigma, num_neg
         graph = getattr(args, "step_graph", _env("GEOSSL_NO_STEP_GRAPH") is None)
     if graph and torch.is_grad_enabled() and not torch.cuda.is_current_stream_capturing():
         cargs.step_graph_mode = getattr(args, "step_graph_mode", "auto")
-        out = _contrastive_step(model, objective).run(cargs, batch, mu, sigma, noise, device_noise)
+        eng = engine_for(model, "_geossl_contrastive_step_" + objective, obj)
+        out = eng.run(cargs, batch, mu, sigma, noise, device_noise)
         if out is not None:
             loss, counts = out
             return loss, contrastive_acc(objective, counts, batch.num_graphs, num_neg)
@@ -1552,18 +1467,18 @@ def do_InfoNCE(args, batch, model, criterion=None, mu=0.0, sigma=0.3, num_neg=1,
     """pretrain_GeoSSL.py:141-176 -> (loss, acc): loss an fp32 scalar tensor, acc a Python float.  `criterion` and
     `num_neg` are ignored like in the reference (it uses the module global CE_criterion).  noise: optional
     {"pos_noise": [N, 3]}; device_noise / graph as in do_DDM (graph: HIP graphs of forward + backward, capacity buckets included)."""
-    return _do_contrastive("InfoNCE", args, batch, model, criterion, mu, sigma, num_neg, noise, device_noise, graph)
+    return _do_contrastive(INFONCE, args, batch, model, criterion, mu, sigma, num_neg, noise, device_noise, graph)
 
 
 def do_EBM_NCE(args, batch, model, criterion=None, mu=0.0, sigma=0.3, num_neg=1, noise=None, device_noise=False,
                graph=None):
     """pretrain_GeoSSL.py:103-138 -> (loss, acc): loss a float64 scalar tensor, acc a Python float.  criterion: None or
     the reference's nn.BCEWithLogitsLoss() run on the kernels; any other criterion on the eager fallback."""
-    return _do_contrastive("EBM_NCE", args, batch, model, criterion, mu, sigma, int(num_neg), noise, device_noise,
+    return _do_contrastive(EBM_NCE, args, batch, model, criterion, mu, sigma, int(num_neg), noise, device_noise,
                            graph)
 
 
-class ContrastiveTrainer:
+class ContrastiveTrainer(StepTrainer):
     """The body of ``train()`` (pretrain_GeoSSL.py:234-260) for --GeoSSL_option InfoNCE / EBM_NCE: forward of both views,
     readout, contrastive loss, backward, gradient all-reduce, Adam - all parameters in one flat buffer (one fused Adam
     launch, one all-reduce), like DDMTrainer.  ``step(batch) -> (loss, counts)``: both device tensors, no host sync
@@ -1575,65 +1490,36 @@ class ContrastiveTrainer:
     def __init__(self, model, option="InfoNCE", lr=5e-4, weight_decay=0.0, mu=0.0, sigma=0.3, T=0.1, num_neg=1,
                  normalize=False, model_3d="schnet", device_noise=True, use_graph=False, max_graphs=256,
                  graph_mode="auto"):
-        from .optim import FlatParams, FusedAdam
-        from .parallel import GradAllReduce
         if option not in CONTRASTIVE_OPTIONS:
             raise ValueError("option is one of %s" % (CONTRASTIVE_OPTIONS,))
-        self.model, self.option = model, option
+        self.option = option
         self.args = ContrastiveArgs(model_3d, normalize, T, num_neg)
         self.mu, self.sigma = mu, sigma
         self.device_noise = device_noise
-        self.flat = FlatParams([model])
-        self.opt = FusedAdam(self.flat, lr=lr, weight_decay=weight_decay)
-        self.reduce = GradAllReduce(self.flat.grad)
-        self.use_graph = use_graph
-        # (capacity buckets with no heads; `normalize` is over the 2B readout rows and does not keep a batch off them)
-        self.step_graphs = StepGraphs(self._fwd_bwd, model_3d, max_graphs, mode=graph_mode, modules=(model, None, None),
-                                      noise_keys=("pos_noise",))
-        self.step_graphs.zero_with_refresh = self.flat.grad
-        dev = self.flat.grad.device
-        self._one = torch.ones((), dtype=torch.float64 if option == "EBM_NCE" else torch.float32, device=dev)
+        # (capacity buckets with no heads; `normalize` is over the 2B readout rows and does not keep a batch off them;
+        # EBM-NCE's loss is a float64 scalar: so is the standing 1.0 of its backward)
+        super().__init__([model], model_3d, lr, weight_decay, use_graph, max_graphs, graph_mode, noise_keys=("pos_noise",),
+                         views=2, one_dtype=torch.float64 if option == "EBM_NCE" else torch.float32)
 
-    def _fwd_bwd(self, batch, noise):
-        if not own_capture_open():
-            self.flat.zero_grad()  # (a replayed step: cleared with the refresh of the graph's inputs, StepGraphs.refresh)
+    with_extra = True
+
+    def _forward(self, batch, noise):
         if noise is None:
             noise = draw_views_noise(batch, self.mu, self.sigma, self.device_noise)
-        loss, counts = _contrastive_eager(self.option, self.args, batch, self.model, self.mu, self.sigma, noise,
-                                          self.device_noise)
-        with _lib.direct_grads():  # every p.grad is a view of self.flat.grad: kernels accumulate into it directly
-            loss.backward(self._one)
-        self.flat.rebind_grads()
-        return loss.detach(), counts
+        return _contrastive_eager(self.option, self.args, batch, self.model, self.mu, self.sigma, noise,
+                                  self.device_noise)
 
-    def _graph_fwd_bwd(self, batch, noise):
-        sg = self.step_graphs
-        g = sg.lookup(batch)
-        if g is None:
-            if not sg.capture_now(batch):  # a structure seen for the first time: eager
-                return self._fwd_bwd(batch, noise)
-            noise = draw_views_noise(batch, self.mu, self.sigma, self.device_noise, noise)
-            g = sg.capture(batch, noise)
-            if g is None:  # capture failed: eager from now on
-                self.use_graph = False
-                return self._fwd_bwd(batch, noise)
-        if not sg.refresh(g, batch, noise):
-            return self._fwd_bwd(batch, noise)
+    def _capture_inputs(self, batch, noise):
+        return draw_views_noise(batch, self.mu, self.sigma, self.device_noise, noise)
+
+    def _write_inputs(self, g, batch, noise):
         if noise is None:   # the step's own draw straight into the graph's static input
             draw_views_noise(g["batch"], self.mu, self.sigma, self.device_noise, into=g["noise"])
-        g["graph"].replay()
-        return g["loss"].clone(), g["extra"].clone()
+        else:
+            StepGraphs.copy_noise(g, noise)
 
     def step(self, batch, noise=None):
         """One training step -> (loss, counts) on the device."""
         if self.use_graph and (noise is not None or self.device_noise):
-            loss, counts = self._graph_fwd_bwd(batch, noise)
-        else:
-            loss, counts = self._fwd_bwd(batch, noise)
-        st = self.model.__dict__.get("_geossl_status")
-        if st is not None:  # deferred index check of the backbone (a replayed graph cannot queue the host copy itself)
-            st.poll()
-            st.arm(every=8)
-        scale = self.reduce()
-        self.opt.step(grad_scale=scale)
-        return loss, counts
+            return self._finish(self._graph_fwd_bwd(batch, noise))
+        return self._finish(self._fwd_bwd(batch, noise))

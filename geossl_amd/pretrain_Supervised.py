@@ -14,7 +14,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib, ops
+from . import ops
+from .step import Objective, StepTrainer, backbone_forward, backbone_latent, engine_for
 from .switches import env as _env
 
 
@@ -157,53 +158,22 @@ class _Stats:
 
 
 # --------------------------------------------------------------------------------------------------------- steps
-def _latent(args, batch, model):
-    """The backbone call of :86-90 with the readout left to the head -> h [N, F]."""
-    if args.model_3d == "schnet":
-        _, h = model(batch.x[:, 0], batch.positions, batch.batch, return_latent=True, latent_only=True)
-    elif args.model_3d == "painn":
-        _, h = model(batch.x, batch.positions, batch.radius_edge_index, batch.batch, return_latent=True,
-                     latent_only=True)
-    else:
-        raise Exception("3D model {} not included.".format(args.model_3d))
-    return h
-
-
-def _latent_and_layout(args, batch, model):
-    bucket = getattr(batch, "_bucket", None)
-    if bucket is not None:
-        # the static batch of a one-view capacity bucket (geossl_amd/bucket.py): capacity-sized atom rows, the real atom
-        # count in bucket.dyn; lay2.mol_ptr holds the B real offsets of view 0
-        if args.model_3d != bucket.kind or bucket.views != 1:
-            raise _lib.GeosslHipError("the Supervised step needs a one-view bucket of its own backbone")
-        if bucket.kind == "schnet":
-            _, h = model(batch.x[:, 0], batch.positions, bucket.b2, return_latent=True, latent_only=True,
-                         layout=bucket.lay2)
-        else:
-            _, h = model(batch.x, batch.positions, bucket.e2, bucket.b2, return_latent=True, latent_only=True,
-                         layout=bucket.lay2, edge_layout=bucket.el)
-        return h, bucket.lay2, bucket.dyn
-    from .layout import get_layout
-    h = _latent(args, batch, model)
-    return h, get_layout(batch.batch), None
+def _x_of(args, batch):
+    """The backbone's first argument in :86-90: SchNet gets the atom-type column, PaiNN batch.x unsliced."""
+    return batch.x if args.model_3d == "painn" else batch.x[:, 0]
 
 
 def supervised_step_fused(args, batch, model, graph_pred_linear, target, stats, loss):
     """The step as eager launches: the backbone's latent, then the fused head with the backbone's readout in it ->
     (loss fp32 scalar, normalised pred [B]).  target [B]: the task column; stats: float32 [2] (mean, std) on the
     device."""
-    h, lay, dyn = _latent_and_layout(args, batch, model)
+    h, lay, dyn = backbone_latent(args.model_3d, batch, model, x=_x_of(args, batch), what="Supervised", layout=True)
     return ops.property_head(h, head_params(graph_pred_linear), lay, readout_of(model), target, stats, loss, dyn=dyn)
 
 
 def supervised_step_aten(args, batch, model, graph_pred_linear, TRAIN_mean, TRAIN_std, task_id, criterion):
     """:84-101 as the reference writes them, on our backbone."""
-    if args.model_3d == "schnet":
-        molecule_3D_repr = model(batch.x[:, 0], batch.positions, batch.batch)
-    elif args.model_3d == "painn":
-        molecule_3D_repr = model(batch.x, batch.positions, batch.radius_edge_index, batch.batch)
-    else:
-        raise Exception("3D model {} not included.".format(args.model_3d))
+    molecule_3D_repr = backbone_forward(args, batch, model, False, x=_x_of(args, batch))
 
     if graph_pred_linear is not None:
         pred = graph_pred_linear(molecule_3D_repr).squeeze()
@@ -226,16 +196,18 @@ class _StepArgs:
         self.step_graph_mode = mode
 
 
-def _supervised_step(model, graph_pred_linear):
-    """The _AutogradStep of (backbone, head), kept on the backbone module; rebuilt when a parameter was replaced, moved or
-    frozen since (the graphs bind parameter addresses)."""
-    from .pretrain_GeoSSL import _AutogradStep
-    eng = model.__dict__.get("_geossl_supervised_step")
-    if eng is None or eng.n1 is not graph_pred_linear or not eng.unchanged():
-        eng = _AutogradStep(model, graph_pred_linear, None, objective="Supervised")
-        eng.stats = _Stats(eng.gflat.device)
-        model.__dict__["_geossl_supervised_step"] = eng
-    return eng
+# (no draws: the batch's target column, the graph's static input "target", is the one per-step input beside the
+# molecules; a graph binds the loss kind, the task column is chosen when the targets are written)
+SUPERVISED = Objective(
+    "Supervised",
+    lambda eng, args, mu, sigma, batch, noise:
+        supervised_step_fused(args, batch, eng.model, eng.n1, noise["target"], args.stats, args.loss)[0],
+    graph_key=lambda args: ("Supervised", args.model_3d, args.loss, args.task_id),
+    noise_keys=lambda args: ("target",),
+    capture_inputs=lambda eng, args, batch, mu, sigma, noise, device_noise:
+        {"target": target_column(batch, args.task_id)},
+    write_inputs=lambda eng, args, sg, g, batch, mu, sigma, noise, device_noise:
+        write_targets(g, batch, args.task_id))
 
 
 def _raise_like_squeeze(B):
@@ -264,7 +236,9 @@ def do_Supervised(args, batch, model, graph_pred_linear, TRAIN_mean, TRAIN_std, 
     if graph is None:
         graph = getattr(args, "step_graph", _env("GEOSSL_NO_STEP_GRAPH") is None)
     if graph and torch.is_grad_enabled() and not torch.cuda.is_current_stream_capturing():
-        eng = _supervised_step(model, graph_pred_linear)
+        eng = engine_for(model, "_geossl_supervised_step", SUPERVISED, graph_pred_linear)
+        if "stats" not in eng.__dict__:
+            eng.stats = _Stats(eng.gflat.device)
         a = _StepArgs(args.model_3d, kind, task_id, eng.stats.set(TRAIN_mean, TRAIN_std),
                       getattr(args, "step_graph_mode", "auto"))
         loss = eng.run(a, batch, 0.0, 0.0, None, False)
@@ -287,10 +261,7 @@ def predict_Supervised(args, batch, model, graph_pred_linear, TRAIN_mean, TRAIN_
     pos = getattr(batch, "positions", None) if getattr(batch, "_dataset", None) is None else None
     cuda = getattr(batch, "_dataset", None) is not None or (pos is not None and pos.is_cuda)
     if (ps is None or readout_of(model) is None or model_width(model) != ps[0].size(1) or not cuda):
-        if args.model_3d == "schnet":
-            molecule_3D_repr = model(batch.x[:, 0], batch.positions, batch.batch)
-        else:
-            molecule_3D_repr = model(batch.x, batch.positions, batch.radius_edge_index, batch.batch)
+        molecule_3D_repr = backbone_forward(args, batch, model, False, x=_x_of(args, batch))
         if graph_pred_linear is not None:
             pred = graph_pred_linear(molecule_3D_repr).squeeze()
         else:
@@ -298,12 +269,12 @@ def predict_Supervised(args, batch, model, graph_pred_linear, TRAIN_mean, TRAIN_
         B = pred.size()[0]  # noqa: F841  (the reference's, :370: raises at B = 1)
         return pred * TRAIN_std + TRAIN_mean
     _raise_like_squeeze(_n_mols(batch))
-    h, lay, dyn = _latent_and_layout(args, batch, model)
+    h, lay, dyn = backbone_latent(args.model_3d, batch, model, x=_x_of(args, batch), what="Supervised", layout=True)
     return ops.property_predict(h, ps, lay, readout_of(model), _stats_tensor(h.device, TRAIN_mean, TRAIN_std), dyn=dyn)
 
 
 # -------------------------------------------------------------------------------------------------------- trainer
-class SupervisedTrainer:
+class SupervisedTrainer(StepTrainer):
     """The body of ``train()`` (pretrain_Supervised.py:66-119, finetune_qm9.py:163-275): backbone latent, fused property
     head with the readout in it, backward, gradient all-reduce, Adam - backbone and graph_pred_linear in one flat buffer
     (one fused Adam launch: both of the reference's groups run at args.lr), no host sync inside ``step``.
@@ -315,9 +286,6 @@ class SupervisedTrainer:
 
     def __init__(self, model, graph_pred_linear, TRAIN_mean, TRAIN_std, task_id=6, loss="mae", lr=5e-4,
                  weight_decay=0.0, model_3d="schnet", use_graph=False, max_graphs=256, graph_mode="auto"):
-        from .optim import FlatParams, FusedAdam
-        from .parallel import GradAllReduce
-        from .pretrain_GeoSSL import StepGraphs
         if loss not in ops.PROPERTY_LOSSES:
             raise ValueError("loss is 'mae' or 'mse', got %r" % (loss,))
         ps = head_params(graph_pred_linear)
@@ -325,19 +293,13 @@ class SupervisedTrainer:
             raise ValueError("SupervisedTrainer needs graph_pred_linear = Linear(F, 1) or PaiNN's default "
                              "create_output_layers() at F = 64, 128 or 256 on the GPU and a backbone of that width with an "
                              "unscaled mean / add readout; use do_Supervised for anything else")
-        self.model, self.head = model, graph_pred_linear
+        self.head = graph_pred_linear
         self.model_3d, self.loss_kind, self.task_id = model_3d, loss, int(task_id)
-        self.flat = FlatParams([model, graph_pred_linear])
-        self.opt = FusedAdam(self.flat, lr=lr, weight_decay=weight_decay)
-        self.reduce = GradAllReduce(self.flat.grad)
+        super().__init__([model, graph_pred_linear], model_3d, lr, weight_decay, use_graph, max_graphs, graph_mode,
+                         noise_keys=("target",))
         self.stats = _Stats(self.flat.grad.device)
         self.stats.set(TRAIN_mean, TRAIN_std)
         self.args = _StepArgs(model_3d, loss, task_id, self.stats.t)
-        self.use_graph = use_graph
-        self.step_graphs = StepGraphs(self._fwd_bwd, model_3d, max_graphs, mode=graph_mode,
-                                      modules=(model, graph_pred_linear, None), noise_keys=("target",), views=1)
-        self.step_graphs.zero_with_refresh = self.flat.grad
-        self._one = torch.ones((), dtype=torch.float32, device=self.flat.grad.device)
 
     @property
     def lr(self):
@@ -351,44 +313,20 @@ class SupervisedTrainer:
         """TRAIN_mean / TRAIN_std of the following steps (read on the device: no recapture)."""
         self.stats.set(mean, std)
 
-    def _fwd_bwd(self, batch, noise=None):
-        from .pretrain_GeoSSL import own_capture_open
-        if not own_capture_open():
-            self.flat.zero_grad()  # (a replayed step: cleared with the refresh of the graph's inputs, StepGraphs.refresh)
+    def _forward(self, batch, noise):
         target = noise["target"] if noise is not None else target_column(batch, self.task_id)
-        loss, _ = supervised_step_fused(self.args, batch, self.model, self.head, target, self.stats.t, self.loss_kind)
-        with _lib.direct_grads():  # every p.grad is a view of self.flat.grad: kernels accumulate into it directly
-            loss.backward(self._one)
-        self.flat.rebind_grads()
-        return loss.detach()
+        return supervised_step_fused(self.args, batch, self.model, self.head, target, self.stats.t, self.loss_kind)[0]
 
-    def _graph_fwd_bwd(self, batch):
-        sg = self.step_graphs
-        g = sg.lookup(batch)
-        if g is None:
-            if not sg.capture_now(batch):  # a structure seen for the first time: eager
-                return self._fwd_bwd(batch)
-            g = sg.capture(batch, {"target": target_column(batch, self.task_id)})
-            if g is None:  # capture failed: eager from now on
-                self.use_graph = False
-                return self._fwd_bwd(batch)
-        if not sg.refresh(g, batch):
-            return self._fwd_bwd(batch)
+    def _capture_inputs(self, batch, noise):
+        return {"target": target_column(batch, self.task_id)}
+
+    def _write_inputs(self, g, batch, noise):
         write_targets(g, batch, self.task_id)
-        g["graph"].replay()
-        return g["loss"].clone()
 
     def step(self, batch):
         """One training step -> the loss on the device."""
         _raise_like_squeeze(_n_mols(batch))
-        loss = self._graph_fwd_bwd(batch) if self.use_graph else self._fwd_bwd(batch)
-        st = self.model.__dict__.get("_geossl_status")
-        if st is not None:  # deferred index check of the backbone (a replayed graph cannot queue the host copy itself)
-            st.poll()
-            st.arm(every=8)
-        scale = self.reduce()
-        self.opt.step(grad_scale=scale)
-        return loss
+        return super().step(batch)
 
     def predict(self, batch):
         """eval()'s predictions of one batch with the trainer's parameters and (mean, std)."""

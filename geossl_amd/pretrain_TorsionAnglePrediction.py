@@ -20,7 +20,8 @@ import torch.nn as nn
 
 from . import _lib, ops
 from .layout import UngroupedSuperEdges
-from .pretrain_GeoSSL import TripleBatch  # noqa: F401  (the device batch type of collated triple batches)
+from .pretrain_GeoSSL import Args, TripleBatch  # (TripleBatch: the device batch type of collated triple batches)
+from .step import Objective, StepTrainer, backbone_forward, backbone_latent, engine_for
 from .switches import env as _env
 
 
@@ -51,18 +52,6 @@ def fused_head_ok(torsion_angle_predictor):
             and ops.torsion_head_width_ok(lin.in_features // 3))
 
 
-def _node_repr(args, batch, model):
-    """:66-71 -> node_repr [N, F] (the readout is not evaluated: the step never reads it)."""
-    x = batch.x[:, 0]
-    if args.model_3d == "schnet":
-        _, h = model(x, batch.positions, batch.batch, return_latent=True, latent_only=True)
-    elif args.model_3d == "painn":
-        _, h = model(x, batch.positions, batch.radius_edge_index, batch.batch, return_latent=True, latent_only=True)
-    else:
-        raise Exception("3D model {} not included.".format(args.model_3d))
-    return h
-
-
 def _check_grouped(batch_vec, triples):
     """The fused backward finds a molecule's triples as ONE run of the list: the triples must be grouped by molecule in
     batch order with their three atoms in one molecule.  Collated AtomTripleExtractor output is (marked by the collation:
@@ -90,31 +79,22 @@ def torsion_step_fused(args, batch, model, torsion_angle_predictor):
         # atom and triple counts in bucket.dyn
         if args.model_3d != bucket.kind or bucket.views != 1 or bucket.T_cap < 1:
             raise _lib.GeosslHipError("the angle-prediction step needs a one-view triples bucket of its own backbone")
-        x = batch.x[:, 0]
-        if bucket.kind == "schnet":
-            _, h = model(x, batch.positions, bucket.b2, return_latent=True, latent_only=True, layout=bucket.lay2)
-        else:
-            _, h = model(x, batch.positions, bucket.e2, bucket.b2, return_latent=True, latent_only=True,
-                         layout=bucket.lay2, edge_layout=bucket.el)
-        loss, _ = ops.torsion_head(h, lin.weight, lin.bias, batch.super_edge_index, batch.super_edge_angle,
-                                   bucket.lay2.mol_ptr, dyn=bucket.dyn)
-        return loss
-    from .layout import get_layout
-    _check_grouped(batch.batch, batch.super_edge_index)
-    h = _node_repr(args, batch, model)
-    loss, _ = ops.torsion_head(h, lin.weight, lin.bias, batch.super_edge_index, batch.super_edge_angle,
-                               get_layout(batch.batch).mol_ptr)
+    else:
+        _check_grouped(batch.batch, batch.super_edge_index)
+    h, lay, dyn = backbone_latent(args.model_3d, batch, model, what="angle-prediction", layout=True)
+    loss, _ = ops.torsion_head(h, lin.weight, lin.bias, batch.super_edge_index, batch.super_edge_angle, lay.mol_ptr,
+                               dyn=dyn)
     return loss
+
+
+# (no random draws; triples and targets are the batch's own: static inputs of a "triples" bucket that its fill refreshes)
+TORSION = Objective("TorsionAnglePrediction",
+                    lambda eng, args, mu, sigma, batch, noise: torsion_step_fused(args, batch, eng.model, eng.n1))
 
 
 def torsion_step_aten(args, batch, model, torsion_angle_predictor):
     """:64-78 restated in ATen on our backbone: the fallback for predictors and batches the fused head does not take."""
-    if args.model_3d == "schnet":
-        _, node_repr = model(batch.x[:, 0], batch.positions, batch.batch, return_latent=True)
-    elif args.model_3d == "painn":
-        _, node_repr = model(batch.x[:, 0], batch.positions, batch.radius_edge_index, batch.batch, return_latent=True)
-    else:
-        raise Exception("3D model {} not included.".format(args.model_3d))
+    _, node_repr = backbone_forward(args, batch, model, True)
     super_edge_index = batch.super_edge_index
     u_node_repr = torch.index_select(node_repr, dim=0, index=super_edge_index[0])
     v_node_repr = torch.index_select(node_repr, dim=0, index=super_edge_index[1])
@@ -149,17 +129,6 @@ def _as_triple_batch(batch):
     return tb[1]
 
 
-def _torsion_step(model, torsion_angle_predictor):
-    """The _AutogradStep of (backbone, predictor), kept on the backbone module; rebuilt when a parameter was replaced,
-    moved or frozen since (the graphs bind parameter addresses)."""
-    from .pretrain_GeoSSL import _AutogradStep
-    eng = model.__dict__.get("_geossl_torsion_step")
-    if eng is None or eng.n1 is not torsion_angle_predictor or not eng.unchanged():
-        eng = _AutogradStep(model, torsion_angle_predictor, None, objective="TorsionAnglePrediction")
-        model.__dict__["_geossl_torsion_step"] = eng
-    return eng
-
-
 def do_TorsionAnglePrediction(args, batch, model, torsion_angle_predictor, graph=None):
     """examples/pretrain_TorsionAnglePrediction.py:64-78 -> torsion_angle_loss (fp32 scalar tensor).  args.model_3d picks
     the backbone call ("schnet" / "painn").  The fused head runs whenever the predictor and the batch allow it
@@ -176,12 +145,12 @@ def do_TorsionAnglePrediction(args, batch, model, torsion_angle_predictor, graph
     try:
         tb = _as_triple_batch(batch)
         if graph and torch.is_grad_enabled() and not torch.cuda.is_current_stream_capturing():
-            from .pretrain_GeoSSL import Args
             if getattr(tb, "_dataset", None) is None:
                 _check_grouped(tb.batch, tb.super_edge_index)   # (before a graph binds or a bucket copies the list)
             a = Args(args.model_3d)
             a.step_graph_mode = getattr(args, "step_graph_mode", "auto")
-            loss = _torsion_step(model, torsion_angle_predictor).run(a, tb, 0.0, 0.0, None, False)
+            eng = engine_for(model, "_geossl_torsion_step", TORSION, torsion_angle_predictor)
+            loss = eng.run(a, tb, 0.0, 0.0, None, False)
             if loss is not None:
                 return loss
         return torsion_step_fused(args, tb, model, torsion_angle_predictor)
@@ -190,7 +159,7 @@ def do_TorsionAnglePrediction(args, batch, model, torsion_angle_predictor, graph
         return torsion_step_aten(args, batch, model, torsion_angle_predictor)
 
 
-class TorsionAnglePredictionTrainer:
+class TorsionAnglePredictionTrainer(StepTrainer):
     """The body of ``train()`` (examples/pretrain_TorsionAnglePrediction.py:51-83): backbone latent, fused triple head,
     backward, gradient all-reduce, Adam - backbone and predictor in one flat buffer (one fused Adam launch at one
     learning rate: the reference's gnn_3d_lr_scale is 1 by default), no host sync inside ``step``.
@@ -201,47 +170,15 @@ class TorsionAnglePredictionTrainer:
 
     def __init__(self, model, torsion_angle_predictor, lr=5e-4, weight_decay=0.0, model_3d="schnet", use_graph=False,
                  max_graphs=256, graph_mode="auto"):
-        from .optim import FlatParams, FusedAdam
-        from .parallel import GradAllReduce
-        from .pretrain_GeoSSL import Args, StepGraphs
         if not fused_head_ok(torsion_angle_predictor):
             raise ValueError("TorsionAnglePredictionTrainer needs the reference predictor at a width of the fused head "
                              "(64, 128, 256 or 512) on the GPU; use do_TorsionAnglePrediction for anything else")
-        self.model, self.predictor = model, torsion_angle_predictor
+        self.predictor = torsion_angle_predictor
         self.args = Args(model_3d)
-        self.flat = FlatParams([model, torsion_angle_predictor])
-        self.opt = FusedAdam(self.flat, lr=lr, weight_decay=weight_decay)
-        self.reduce = GradAllReduce(self.flat.grad)
-        self.use_graph = use_graph
-        self.step_graphs = StepGraphs(self._fwd_bwd, model_3d, max_graphs, mode=graph_mode,
-                                      modules=(model, torsion_angle_predictor, None), noise_keys=(), views=1)
-        self.step_graphs.zero_with_refresh = self.flat.grad
-        self._one = torch.ones((), dtype=torch.float32, device=self.flat.grad.device)
+        super().__init__([model, torsion_angle_predictor], model_3d, lr, weight_decay, use_graph, max_graphs, graph_mode)
 
-    def _fwd_bwd(self, batch, noise=None):
-        from .pretrain_GeoSSL import own_capture_open
-        if not own_capture_open():
-            self.flat.zero_grad()  # (a replayed step: cleared with the refresh of the graph's inputs, StepGraphs.refresh)
-        loss = torsion_step_fused(self.args, batch, self.model, self.predictor)
-        with _lib.direct_grads():  # every p.grad is a view of self.flat.grad: kernels accumulate into it directly
-            loss.backward(self._one)
-        self.flat.rebind_grads()
-        return loss.detach()
-
-    def _graph_fwd_bwd(self, batch):
-        sg = self.step_graphs
-        g = sg.lookup(batch)
-        if g is None:
-            if not sg.capture_now(batch):  # a structure seen for the first time: eager
-                return self._fwd_bwd(batch)
-            g = sg.capture(batch, {})
-            if g is None:  # capture failed: eager from now on
-                self.use_graph = False
-                return self._fwd_bwd(batch)
-        if not sg.refresh(g, batch):
-            return self._fwd_bwd(batch)
-        g["graph"].replay()
-        return g["loss"].clone()
+    def _forward(self, batch, noise):
+        return torsion_step_fused(self.args, batch, self.model, self.predictor)
 
     def step(self, batch):
         """One training step -> the loss on the device.  batch: a TripleBatch, a collated BatchAtomTriple on the device, or
@@ -249,11 +186,4 @@ class TorsionAnglePredictionTrainer:
         batch = _as_triple_batch(batch)
         if getattr(batch, "_dataset", None) is None:
             _check_grouped(batch.batch, batch.super_edge_index)
-        loss = self._graph_fwd_bwd(batch) if self.use_graph else self._fwd_bwd(batch)
-        st = self.model.__dict__.get("_geossl_status")
-        if st is not None:  # deferred index check of the backbone (a replayed graph cannot queue the host copy itself)
-            st.poll()
-            st.arm(every=8)
-        scale = self.reduce()
-        self.opt.step(grad_scale=scale)
-        return loss
+        return super().step(batch)
