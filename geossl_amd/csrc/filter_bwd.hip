@@ -1248,7 +1248,8 @@ extern "C" int geossl_cfconv_filter_bwd_dyn(const float* pair_d, const float* pa
                                             const GeosslFilterGradOut* out, float* workspace, int accumulate,
                                             const int32_t* dyn_P, const int32_t* dyn_N, hipStream_t stream) {
   if (P <= 0 || L <= 0) return 0;
-  if (L > GEOSSL_MAX_L || (F != 32 && F != 64 && F != 128) || G > 64) return (int)hipErrorInvalidValue;
+  // (G < 1: the kernels clamp the padded Gaussian index to G - 1, which would read in front of w1 and offset)
+  if (L > GEOSSL_MAX_L || (F != 32 && F != 64 && F != 128) || G > 64 || G < 1) return (int)hipErrorInvalidValue;
   const int ntiles = (int)((P + TR - 1) / TR);
   const int nb = blocks_per_layer(L, ntiles);
   dim3 grid(nb, L);

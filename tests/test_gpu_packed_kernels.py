@@ -24,6 +24,7 @@ from conftest import REPO
 sys.path.insert(0, os.path.join(REPO, "tools"))
 
 import packed_opsel_registry as reg  # noqa: E402
+from filter_twin import _filter_ref_and_bound  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -115,35 +116,6 @@ def filter_problems():
             cache[F] = _filter_problem(nmol=reg.BENCH_MOLS, seed=21, F=F, G=G, L=reg.FILTER_L, mode="B")
         return cache[F]
     return get
-
-
-def _filter_ref_and_bound(run, daggs):
-    """fp64 weight gradients and their S (schnet.py:141-145,186-195 differentiated w.r.t. the filter weights; the
-    hidden rows T = softplus(u) - log 2 with S(T) = softplus(u) + log 2 + sigmoid(u) S(u))."""
-    inp, lay = run.inputs, run.lay
-    i, j = lay.pair_i.long(), lay.pair_j.long()
-    fl = inp["pair_flag"].long()
-    c = inp["pair_c"].double()
-    m0, m1 = ((fl & 1) > 0).double() * c, ((fl & 2) > 0).double() * c
-    rbf = torch.exp(inp["coeff"] * (inp["pair_d"].double()[:, None] - inp["offset"].double()[None, :]) ** 2)
-    # two fp16 pieces under power-of-two block scales: an operand element is exact to 22 bits of itself, or of 2^-12 of
-    # the largest element of its operand where it is smaller than that
-    fl_ = lambda a: a.abs() + 2.0 ** -12 * a.abs().max()
-    out = []
-    for l, (w1, b1, w2, b2) in enumerate(inp["ws"]):
-        x, dg = inp["xs"][l].double(), daggs[l].double()
-        dO = m0[:, None] * (dg[i] * x[j]) + m1[:, None] * (dg[j] * x[i])
-        SdO = m0[:, None] * (fl_(dg)[i] * fl_(x)[j]) + m1[:, None] * (fl_(dg)[j] * fl_(x)[i])
-        u = rbf @ w1.double().t() + b1.double()
-        Su = fl_(rbf) @ fl_(w1.double()).t() + b1.double().abs()
-        sg = torch.sigmoid(u)
-        sp_ = torch.nn.functional.softplus(u)
-        tt, Stt = sp_ - math.log(2.0), sp_ + math.log(2.0) + sg * Su
-        g = dO @ w2.double()
-        dU, SdU = g * sg, (SdO @ fl_(w2.double())) * sg + g.abs() * 0.25 * Su
-        out.append(dict(ref=[dU.t() @ rbf, dU.sum(0), dO.t() @ tt, dO.sum(0)],
-                        S=[SdU.t() @ fl_(rbf), SdU.sum(0), SdO.t() @ fl_(Stt), SdO.sum(0)], dO=dO, tt=tt, Stt=Stt))
-    return out
 
 
 @pytest.mark.parametrize("form", ["saved", "recompute", "bf16x3"])

@@ -752,26 +752,34 @@ def test_schnet_latent_only_skips_the_readout():
 
 
 # ------------------------------------------------------------------- two-fp16-piece kernels: scales and accuracy
-def _filter_problem(nmol, seed, F=128, G=51, L=2, cutoff=5.0, mode="B"):
+def _filter_problem(nmol, seed, F=128, G=51, L=2, cutoff=5.0, mode="B", sizes=None, move=None, geometry=None):
     """A two-layer filter-network problem on synthetic molecules, through the raw C ABI: returns the tensors the
     backward kernel consumes and an fp64 evaluation of what it must produce (schnet.py:141-145,186-195 differentiated
-    w.r.t. the filter weights)."""
+    w.r.t. the filter weights).  `sizes`: the molecules' atom counts instead of the set's own; `move(positions)`: edits
+    the host positions in place; `geometry(pair_d, pair_c, pair_flag)`: edits the pair-slot tensors in place before
+    any kernel reads them."""
     import ctypes as C
     import math
     from geossl_amd import _lib, ops
     from geossl_amd._lib import call, ptr, stream
     from geossl_amd.layout import MolLayout
     from geossl_amd.synthetic import make_batch
-    b = make_batch(nmol, seed=seed, mode=mode)
+    b = make_batch(nmol, seed=seed, mode=mode, sizes=sizes)
     sizes = [int(n) for n in b["sizes"]]
     batch = torch.arange(len(sizes), device=DEV).repeat_interleave(torch.tensor(sizes, device=DEV))
     lay = MolLayout(batch, len(sizes), sizes=sizes)
-    pos = torch.from_numpy(np.asarray(b["positions"], dtype=np.float32)).to(DEV)
+    positions = np.array(b["positions"], dtype=np.float32)
+    if move is not None:
+        move(positions)
+    pos = torch.from_numpy(positions).to(DEV)
     pair_d, pair_c, pair_flag = ops.pair_geometry(pos, lay, cutoff)
+    if geometry is not None:
+        geometry(pair_d, pair_c, pair_flag)
     gen = torch.Generator().manual_seed(seed)
     N, P = lay.N, lay.P
     offset = torch.linspace(0.0, cutoff, G).to(DEV)
-    coeff = -0.5 / float(offset[1] - offset[0]) ** 2
+    # (a single Gaussian has no spacing: it gets the width of the whole range)
+    coeff = -0.5 / (float(offset[1] - offset[0]) if G > 1 else float(cutoff)) ** 2
     ws = [[(torch.randn(F, G, generator=gen) / G ** 0.5).to(DEV), (0.3 * torch.randn(F, generator=gen)).to(DEV),
            (torch.randn(F, F, generator=gen) / F ** 0.5).to(DEV), (0.3 * torch.randn(F, generator=gen)).to(DEV)] for _ in range(L)]
     xs = [torch.randn(N, F, generator=gen).to(DEV) for _ in range(L)]
@@ -783,9 +791,10 @@ def _filter_problem(nmol, seed, F=128, G=51, L=2, cutoff=5.0, mode="B"):
     T = torch.empty(L, P, F, device=DEV)
     call("geossl_cfconv_filter_fwd", ptr(pair_d), ptr(pair_c), P, C.byref(fw), L, F, G, ptr(offset), coeff, ptr(T), ptr(Wf), stream())
 
-    def run(daggs_, saved_T=True, outs=None):
+    def run(daggs_, saved_T=True, outs=None, dyn_P=None):
         """saved_T=False: T = NULL, the kernel rebuilds the hidden rows (GEOSSL_FILTER_RECOMPUTE_T); `outs`: the output
-        tensors to write (else zeros)."""
+        tensors to write (else zeros); `dyn_P`: an int32 device tensor with the number of pair slots that exist (the
+        capacity launch geossl_cfconv_filter_bwd_dyn)."""
         gin, gout = _lib.FilterGradIn(), _lib.FilterGradOut()
         if outs is None:
             outs = [[torch.zeros(F, G, device=DEV), torch.zeros(F, device=DEV), torch.zeros(F, F, device=DEV),
@@ -795,8 +804,12 @@ def _filter_problem(nmol, seed, F=128, G=51, L=2, cutoff=5.0, mode="B"):
             gout.dw1[l], gout.db1[l], gout.dw2[l], gout.db2[l] = (ptr(o) for o in outs[l])
         nfl = _lib.load().geossl_cfconv_filter_bwd_workspace_floats(P, L, F, G)
         wsp = torch.empty(nfl, device=DEV)
-        call("geossl_cfconv_filter_bwd", ptr(pair_d), ptr(pair_c), ptr(pair_flag), ptr(lay.pair_i), ptr(lay.pair_j), P, N, C.byref(fw),
-             C.byref(gin), L, F, G, ptr(offset), coeff, ptr(T) if saved_T else None, C.byref(gout), ptr(wsp), 0, stream())
+        args = (ptr(pair_d), ptr(pair_c), ptr(pair_flag), ptr(lay.pair_i), ptr(lay.pair_j), P, N, C.byref(fw),
+                C.byref(gin), L, F, G, ptr(offset), coeff, ptr(T) if saved_T else None, C.byref(gout), ptr(wsp), 0)
+        if dyn_P is None:
+            call("geossl_cfconv_filter_bwd", *args, stream())
+        else:
+            call("geossl_cfconv_filter_bwd_dyn", *args, ptr(dyn_P), None, stream())
         torch.cuda.synchronize()
         return outs
 
@@ -816,7 +829,8 @@ def _filter_problem(nmol, seed, F=128, G=51, L=2, cutoff=5.0, mode="B"):
             outs.append([dU.t() @ rbf, dU.sum(0), dO.t() @ tt, dO.sum(0)])
         return outs
 
-    run.inputs = dict(pair_d=pair_d, pair_c=pair_c, pair_flag=pair_flag, ws=ws, xs=xs, offset=offset, coeff=coeff, P=P)
+    run.inputs = dict(pair_d=pair_d, pair_c=pair_c, pair_flag=pair_flag, ws=ws, xs=xs, offset=offset, coeff=coeff, P=P,
+                      pos=pos, cutoff=cutoff, fw=fw)
     return lay, daggs, run, ref64
 
 
