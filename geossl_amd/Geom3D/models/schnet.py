@@ -149,7 +149,20 @@ class _SchNetCore(torch.autograd.Function):
         if cfg["debug"]:
             status.check()
         # radius graph + edge length + envelope (schnet.py:91-93,186)
-        pair_d, pair_c, pair_flag = ops.pair_geometry(pos, lay, cfg["cutoff"])
+        # A SPARSE layout (a structure above 255 atoms, layout.want_sparse) runs on the compacted list of the pairs that
+        # carry an edge: P is then the list's capacity, its real row count stays on the device (the dyn_P of the filter
+        # kernels), and only the geometry, the two aggregations and the position scatter differ from the dense branch.
+        sp = None
+        if getattr(lay, "sparse", False):
+            if dyn is not None:
+                raise _lib.GeosslHipError("capacity buckets hold molecules of at most 255 atoms (bucket.MAX_N)")
+            sp = ops.sparse_pair_geometry(pos, lay, cfg["cutoff"])
+            pair_d, pair_c, pair_flag, dP2 = sp.pair_d, sp.pair_c, sp.pair_flag, sp.dyn_P
+            aggregate = lambda x_, W_, out=None, swap=False, mols=None: ops.aggregate_sparse(x_, W_, sp, swap=swap, out=out)
+        else:
+            pair_d, pair_c, pair_flag = ops.pair_geometry(pos, lay, cfg["cutoff"])
+            aggregate = lambda x_, W_, out=None, swap=False, mols=None: ops.aggregate(x_, W_, pair_flag, lay, swap=swap,
+                                                                                      out=out, mols=mols)
         P = lay.P
         # continuous-filter network of every block in one launch (schnet.py:94,187)
         fw = _lib.FilterWeights()
@@ -203,7 +216,7 @@ class _SchNetCore(torch.autograd.Function):
                     if todo is not None:
                         todo.append(("agg", xs[l], Wf[l], aggs[l], False))
                     else:
-                        ops.aggregate(xs[l], Wf[l], pair_flag, lay, out=aggs[l], mols=mols)            # propagate   :190
+                        aggregate(xs[l], Wf[l], out=aggs[l], mols=mols)                                # propagate   :190
                     stages = [dict(image=i_lin2[l], bias=lp[6], flags=_lib.EPI_SSP, out=rows(ts[l])),  # conv.lin2 + act
                               dict(image=i_lin[l], bias=lp[8], res=rows(hs[l]), out=rows(hs[l + 1]))]  # lin + residual
                     if l + 1 < L:
@@ -215,7 +228,8 @@ class _SchNetCore(torch.autograd.Function):
 
             # One launch for the whole loop where the shape allows (every block carries its molecules through all
             # operations, ops.layer_loop), else 14 launches
-            todo = [] if (cfg["loop"] and P > 0 and 2 * L + 2 <= _lib.LOOP_MAX_OPS) else None
+            # (the loop's aggregation walks dense pair slots: not on a sparse layout)
+            todo = [] if (cfg["loop"] and P > 0 and sp is None and 2 * L + 2 <= _lib.LOOP_MAX_OPS) else None
             if todo is not None:
                 run_rows(0, N, None, todo)
                 if not ops.layer_loop(todo, lay, pair_flag, N, F, stagger=cfg["loop_stagger"]):
@@ -234,7 +248,7 @@ class _SchNetCore(torch.autograd.Function):
                 layers = [lp[:4] + [pw[3 * l], pw[3 * l + 1], lp[6], pw[3 * l + 2], lp[8]] for l, lp in enumerate(layers)]
             for l, lp in enumerate(layers):
                 x = ops.linear(h, lp[4])                                    # conv.lin1 (no bias)   :189
-                agg = ops.aggregate(x, Wf[l], pair_flag, lay)               # propagate(add)        :190
+                agg = aggregate(x, Wf[l])                                   # propagate(add)        :190
                 t = ops.linear(agg, lp[5], bias=lp[6], flags=_lib.EPI_SSP)  # conv.lin2 + act       :191,165
                 hn = ops.linear(t, lp[7], bias=lp[8], res=h)                # lin + residual        :166,97
                 if training:
@@ -250,7 +264,7 @@ class _SchNetCore(torch.autograd.Function):
             ctx.ps = ps
             ctx.params = params
             ctx.saved = dict(pair_d=pair_d, pair_c=pair_c, pair_flag=pair_flag, Wf=Wf, T=T, hs=hs, xs=xs, aggs=aggs,
-                             ts=ts, h_last=h, u=u, img_bwd=img_bwd if cfg["chain"] else None)
+                             ts=ts, h_last=h, u=u, img_bwd=img_bwd if cfg["chain"] else None, sparse=sp)
         return hout
 
     @staticmethod
@@ -262,6 +276,9 @@ class _SchNetCore(torch.autograd.Function):
             # first-order kernels, but as the outputs of a node that knows how to be differentiated
             # (geossl_amd/higher_order.py); evaluation loops that detach the force never pay for that.
             from ...higher_order import SchNetGradNode
+            if ctx.saved.get("sparse") is not None:
+                raise NotImplementedError("second-order gradients (create_graph=True, training on forces) are limited to "
+                                          "dense layouts: structures of at most 255 atoms, GEOSSL_SPARSE_PAIRS unset")
             dpos, grads = SchNetGradNode.run(ctx, dhout, want_pos, want_params)
             return (None, dpos, None, None) + tuple(grads)
         dpos, grads = _SchNetCore.fused_backward(ctx, dhout, want_pos, want_params, allow_direct=True)
@@ -288,6 +305,14 @@ class _SchNetCore(torch.autograd.Function):
         dh_out = dhout.contiguous()
         dyn = getattr(lay, "dyn", None)
         dN2, dP2 = (dyn.n_atoms2, dyn.n_pairs2) if dyn is not None else (None, None)
+        sp = sv.get("sparse")  # the forward's pair list on a sparse layout (see forward)
+        if sp is not None:
+            dP2, pair_i, pair_j = sp.dyn_P, sp.pair_i, sp.pair_j
+            aggregate = lambda x_, W_, out=None, mols=None: ops.aggregate_sparse(x_, W_, sp, swap=True, out=out)
+        else:
+            pair_i, pair_j = lay.pair_i, lay.pair_j
+            aggregate = lambda x_, W_, out=None, mols=None: ops.aggregate(x_, W_, sv["pair_flag"], lay, swap=True,
+                                                                          out=out, mols=mols)
         probs = []  # (A = dY, B = X, dW, db)
         daggs = [None] * L
         if cfg["chain"]:
@@ -320,15 +345,14 @@ class _SchNetCore(torch.autograd.Function):
                     if todo is not None:
                         todo.append(("agg", daggs[l], sv["Wf"][l], dxs[l], True))
                     else:
-                        ops.aggregate(daggs[l], sv["Wf"][l], sv["pair_flag"], lay, swap=True, out=dxs[l],
-                                      mols=mols)                                    # transposed graph
+                        aggregate(daggs[l], sv["Wf"][l], out=dxs[l], mols=mols)     # transposed graph
                     stages = [dict(image=i_lin1[l], res=rows(dhs[l + 1]), out=rows(dhs[l]))]      # conv.lin1 + residual
                     if l > 0:
                         stages += [dict(image=i_lin[l - 1], tprev=rows(sv["ts"][l - 1]), out=rows(dys[l - 1])),
                                    dict(image=i_lin2[l - 1], out=rows(daggs[l - 1]))]
                     chain(rows(dxs[l]), stages)
 
-            todo = [] if (cfg["loop"] and lay.P > 0 and 2 * L + 2 <= _lib.LOOP_MAX_OPS) else None
+            todo = [] if (cfg["loop"] and lay.P > 0 and sp is None and 2 * L + 2 <= _lib.LOOP_MAX_OPS) else None
             if todo is not None:
                 run_rows(0, N, None, todo)
                 if not ops.layer_loop(todo, lay, sv["pair_flag"], N, F, stagger=cfg["loop_stagger"]):
@@ -355,7 +379,7 @@ class _SchNetCore(torch.autograd.Function):
                 w_lin1, w_lin2, w_lin = (pw[3 * l], pw[3 * l + 1], pw[3 * l + 2]) if pw is not None else (lp[4], lp[5], lp[7])
                 dy = ops.linear(dh, w_lin, transB=False, tprev=sv["ts"][l])        # through lin and act
                 dagg = ops.linear(dy, w_lin2, transB=False)                        # through conv.lin2
-                dx = ops.aggregate(dagg, sv["Wf"][l], sv["pair_flag"], lay, swap=True)  # transposed graph
+                dx = aggregate(dagg, sv["Wf"][l])                                  # transposed graph
                 dh_new = ops.linear(dx, w_lin1, transB=False, res=dh)              # through conv.lin1 + residual
                 probs.append((dh, sv["ts"][l], gl[7], gl[8]))
                 probs.append((dy, sv["aggs"][l], gl[5], gl[6]))
@@ -385,7 +409,7 @@ class _SchNetCore(torch.autograd.Function):
                 nfl = _lib.load().geossl_cfconv_filter_bwd_workspace_floats(P, L, F, G)
                 ws2 = torch.empty(nfl, dtype=torch.float32, device=dev)
                 call("geossl_cfconv_filter_bwd_dyn", ptr(sv["pair_d"]), ptr(sv["pair_c"]), ptr(sv["pair_flag"]),
-                     ptr(lay.pair_i), ptr(lay.pair_j), P, N, C.byref(fw), C.byref(gin), L, F, G, ptr(cfg["offset"]),
+                     ptr(pair_i), ptr(pair_j), P, N, C.byref(fw), C.byref(gin), L, F, G, ptr(cfg["offset"]),
                      cfg["coeff"], ptr(sv["T"]), C.byref(gout), ptr(ws2), accum, dP2, dN2, st)
             elif not direct:
                 for gl in g_layers:
@@ -399,10 +423,13 @@ class _SchNetCore(torch.autograd.Function):
             if P > 0:
                 dd = torch.empty(L, P, dtype=torch.float32, device=dev)
                 call("geossl_cfconv_filter_dpos", ptr(sv["pair_d"]), ptr(sv["pair_c"]), ptr(sv["pair_flag"]),
-                     ptr(lay.pair_i), ptr(lay.pair_j), P, C.byref(fw), C.byref(gin), L, F, G, ptr(cfg["offset"]),
+                     ptr(pair_i), ptr(pair_j), P, C.byref(fw), C.byref(gin), L, F, G, ptr(cfg["offset"]),
                      cfg["coeff"], cfg["cutoff"], ptr(sv["T"]), ptr(sv["Wf"]), ptr(dd), st)
-                call("geossl_pair_position_grad", ptr(ctx.pos), ptr(sv["pair_d"]), ptr(dd), ptr(lay.mol_ptr),
-                     ptr(lay.pair_ptr), lay.B, P, L, ptr(dpos), st)
+                if sp is not None:   # (rows past the list's real count are never looked at: no incidence entry names one)
+                    ops.pair_position_grad_sparse(ctx.pos, sp, dd, out=dpos)
+                else:
+                    call("geossl_pair_position_grad", ptr(ctx.pos), ptr(sv["pair_d"]), ptr(dd), ptr(lay.mol_ptr),
+                         ptr(lay.pair_ptr), lay.B, P, L, ptr(dpos), st)
         # ctx.saved stays: finetune_md17.py:46 differentiates with retain_graph=True and runs this node again
         if direct:
             return dpos, [None] * len(grads)
@@ -571,6 +598,10 @@ class SchNet(torch.nn.Module):
         if fused:
             h = _SchNetCore.apply(z, pos.contiguous(), lay, cfg, *_core_params(self))
         else:   # any other widths (schnet.py:17-30 takes any): the general path on the library's tape
+            if getattr(lay, "sparse", False):
+                raise NotImplementedError("the general-width path (hidden_channels != num_filters, or widths outside %s) "
+                                          "is limited to structures of at most 255 atoms; the fused widths take up to "
+                                          "1024" % (SUPPORTED_F,))
             if z.numel() and (int(z.min()) < 0 or int(z.max()) >= self.embedding.num_embeddings):   # (Embedding's IndexError)
                 raise IndexError("atom type out of range for the embedding table (node_class=%d)"
                                  % self.embedding.num_embeddings)

@@ -294,6 +294,10 @@ PROTOTYPES = {
                                           vp]),
     "geossl_triple_angles": (i32, [vp, i64, vp, vp, vp, i64, vp, vp]),
     "geossl_gather_triples": (i32, [vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp]),
+    # sparse pair list (csrc/sparse_pairs.hip)
+    "geossl_sparse_pairs_build": (i32, [vp, vp, i64, i64, i32, f32, i32, f32, i64] + [vp] * 13),
+    "geossl_cfconv_aggregate_sparse": (i32, [vp, vp, vp, vp, vp, i64, i32, i32, vp, vp]),
+    "geossl_pair_position_grad_sparse": (i32, [vp, vp, vp, vp, vp, vp, i64, i64, i32, vp, vp]),
 }
 
 _lib = None

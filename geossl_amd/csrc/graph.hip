@@ -5,16 +5,12 @@
 // the adjacency is kept as an n x ceil(n/64) bit matrix in LDS.  All outputs are written in the canonical
 // order (target-major, sources ascending) without atomics, so edge lists are bit-reproducible.
 #include "common.h"
+#include "radius_adj.h"
 #include "geossl_hip.h"
 
 using namespace geossl;
 
 namespace {
-
-__device__ __forceinline__ float dist2_nofma(const float* pi, const float* pj) {
-  // fl32(fl32(fl32(dx*dx)+fl32(dy*dy))+fl32(dz*dz)), d = x_j - x_i, nothing contracted (common.h)
-  return norm2_rn(pj[0] - pi[0], pj[1] - pi[1], pj[2] - pi[2]);
-}
 
 // ---------------------------------------------------------------------------------------------- layout
 __global__ __launch_bounds__(1024) void k_layout_build(const int64_t* __restrict__ batch, int N, int B,
@@ -144,23 +140,11 @@ __global__ __launch_bounds__(64) void k_radius(const float* __restrict__ pos, co
   __syncthreads();
   const unsigned long long lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
   for (int i = 0; i < n; ++i) {
-    int found = 0, d_in = 0;
     int64_t ebase = 0;
     if (MODE == 1) ebase = edge_ptr[a0 + i];
-    for (int c = 0; c * 64 < n; ++c) {
-      const int jn = c * 64 + lane;
-      float d2 = 0.0f;
-      bool hit = false;
-      if (jn < n) {
-        d2 = dist2_nofma(sp + 3 * i, sp + 3 * jn);
-        hit = d2 < r2;
-      }
-      const unsigned long long mask = __ballot(hit);
-      const int rank = found + __popcll(mask & lt);
-      bool keep = hit && rank < cap;
-      found += __popcll(mask);
-      if (jn == i) keep = false;  // self edge dropped after the cap was applied
-      const unsigned long long kept = __ballot(keep);
+    // which edges exist: radius_adj.h
+    const int d_all = radius_scan_target(sp, n, i, lane, r2, cap,
+                                         [&](int c, int jn, float d2, bool keep, unsigned long long kept, int d_in) {
       if (MODE == 2 && lane == 0) adj[(size_t)i * words + c] = kept;
       if (MODE == 1 && keep) {
         const int64_t e = ebase + d_in + __popcll(kept & lt);
@@ -168,9 +152,8 @@ __global__ __launch_bounds__(64) void k_radius(const float* __restrict__ pos, co
         edge_dst[e] = a0 + i;
         edge_weight[e] = sqrtf(d2);
       }
-      d_in += __popcll(kept);
-    }
-    if (MODE == 0 && lane == 0) deg[a0 + i] = d_in;
+    });
+    if (MODE == 0 && lane == 0) deg[a0 + i] = d_all;
   }
   if (MODE == 2) {
     __syncthreads();
@@ -183,8 +166,7 @@ __global__ __launch_bounds__(64) void k_radius(const float* __restrict__ pos, co
         const unsigned f1 = (adj[(size_t)b * words + (a >> 6)] >> (a & 63)) & 1ull;  // edge a -> b (target b)
         const float d = sqrtf(d2);
         pair_d[row + b] = d;
-        // CFConv envelope, schnet.py:186: 0.5 * (cos(d * PI / cutoff) + 1.0), fp32 op by op
-        pair_c[row + b] = 0.5f * (cosf(mul_rn(d, GEOSSL_PI_F) / cutoff) + 1.0f);
+        pair_c[row + b] = pair_envelope(d, cutoff);
         pair_flag[row + b] = (uint8_t)(f0 | (f1 << 1));
       }
     }
@@ -217,14 +199,9 @@ __global__ __launch_bounds__(64) void k_pair_geometry_flat(const float* __restri
     const float d2 = dist2_nofma(sp + 3 * a, sp + 3 * b);
     const float d = sqrtf(d2);
     pair_d[base + q] = d;
-    pair_c[base + q] = 0.5f * (cosf(mul_rn(d, GEOSSL_PI_F) / cutoff) + 1.0f);  // schnet.py:186, fp32 op by op
+    pair_c[base + q] = pair_envelope(d, cutoff);
     pair_flag[base + q] = d2 < r2 ? (uint8_t)3 : (uint8_t)0;
   }
-}
-
-inline size_t radius_lds(int max_n) {
-  const size_t words = (max_n + 63) / 64;
-  return (size_t)max_n * words * 8 + (size_t)max_n * 12;
 }
 
 // ------------------------------------------------------------------------------- super-edge bookkeeping
@@ -434,6 +411,8 @@ extern "C" int geossl_atom_tuples(const int32_t* mol_ptr, const int64_t* tuple_p
 extern "C" int geossl_radius_graph_count(const float* pos, const int32_t* mol_ptr, int64_t B, int max_n, float r2,
                                          int cap, int32_t* deg, hipStream_t stream) {
   if (B <= 0) return 0;
+  if (max_n < 1 || max_n > GEOSSL_RADIUS_MAX_N) return (int)hipErrorInvalidValue;
+  allow_big_lds(&k_radius<0>);  // more than 64 KB from about 650 atoms on
   hipLaunchKernelGGL((k_radius<0>), dim3((unsigned)B), dim3(64), radius_lds(max_n), stream, pos, mol_ptr, nullptr,
                      (int)B, max_n, r2, cap, deg, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1.0f, nullptr);
   GEOSSL_CHECK_LAUNCH();
@@ -444,6 +423,8 @@ extern "C" int geossl_radius_graph_fill(const float* pos, const int32_t* mol_ptr
                                         int cap, const int64_t* edge_ptr, int64_t* edge_src, int64_t* edge_dst,
                                         float* edge_weight, hipStream_t stream) {
   if (B <= 0) return 0;
+  if (max_n < 1 || max_n > GEOSSL_RADIUS_MAX_N) return (int)hipErrorInvalidValue;
+  allow_big_lds(&k_radius<1>);
   hipLaunchKernelGGL((k_radius<1>), dim3((unsigned)B), dim3(64), radius_lds(max_n), stream, pos, mol_ptr, nullptr,
                      (int)B, max_n, r2, cap, nullptr, edge_ptr, edge_src, edge_dst, edge_weight, nullptr, nullptr, 1.0f,
                      nullptr);
@@ -461,6 +442,8 @@ extern "C" int geossl_pair_geometry(const float* pos, const int32_t* mol_ptr, co
     GEOSSL_CHECK_LAUNCH();
     return 0;
   }
+  if (max_n < 1 || max_n > GEOSSL_RADIUS_MAX_N) return (int)hipErrorInvalidValue;
+  allow_big_lds(&k_radius<2>);
   hipLaunchKernelGGL((k_radius<2>), dim3((unsigned)B), dim3(64), radius_lds(max_n), stream, pos, mol_ptr, pair_ptr,
                      (int)B, max_n, r2, cap, nullptr, nullptr, nullptr, nullptr, nullptr, pair_d, pair_flag, cutoff, pair_c);
   GEOSSL_CHECK_LAUNCH();

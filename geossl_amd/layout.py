@@ -16,6 +16,29 @@ from ._lib import call, ptr, stream
 # largest molecule the one-block-per-molecule aggregation (geossl_cfconv_aggregate: 2 n F floats of LDS, at most 160 KB)
 # takes at every width up to F = 128; larger ones need the work list of the by-target kernels
 AGG_LDS_MAX_N = 128
+# largest molecule of the dense pair-slot form (every geossl_cfconv_aggregate* stops there); a layout with a larger one is
+# SPARSE: SchNet runs on the compacted list of the pairs that carry an edge (ops.sparse_pair_geometry), up to
+# SPARSE_MAX_N atoms per structure (the bit matrix of the graph kernels in LDS)
+DENSE_MAX_N = 255
+SPARSE_MAX_N = 1024
+# radius_graph keeps at most max_num_neighbors + 1 = 33 hits per target, the self hit among them unless 33 others come
+# first: at most 33 edges into an atom, and every listed pair has one
+SPARSE_EDGES_PER_ATOM = 33
+
+
+def sparse_pair_capacity(sizes, per_atom=SPARSE_EDGES_PER_ATOM):
+    """Rows of the sparse pair list of molecules of `sizes` atoms, from host integers: sum_m min(n (n - 1) / 2, 33 n)."""
+    return sum(min(n * (n - 1) // 2, per_atom * n) for n in (int(k) for k in sizes))
+
+
+def want_sparse(max_n):
+    """GEOSSL_SPARSE_PAIRS = 1 makes every layout sparse, = 0 none; unset: the layouts with a molecule above 255 atoms."""
+    sw = _env("GEOSSL_SPARSE_PAIRS")
+    if sw == "1":
+        return True
+    if sw == "0":
+        return False
+    return max_n > DENSE_MAX_N
 
 
 class MolLayout:
@@ -61,9 +84,18 @@ class MolLayout:
                 raise ValueError("batch vector must be sorted ascending with ids in [0, num_graphs) "
                                  "(collated batches are; dataloaders_AtomTuple.py:61,72)")
         self.max_n, self.P = int(max_n), int(P)
-        self.pair_i = torch.empty(self.P, dtype=torch.int32, device=dev)
-        self.pair_j = torch.empty(self.P, dtype=torch.int32, device=dev)
-        if self.P > 0:
+        # A sparse layout has no dense pair index, work list or loop plan: it carries the capacity of the pair list
+        # (`P`, rows of every per-pair array) and the list itself is built from the positions, per forward
+        # (ops.sparse_pair_geometry).  Without host sizes they are read back once, here.
+        self.sparse = B > 0 and want_sparse(self.max_n)
+        if self.sparse:
+            cap_sizes = sizes if sizes is not None else (self.mol_ptr[1:] - self.mol_ptr[:-1]).tolist()
+            self.P = self.pair_capacity = sparse_pair_capacity(cap_sizes)
+            self.pair_i = self.pair_j = None
+        else:
+            self.pair_i = torch.empty(self.P, dtype=torch.int32, device=dev)
+            self.pair_j = torch.empty(self.P, dtype=torch.int32, device=dev)
+        if self.P > 0 and not self.sparse:
             call("geossl_pair_index_fill", ptr(self.mol_ptr), ptr(self.pair_ptr), B, ptr(self.pair_i),
                  ptr(self.pair_j), stream())
         # molecules by descending size: the sequence in which the per-molecule blocks of the aggregation are started
@@ -82,7 +114,8 @@ class MolLayout:
         work_sizes = sizes
         if sizes is None and AGG_LDS_MAX_N < self.max_n <= 255:
             work_sizes = (self.mol_ptr[1:] - self.mol_ptr[:-1]).tolist()
-        if work_sizes is not None and 20 < self.max_n <= 255 and B < (1 << 24) and not _env("GEOSSL_AGG_NO_SPLIT"):
+        if (work_sizes is not None and 20 < self.max_n <= 255 and B < (1 << 24) and not _env("GEOSSL_AGG_NO_SPLIT")
+                and not self.sparse):
             self.agg_targets = aggregate_by_targets(B)
             self.agg_work = torch.from_numpy(aggregate_work_list(np.asarray(work_sizes, dtype=np.int64),
                                                                  self.agg_targets)).to(dev)
@@ -114,6 +147,8 @@ class MolLayout:
         most `max_rows` atom rows -> (int32 tensor [nblocks, 4] = first row, end row, first molecule, end molecule;
         nblocks), or (None, 0) when the batch has no such plan or the layout was not built from host sizes (a loader that
         knows them passes them: prepare_batch, BatchAtomTuple.from_sizes / from_data_list)."""
+        if self.sparse:
+            return (None, 0)
         if self._loop_plan is None:
             sizes = self._sizes_host
             if sizes is not None and torch.cuda.is_current_stream_capturing():

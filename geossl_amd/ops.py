@@ -10,7 +10,7 @@ from .switches import env as _env
 
 from . import _lib
 from ._lib import call, ptr, stream
-from .layout import MolLayout, get_layout
+from .layout import MolLayout, SPARSE_MAX_N, get_layout
 
 PI_F32 = float(torch.tensor(math.pi, dtype=torch.float32))
 # molecules of the (two-view) batch up to which ragged batches take the layer loop.  Same-box A/B on set B (trainer, one
@@ -33,6 +33,13 @@ def radius_cap(max_num_neighbors, loop=False):
     return max_num_neighbors if loop else max_num_neighbors + 1
 
 
+def _check_graph_size(layout):
+    """The graph kernels keep a molecule's positions and bit matrix in LDS: 1024 atoms at most."""
+    if layout.max_n > SPARSE_MAX_N:
+        raise ValueError("the radius graph takes structures of at most %d atoms (the largest here has %d)"
+                         % (SPARSE_MAX_N, layout.max_n))
+
+
 def radius_graph(pos, r, batch=None, loop=False, max_num_neighbors=32, layout=None, return_weight=False):
     """torch_geometric.nn.radius_graph(pos, r, batch) as called at schnet.py:91 and
     datasets_3D_Radius.py:120 -> int64 [2, E] = [source j; target i], target-major, sources ascending."""
@@ -44,6 +51,7 @@ def radius_graph(pos, r, batch=None, loop=False, max_num_neighbors=32, layout=No
     if batch is None:
         batch = torch.zeros(N, dtype=torch.long, device=pos.device)
     lay = layout or get_layout(batch)
+    _check_graph_size(lay)
     r2 = float(torch.tensor(float(r) * float(r), dtype=torch.float32))
     cap = radius_cap(max_num_neighbors)
     deg = torch.zeros(N, dtype=torch.int32, device=pos.device)
@@ -61,6 +69,10 @@ def radius_graph(pos, r, batch=None, loop=False, max_num_neighbors=32, layout=No
 
 def pair_geometry(pos, layout, cutoff, max_num_neighbors=32):
     """Radius graph in pair-slot form: (pair_d [P], pair_c [P], pair_flag [P] u8)."""
+    if getattr(layout, "sparse", False):
+        raise _lib.GeosslHipError("a sparse layout (a structure above 255 atoms, or GEOSSL_SPARSE_PAIRS=1) has no dense "
+                                  "pair slots: ops.sparse_pair_geometry builds its pair list")
+    _check_graph_size(layout)
     pos = _f32(pos)
     dev = pos.device
     P = layout.P
@@ -72,6 +84,72 @@ def pair_geometry(pos, layout, cutoff, max_num_neighbors=32):
         call("geossl_pair_geometry", ptr(pos), ptr(layout.mol_ptr), ptr(layout.pair_ptr), layout.B, layout.max_n, r2,
              radius_cap(max_num_neighbors), float(cutoff), ptr(pair_d), ptr(pair_c), ptr(pair_flag), stream())
     return pair_d, pair_c, pair_flag
+
+
+class SparsePairs:
+    """The radius graph of one forward as a compacted pair list (csrc/sparse_pairs.hip): pair_i, pair_j (int32 global
+    atom ids, a < b, lexicographic per molecule in batch order), pair_d, pair_c, pair_flag as in the dense form, and the
+    per-atom incidence lists inc_ptr [N + 1], inc_pair / inc_src [2 P] (atom t's pairs in ascending partner order: row,
+    partner | edge partner -> t << 30 | edge t -> partner << 31).  ``P`` is the CAPACITY every array is sized by (from
+    host sizes, layout.sparse_pair_capacity); ``n_pairs`` (int32 [1], device) the real number of rows, which nothing
+    here reads back - the filter kernels take its address as their dyn_P.  Rows past it hold flag 0, pair_i = pair_j = 0,
+    pair_c = 0, pair_d = cutoff."""
+
+    __slots__ = ("P", "N", "pair_i", "pair_j", "pair_d", "pair_c", "pair_flag", "inc_ptr", "inc_pair", "inc_src",
+                 "n_pairs")
+
+    @property
+    def dyn_P(self):
+        return self.n_pairs.data_ptr()
+
+
+def sparse_pair_geometry(pos, layout, cutoff, max_num_neighbors=32):
+    """Radius graph as a sparse pair list -> SparsePairs.  No device-to-host read."""
+    if not getattr(layout, "sparse", False):
+        raise _lib.GeosslHipError("sparse_pair_geometry needs a sparse layout (GEOSSL_SPARSE_PAIRS=1 makes any layout one)")
+    _check_graph_size(layout)
+    if radius_cap(max_num_neighbors) > 33:
+        raise ValueError("the capacity of the sparse pair list is sized for max_num_neighbors <= 32")
+    pos = _f32(pos)
+    dev, N, P = pos.device, layout.N, layout.P
+    i32 = dict(dtype=torch.int32, device=dev)
+    sp = SparsePairs()
+    sp.P, sp.N = P, N
+    sp.pair_i, sp.pair_j = torch.empty(max(P, 1), **i32), torch.empty(max(P, 1), **i32)
+    sp.pair_d = torch.empty(max(P, 1), dtype=torch.float32, device=dev)
+    sp.pair_c = torch.empty(max(P, 1), dtype=torch.float32, device=dev)
+    sp.pair_flag = torch.empty(max(P, 1), dtype=torch.uint8, device=dev)
+    sp.inc_ptr = torch.empty(N + 1, **i32)
+    sp.inc_pair, sp.inc_src = torch.empty(max(2 * P, 1), **i32), torch.empty(max(2 * P, 1), **i32)
+    sp.n_pairs = torch.empty(1, **i32)
+    work = torch.empty(layout.B + 2 * N, **i32)
+    r2 = float(torch.tensor(float(cutoff) * float(cutoff), dtype=torch.float32))
+    call("geossl_sparse_pairs_build", ptr(pos), ptr(layout.mol_ptr), layout.B, N, layout.max_n, r2,
+         radius_cap(max_num_neighbors), float(cutoff), P, ptr(work), ptr(work[layout.B:]), ptr(work[layout.B + N:]),
+         ptr(sp.pair_i), ptr(sp.pair_j), ptr(sp.pair_d), ptr(sp.pair_c), ptr(sp.pair_flag), ptr(sp.inc_ptr),
+         ptr(sp.inc_pair), ptr(sp.inc_src), ptr(sp.n_pairs), stream())
+    return sp
+
+
+def aggregate_sparse(x, Wf_l, pairs, swap=False, out=None):
+    """Neighbour aggregation over a sparse pair list: x, out [N, F]; Wf_l [P, F] rows of the list.  swap: the transposed
+    graph (the backward).  Bit-identical to `aggregate` on the same filter rows."""
+    N, F = x.shape
+    if out is None:
+        out = torch.empty_like(x)
+    call("geossl_cfconv_aggregate_sparse", ptr(x), ptr(Wf_l), ptr(pairs.inc_ptr), ptr(pairs.inc_pair), ptr(pairs.inc_src),
+         N, F, 1 if swap else 0, ptr(out), stream())
+    return out
+
+
+def pair_position_grad_sparse(pos, pairs, dd, out=None):
+    """dd [L, P] (dL/d length per block and row, geossl_cfconv_filter_dpos) -> dpos [N, 3] through the incidence lists."""
+    N = pos.size(0)
+    if out is None:
+        out = torch.empty(N, 3, dtype=torch.float32, device=pos.device)
+    call("geossl_pair_position_grad_sparse", ptr(pos), ptr(pairs.pair_d), ptr(dd), ptr(pairs.inc_ptr), ptr(pairs.inc_pair),
+         ptr(pairs.inc_src), N, pairs.P, dd.size(0), ptr(out), stream())
+    return out
 
 
 def gaussian_smearing(dist, offset, coeff):

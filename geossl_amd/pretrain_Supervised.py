@@ -159,8 +159,9 @@ class _Stats:
 
 # --------------------------------------------------------------------------------------------------------- steps
 def _x_of(args, batch):
-    """The backbone's first argument in :86-90: SchNet gets the atom-type column, PaiNN batch.x unsliced."""
-    return batch.x if args.model_3d == "painn" else batch.x[:, 0]
+    """The backbone's first argument in :86-90: SchNet gets the atom-type column, PaiNN batch.x unsliced.  (A 1-D
+    batch.x - DatasetLBA's atomic numbers, which finetune_lba.py hands to the backbone as they are - is that column.)"""
+    return batch.x if args.model_3d == "painn" or batch.x.dim() == 1 else batch.x[:, 0]
 
 
 def supervised_step_fused(args, batch, model, graph_pred_linear, target, stats, loss):

@@ -991,6 +991,32 @@ int geossl_gather_triples(const int32_t* tri_src, int64_t stride, const float* a
                           const int32_t* t_ptr, const int32_t* mol_ptr, int64_t B, int64_t* tri0, int64_t* tri1,
                           int64_t* tri2, float* angle_dst, hipStream_t stream);
 
+/* ---- sparse pair list (csrc/sparse_pairs.hip): SchNet on structures of up to 1024 atoms ----------------------------
+ * The radius graph of geossl_pair_geometry as a compacted list: per molecule in batch order the pairs (a < b) with an
+ * edge in at least one direction, lexicographic, as int32 global atom ids; pair_d / pair_c / pair_flag as in the dense
+ * form (same fp32 arithmetic, op by op).  Nothing is read back: every array has `capacity` rows (the caller's bound
+ * sum_m min(n_m (n_m - 1) / 2, (cap) n_m), cap = max_num_neighbors + 1), n_pairs[0] receives the real number of rows
+ * (the dyn_P of the filter kernels) and the rows past it are rewritten on every call as flag 0, pair_i = pair_j = 0,
+ * pair_c = 0, pair_d = cutoff.  Incidence lists: inc_ptr[N + 1], and for atom t the entries [inc_ptr[t], inc_ptr[t+1])
+ * in ascending partner order (pair_j == t first, then pair_i == t): inc_pair = row of the pair, inc_src = partner |
+ * (edge partner -> t) << 30 | (edge t -> partner) << 31; inc_pair / inc_src hold 2 * capacity entries.
+ * Work arrays: mol_cnt[B], up_cnt[N], lo_cnt[N].  1 <= max_n <= 1024, else hipErrorInvalidValue.                    */
+int geossl_sparse_pairs_build(const float* pos, const int32_t* mol_ptr, int64_t B, int64_t N, int max_n, float r2,
+                              int cap, float cutoff, int64_t capacity, int32_t* mol_cnt, int32_t* up_cnt,
+                              int32_t* lo_cnt, int32_t* pair_i, int32_t* pair_j, float* pair_d, float* pair_c,
+                              uint8_t* pair_flag, int32_t* inc_ptr, int32_t* inc_pair, uint32_t* inc_src,
+                              int32_t* n_pairs, hipStream_t stream);
+/* out[t] = sum over t's incidence entries with the edge partner -> t (swap = 1: t -> partner, the transposed graph) of
+ * x[partner] * Wf[row], ascending partner, separate multiply and add (the rounding sequence of geossl_cfconv_aggregate);
+ * F in {32, 64, 128}; no atomics; every row of out is written (zeros for an atom without such pairs).               */
+int geossl_cfconv_aggregate_sparse(const float* x, const float* Wf, const int32_t* inc_ptr, const int32_t* inc_pair,
+                                   const uint32_t* inc_src, int64_t N, int F, int swap, float* out,
+                                   hipStream_t stream);
+/* geossl_pair_position_grad through the incidence lists: dd is [L, P] (P = capacity) from geossl_cfconv_filter_dpos. */
+int geossl_pair_position_grad_sparse(const float* pos, const float* pair_d, const float* dd, const int32_t* inc_ptr,
+                                     const int32_t* inc_pair, const uint32_t* inc_src, int64_t N, int64_t P, int L,
+                                     float* dpos, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
