@@ -152,7 +152,7 @@ class _SchNetCore(torch.autograd.Function):
         # A SPARSE layout (a structure above 255 atoms, layout.want_sparse) runs on the compacted list of the pairs that
         # carry an edge: P is then the list's capacity, its real row count stays on the device (the dyn_P of the filter
         # kernels), and only the geometry, the two aggregations and the position scatter differ from the dense branch.
-        sp = None
+        sp = live = None
         if getattr(lay, "sparse", False):
             if dyn is not None:
                 raise _lib.GeosslHipError("capacity buckets hold molecules of at most 255 atoms (bucket.MAX_N)")
@@ -160,7 +160,19 @@ class _SchNetCore(torch.autograd.Function):
             pair_d, pair_c, pair_flag, dP2 = sp.pair_d, sp.pair_c, sp.pair_flag, sp.dyn_P
             aggregate = lambda x_, W_, out=None, swap=False, mols=None: ops.aggregate_sparse(x_, W_, sp, swap=swap, out=out)
         else:
-            pair_d, pair_c, pair_flag = ops.pair_geometry(pos, lay, cfg["cutoff"])
+            # The filter network has work only for the slots that carry an edge (93 % of them in QM9-sized molecules at
+            # 5 A, fewer in extended ones): on the path without position gradients it runs on the list of those rows
+            # (ops.live_pairs, one launch; the row count stays on the device), storing Wf at the dense slot - what the
+            # aggregation walks address - and T at the list's row, which is what the weight-gradient kernel walks.  The
+            # position gradient reads T and Wf by one index and keeps the dense rows in the forward; where it is asked
+            # for together with parameter gradients the list is built all the same and the backward regroups T, so that
+            # the filter weight gradients are those of the path without it, bit for bit.  GEOSSL_LIVE_PAIRS=0: every slot.
+            use_live = (lay.P > 0 and ops.live_pairs_enabled() and (want_params or not ctx.needs_input_grad[1]))
+            live_fwd = use_live and not ctx.needs_input_grad[1]
+            mol_live = torch.empty(lay.B, dtype=torch.int32, device=dev) if use_live else None
+            pair_d, pair_c, pair_flag = ops.pair_geometry(pos, lay, cfg["cutoff"], mol_live=mol_live)
+            if use_live:
+                live = ops.live_pairs(pair_d, pair_c, pair_flag, lay, mol_live, cfg["cutoff"])
             aggregate = lambda x_, W_, out=None, swap=False, mols=None: ops.aggregate(x_, W_, pair_flag, lay, swap=swap,
                                                                                       out=out, mols=mols)
         P = lay.P
@@ -180,7 +192,11 @@ class _SchNetCore(torch.autograd.Function):
                                or bool(_env("GEOSSL_FILTER_BWD_BF16X3"))
                                or bool(_env("GEOSSL_ARITH_24BIT")))
         T = torch.empty(L, P, F, dtype=torch.float32, device=dev) if keep_T else None
-        if P > 0:
+        if live is not None and live_fwd:
+            # (the Wf rows of dead slots stay unwritten: every aggregation form drops them with a select)
+            call("geossl_cfconv_filter_fwd_rows", ptr(live.pair_d), ptr(live.pair_c), P, C.byref(fw), L, F, G,
+                 ptr(cfg["offset"]), cfg["coeff"], ptr(T), ptr(Wf), live.dyn_P, ptr(live.row_slot), st)
+        elif P > 0:
             call("geossl_cfconv_filter_fwd_dyn", ptr(pair_d), ptr(pair_c), P, C.byref(fw), L, F, G, ptr(cfg["offset"]),
                  cfg["coeff"], ptr(T), ptr(Wf), dP2, st)
         hs, xs, aggs, ts = [], [], [], []
@@ -264,7 +280,8 @@ class _SchNetCore(torch.autograd.Function):
             ctx.ps = ps
             ctx.params = params
             ctx.saved = dict(pair_d=pair_d, pair_c=pair_c, pair_flag=pair_flag, Wf=Wf, T=T, hs=hs, xs=xs, aggs=aggs,
-                             ts=ts, h_last=h, u=u, img_bwd=img_bwd if cfg["chain"] else None, sparse=sp)
+                             ts=ts, h_last=h, u=u, img_bwd=img_bwd if cfg["chain"] else None, sparse=sp, live=live,
+                             live_T=live is not None and live_fwd)
         return hout
 
     @staticmethod
@@ -408,9 +425,21 @@ class _SchNetCore(torch.autograd.Function):
                     gout.dw1[l], gout.db1[l], gout.dw2[l], gout.db2[l] = ptr(gl[0]), ptr(gl[1]), ptr(gl[2]), ptr(gl[3])
                 nfl = _lib.load().geossl_cfconv_filter_bwd_workspace_floats(P, L, F, G)
                 ws2 = torch.empty(nfl, dtype=torch.float32, device=dev)
-                call("geossl_cfconv_filter_bwd_dyn", ptr(sv["pair_d"]), ptr(sv["pair_c"]), ptr(sv["pair_flag"]),
-                     ptr(pair_i), ptr(pair_j), P, N, C.byref(fw), C.byref(gin), L, F, G, ptr(cfg["offset"]),
-                     cfg["coeff"], ptr(sv["T"]), C.byref(gout), ptr(ws2), accum, dP2, dN2, st)
+                live = sv.get("live")  # the forward's live-pair list: its rows are the rows of T
+                if live is not None:
+                    T_rows = sv["T"]
+                    if T_rows is not None and not sv["live_T"]:  # stored per dense slot (a forward with position gradients)
+                        T_rows = torch.empty_like(T_rows)
+                        call("geossl_gather_live_rows", ptr(sv["T"]), ptr(live.row_slot), ptr(live.n_live), P, L, F,
+                             ptr(T_rows), st)
+                    call("geossl_cfconv_filter_bwd_dyn", ptr(live.pair_d), ptr(live.pair_c), ptr(live.pair_flag),
+                         ptr(live.pair_i), ptr(live.pair_j), P, N, C.byref(fw), C.byref(gin), L, F, G,
+                         ptr(cfg["offset"]), cfg["coeff"], ptr(T_rows), C.byref(gout), ptr(ws2), accum, live.dyn_P,
+                         dN2, st)
+                else:
+                    call("geossl_cfconv_filter_bwd_dyn", ptr(sv["pair_d"]), ptr(sv["pair_c"]), ptr(sv["pair_flag"]),
+                         ptr(pair_i), ptr(pair_j), P, N, C.byref(fw), C.byref(gin), L, F, G, ptr(cfg["offset"]),
+                         cfg["coeff"], ptr(sv["T"]), C.byref(gout), ptr(ws2), accum, dP2, dN2, st)
             elif not direct:
                 for gl in g_layers:
                     for k in range(4):

@@ -298,6 +298,10 @@ PROTOTYPES = {
     "geossl_sparse_pairs_build": (i32, [vp, vp, i64, i64, i32, f32, i32, f32, i64] + [vp] * 13),
     "geossl_cfconv_aggregate_sparse": (i32, [vp, vp, vp, vp, vp, i64, i32, i32, vp, vp]),
     "geossl_pair_position_grad_sparse": (i32, [vp, vp, vp, vp, vp, vp, i64, i64, i32, vp, vp]),
+    "geossl_pair_geometry_live": (i32, [vp, vp, vp, i64, i32, f32, i32, f32, vp, vp, vp, vp, vp]),
+    "geossl_gather_live_rows": (i32, [vp, vp, vp, i64, i32, i32, vp, vp]),
+    "geossl_live_pairs_build": (i32, [vp] * 8 + [i64, i64, f32] + [vp] * 9),
+    "geossl_cfconv_filter_fwd_rows": (i32, [vp, vp, i64, P(FilterWeights), i32, i32, i32, vp, f32, vp, vp, vp, vp, vp]),
 }
 
 _lib = None
@@ -445,6 +449,8 @@ def call(name, *args):
         CALLS += 1
     timers = TIMERS
     key = name[:-4] if name.endswith("_dyn") else name  # (a `_dyn` entry point is timed under its namesake)
+    if key == "geossl_cfconv_filter_fwd_rows":              # (and so is the filter forward on a live-pair list)
+        key = "geossl_cfconv_filter_fwd"
     if timers is not None and key in timers:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()

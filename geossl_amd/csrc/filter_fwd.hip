@@ -35,13 +35,17 @@ __device__ long long ff_dbg[2 * 64 * 8 + 2 * 64];  // + wall clock (100 MHz) at 
 #endif
 
 // NMB = F/32 row blocks of the weight matrices; K1S = 16-wide k-steps of the first GEMM (>= ceil(G/16))
-template <int NMB, int K1S>
-__global__ __launch_bounds__(512) void k_filter_fwd(const float* __restrict__ pair_d,
+// MAP: the rows are a compacted list of the live pair slots (geossl_live_pairs_build): row r stores its hidden row at T
+// row r (compact, what the backward walks) and its filter row at Wf row row_slot[r] (the dense slot the aggregation walks
+// address); the Wf rows of dead slots are never written.
+template <int NMB, int K1S, bool MAP>
+__device__ __forceinline__ void filter_fwd_body(const float* __restrict__ pair_d,
                                                     const float* __restrict__ pair_c, int P,
-                                                    GeosslFilterWeights w, int G,
+                                                    const GeosslFilterWeights& w, int G,
                                                     const float* __restrict__ offset, float coeff,
                                                     float* __restrict__ Tout, float* __restrict__ Wf,
-                                                    const int32_t* __restrict__ dyn_P) {
+                                                    const int32_t* __restrict__ dyn_P,
+                                                    const int32_t* __restrict__ row_slot) {
   constexpr int F = 32 * NMB, K2S = F / 16;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
   u32x4* W2f = reinterpret_cast<u32x4*>(smem_raw);          // [NMB][K2S][3][64] A fragments of A2
@@ -112,6 +116,7 @@ __global__ __launch_bounds__(512) void k_filter_fwd(const float* __restrict__ pa
     const bool live = row < P;
     const float d = live ? pair_d[row] : 0.0f;
     const float cw = live ? pair_c[row] : 0.0f;
+    const int slot = MAP ? (live ? row_slot[row] : 0) : row;
     // first GEMM, transposed: acc1[mb] = (A1 rbf^T)[32mb.., rows]; bias along the register (feature) axis
     f32x16 acc1[NMB];
 #pragma unroll
@@ -188,7 +193,7 @@ __global__ __launch_bounds__(512) void k_filter_fwd(const float* __restrict__ pa
     FF_MARK(3);
     // second GEMM, transposed, two 32-feature output blocks at a time
     constexpr int MP = NMB >= 2 ? 2 : 1;
-    float* orow = Wf + (lbase + row) * F + 4 * kh;
+    float* orow = Wf + (lbase + slot) * F + 4 * kh;
 #pragma unroll
     for (int mb0 = 0; mb0 < NMB; mb0 += MP) {
       f32x16 acc2[MP];
@@ -257,7 +262,25 @@ __global__ __launch_bounds__(512) void k_filter_fwd(const float* __restrict__ pa
   }
 }
 
-
+// the plain launch (every row stores T and Wf at its own index) and the launch on a live-pair list, as kernels of their
+// own names: the plain ones keep theirs (profiles, the per-class coverage test of the built library)
+template <int NMB, int K1S>
+__global__ __launch_bounds__(512) void k_filter_fwd(const float* __restrict__ pair_d, const float* __restrict__ pair_c,
+                                                    int P, GeosslFilterWeights w, int G,
+                                                    const float* __restrict__ offset, float coeff,
+                                                    float* __restrict__ Tout, float* __restrict__ Wf,
+                                                    const int32_t* __restrict__ dyn_P) {
+  filter_fwd_body<NMB, K1S, false>(pair_d, pair_c, P, w, G, offset, coeff, Tout, Wf, dyn_P, nullptr);
+}
+template <int NMB, int K1S>
+__global__ __launch_bounds__(512) void k_filter_fwd_rows(const float* __restrict__ pair_d,
+                                                         const float* __restrict__ pair_c, int P, GeosslFilterWeights w,
+                                                         int G, const float* __restrict__ offset, float coeff,
+                                                         float* __restrict__ Tout, float* __restrict__ Wf,
+                                                         const int32_t* __restrict__ dyn_P,
+                                                         const int32_t* __restrict__ row_slot) {
+  filter_fwd_body<NMB, K1S, true>(pair_d, pair_c, P, w, G, offset, coeff, Tout, Wf, dyn_P, row_slot);
+}
 
 // ---- The same network on TWO fp16 pieces per operand (split.h): 3 MFMAs per product instead of 6.  Scales (powers of
 // two, exact): A1 and A2 by their largest magnitude (once per block), the Gaussians by 2^14 (they are <= 1), the hidden
@@ -266,13 +289,14 @@ __global__ __launch_bounds__(512) void k_filter_fwd(const float* __restrict__ pa
 #ifndef FFH_THREADS
 #define FFH_THREADS 512  // 8 waves per CU; 768 / 1024 were slower inside the step
 #endif
-template <int NMB, int K1S>
-__global__ __launch_bounds__(FFH_THREADS) void k_filter_fwd_h(const float* __restrict__ pair_d,
+template <int NMB, int K1S, bool MAP>
+__device__ __forceinline__ void filter_fwd_h_body(const float* __restrict__ pair_d,
                                                       const float* __restrict__ pair_c, int P,
-                                                      GeosslFilterWeights w, int G,
+                                                      const GeosslFilterWeights& w, int G,
                                                       const float* __restrict__ offset, float coeff,
                                                       float* __restrict__ Tout, float* __restrict__ Wf,
-                                                    const int32_t* __restrict__ dyn_P) {
+                                                    const int32_t* __restrict__ dyn_P,
+                                                    const int32_t* __restrict__ row_slot) {
   constexpr int F = 32 * NMB, K2S = F / 16;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
   u32x4* W2f = reinterpret_cast<u32x4*>(smem_raw);          // [NMB][K2S][2][64] A fragments of A2 * s2
@@ -358,14 +382,17 @@ __global__ __launch_bounds__(FFH_THREADS) void k_filter_fwd_h(const float* __res
   };
   int rb = take();
   float d_n = pair_d[min(32 * rb + j, P - 1)], cw_n = pair_c[min(32 * rb + j, P - 1)];
+  int slot_n = MAP ? row_slot[min(32 * rb + j, P - 1)] : 0;  // (MAP: the dense slot of the row, see k_filter_fwd)
   while (rb < nrb) {
     const int row = 32 * rb + j;
     const bool live = row < P;
     const float d = d_n;
     const float cw = live ? cw_n : 0.0f;
+    const int slot = MAP ? slot_n : row;
     const int rb_next = take();
     d_n = pair_d[min(32 * rb_next + j, P - 1)];
     cw_n = pair_c[min(32 * rb_next + j, P - 1)];
+    if (MAP) slot_n = row_slot[min(32 * rb_next + j, P - 1)];
     // every LDS read of the loop is tile-invariant: an opaque zero in the addresses keeps the compiler from hoisting
     // (and then spilling) fragments, biases and centres across the tile loop
     int z = 0;
@@ -435,7 +462,7 @@ __global__ __launch_bounds__(FFH_THREADS) void k_filter_fwd_h(const float* __res
     }
     // second GEMM, transposed, two 32-feature output blocks at a time
     constexpr int MP = NMB >= 2 ? 2 : 1;
-    float* orow = Wf + (lbase + row) * F + 4 * kh;
+    float* orow = Wf + (lbase + slot) * F + 4 * kh;
 #pragma unroll
     for (int mb0 = 0; mb0 < NMB; mb0 += MP) {
       f32x16 acc2[MP];
@@ -473,6 +500,26 @@ __global__ __launch_bounds__(FFH_THREADS) void k_filter_fwd_h(const float* __res
   }
 }
 
+template <int NMB, int K1S>
+__global__ __launch_bounds__(FFH_THREADS) void k_filter_fwd_h(const float* __restrict__ pair_d,
+                                                              const float* __restrict__ pair_c, int P,
+                                                              GeosslFilterWeights w, int G,
+                                                              const float* __restrict__ offset, float coeff,
+                                                              float* __restrict__ Tout, float* __restrict__ Wf,
+                                                              const int32_t* __restrict__ dyn_P) {
+  filter_fwd_h_body<NMB, K1S, false>(pair_d, pair_c, P, w, G, offset, coeff, Tout, Wf, dyn_P, nullptr);
+}
+template <int NMB, int K1S>
+__global__ __launch_bounds__(FFH_THREADS) void k_filter_fwd_rows_h(const float* __restrict__ pair_d,
+                                                                   const float* __restrict__ pair_c, int P,
+                                                                   GeosslFilterWeights w, int G,
+                                                                   const float* __restrict__ offset, float coeff,
+                                                                   float* __restrict__ Tout, float* __restrict__ Wf,
+                                                                   const int32_t* __restrict__ dyn_P,
+                                                                   const int32_t* __restrict__ row_slot) {
+  filter_fwd_h_body<NMB, K1S, true>(pair_d, pair_c, P, w, G, offset, coeff, Tout, Wf, dyn_P, row_slot);
+}
+
 #ifdef FF_TIMING
 }  // namespace
 extern "C" int geossl_filter_fwd_debug_read(long long* host) {
@@ -493,6 +540,13 @@ extern "C" int geossl_cfconv_filter_fwd_dyn(const float* pair_d, const float* pa
                                             const GeosslFilterWeights* w, int L, int F, int G, const float* offset,
                                             float coeff, float* T, float* Wf, const int32_t* dyn_P,
                                             hipStream_t stream) {
+  return geossl_cfconv_filter_fwd_rows(pair_d, pair_c, P, w, L, F, G, offset, coeff, T, Wf, dyn_P, nullptr, stream);
+}
+
+extern "C" int geossl_cfconv_filter_fwd_rows(const float* pair_d, const float* pair_c, int64_t P,
+                                             const GeosslFilterWeights* w, int L, int F, int G, const float* offset,
+                                             float coeff, float* T, float* Wf, const int32_t* dyn_P,
+                                             const int32_t* row_slot, hipStream_t stream) {
   if (P <= 0 || L <= 0) return 0;
   if (L > GEOSSL_MAX_L || (F != 32 && F != 64 && F != 128) || G > 64 || G < 1) return (int)hipErrorInvalidValue;
   const int nrb = (int)((P + 31) / 32);
@@ -503,9 +557,15 @@ extern "C" int geossl_cfconv_filter_fwd_dyn(const float* pair_d, const float* pa
 #define LAUNCH(NMB, K1S)                                                                                        \
   do {                                                                                                          \
     const size_t lds = (size_t)(NMB * (2 * NMB) + NMB * K1S) * 3 * 1024 + (2 * 32 * NMB + 16 * K1S) * 4;        \
-    allow_big_lds(&k_filter_fwd<NMB, K1S>);                                                                     \
-    hipLaunchKernelGGL((k_filter_fwd<NMB, K1S>), grid, dim3(512), lds, stream, pair_d, pair_c, (int)P, *w, G,   \
-                       offset, coeff, T, Wf, dyn_P);                                                            \
+    if (row_slot != nullptr) {                                                                                  \
+      allow_big_lds(&k_filter_fwd_rows<NMB, K1S>);                                                              \
+      hipLaunchKernelGGL((k_filter_fwd_rows<NMB, K1S>), grid, dim3(512), lds, stream, pair_d, pair_c, (int)P,   \
+                         *w, G, offset, coeff, T, Wf, dyn_P, row_slot);                                         \
+    } else {                                                                                                    \
+      allow_big_lds(&k_filter_fwd<NMB, K1S>);                                                                   \
+      hipLaunchKernelGGL((k_filter_fwd<NMB, K1S>), grid, dim3(512), lds, stream, pair_d, pair_c, (int)P,        \
+                         *w, G, offset, coeff, T, Wf, dyn_P);                                                   \
+    }                                                                                                           \
   } while (0)
 #define LAUNCH_F(NMB)                   \
   do {                                  \
@@ -519,9 +579,15 @@ extern "C" int geossl_cfconv_filter_fwd_dyn(const float* pair_d, const float* pa
 #define LAUNCH_H(NMB, K1S)                                                                                      \
   do {                                                                                                          \
     const size_t lds = (size_t)(NMB * (2 * NMB) + NMB * K1S) * 2 * 1024 + (2 * 32 * NMB + 16 * K1S + 36) * 4;   \
-    allow_big_lds(&k_filter_fwd_h<NMB, K1S>);                                                                   \
-    hipLaunchKernelGGL((k_filter_fwd_h<NMB, K1S>), grid, dim3(FFH_THREADS), lds, stream, pair_d, pair_c, (int)P, *w, G, \
-                       offset, coeff, T, Wf, dyn_P);                                                            \
+    if (row_slot != nullptr) {                                                                                  \
+      allow_big_lds(&k_filter_fwd_rows_h<NMB, K1S>);                                                            \
+      hipLaunchKernelGGL((k_filter_fwd_rows_h<NMB, K1S>), grid, dim3(FFH_THREADS), lds, stream, pair_d, pair_c, \
+                         (int)P, *w, G, offset, coeff, T, Wf, dyn_P, row_slot);                                 \
+    } else {                                                                                                    \
+      allow_big_lds(&k_filter_fwd_h<NMB, K1S>);                                                                 \
+      hipLaunchKernelGGL((k_filter_fwd_h<NMB, K1S>), grid, dim3(FFH_THREADS), lds, stream, pair_d, pair_c,      \
+                         (int)P, *w, G, offset, coeff, T, Wf, dyn_P);                                           \
+    }                                                                                                           \
   } while (0)
 #define LAUNCH_HF(NMB)                    \
   do {                                    \

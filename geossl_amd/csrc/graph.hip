@@ -127,7 +127,7 @@ __global__ __launch_bounds__(64) void k_radius(const float* __restrict__ pos, co
                                                int64_t* __restrict__ edge_src, int64_t* __restrict__ edge_dst,
                                                float* __restrict__ edge_weight, float* __restrict__ pair_d,
                                                uint8_t* __restrict__ pair_flag, float cutoff,
-                                               float* __restrict__ pair_c) {
+                                               float* __restrict__ pair_c, int32_t* __restrict__ mol_live) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int m = blockIdx.x;
   if (m >= B) return;
@@ -158,6 +158,7 @@ __global__ __launch_bounds__(64) void k_radius(const float* __restrict__ pos, co
   if (MODE == 2) {
     __syncthreads();
     const int base = pair_ptr[m];
+    int cnt = 0;  // slots of the molecule with an edge (lane 0 is in every round of the loops below)
     for (int a = 0; a + 1 < n; ++a) {
       const int row = base + a * n - a * (a + 1) / 2 - a - 1;
       for (int b = a + 1 + lane; b < n; b += 64) {
@@ -168,19 +169,23 @@ __global__ __launch_bounds__(64) void k_radius(const float* __restrict__ pos, co
         pair_d[row + b] = d;
         pair_c[row + b] = pair_envelope(d, cutoff);
         pair_flag[row + b] = (uint8_t)(f0 | (f1 << 1));
+        cnt += __popcll(__ballot((f0 | f1) != 0u));
       }
     }
+    if (mol_live != nullptr && lane == 0) mol_live[m] = cnt;
   }
 }
 
 // MODE 2 for molecules of at most `cap` atoms (the neighbour cap of torch_cluster.radius_graph, self hit included, can
 // then never cut a list: the flags are the plain threshold test, symmetric bit for bit because the squared distance is):
 // no adjacency pass, the pair slots of a molecule dealt flat to the 64 lanes of its wave - 3 rounds for 18 atoms where
-// the general kernel walks 18 + 17 dependent rows.  Same arithmetic, same outputs.
+// the general kernel walks 18 + 17 dependent rows.  Same arithmetic, same outputs.  mol_live (nullable): the number of the
+// molecule's slots that carry an edge, for the live-pair list (sparse_pairs.hip: k_live_pairs).
 __global__ __launch_bounds__(64) void k_pair_geometry_flat(const float* __restrict__ pos, const int32_t* __restrict__ mol_ptr,
                                                            const int32_t* __restrict__ pair_ptr, int B, float r2,
                                                            float cutoff, float* __restrict__ pair_d,
-                                                           float* __restrict__ pair_c, uint8_t* __restrict__ pair_flag) {
+                                                           float* __restrict__ pair_c, uint8_t* __restrict__ pair_flag,
+                                                           int32_t* __restrict__ mol_live) {
   __shared__ float sp[3 * 64];
   const int m = blockIdx.x, lane = threadIdx.x;
   if (m >= B) return;
@@ -189,6 +194,7 @@ __global__ __launch_bounds__(64) void k_pair_geometry_flat(const float* __restri
   for (int i = lane; i < 3 * n; i += 64) sp[i] = pos[(size_t)a0 * 3 + i];
   __syncthreads();
   const float tn = (float)(2 * n - 1);
+  int cnt = 0;  // (lane 0 is in every round)
   for (int q = lane; q < np; q += 64) {
     // slot q = a n - a (a + 1) / 2 + (b - a - 1), a < b: the row from the closed form, corrected by one either way
     int a = (int)((tn - sqrtf(fmaxf(tn * tn - 8.0f * (float)q, 0.0f))) * 0.5f);
@@ -201,7 +207,9 @@ __global__ __launch_bounds__(64) void k_pair_geometry_flat(const float* __restri
     pair_d[base + q] = d;
     pair_c[base + q] = pair_envelope(d, cutoff);
     pair_flag[base + q] = d2 < r2 ? (uint8_t)3 : (uint8_t)0;
+    cnt += __popcll(__ballot(d2 < r2));
   }
+  if (mol_live != nullptr && lane == 0) mol_live[m] = cnt;
 }
 
 // ------------------------------------------------------------------------------- super-edge bookkeeping
@@ -414,7 +422,7 @@ extern "C" int geossl_radius_graph_count(const float* pos, const int32_t* mol_pt
   if (max_n < 1 || max_n > GEOSSL_RADIUS_MAX_N) return (int)hipErrorInvalidValue;
   allow_big_lds(&k_radius<0>);  // more than 64 KB from about 650 atoms on
   hipLaunchKernelGGL((k_radius<0>), dim3((unsigned)B), dim3(64), radius_lds(max_n), stream, pos, mol_ptr, nullptr,
-                     (int)B, max_n, r2, cap, deg, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1.0f, nullptr);
+                     (int)B, max_n, r2, cap, deg, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1.0f, nullptr, nullptr);
   GEOSSL_CHECK_LAUNCH();
   return 0;
 }
@@ -427,7 +435,7 @@ extern "C" int geossl_radius_graph_fill(const float* pos, const int32_t* mol_ptr
   allow_big_lds(&k_radius<1>);
   hipLaunchKernelGGL((k_radius<1>), dim3((unsigned)B), dim3(64), radius_lds(max_n), stream, pos, mol_ptr, nullptr,
                      (int)B, max_n, r2, cap, nullptr, edge_ptr, edge_src, edge_dst, edge_weight, nullptr, nullptr, 1.0f,
-                     nullptr);
+                     nullptr, nullptr);
   GEOSSL_CHECK_LAUNCH();
   return 0;
 }
@@ -435,17 +443,25 @@ extern "C" int geossl_radius_graph_fill(const float* pos, const int32_t* mol_ptr
 extern "C" int geossl_pair_geometry(const float* pos, const int32_t* mol_ptr, const int32_t* pair_ptr, int64_t B,
                                     int max_n, float r2, int cap, float cutoff, float* pair_d, float* pair_c,
                                     uint8_t* pair_flag, hipStream_t stream) {
+  return geossl_pair_geometry_live(pos, mol_ptr, pair_ptr, B, max_n, r2, cap, cutoff, pair_d, pair_c, pair_flag, nullptr,
+                                   stream);
+}
+
+extern "C" int geossl_pair_geometry_live(const float* pos, const int32_t* mol_ptr, const int32_t* pair_ptr, int64_t B,
+                                         int max_n, float r2, int cap, float cutoff, float* pair_d, float* pair_c,
+                                         uint8_t* pair_flag, int32_t* mol_live, hipStream_t stream) {
   if (B <= 0) return 0;
   if (max_n <= cap && max_n <= 64) {
     hipLaunchKernelGGL(k_pair_geometry_flat, dim3((unsigned)B), dim3(64), 0, stream, pos, mol_ptr, pair_ptr, (int)B, r2,
-                       cutoff, pair_d, pair_c, pair_flag);
+                       cutoff, pair_d, pair_c, pair_flag, mol_live);
     GEOSSL_CHECK_LAUNCH();
     return 0;
   }
   if (max_n < 1 || max_n > GEOSSL_RADIUS_MAX_N) return (int)hipErrorInvalidValue;
   allow_big_lds(&k_radius<2>);
   hipLaunchKernelGGL((k_radius<2>), dim3((unsigned)B), dim3(64), radius_lds(max_n), stream, pos, mol_ptr, pair_ptr,
-                     (int)B, max_n, r2, cap, nullptr, nullptr, nullptr, nullptr, nullptr, pair_d, pair_flag, cutoff, pair_c);
+                     (int)B, max_n, r2, cap, nullptr, nullptr, nullptr, nullptr, nullptr, pair_d, pair_flag, cutoff, pair_c,
+                     mol_live);
   GEOSSL_CHECK_LAUNCH();
   return 0;
 }

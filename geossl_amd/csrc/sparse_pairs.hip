@@ -265,6 +265,101 @@ __global__ __launch_bounds__(SP_THREADS) void k_sparse_fill(
   }
 }
 
+// ---- live-pair list of a DENSE layout --------------------------------------------------------------------------------
+// The pair slots with pair_flag != 0, in slot order, packed back to back: the rows the filter network has work for (a
+// slot without an edge gets no filter row and sends no gradient).  row_slot[r] = dense slot of row r; n_live[0] = the
+// number of rows, which stays on the device (the dyn_P of the filter kernels).  mol_live[m] = live slots of molecule m
+// (geossl_pair_geometry_live); a wave compacts one molecule, its first row = the live slots of the molecules before it
+// (summed by the block, as in k_sparse_fill).  Rows past n_live are rewritten on every call in the convention of the
+// sparse list (flag 0, pair_i = pair_j = 0, pair_c = 0, pair_d = cutoff; row_slot = 0).  No atomics: deterministic.
+constexpr int LP_THREADS = 256, LP_WAVES = LP_THREADS / 64;
+__global__ __launch_bounds__(LP_THREADS) void k_live_pairs(
+    const float* __restrict__ pair_d, const float* __restrict__ pair_c, const uint8_t* __restrict__ pair_flag,
+    const int32_t* __restrict__ pair_i, const int32_t* __restrict__ pair_j, const int32_t* __restrict__ mol_ptr,
+    const int32_t* __restrict__ pair_ptr, const int32_t* __restrict__ mol_live, int B, int P, float cutoff,
+    const int32_t* __restrict__ dyn_P, float* __restrict__ out_d, float* __restrict__ out_c,
+    uint8_t* __restrict__ out_flag, int32_t* __restrict__ out_i, int32_t* __restrict__ out_j,
+    int32_t* __restrict__ row_slot, int32_t* __restrict__ n_live) {
+  __shared__ int s_before[LP_WAVES], s_all[LP_WAVES];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int m0 = blockIdx.x * LP_WAVES;
+  const int Preal = dyn_count(P, dyn_P);  // slots at and past it do not exist
+  {
+    int before = 0, all = 0;
+    for (int k = tid; k < B; k += LP_THREADS) {
+      const int v = mol_live[k];
+      all += v;
+      if (k < m0) before += v;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      before += __shfl_xor(before, o, 64);
+      all += __shfl_xor(all, o, 64);
+    }
+    if (lane == 0) {
+      s_before[wave] = before;
+      s_all[wave] = all;
+    }
+    __syncthreads();
+  }
+  int base = 0, total = 0;
+#pragma unroll
+  for (int w = 0; w < LP_WAVES; ++w) {
+    base += s_before[w];
+    total += s_all[w];
+  }
+  total = min(total, P);
+  if (blockIdx.x == 0 && tid == 0) n_live[0] = total;
+  for (int p = total + blockIdx.x * LP_THREADS + tid; p < P; p += gridDim.x * LP_THREADS) {
+    out_i[p] = 0;
+    out_j[p] = 0;
+    out_d[p] = cutoff;
+    out_c[p] = 0.0f;
+    out_flag[p] = 0;
+    row_slot[p] = 0;
+  }
+  const int m = m0 + wave;
+  if (m >= B) return;
+  for (int k = m0; k < m; ++k) base += mol_live[k];
+  const int n = mol_ptr[m + 1] - mol_ptr[m], s0 = pair_ptr[m], np = n * (n - 1) / 2;
+  const unsigned long long lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  for (int q0 = 0; q0 < np; q0 += 64) {  // (uniform over the wave)
+    const int slot = s0 + q0 + lane;
+    const bool in = q0 + lane < np && slot < Preal;
+    const unsigned fl = in ? pair_flag[slot] : 0u;
+    const unsigned long long mk = __ballot(fl != 0u);
+    const int r = base + __popcll(mk & lt);
+    if (fl != 0u && r < P) {
+      out_i[r] = pair_i[slot];
+      out_j[r] = pair_j[slot];
+      out_d[r] = pair_d[slot];
+      out_c[r] = pair_c[slot];
+      out_flag[r] = (uint8_t)fl;
+      row_slot[r] = slot;
+    }
+    base += __popcll(mk);
+  }
+}
+
+// dst[l][r] = src[l][row_slot[r]] for the rows r < n_live of every layer (F floats each, 16-byte pieces): the hidden rows
+// T of a forward that stored them per dense slot (the path with position gradients: filter_dpos reads T and Wf by one
+// index), regrouped for the weight-gradient kernel on the live-pair list - so that this path forms the filter weight
+// gradients in the launch, and to the bits, of the path without position gradients.
+__global__ __launch_bounds__(256) void k_gather_live_rows(const float* __restrict__ src,
+                                                          const int32_t* __restrict__ row_slot,
+                                                          const int32_t* __restrict__ n_live, int P, int F4,
+                                                          float* __restrict__ dst) {
+  const int n = min(P, n_live[0]);
+  const size_t lbase = (size_t)blockIdx.y * P;
+  const float4* __restrict__ s4 = reinterpret_cast<const float4*>(src);
+  float4* __restrict__ d4 = reinterpret_cast<float4*>(dst);
+  const int64_t total = (int64_t)n * F4;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int r = (int)(i / F4), c = (int)(i - (int64_t)r * F4);
+    d4[(lbase + r) * F4 + c] = s4[(lbase + row_slot[r]) * F4 + c];
+  }
+}
+
 // ---- neighbour aggregation over the list ----------------------------------------------------------------------------
 // out[t] = sum over t's incident pairs with the edge partner -> t (swap: t -> partner) of x[partner] * Wf[row], ascending
 // partner, separate multiply and add: the rounding sequence of k_aggregate.  One wave per target atom, a lane owns VW
@@ -369,6 +464,31 @@ extern "C" int geossl_sparse_pairs_build(const float* pos, const int32_t* mol_pt
   hipLaunchKernelGGL(k_sparse_fill, dim3((unsigned)B), dim3(SP_THREADS), lds, stream, pos, mol_ptr, (int)B, (int)N, max_n,
                      r2, cap, cutoff, mol_cnt, up_cnt, lo_cnt, (int)capacity, pair_i, pair_j, pair_d, pair_c, pair_flag,
                      inc_ptr, inc_pair, inc_src, n_pairs);
+  GEOSSL_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int geossl_live_pairs_build(const float* pair_d, const float* pair_c, const uint8_t* pair_flag,
+                                       const int32_t* pair_i, const int32_t* pair_j, const int32_t* mol_ptr,
+                                       const int32_t* pair_ptr, const int32_t* mol_live, int64_t B, int64_t P,
+                                       float cutoff, const int32_t* dyn_P, float* live_d, float* live_c,
+                                       uint8_t* live_flag, int32_t* live_i, int32_t* live_j, int32_t* row_slot,
+                                       int32_t* n_live, hipStream_t stream) {
+  if (B <= 0 || P < 0 || P > (1ll << 30) || mol_live == nullptr || n_live == nullptr) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_live_pairs, dim3((unsigned)((B + LP_WAVES - 1) / LP_WAVES)), dim3(LP_THREADS), 0, stream, pair_d,
+                     pair_c, pair_flag, pair_i, pair_j, mol_ptr, pair_ptr, mol_live, (int)B, (int)P, cutoff, dyn_P, live_d,
+                     live_c, live_flag, live_i, live_j, row_slot, n_live);
+  GEOSSL_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int geossl_gather_live_rows(const float* src, const int32_t* row_slot, const int32_t* n_live, int64_t P, int L,
+                                       int F, float* dst, hipStream_t stream) {
+  if (P <= 0 || L <= 0) return 0;
+  if (F <= 0 || (F & 3) || P > (1ll << 30) || L > 65535 || n_live == nullptr) return (int)hipErrorInvalidValue;
+  const int64_t work = (P * (F / 4) + 255) / 256;
+  hipLaunchKernelGGL(k_gather_live_rows, dim3((unsigned)(work < 2048 ? work : 2048), (unsigned)L), dim3(256), 0, stream,
+                     src, row_slot, n_live, (int)P, F / 4, dst);
   GEOSSL_CHECK_LAUNCH();
   return 0;
 }

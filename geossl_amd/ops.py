@@ -67,8 +67,9 @@ def radius_graph(pos, r, batch=None, loop=False, max_num_neighbors=32, layout=No
     return (edge_index, weight) if return_weight else edge_index
 
 
-def pair_geometry(pos, layout, cutoff, max_num_neighbors=32):
-    """Radius graph in pair-slot form: (pair_d [P], pair_c [P], pair_flag [P] u8)."""
+def pair_geometry(pos, layout, cutoff, max_num_neighbors=32, mol_live=None):
+    """Radius graph in pair-slot form: (pair_d [P], pair_c [P], pair_flag [P] u8).  mol_live (int32 [B], optional)
+    receives the number of slots with an edge per molecule (what `live_pairs` starts from)."""
     if getattr(layout, "sparse", False):
         raise _lib.GeosslHipError("a sparse layout (a structure above 255 atoms, or GEOSSL_SPARSE_PAIRS=1) has no dense "
                                   "pair slots: ops.sparse_pair_geometry builds its pair list")
@@ -81,9 +82,59 @@ def pair_geometry(pos, layout, cutoff, max_num_neighbors=32):
     pair_flag = torch.empty(P, dtype=torch.uint8, device=dev)
     r2 = float(torch.tensor(float(cutoff) * float(cutoff), dtype=torch.float32))
     if P > 0:
-        call("geossl_pair_geometry", ptr(pos), ptr(layout.mol_ptr), ptr(layout.pair_ptr), layout.B, layout.max_n, r2,
-             radius_cap(max_num_neighbors), float(cutoff), ptr(pair_d), ptr(pair_c), ptr(pair_flag), stream())
+        if mol_live is not None:
+            call("geossl_pair_geometry_live", ptr(pos), ptr(layout.mol_ptr), ptr(layout.pair_ptr), layout.B, layout.max_n,
+                 r2, radius_cap(max_num_neighbors), float(cutoff), ptr(pair_d), ptr(pair_c), ptr(pair_flag),
+                 ptr(mol_live), stream())
+        else:
+            call("geossl_pair_geometry", ptr(pos), ptr(layout.mol_ptr), ptr(layout.pair_ptr), layout.B, layout.max_n, r2,
+                 radius_cap(max_num_neighbors), float(cutoff), ptr(pair_d), ptr(pair_c), ptr(pair_flag), stream())
     return pair_d, pair_c, pair_flag
+
+
+def live_pairs_enabled():
+    """GEOSSL_LIVE_PAIRS=0: the filter network runs on every pair slot of a dense layout, as before the live-pair list."""
+    return _env("GEOSSL_LIVE_PAIRS", "1") != "0"
+
+
+class LivePairs:
+    """The pair slots of a dense layout that carry an edge, in slot order, packed back to back (csrc/sparse_pairs.hip:
+    k_live_pairs): pair_d, pair_c, pair_flag, pair_i, pair_j of those rows, ``row_slot`` (the dense slot of each row) and
+    ``n_live`` (int32 [1], device), the number of rows - never read back: the filter kernels take its address as their
+    dyn_P.  Every array has the layout's P rows (a capacity); rows past n_live hold flag 0, pair_i = pair_j = 0,
+    pair_c = 0, pair_d = cutoff, row_slot = 0."""
+
+    __slots__ = ("P", "pair_d", "pair_c", "pair_flag", "pair_i", "pair_j", "row_slot", "n_live")
+
+    @property
+    def dyn_P(self):
+        return self.n_live.data_ptr()
+
+
+def live_pairs(pair_d, pair_c, pair_flag, layout, mol_live, cutoff, out=None):
+    """(pair_d, pair_c, pair_flag) of `pair_geometry` called with mol_live -> LivePairs.  One launch, no read-back.  `out`:
+    a LivePairs of an earlier call on the same layout whose buffers are written again."""
+    P = layout.P
+    dev = pair_d.device
+    lp = out
+    if lp is None:
+        lp = LivePairs()
+        lp.P = P
+        i32 = dict(dtype=torch.int32, device=dev)
+        lp.pair_d = torch.empty(max(P, 1), dtype=torch.float32, device=dev)
+        lp.pair_c = torch.empty(max(P, 1), dtype=torch.float32, device=dev)
+        lp.pair_flag = torch.empty(max(P, 1), dtype=torch.uint8, device=dev)
+        lp.pair_i, lp.pair_j = torch.empty(max(P, 1), **i32), torch.empty(max(P, 1), **i32)
+        lp.row_slot = torch.empty(max(P, 1), **i32)
+        lp.n_live = torch.empty(1, **i32)
+    elif lp.P != P:
+        raise ValueError("the LivePairs given as `out` was made for another capacity")
+    dyn = getattr(layout, "dyn", None)
+    call("geossl_live_pairs_build", ptr(pair_d), ptr(pair_c), ptr(pair_flag), ptr(layout.pair_i), ptr(layout.pair_j),
+         ptr(layout.mol_ptr), ptr(layout.pair_ptr), ptr(mol_live), layout.B, P, float(cutoff),
+         dyn.n_pairs2 if dyn is not None else None, ptr(lp.pair_d), ptr(lp.pair_c), ptr(lp.pair_flag), ptr(lp.pair_i),
+         ptr(lp.pair_j), ptr(lp.row_slot), ptr(lp.n_live), stream())
+    return lp
 
 
 class SparsePairs:

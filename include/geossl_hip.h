@@ -1006,6 +1006,35 @@ int geossl_sparse_pairs_build(const float* pos, const int32_t* mol_ptr, int64_t 
                               int32_t* lo_cnt, int32_t* pair_i, int32_t* pair_j, float* pair_d, float* pair_c,
                               uint8_t* pair_flag, int32_t* inc_ptr, int32_t* inc_pair, uint32_t* inc_src,
                               int32_t* n_pairs, hipStream_t stream);
+
+/* ---- live-pair list of a dense layout (csrc/sparse_pairs.hip, csrc/graph.hip) -------------------------------------
+ * The filter network has work only for the pair slots that carry an edge (pair_flag != 0).
+ *   geossl_pair_geometry_live : geossl_pair_geometry, and mol_live[B] (nullable) = live slots per molecule.
+ *   geossl_live_pairs_build   : the live slots in slot order (stable: pair_i still ascends), packed back to back into
+ *            live_d / live_c / live_flag / live_i / live_j; row_slot[r] = dense slot of row r; n_live[0] = the number
+ *            of rows, on the device (the dyn_P of the filter kernels).  Every output has P rows (the capacity: nothing is
+ *            sized by a read-back); rows past n_live are rewritten on every call as flag 0, pair_i = pair_j = 0,
+ *            pair_c = 0, pair_d = cutoff, row_slot = 0.  dyn_P (nullable): the real slot count of a capacity bucket.
+ *            One launch, no atomics, deterministic.
+ *   geossl_cfconv_filter_fwd_rows : geossl_cfconv_filter_fwd_dyn on such a list: row r stores its hidden row at T row r
+ *            and its filter row at Wf row row_slot[r] (row_slot == NULL: row r, the plain call); Wf rows of dead slots are
+ *            not written.  The values of a row do not depend on where it stands in the list.
+ *   geossl_gather_live_rows : dst[l][r][:] = src[l][row_slot[r]][:] for r < n_live, l < L ([L][P][F] tensors, F a multiple
+ *            of 4): hidden rows stored per dense slot regrouped to the list's rows.                                   */
+int geossl_pair_geometry_live(const float* pos, const int32_t* mol_ptr, const int32_t* pair_ptr, int64_t B, int max_n,
+                              float r2, int cap, float cutoff, float* pair_d, float* pair_c, uint8_t* pair_flag,
+                              int32_t* mol_live, hipStream_t stream);
+int geossl_live_pairs_build(const float* pair_d, const float* pair_c, const uint8_t* pair_flag, const int32_t* pair_i,
+                            const int32_t* pair_j, const int32_t* mol_ptr, const int32_t* pair_ptr,
+                            const int32_t* mol_live, int64_t B, int64_t P, float cutoff, const int32_t* dyn_P,
+                            float* live_d, float* live_c, uint8_t* live_flag, int32_t* live_i, int32_t* live_j,
+                            int32_t* row_slot, int32_t* n_live, hipStream_t stream);
+int geossl_cfconv_filter_fwd_rows(const float* pair_d, const float* pair_c, int64_t P, const GeosslFilterWeights* w, int L,
+                                  int F, int G, const float* offset, float coeff, float* T, float* Wf,
+                                  const int32_t* dyn_P, const int32_t* row_slot, hipStream_t stream);
+int geossl_gather_live_rows(const float* src, const int32_t* row_slot, const int32_t* n_live, int64_t P, int L, int F,
+                            float* dst, hipStream_t stream);
+
 /* out[t] = sum over t's incidence entries with the edge partner -> t (swap = 1: t -> partner, the transposed graph) of
  * x[partner] * Wf[row], ascending partner, separate multiply and add (the rounding sequence of geossl_cfconv_aggregate);
  * F in {32, 64, 128}; no atomics; every row of out is written (zeros for an atom without such pairs).               */
