@@ -119,6 +119,27 @@ def _core_params(model):
     return ps
 
 
+def _fill(struct, fields, rows):
+    """struct.<k-th field>[l] = address of rows[l][k] (the per-block pointer tables of the filter-network kernels)"""
+    for l, row in enumerate(rows):
+        for name, t_ in zip(fields, row):
+            getattr(struct, name)[l] = ptr(t_)
+    return struct
+
+
+def _filter_weights(layers):
+    return _fill(_lib.FilterWeights(), ("w1", "b1", "w2", "b2"), layers)
+
+
+def _run_ops(todo, graph, cfg, N, dyn_rows):
+    """The operations of the layer loop - ("chain", x, stages) / ("agg", x, Wf_l, out, swap) - as ONE launch where the
+    shape allows (every block carries its molecules through all of them, ops.layer_loop; its aggregation walks dense
+    pair slots), else one launch each"""
+    if not (cfg["loop"] and graph.loop_flag is not None and len(todo) <= _lib.LOOP_MAX_OPS
+            and ops.layer_loop(todo, graph.layout, graph.loop_flag, N, cfg["F"], stagger=cfg["loop_stagger"])):
+        ops.launch_ops(todo, graph, dyn_rows=dyn_rows)
+
+
 class _SchNetCore(torch.autograd.Function):
     """(z, pos) -> atom features after the head (schnet.py:89-101) as ONE autograd node."""
 
@@ -141,45 +162,18 @@ class _SchNetCore(torch.autograd.Function):
         # a layout of a capacity bucket (geossl_amd/bucket.py) carries the device addresses of the batch's real counts:
         # N, P are then capacities and every row-count-driven launch below is told where the real count lives
         dyn = getattr(lay, "dyn", None)
-        dN2, dP2 = (dyn.n_atoms2, dyn.n_pairs2) if dyn is not None else (None, None)
+        dN2 = dyn.n_atoms2 if dyn is not None else None
         if dyn is not None and (ctx.needs_input_grad[1] or F != 128 or not cfg["chain"]):
             raise _lib.GeosslHipError("a capacity-bucket layout serves the F = 128 chain path without position gradients")
         call("geossl_embedding_fwd_dyn", ptr(z), z.stride(0) if z.numel() else 1, ptr(emb_w), emb_w.size(0), N, F, ptr(h),
              ptr(status.word), dN2, st)
         if cfg["debug"]:
             status.check()
-        # radius graph + edge length + envelope (schnet.py:91-93,186)
-        # A SPARSE layout (a structure above 255 atoms, layout.want_sparse) runs on the compacted list of the pairs that
-        # carry an edge: P is then the list's capacity, its real row count stays on the device (the dyn_P of the filter
-        # kernels), and only the geometry, the two aggregations and the position scatter differ from the dense branch.
-        sp = live = None
-        if getattr(lay, "sparse", False):
-            if dyn is not None:
-                raise _lib.GeosslHipError("capacity buckets hold molecules of at most 255 atoms (bucket.MAX_N)")
-            sp = ops.sparse_pair_geometry(pos, lay, cfg["cutoff"])
-            pair_d, pair_c, pair_flag, dP2 = sp.pair_d, sp.pair_c, sp.pair_flag, sp.dyn_P
-            aggregate = lambda x_, W_, out=None, swap=False, mols=None: ops.aggregate_sparse(x_, W_, sp, swap=swap, out=out)
-        else:
-            # The filter network has work only for the slots that carry an edge (93 % of them in QM9-sized molecules at
-            # 5 A, fewer in extended ones): on the path without position gradients it runs on the list of those rows
-            # (ops.live_pairs, one launch; the row count stays on the device), storing Wf at the dense slot - what the
-            # aggregation walks address - and T at the list's row, which is what the weight-gradient kernel walks.  The
-            # position gradient reads T and Wf by one index and keeps the dense rows in the forward; where it is asked
-            # for together with parameter gradients the list is built all the same and the backward regroups T, so that
-            # the filter weight gradients are those of the path without it, bit for bit.  GEOSSL_LIVE_PAIRS=0: every slot.
-            use_live = (lay.P > 0 and ops.live_pairs_enabled() and (want_params or not ctx.needs_input_grad[1]))
-            live_fwd = use_live and not ctx.needs_input_grad[1]
-            mol_live = torch.empty(lay.B, dtype=torch.int32, device=dev) if use_live else None
-            pair_d, pair_c, pair_flag = ops.pair_geometry(pos, lay, cfg["cutoff"], mol_live=mol_live)
-            if use_live:
-                live = ops.live_pairs(pair_d, pair_c, pair_flag, lay, mol_live, cfg["cutoff"])
-            aggregate = lambda x_, W_, out=None, swap=False, mols=None: ops.aggregate(x_, W_, pair_flag, lay, swap=swap,
-                                                                                      out=out, mols=mols)
+        # radius graph + edge length + envelope (schnet.py:91-93,186): pair slots, a sparse list or a live-pair list
+        graph = ops.pair_graph(pos, lay, cfg["cutoff"], want_params, ctx.needs_input_grad[1])
         P = lay.P
         # continuous-filter network of every block in one launch (schnet.py:94,187)
-        fw = _lib.FilterWeights()
-        for l, lp in enumerate(layers):
-            fw.w1[l], fw.b1[l], fw.w2[l], fw.b2[l] = ptr(lp[0]), ptr(lp[1]), ptr(lp[2]), ptr(lp[3])
+        fw = _filter_weights(layers)
         Wf = torch.empty(L, P, F, dtype=torch.float32, device=dev)
         # The hidden rows T = ssp(W1 rbf + b1) of the filter network are saved for the backward (0.96 GB written and read
         # again per step at the bench size).  They are a function of the pair's distance alone, and the weight-gradient
@@ -192,15 +186,19 @@ class _SchNetCore(torch.autograd.Function):
                                or bool(_env("GEOSSL_FILTER_BWD_BF16X3"))
                                or bool(_env("GEOSSL_ARITH_24BIT")))
         T = torch.empty(L, P, F, dtype=torch.float32, device=dev) if keep_T else None
-        if live is not None and live_fwd:
-            # (the Wf rows of dead slots stay unwritten: every aggregation form drops them with a select)
-            call("geossl_cfconv_filter_fwd_rows", ptr(live.pair_d), ptr(live.pair_c), P, C.byref(fw), L, F, G,
-                 ptr(cfg["offset"]), cfg["coeff"], ptr(T), ptr(Wf), live.dyn_P, ptr(live.row_slot), st)
+        if graph.fwd_on_rows:
+            # Wf at the dense slot - what the aggregation walks address - and T at the list's row, which is what the
+            # weight-gradient kernel walks (the Wf rows of dead slots stay unwritten: every aggregation form drops them
+            # with a select)
+            r = graph.rows
+            call("geossl_cfconv_filter_fwd_rows", ptr(r.pair_d), ptr(r.pair_c), P, C.byref(fw), L, F, G,
+                 ptr(cfg["offset"]), cfg["coeff"], ptr(T), ptr(Wf), r.dyn_P, ptr(r.row_slot), st)
         elif P > 0:
-            call("geossl_cfconv_filter_fwd_dyn", ptr(pair_d), ptr(pair_c), P, C.byref(fw), L, F, G, ptr(cfg["offset"]),
-                 cfg["coeff"], ptr(T), ptr(Wf), dP2, st)
+            s = graph.slots
+            call("geossl_cfconv_filter_fwd_dyn", ptr(s.pair_d), ptr(s.pair_c), P, C.byref(fw), L, F, G, ptr(cfg["offset"]),
+                 cfg["coeff"], ptr(T), ptr(Wf), s.dyn_P, st)
         hs, xs, aggs, ts = [], [], [], []
-        heads = None
+        img_bwd = None
         if cfg["chain"]:
             # The row-local layers between two aggregations run as ONE launch each (geossl_linear_chain): conv.lin2 + act,
             # lin + residual and the next block's conv.lin1 (after the last block: the head).  Operand images of all
@@ -210,48 +208,24 @@ class _SchNetCore(torch.autograd.Function):
             if want_params and 2 * len(chain_w) <= _lib.PREPARE_MAX:  # the backward's images from the same launch
                 img, img_bwd = ops.prepare_chain(chain_w, both=True)
             else:
-                img, img_bwd = ops.prepare_chain(chain_w, transB=True), None
+                img = ops.prepare_chain(chain_w, transB=True)
             i_lin1, i_lin2, i_lin = img[0:3 * L:3], img[1:3 * L:3], img[2:3 * L:3]
             full = lambda: torch.empty(N, F, dtype=torch.float32, device=dev)
             hs, xs, aggs, ts = [h] + [full() for _ in range(L)], [full() for _ in range(L)], [full() for _ in range(L)], \
                 [full() for _ in range(L)]
             u, hout = full(), full()
-
-            def run_rows(a0, a1, mols, todo=None):
-                """the operations of the layer loop: launched one by one, or collected in `todo`"""
-                rows = lambda t_: t_[a0:a1]
-
-                def chain(x_, stages):
-                    if todo is not None:
-                        todo.append(("chain", x_, stages))
-                    else:
-                        ops.linear_chain(x_, stages, dyn_rows=dN2)
-
-                chain(rows(hs[0]), [dict(image=i_lin1[0], out=rows(xs[0]))])                           # conv.lin1   :189
-                for l, lp in enumerate(layers):
-                    if todo is not None:
-                        todo.append(("agg", xs[l], Wf[l], aggs[l], False))
-                    else:
-                        aggregate(xs[l], Wf[l], out=aggs[l], mols=mols)                                # propagate   :190
-                    stages = [dict(image=i_lin2[l], bias=lp[6], flags=_lib.EPI_SSP, out=rows(ts[l])),  # conv.lin2 + act
-                              dict(image=i_lin[l], bias=lp[8], res=rows(hs[l]), out=rows(hs[l + 1]))]  # lin + residual
-                    if l + 1 < L:
-                        stages.append(dict(image=i_lin1[l + 1], out=rows(xs[l + 1])))                  # next conv.lin1
-                    else:
-                        stages.append(dict(image=img[3 * L], bias=head[1], flags=_lib.EPI_SSP, out=rows(u)))  # :99-100
-                    chain(rows(aggs[l]), stages)
-                chain(rows(u), [dict(image=img[3 * L + 1], bias=head[3], out=rows(hout))])             # lin2        :101
-
-            # One launch for the whole loop where the shape allows (every block carries its molecules through all
-            # operations, ops.layer_loop), else 14 launches
-            # (the loop's aggregation walks dense pair slots: not on a sparse layout)
-            todo = [] if (cfg["loop"] and P > 0 and sp is None and 2 * L + 2 <= _lib.LOOP_MAX_OPS) else None
-            if todo is not None:
-                run_rows(0, N, None, todo)
-                if not ops.layer_loop(todo, lay, pair_flag, N, F, stagger=cfg["loop_stagger"]):
-                    todo = None
-            if todo is None:
-                run_rows(0, N, None)
+            todo = [("chain", hs[0], [dict(image=i_lin1[0], out=xs[0])])]                          # conv.lin1   :189
+            for l, lp in enumerate(layers):
+                todo.append(("agg", xs[l], Wf[l], aggs[l], False))                                 # propagate   :190
+                stages = [dict(image=i_lin2[l], bias=lp[6], flags=_lib.EPI_SSP, out=ts[l]),        # conv.lin2 + act
+                          dict(image=i_lin[l], bias=lp[8], res=hs[l], out=hs[l + 1])]              # lin + residual
+                if l + 1 < L:
+                    stages.append(dict(image=i_lin1[l + 1], out=xs[l + 1]))                        # next conv.lin1
+                else:
+                    stages.append(dict(image=img[3 * L], bias=head[1], flags=_lib.EPI_SSP, out=u))  # lin1 + act :99-100
+                todo.append(("chain", aggs[l], stages))
+            todo.append(("chain", u, [dict(image=img[3 * L + 1], bias=head[3], out=hout)]))        # lin2        :101
+            _run_ops(todo, graph, cfg, N, dN2)
             h = hs[L]
             hs = hs[:L]
             if not training:
@@ -264,7 +238,7 @@ class _SchNetCore(torch.autograd.Function):
                 layers = [lp[:4] + [pw[3 * l], pw[3 * l + 1], lp[6], pw[3 * l + 2], lp[8]] for l, lp in enumerate(layers)]
             for l, lp in enumerate(layers):
                 x = ops.linear(h, lp[4])                                    # conv.lin1 (no bias)   :189
-                agg = aggregate(x, Wf[l])                                   # propagate(add)        :190
+                agg = graph.aggregate(x, Wf[l])                             # propagate(add)        :190
                 t = ops.linear(agg, lp[5], bias=lp[6], flags=_lib.EPI_SSP)  # conv.lin2 + act       :191,165
                 hn = ops.linear(t, lp[7], bias=lp[8], res=h)                # lin + residual        :166,97
                 if training:
@@ -279,9 +253,8 @@ class _SchNetCore(torch.autograd.Function):
             ctx.want_params = want_params
             ctx.ps = ps
             ctx.params = params
-            ctx.saved = dict(pair_d=pair_d, pair_c=pair_c, pair_flag=pair_flag, Wf=Wf, T=T, hs=hs, xs=xs, aggs=aggs,
-                             ts=ts, h_last=h, u=u, img_bwd=img_bwd if cfg["chain"] else None, sparse=sp, live=live,
-                             live_T=live is not None and live_fwd)
+            ctx.graph = graph
+            ctx.saved = dict(Wf=Wf, T=T, hs=hs, xs=xs, aggs=aggs, ts=ts, h_last=h, u=u, img_bwd=img_bwd)
         return hout
 
     @staticmethod
@@ -293,7 +266,7 @@ class _SchNetCore(torch.autograd.Function):
             # first-order kernels, but as the outputs of a node that knows how to be differentiated
             # (geossl_amd/higher_order.py); evaluation loops that detach the force never pay for that.
             from ...higher_order import SchNetGradNode
-            if ctx.saved.get("sparse") is not None:
+            if ctx.graph.sparse:
                 raise NotImplementedError("second-order gradients (create_graph=True, training on forces) are limited to "
                                           "dense layouts: structures of at most 255 atoms, GEOSSL_SPARSE_PAIRS unset")
             dpos, grads = SchNetGradNode.run(ctx, dhout, want_pos, want_params)
@@ -304,7 +277,7 @@ class _SchNetCore(torch.autograd.Function):
     @staticmethod
     def fused_backward(ctx, dhout, want_pos, want_params, allow_direct):
         """First-order gradients by the fused kernels -> (dpos or None, [one entry per parameter, None = not returned])."""
-        cfg, lay, sv, ps = ctx.cfg, ctx.lay, ctx.saved, ctx.ps
+        cfg, lay, sv, ps, graph = ctx.cfg, ctx.lay, ctx.saved, ctx.ps, ctx.graph
         L, F, G = cfg["L"], cfg["F"], cfg["G"]
         dev = dhout.device
         N = dhout.size(0)
@@ -321,21 +294,13 @@ class _SchNetCore(torch.autograd.Function):
         g_layers = [grads[1 + 9 * l: 1 + 9 * (l + 1)] for l in range(L)]
         dh_out = dhout.contiguous()
         dyn = getattr(lay, "dyn", None)
-        dN2, dP2 = (dyn.n_atoms2, dyn.n_pairs2) if dyn is not None else (None, None)
-        sp = sv.get("sparse")  # the forward's pair list on a sparse layout (see forward)
-        if sp is not None:
-            dP2, pair_i, pair_j = sp.dyn_P, sp.pair_i, sp.pair_j
-            aggregate = lambda x_, W_, out=None, mols=None: ops.aggregate_sparse(x_, W_, sp, swap=True, out=out)
-        else:
-            pair_i, pair_j = lay.pair_i, lay.pair_j
-            aggregate = lambda x_, W_, out=None, mols=None: ops.aggregate(x_, W_, sv["pair_flag"], lay, swap=True,
-                                                                          out=out, mols=mols)
+        dN2 = dyn.n_atoms2 if dyn is not None else None
         probs = []  # (A = dY, B = X, dW, db)
         daggs = [None] * L
         if cfg["chain"]:
             # the same chains walked backwards: [head.lin2 + act', head.lin1], [lin_{L-1} + act', conv.lin2_{L-1}], then per
             # block  dX through conv.lin1_l (+ the residual branch), lin_{l-1} + act', conv.lin2_{l-1}
-            img = sv.get("img_bwd")  # converted with the forward's images (the weights have not changed since)
+            img = sv["img_bwd"]  # converted with the forward's images (the weights have not changed since)
             if img is None:
                 img = ops.prepare_chain([lp[k] for lp in layers for k in (4, 5, 7)] + [head[0], head[2]], transB=False)
             i_lin1, i_lin2, i_lin = img[0:3 * L:3], img[1:3 * L:3], img[2:3 * L:3]
@@ -344,38 +309,17 @@ class _SchNetCore(torch.autograd.Function):
             dhs = [full() for _ in range(L + 1)]      # dhs[l] = gradient at the input of block l (dhs[L]: at the head's input)
             dys, dxs = [full() for _ in range(L)], [full() for _ in range(L)]
             daggs = [full() for _ in range(L)]
-
-            def run_rows(a0, a1, mols, todo=None):
-                rows = lambda t_: t_[a0:a1]
-
-                def chain(x_, stages):
-                    if todo is not None:
-                        todo.append(("chain", x_, stages))
-                    else:
-                        ops.linear_chain(x_, stages, dyn_rows=dN2)
-
-                chain(rows(dh_out), [dict(image=img[3 * L + 1], tprev=rows(sv["u"]), out=rows(du)),
-                                     dict(image=img[3 * L], out=rows(dhs[L]))])
-                chain(rows(dhs[L]), [dict(image=i_lin[L - 1], tprev=rows(sv["ts"][L - 1]), out=rows(dys[L - 1])),
-                                     dict(image=i_lin2[L - 1], out=rows(daggs[L - 1]))])
-                for l in reversed(range(L)):
-                    if todo is not None:
-                        todo.append(("agg", daggs[l], sv["Wf"][l], dxs[l], True))
-                    else:
-                        aggregate(daggs[l], sv["Wf"][l], out=dxs[l], mols=mols)     # transposed graph
-                    stages = [dict(image=i_lin1[l], res=rows(dhs[l + 1]), out=rows(dhs[l]))]      # conv.lin1 + residual
-                    if l > 0:
-                        stages += [dict(image=i_lin[l - 1], tprev=rows(sv["ts"][l - 1]), out=rows(dys[l - 1])),
-                                   dict(image=i_lin2[l - 1], out=rows(daggs[l - 1]))]
-                    chain(rows(dxs[l]), stages)
-
-            todo = [] if (cfg["loop"] and lay.P > 0 and sp is None and 2 * L + 2 <= _lib.LOOP_MAX_OPS) else None
-            if todo is not None:
-                run_rows(0, N, None, todo)
-                if not ops.layer_loop(todo, lay, sv["pair_flag"], N, F, stagger=cfg["loop_stagger"]):
-                    todo = None
-            if todo is None:
-                run_rows(0, N, None)
+            todo = [("chain", dh_out, [dict(image=img[3 * L + 1], tprev=sv["u"], out=du), dict(image=img[3 * L], out=dhs[L])]),
+                    ("chain", dhs[L], [dict(image=i_lin[L - 1], tprev=sv["ts"][L - 1], out=dys[L - 1]),
+                                       dict(image=i_lin2[L - 1], out=daggs[L - 1])])]
+            for l in reversed(range(L)):
+                todo.append(("agg", daggs[l], sv["Wf"][l], dxs[l], True))                      # transposed graph
+                stages = [dict(image=i_lin1[l], res=dhs[l + 1], out=dhs[l])]                   # conv.lin1 + residual
+                if l > 0:
+                    stages += [dict(image=i_lin[l - 1], tprev=sv["ts"][l - 1], out=dys[l - 1]),
+                               dict(image=i_lin2[l - 1], out=daggs[l - 1])]
+                todo.append(("chain", dxs[l], stages))
+            _run_ops(todo, graph, cfg, N, dN2)
             probs.append((dh_out, sv["u"], g_head[2], g_head[3]))
             probs.append((du, sv["h_last"], g_head[0], g_head[1]))
             for l in reversed(range(L)):
@@ -396,7 +340,7 @@ class _SchNetCore(torch.autograd.Function):
                 w_lin1, w_lin2, w_lin = (pw[3 * l], pw[3 * l + 1], pw[3 * l + 2]) if pw is not None else (lp[4], lp[5], lp[7])
                 dy = ops.linear(dh, w_lin, transB=False, tprev=sv["ts"][l])        # through lin and act
                 dagg = ops.linear(dy, w_lin2, transB=False)                        # through conv.lin2
-                dx = aggregate(dagg, sv["Wf"][l])                                  # transposed graph
+                dx = graph.aggregate(dagg, sv["Wf"][l], swap=True)                 # transposed graph
                 dh_new = ops.linear(dx, w_lin1, transB=False, res=dh)              # through conv.lin1 + residual
                 probs.append((dh, sv["ts"][l], gl[7], gl[8]))
                 probs.append((dy, sv["aggs"][l], gl[5], gl[6]))
@@ -404,11 +348,8 @@ class _SchNetCore(torch.autograd.Function):
                 daggs[l] = dagg
                 dh = dh_new
         P = lay.P
-        fw = _lib.FilterWeights()
-        gin = _lib.FilterGradIn()
-        for l, lp in enumerate(layers):
-            fw.w1[l], fw.b1[l], fw.w2[l], fw.b2[l] = ptr(lp[0]), ptr(lp[1]), ptr(lp[2]), ptr(lp[3])
-            gin.x[l], gin.dagg[l] = ptr(sv["xs"][l]), ptr(daggs[l])
+        fw = _filter_weights(layers)
+        gin = _fill(_lib.FilterGradIn(), ("x", "dagg"), zip(sv["xs"], daggs))
         if want_params:
             # every atom-row weight gradient in one batched launch
             ops.linear_wgrad(probs, N, F, F, accumulate=bool(accum), dyn_rows=dN2)
@@ -418,28 +359,15 @@ class _SchNetCore(torch.autograd.Function):
             z = ctx.z
             call("geossl_embedding_bwd_dyn", ptr(z), z.stride(0) if z.numel() else 1, ptr(dh), emb_w.size(0), N, F,
                  ptr(g_emb), ptr(ws), accum, dN2, st)
-            # continuous-filter network weights, all blocks at once
+            # continuous-filter network weights, all blocks at once, over the graph's rows (T at those rows)
             if P > 0:
-                gout = _lib.FilterGradOut()
-                for l, gl in enumerate(g_layers):
-                    gout.dw1[l], gout.db1[l], gout.dw2[l], gout.db2[l] = ptr(gl[0]), ptr(gl[1]), ptr(gl[2]), ptr(gl[3])
+                gout = _fill(_lib.FilterGradOut(), ("dw1", "db1", "dw2", "db2"), g_layers)
                 nfl = _lib.load().geossl_cfconv_filter_bwd_workspace_floats(P, L, F, G)
                 ws2 = torch.empty(nfl, dtype=torch.float32, device=dev)
-                live = sv.get("live")  # the forward's live-pair list: its rows are the rows of T
-                if live is not None:
-                    T_rows = sv["T"]
-                    if T_rows is not None and not sv["live_T"]:  # stored per dense slot (a forward with position gradients)
-                        T_rows = torch.empty_like(T_rows)
-                        call("geossl_gather_live_rows", ptr(sv["T"]), ptr(live.row_slot), ptr(live.n_live), P, L, F,
-                             ptr(T_rows), st)
-                    call("geossl_cfconv_filter_bwd_dyn", ptr(live.pair_d), ptr(live.pair_c), ptr(live.pair_flag),
-                         ptr(live.pair_i), ptr(live.pair_j), P, N, C.byref(fw), C.byref(gin), L, F, G,
-                         ptr(cfg["offset"]), cfg["coeff"], ptr(T_rows), C.byref(gout), ptr(ws2), accum, live.dyn_P,
-                         dN2, st)
-                else:
-                    call("geossl_cfconv_filter_bwd_dyn", ptr(sv["pair_d"]), ptr(sv["pair_c"]), ptr(sv["pair_flag"]),
-                         ptr(pair_i), ptr(pair_j), P, N, C.byref(fw), C.byref(gin), L, F, G, ptr(cfg["offset"]),
-                         cfg["coeff"], ptr(sv["T"]), C.byref(gout), ptr(ws2), accum, dP2, dN2, st)
+                r = graph.rows
+                call("geossl_cfconv_filter_bwd_dyn", ptr(r.pair_d), ptr(r.pair_c), ptr(r.pair_flag), ptr(r.pair_i),
+                     ptr(r.pair_j), P, N, C.byref(fw), C.byref(gin), L, F, G, ptr(cfg["offset"]), cfg["coeff"],
+                     ptr(graph.T_for_rows(sv["T"])), C.byref(gout), ptr(ws2), accum, r.dyn_P, dN2, st)
             elif not direct:
                 for gl in g_layers:
                     for k in range(4):
@@ -451,14 +379,11 @@ class _SchNetCore(torch.autograd.Function):
             dpos = torch.zeros(N, 3, dtype=torch.float32, device=dev)
             if P > 0:
                 dd = torch.empty(L, P, dtype=torch.float32, device=dev)
-                call("geossl_cfconv_filter_dpos", ptr(sv["pair_d"]), ptr(sv["pair_c"]), ptr(sv["pair_flag"]),
-                     ptr(pair_i), ptr(pair_j), P, C.byref(fw), C.byref(gin), L, F, G, ptr(cfg["offset"]),
-                     cfg["coeff"], cfg["cutoff"], ptr(sv["T"]), ptr(sv["Wf"]), ptr(dd), st)
-                if sp is not None:   # (rows past the list's real count are never looked at: no incidence entry names one)
-                    ops.pair_position_grad_sparse(ctx.pos, sp, dd, out=dpos)
-                else:
-                    call("geossl_pair_position_grad", ptr(ctx.pos), ptr(sv["pair_d"]), ptr(dd), ptr(lay.mol_ptr),
-                         ptr(lay.pair_ptr), lay.B, P, L, ptr(dpos), st)
+                s = graph.slots
+                call("geossl_cfconv_filter_dpos", ptr(s.pair_d), ptr(s.pair_c), ptr(s.pair_flag), ptr(s.pair_i),
+                     ptr(s.pair_j), P, C.byref(fw), C.byref(gin), L, F, G, ptr(cfg["offset"]), cfg["coeff"],
+                     cfg["cutoff"], ptr(sv["T"]), ptr(sv["Wf"]), ptr(dd), st)
+                graph.position_grad(ctx.pos, dd, dpos)
         # ctx.saved stays: finetune_md17.py:46 differentiates with retain_graph=True and runs this node again
         if direct:
             return dpos, [None] * len(grads)

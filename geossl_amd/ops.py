@@ -3,6 +3,7 @@ stream).  Every function takes/returns CUDA tensors; nothing here computes on th
 import ctypes as C
 import math
 import os
+import types
 
 import numpy as np
 import torch
@@ -201,6 +202,71 @@ def pair_position_grad_sparse(pos, pairs, dd, out=None):
     call("geossl_pair_position_grad_sparse", ptr(pos), ptr(pairs.pair_d), ptr(dd), ptr(pairs.inc_ptr), ptr(pairs.inc_pair),
          ptr(pairs.inc_src), N, pairs.P, dd.size(0), ptr(out), stream())
     return out
+
+
+class PairGraph:
+    """The radius graph of one SchNet forward, whichever of its three forms it has (`pair_graph` decides):
+    ``slots``: the arrays addressed like Wf (pair_d, pair_c, pair_flag, pair_i, pair_j, dyn_P = device address of the
+    real row count or None) - the dense pair slots, or the SparsePairs of a sparse layout.  The filter forward runs on
+    them when it writes every row, filter_dpos always;
+    ``rows``: the arrays the filter weight-gradient launch walks - the LivePairs (with ``row_slot`` and dyn_P = n_live)
+    where a live-pair list was built, else ``slots`` itself;
+    ``fwd_on_rows``: the filter forward runs on ``rows`` through the row map (T compact, Wf per slot), not on ``slots``;
+    ``loop_flag``: the pair_flag the layer loop walks, None where it may not be used (dense layouts with pairs only)."""
+
+    __slots__ = ("layout", "sparse", "slots", "rows", "fwd_on_rows", "loop_flag")
+
+    def T_for_rows(self, T):
+        """T [L, P, F] as the forward stored it -> T at the rows of ``rows`` (regrouped if it was stored per slot)."""
+        if T is None or self.rows is self.slots or self.fwd_on_rows:
+            return T
+        out = torch.empty_like(T)
+        call("geossl_gather_live_rows", ptr(T), ptr(self.rows.row_slot), ptr(self.rows.n_live), T.size(1), T.size(0),
+             T.size(2), ptr(out), stream())
+        return out
+
+    def aggregate(self, x, Wf_l, swap=False, out=None):
+        if self.sparse:
+            return aggregate_sparse(x, Wf_l, self.slots, swap=swap, out=out)
+        return aggregate(x, Wf_l, self.slots.pair_flag, self.layout, swap=swap, out=out)
+
+    def position_grad(self, pos, dd, out):
+        """dd [L, P] (geossl_cfconv_filter_dpos on ``slots``) -> out [N, 3] (zeroed by the caller)."""
+        if self.sparse:   # (rows past the list's real count are never looked at: no incidence entry names one)
+            return pair_position_grad_sparse(pos, self.slots, dd, out=out)
+        lay = self.layout
+        call("geossl_pair_position_grad", ptr(pos), ptr(self.slots.pair_d), ptr(dd), ptr(lay.mol_ptr), ptr(lay.pair_ptr),
+             lay.B, lay.P, dd.size(0), ptr(out), stream())
+        return out
+
+
+def pair_graph(pos, layout, cutoff, want_rows, want_pos):
+    """-> PairGraph.  A SPARSE layout (a structure above 255 atoms, layout.want_sparse) gets the compacted list of the
+    pairs that carry an edge: P is then the list's capacity and its real row count stays on the device.  A dense layout
+    gets its pair slots, and - unless GEOSSL_LIVE_PAIRS=0 - the list of the slots that carry an edge (93 % of them in
+    QM9-sized molecules at 5 A, fewer in extended ones; `live_pairs`, one launch) for the filter network to run on: with
+    parameter gradients (want_rows) or without a position gradient (want_pos).  The position gradient reads T and Wf by
+    one index, so with it the forward keeps the dense rows and the backward regroups T (`T_for_rows`): the filter
+    weight gradients are then those of the path without it, bit for bit."""
+    g = PairGraph()
+    g.layout, g.sparse = layout, bool(getattr(layout, "sparse", False))
+    dyn = getattr(layout, "dyn", None)
+    if g.sparse:
+        if dyn is not None:
+            raise _lib.GeosslHipError("capacity buckets hold molecules of at most 255 atoms (bucket.MAX_N)")
+        g.slots = g.rows = sparse_pair_geometry(pos, layout, cutoff)
+        g.fwd_on_rows, g.loop_flag = False, None
+        return g
+    use_live = layout.P > 0 and live_pairs_enabled() and (want_rows or not want_pos)
+    mol_live = torch.empty(layout.B, dtype=torch.int32, device=pos.device) if use_live else None
+    pair_d, pair_c, pair_flag = pair_geometry(pos, layout, cutoff, mol_live=mol_live)
+    g.slots = g.rows = types.SimpleNamespace(pair_d=pair_d, pair_c=pair_c, pair_flag=pair_flag, pair_i=layout.pair_i,
+                                             pair_j=layout.pair_j, dyn_P=_dyn(dyn, "n_pairs2"))
+    if use_live:
+        g.rows = live_pairs(pair_d, pair_c, pair_flag, layout, mol_live, cutoff)
+    g.fwd_on_rows = use_live and not want_pos
+    g.loop_flag = pair_flag if layout.P > 0 else None
+    return g
 
 
 def gaussian_smearing(dist, offset, coeff):
@@ -402,6 +468,15 @@ def layer_loop(ops_list, layout, pair_flag, N, F, stagger=0):
     return True
 
 
+def launch_ops(ops_list, graph, dyn_rows=None):
+    """The operations of `ops_list` (see layer_loop) as one launch each; the aggregations over `graph` (a PairGraph)."""
+    for op in ops_list:
+        if op[0] == "chain":
+            linear_chain(op[1], op[2], dyn_rows=dyn_rows)
+        else:
+            graph.aggregate(op[1], op[2], swap=op[4], out=op[3])
+
+
 def linear_wgrad(problems, R, M, N, accumulate=False, lda=None, ldb=None, ldw=None, dyn_rows=None):
     """Batched weight gradients.  problems: list of (A [R,M], B [R,N], dW [M,N], db [M] or None); lda/ldb/ldw are
     the row strides when A / B / dW are column slices of wider tensors."""
@@ -418,15 +493,13 @@ def linear_wgrad(problems, R, M, N, accumulate=False, lda=None, ldb=None, ldw=No
              dyn_rows, stream())
 
 
-def aggregate(x, Wf_l, pair_flag, layout, swap=False, out=None, mols=None):
-    """x, out: full [N, F] tensors (rows are addressed by global atom index).  mols = (m0, m1, order): only molecules
-    m0 .. m1-1 are processed (their rows of `out` written), started in the sequence `order` (int32 global molecule ids,
-    or None for m0, m0+1, ...): independent sections of a batch can then run on different streams."""
+def aggregate(x, Wf_l, pair_flag, layout, swap=False, out=None):
+    """x, out: full [N, F] tensors (rows are addressed by global atom index)."""
     N, F = x.shape
     if out is None:
         out = torch.empty_like(x)
     work = getattr(layout, "agg_work", None)
-    if mols is None and work is not None and 32 < F <= 128:
+    if work is not None and 32 < F <= 128:
         call("geossl_cfconv_aggregate_targets_dyn" if getattr(layout, "agg_targets", False)
              else "geossl_cfconv_aggregate_work_dyn", ptr(x), ptr(Wf_l), ptr(pair_flag), ptr(layout.mol_ptr),
              ptr(layout.pair_ptr), ptr(work), work.numel(), layout.max_n, F, 1 if swap else 0, ptr(out),
@@ -434,17 +507,8 @@ def aggregate(x, Wf_l, pair_flag, layout, swap=False, out=None, mols=None):
         return out
     if getattr(layout, "dyn", None) is not None:
         raise _lib.GeosslHipError("a capacity-bucket layout needs the work-list aggregation (64 or 128 features)")
-    if mols is None:
-        mp, pp, order, B = ptr(layout.mol_ptr), ptr(layout.pair_ptr), layout.order, layout.B
-    else:
-        m0, m1, order = mols
-        B = m1 - m0
-        if order is not None:  # ids are global: the pointer arrays stay whole
-            mp, pp = ptr(layout.mol_ptr), ptr(layout.pair_ptr)
-        else:                  # molecule blockIdx.x of the launch is m0 + blockIdx.x: shift the (int32) pointer arrays
-            mp, pp = ptr(layout.mol_ptr) + 4 * m0, ptr(layout.pair_ptr) + 4 * m0
-    call("geossl_cfconv_aggregate", ptr(x), ptr(Wf_l), ptr(pair_flag), mp, pp, ptr(order), B, layout.max_n, F,
-         1 if swap else 0, ptr(out), stream())
+    call("geossl_cfconv_aggregate", ptr(x), ptr(Wf_l), ptr(pair_flag), ptr(layout.mol_ptr), ptr(layout.pair_ptr),
+         ptr(layout.order), layout.B, layout.max_n, F, 1 if swap else 0, ptr(out), stream())
     return out
 
 

@@ -437,6 +437,7 @@ def test_fused_schnet_at_the_new_gaussian_counts_vs_fp64_oracle(F, G, cutoff, mo
     forces against oracle.nets.schnet_forward in fp64, on the fused kernels."""
     import geossl_amd.Geom3D.models.schnet as sm
     from conftest import assert_close, rel_err
+    from geossl_amd import ops
     from helpers import product_schnet, schnet_oracle_params, t, unique_named_grads
     from oracle import nets
     from oracle.graph import radius_graph_np
@@ -455,6 +456,7 @@ def test_fused_schnet_at_the_new_gaussian_counts_vs_fp64_oracle(F, G, cutoff, mo
         return real_call(name, *args)
 
     monkeypatch.setattr(sm, "call", spy)
+    monkeypatch.setattr(ops, "call", spy)   # (the position scatter is launched by the forward's ops.PairGraph)
     model = product_schnet(cfg, DEV)
     w = torch.cos(torch.arange(F, dtype=torch.float64))
     pos = t(b["positions"], DEV).requires_grad_(True)

@@ -547,6 +547,7 @@ def test_position_gradient_path_forms_the_filter_gradients_of_the_live_path(monk
     backward regroups T to the list's rows (geossl_gather_live_rows) and runs the weight-gradient kernel on the list:
     every parameter gradient is the one of the path without the position gradient, bit for bit."""
     import geossl_amd.Geom3D.models.schnet as sm
+    from geossl_amd import ops
     from helpers import product_schnet, t, unique_named_grads
     monkeypatch.setenv("GEOSSL_LIVE_PAIRS", "1")
     b = _model_batch()
@@ -554,7 +555,8 @@ def test_position_gradient_path_forms_the_filter_gradients_of_the_live_path(monk
                readout="add")
     names = []
     real_call = sm.call
-    monkeypatch.setattr(sm, "call", lambda name, *a: (names.append(name), real_call(name, *a))[1])
+    for mod in (sm, ops):   # (the regrouping is launched by the forward's ops.PairGraph)
+        monkeypatch.setattr(mod, "call", lambda name, *a: (names.append(name), real_call(name, *a))[1])
     model = product_schnet(cfg, DEV)
     w = torch.cos(torch.arange(128, dtype=torch.float32, device=DEV))
     grads = {}

@@ -31,7 +31,11 @@ def chain(a0, a1):
 
 
 def agg(m0, m1):
-    ops.aggregate(X, Wf, flag, lay, out=agg_out, mols=None if (m0, m1) == (0, B) else (m0, m1, None))
+    if (m0, m1) == (0, B):
+        return ops.aggregate(X, Wf, flag, lay, out=agg_out)
+    # molecules m0 .. m1-1 only: molecule blockIdx.x of the launch is m0 + blockIdx.x - shift the (int32) pointer arrays
+    _lib.call("geossl_cfconv_aggregate", X.data_ptr(), Wf.data_ptr(), flag.data_ptr(), lay.mol_ptr.data_ptr() + 4 * m0,
+              lay.pair_ptr.data_ptr() + 4 * m0, None, m1 - m0, lay.max_n, F, 0, agg_out.data_ptr(), _lib.stream())
 
 
 side = torch.cuda.Stream()
