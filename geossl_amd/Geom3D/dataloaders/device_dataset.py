@@ -28,7 +28,9 @@ step at the reference's batch size).  Here the molecules are uploaded once:
   ``masking``) over the dataset's bond graph, kept lists drawn on the device (``mask_rng="device"``) or by the
   reference's own np.random draws on the host (``"numpy"``).  A masked handle carries the kept sizes; its gather is
   ``geossl_gather_masked_molecules``.  With radius edges the survivor count depends on the draw: collating such a
-  handle takes a count launch and a read-back of B counts before the gather.
+  handle takes a count launch and a read-back of B counts before the gather; a PaiNN capacity bucket (``bucket.Bucket.
+  fill``) keeps the counts on the device instead (``geossl_masked_edge_offsets``) and is sized by the handle's host-side
+  bound ``n_edges_bound``.
 """
 import ctypes as C
 
@@ -470,7 +472,8 @@ class DatasetBatch:
     """``batch_size`` molecules of a ``DeviceDataset`` by id: what the loader hands to a step.  Host side only - ids,
     sizes, counts; the collated tensors exist once somebody asks for them.  `mask` (masking.MaskDraw): a masked batch
     - its sizes are the kept counts, the original ones are ``_src_n``; the radius edges of a masked batch are counted
-    when it is collated (``n_edges`` is None until then)."""
+    when it is collated (``n_edges`` is None until then; ``n_edges_bound`` is an upper bound known on the host, which is
+    what a PaiNN capacity bucket is sized by - its fill counts the survivors on the device and reads nothing back)."""
 
     def __init__(self, dataset, ids, mask=None):
         self._dataset = dataset
@@ -499,6 +502,12 @@ class DatasetBatch:
         P = int(dataset.pairs[self.ids].sum()) if mask is None else int((self._sizes * (self._sizes - 1) // 2).sum())
         self.n_super = P if dataset.option == "combination" else 2 * P
         self.n_edges = int(dataset.edge_cnt[self.ids].sum()) if dataset.edges is not None and mask is None else None
+        # what a capacity is sized by: the edge count, or - masked - a host-side upper bound on the survivors (a molecule
+        # keeps at most the edges it has and at most the k (k - 1) ordered pairs of its k kept atoms); None without edges
+        self.n_edges_bound = self.n_edges
+        if dataset.edges is not None and mask is not None:
+            k = self._sizes
+            self.n_edges_bound = int(np.minimum(dataset.edge_cnt[self.ids], k * (k - 1)).sum())
         self._batch = None
 
     def materialize(self):

@@ -216,6 +216,7 @@ PROTOTYPES = {
     # PaiNN on a capacity bucket
     "geossl_painn_group_capacity": (i64, [i64, i64]),
     "geossl_painn_edge_layout": (i32, [vp, vp, i64, vp, i64, i64, i64] + [vp] * 12),
+    "geossl_painn_edge_layout_dyn": (i32, [vp, vp, i64, vp, vp, i64, i64, i64] + [vp] * 12),
     "geossl_painn_edge_geom_dyn": (i32, [vp, vp, vp, i64, f32, vp, vp, i32, vp, vp, vp, vp, vp]),
     "geossl_painn_interaction_fwd_mma_dyn": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i64, i32,
                                                    i32, vp, vp, vp, vp]),
@@ -238,6 +239,7 @@ PROTOTYPES = {
     "geossl_painn_mix_pre_bwd_dyn": (i32, [vp, vp, vp, vp, i64, i32, vp, vp, vp, vp]),
     "geossl_gather_molecules": (i32, [P(Gather), i64, vp]),
     "geossl_gather_masked_molecules": (i32, [P(Gather), P(Mask), i64, vp]),
+    "geossl_masked_edge_offsets": (i32, [vp, i64, i64, i32, vp, vp, vp, vp]),
     # contrastive heads (csrc/contrastive.hip)
     "geossl_infonce_fwd": (i32, [vp, vp, i64, i32, f32, vp, vp, vp, vp, vp]),
     "geossl_infonce_bwd": (i32, [vp, vp, vp, vp, i64, i32, f32, vp, vp, vp, vp]),

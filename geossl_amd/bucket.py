@@ -24,7 +24,7 @@ import ctypes as C
 
 import numpy as np
 import torch
-from .switches import env as _env
+from .switches import env as _env, masked_painn_buckets
 
 from . import _lib
 from ._lib import call, ptr, stream
@@ -170,14 +170,24 @@ def eligible(batch, model_3d, normalize=False):
     if lo < 1 or hi > MAX_N or hi < 2:
         return False
     if getattr(batch, "_dataset", None) is not None:   # a handle on a device-resident dataset: gathered by the fill itself
-        # (a masked PaiNN handle: its edge count is drawn - it runs on its collated tensors)
-        return model_3d != "painn" or (batch.n_edges is not None and getattr(batch, "_mask", None) is None)
+        if model_3d != "painn":
+            return True
+        if getattr(batch, "_mask", None) is None:
+            return batch.n_edges is not None
+        # a masked PaiNN handle: its edge count is drawn - the fill counts the survivors on the device and the bucket is
+        # sized by the handle's host-side bound (GEOSSL_MASKED_PAINN_BUCKETS=0: it runs on its collated tensors)
+        return masked_painn_buckets() and getattr(batch, "n_edges_bound", None) is not None
     if model_3d == "painn":
         rei = getattr(batch, "radius_edge_index", None)
         if (rei is None or not rei.is_cuda or rei.dtype != torch.long or rei.dim() != 2 or rei.size(0) != 2
                 or rei.stride(1) != 1):
             return False
     return tensors_ok(batch)
+
+
+def handle_edges(batch):
+    """Edges of a dataset handle as far as the host knows them: the count, or - a masked handle - an upper bound."""
+    return batch.n_edges_bound if getattr(batch, "_mask", None) is not None else batch.n_edges
 
 
 def triple_tensors_ok(batch):
@@ -377,7 +387,8 @@ def host_plan(sizes, option, views=2):
 class Bucket:
     """kind "schnet": pair-slot structures of the two-view batch (pointer arrays and work list from the host, pair-slot
     atoms by geossl_pair_index_fill).  kind "painn": the structures of the batch's radius_edge_index for the two-view batch
-    (geossl_painn_edge_layout: one launch on the batch's own edge tensor, outputs at the edge capacity E_cap).
+    (geossl_painn_edge_layout: one launch on the batch's own edge tensor, outputs at the edge capacity E_cap; a masked
+    handle's edge count stays on the device: geossl_painn_edge_layout_dyn).
 
     views = 1 (a step with no second view: Distance Prediction): the backbone's layout `lay2` and the counts in `dims`
     describe view 0 alone - B molecules, its aggregation work list, its pair slots and edges.  The gather and the PaiNN
@@ -477,6 +488,11 @@ class Bucket:
             self.el_status = _lib.StatusWord(device, "radius_edge_index must be grouped by molecule in batch order with both "
                                              "ends in the same molecule (collated MoleculeDataset3DRadius output is)")
             el.status = self.el_status.word
+            # set by geossl_masked_edge_offsets when a masked batch's surviving edges exceed E_cap (the capacity comes
+            # from a host-side upper bound: it cannot happen)
+            self.ecap_status = _lib.StatusWord(device, "a masked batch kept more radius edges than its bucket's edge "
+                                               "capacity (the handle's n_edges_bound is not an upper bound)")
+            self._keep, self._e_cnt = None, None   # the count launch's kept lists / survivor counts (first masked fill)
             el.dyn = self.dyn
             self.el = el
             self.e2 = torch.zeros(2, 1, **i64)   # placeholder for PaiNN.forward's radius_edge_index argument
@@ -517,8 +533,11 @@ class Bucket:
         device, or a handle on a device-resident dataset (Geom3D.dataloaders.DatasetBatch) whose molecules are gathered
         from there.  One pinned upload (everything that is a function of the molecule sizes) + one launch
         (geossl_gather_molecules: atom rows, batch vector, super-edges, pair-slot atoms, incidence lists, radius edges,
-        the cleared buffer) [+ geossl_painn_edge_layout].  A masked handle (SchNet only) adds the small upload of its
-        mask and launches geossl_gather_masked_molecules instead: the BFS and the gather are that one launch."""
+        the cleared buffer) [+ geossl_painn_edge_layout].  A masked handle adds the small upload of its mask and
+        launches geossl_gather_masked_molecules instead: the BFS and the gather are that one launch.  A masked PaiNN
+        handle is four launches - count (BFS + survivors per molecule), geossl_masked_edge_offsets (e_ptr and
+        dims[D_E2] on the device), gather, geossl_painn_edge_layout_dyn - and nothing is read back: the host only
+        checks the handle's upper bound on the edges against E_cap."""
         global _PARTS
         if _PARTS is None:
             _PARTS = _parts_table()
@@ -538,9 +557,9 @@ class Bucket:
                     or ds.device != self.x.device):
                 raise ValueError("dataset and bucket disagree (tuple option, x columns or device)")
             if self.kind == "painn":
-                if batch.n_edges is None:
+                if ds.edges is None:
                     raise ValueError("PaiNN bucket fill expects a dataset built with radius=...")
-                E = batch.n_edges
+                E = handle_edges(batch)   # (masked: an upper bound for the capacity check - the count is the device's)
         elif self.kind == "painn":
             rei = batch.radius_edge_index
             if (rei is None or not rei.is_cuda or rei.dtype != torch.long or rei.dim() != 2 or rei.size(0) != 2
@@ -559,7 +578,9 @@ class Bucket:
         hp = host_plan(n, self.option, self.views)
         Wr = hp["work"].size          # (the list's real length: 8 queues; <= the bound W the capacity was checked with)
         V = self.views
-        h[0:8] = (N, V * N, V * P, S, Wr, B, 3 * V * N, V * E)
+        masked_edges = ds is not None and self.kind == "painn" and getattr(batch, "_mask", None) is not None
+        # (masked PaiNN: dims[D_E2] and e_ptr are written by geossl_masked_edge_offsets, behind this upload on the stream)
+        h[0:8] = (N, V * N, V * P, S, Wr, B, 3 * V * N, 0 if masked_edges else V * E)
         if triples:
             h[D_T] = T
             if ds is not None:
@@ -587,8 +608,9 @@ class Bucket:
             if self.kind == "painn":
                 h[o["e_src_off"]:o["e_src_off"] + B] = ds.edge_off[batch.ids]
                 ep = h[o["e_ptr"]:o["e_ptr"] + B + 1]
-                ep[0] = 0
-                np.cumsum(ds.edge_cnt[batch.ids], out=ep[1:])
+                ep[:] = 0
+                if not masked_edges:
+                    np.cumsum(ds.edge_cnt[batch.ids], out=ep[1:])
         self.blob.copy_(slot[0], non_blocking=True)
         slot[1] = torch.cuda.Event()
         slot[1].record()
@@ -613,7 +635,7 @@ class Bucket:
             if self.rei is None:
                 self.rei = torch.zeros(2, max(self.E_cap, 1), dtype=torch.int64, device=self.device)
             rei = self.rei
-            if E:
+            if ds.edges.size(1) if masked_edges else E:   # (masked: whether any edge survives is the device's to know)
                 g.e0_src, g.e1_src = ptr(ds.edges[0]), ptr(ds.edges[1])
                 g.e_src_off, g.e_ptr = base + 4 * o["e_src_off"], base + 4 * o["e_ptr"]
                 g.e0_dst, g.e1_dst = ptr(rei[0]), ptr(rei[1])
@@ -622,9 +644,23 @@ class Bucket:
         st_ = stream()
         if ds is not None and getattr(batch, "_mask", None) is not None:
             # a masked handle (DeviceLoader(mask_ratio=...)): the kept atoms are drawn (or read) by the same launch
-            if self.kind == "painn":
-                raise ValueError("a masked PaiNN batch has a drawn edge count: it runs on its collated tensors")
-            m, mblob = ds.mask_plan(batch)
+            m, mblob = ds.mask_plan(batch, with_edges=masked_edges)
+            if masked_edges:
+                # count launch (kept lists + survivors per molecule), then their offsets and the batch's edge count made
+                # on the device: the gather below reads e_ptr, the layout and the captured step the counts, from there
+                if self._keep is None:
+                    self._keep = torch.zeros(max(self.N_cap, 1), dtype=torch.int32, device=self.device)
+                    self._e_cnt = torch.zeros(B, dtype=torch.int32, device=self.device)
+                try:
+                    self.ecap_status.poll()
+                except IndexError as e:
+                    raise ValueError(str(e)) from None
+                m.keep_out, m.e_count = ptr(self._keep), ptr(self._e_cnt)
+                call("geossl_gather_masked_molecules", C.byref(g), C.byref(m), B, st_)
+                call("geossl_masked_edge_offsets", ptr(self._e_cnt), B, self.E_cap, V, base + 4 * o["e_ptr"],
+                     self.dyn.n_edges2, ptr(self.ecap_status.word), st_)
+                self.ecap_status.arm(every=8)
+                m.keep_out, m.e_count, m.keep_in = None, None, ptr(self._keep)
             call("geossl_gather_masked_molecules", C.byref(g), C.byref(m), B, st_)
             del mblob
         else:
@@ -644,11 +680,15 @@ class Bucket:
                 self.el_status.poll()
             except IndexError as e:
                 raise ValueError(str(e)) from None
-            call("geossl_painn_edge_layout", ptr(rei[0]), ptr(rei[1]), E, ptr(lay.mol_ptr), N, B, 2 * self.N_cap,
-                 ptr(el.idx_i), ptr(el.idx_j), ptr(el.inc["i"][0]), ptr(el.inc["i"][1]), ptr(el.inc["j"][0]),
-                 ptr(el.inc["j"][1]), ptr(el.row_edge), ptr(el.grp_atom), ptr(el.mol_grp), ptr(el.mol_grp_end),
-                 ptr(el.status), st_)
+            outs = (ptr(el.idx_i), ptr(el.idx_j), ptr(el.inc["i"][0]), ptr(el.inc["i"][1]), ptr(el.inc["j"][0]),
+                    ptr(el.inc["j"][1]), ptr(el.row_edge), ptr(el.grp_atom), ptr(el.mol_grp), ptr(el.mol_grp_end),
+                    ptr(el.status), st_)
+            if masked_edges:   # (E = e_ptr[B], in device memory)
+                call("geossl_painn_edge_layout_dyn", ptr(rei[0]), ptr(rei[1]), self.E_cap, base + 4 * (o["e_ptr"] + B),
+                     ptr(lay.mol_ptr), N, B, 2 * self.N_cap, *outs)
+            else:
+                call("geossl_painn_edge_layout", ptr(rei[0]), ptr(rei[1]), E, ptr(lay.mol_ptr), N, B, 2 * self.N_cap, *outs)
             self.el_status.arm(every=8)
         self.real = (N, P, S, W)
-        self.real_E = E
+        self.real_E = None if masked_edges else E   # (a masked PaiNN fill: only the device knows; blob[e_ptr + B])
         return self.real

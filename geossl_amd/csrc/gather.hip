@@ -345,6 +345,47 @@ __global__ __launch_bounds__(GATHER_THREADS) void k_gather_masked(GeosslGather g
   }
 }
 
+// ---- edge offsets of a masked batch on the device: the exclusive prefix of the count launch's survivors per molecule.
+// One block; B is scanned in chunks of the block's threads with a carry.  Every offset is clamped to E_cap (the gather
+// and the edge layout behind this launch never leave the capacity-sized buffers) and the status word reports a total
+// above it - the caller sizes E_cap from a host-side upper bound, so that is a guard and not a path.
+__global__ __launch_bounds__(GATHER_THREADS) void k_masked_edge_offsets(const int32_t* __restrict__ e_count, int B,
+                                                                         int E_cap, int views, int32_t* __restrict__ e_ptr,
+                                                                         int32_t* __restrict__ dyn_E2,
+                                                                         int32_t* __restrict__ status) {
+  __shared__ long long part[GATHER_THREADS];
+  const int tid = threadIdx.x;
+  long long carry = 0;
+  bool bad = false;
+  for (int i0 = 0; i0 < B; i0 += GATHER_THREADS) {
+    const int i = i0 + tid;
+    int c = i < B ? e_count[i] : 0;
+    if (c < 0) {   // (a molecule the count launch skipped leaves what was there)
+      c = 0;
+      bad = true;
+    }
+    part[tid] = c;
+    __syncthreads();
+    for (int o = 1; o < GATHER_THREADS; o <<= 1) {   // inclusive Hillis-Steele scan
+      const long long a = tid >= o ? part[tid - o] : 0;
+      __syncthreads();
+      part[tid] += a;
+      __syncthreads();
+    }
+    const long long incl = carry + part[tid];
+    if (i < B) e_ptr[i + 1] = (int32_t)(incl < (long long)E_cap ? incl : (long long)E_cap);
+    carry += part[GATHER_THREADS - 1];
+    __syncthreads();   // (part is rewritten by the next chunk)
+  }
+  if (tid == 0) {
+    const long long E = carry < (long long)E_cap ? carry : (long long)E_cap;
+    e_ptr[0] = 0;
+    *dyn_E2 = (int32_t)(views * E);
+    if (carry > (long long)E_cap) bad = true;
+  }
+  if (bad && status != nullptr) *status = 1;
+}
+
 }  // namespace
 
 extern "C" int geossl_gather_molecules(const GeosslGather* g, int64_t B, hipStream_t stream) {
@@ -409,6 +450,17 @@ extern "C" int geossl_gather_masked_molecules(const GeosslGather* g, const Geoss
     zero_blocks = (int)(want < 1 ? 1 : (want > 256 ? 256 : want));
   }
   hipLaunchKernelGGL(k_gather_masked, dim3((unsigned)(B + zero_blocks)), dim3(GATHER_THREADS), 0, stream, *g, *mk, (int)B);
+  GEOSSL_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int geossl_masked_edge_offsets(const int32_t* e_count, int64_t B, int64_t E_cap, int views, int32_t* e_ptr,
+                                          int32_t* dyn_E2, int32_t* status, hipStream_t stream) {
+  if (B <= 0 || B > (1 << 24) || e_count == nullptr || e_ptr == nullptr || dyn_E2 == nullptr || E_cap < 0 ||
+      2 * E_cap >= ((int64_t)1 << 30) || (views != 1 && views != 2))
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_masked_edge_offsets, dim3(1), dim3(GATHER_THREADS), 0, stream, e_count, (int)B, (int)E_cap, views,
+                     e_ptr, dyn_E2, status);
   GEOSSL_CHECK_LAUNCH();
   return 0;
 }

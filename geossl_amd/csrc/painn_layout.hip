@@ -18,6 +18,8 @@
 //     to groups of four rows; the groups of molecule m start at floor(first edge / 4) + first atom (a bound on the
 //     groups of all molecules before it, so no scan over molecules is needed) and END at mol_grp_end[m].
 // Integer work only; bit-reproducible.
+// geossl_painn_edge_layout_dyn is the same launch with the edge count E read from device memory (a masked batch of a
+// device-resident dataset: its surviving edges are counted on the device, gather.hip); the outputs hold E_cap edges.
 #include "common.h"
 #include "geossl_hip.h"
 
@@ -43,6 +45,7 @@ struct PainnLayoutArgs {
   int32_t* mol_grp;       // [2B + 1]
   int32_t* mol_grp_end;   // [2B]
   int32_t* status;        // set to 1 on an edge that leaves its molecule / a molecule above PL_MAXN atoms
+  const int32_t* dyn_E;   // the `_dyn` entry point: the edge count in device memory (E above: the capacity it is clamped to)
 };
 
 // first e in [0, E) with src[e] >= key (src non-decreasing by molecule), for TWO keys at once, by all 256 threads of the
@@ -86,23 +89,33 @@ __device__ __forceinline__ void block_lower_bound2(const int64_t* __restrict__ s
   out1 = lo[1];
 }
 
+// DYN: the edge count is read from device memory (a masked batch: the survivors are counted on the device) - a value
+// uniform over the grid, clamped to [0, A.E] (the capacity of the outputs) with the status word set when it was not
+// inside; everything below is the one body of both entry points.
+template <bool DYN>
 __global__ __launch_bounds__(256) void k_painn_edge_layout(PainnLayoutArgs A) {
   __shared__ int cnt[2][4][PL_MAXN];   // [side][wave][atom]: edges of the wave's quarter; then the quarter's first list slot
   __shared__ int pre_i[PL_MAXN], pre_j[PL_MAXN], pre_g[PL_MAXN];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int m = blockIdx.x;
   const int a0 = A.mol_ptr[m], n = A.mol_ptr[m + 1] - a0;
+  int E = A.E;
+  if (DYN) {
+    const int got = *A.dyn_E;
+    E = min(max(got, 0), A.E);
+    if (E != got && tid == 0) *A.status = 1;
+  }
   int e0, e1;
-  block_lower_bound2(A.src_i, A.E, (int64_t)a0, (int64_t)a0 + n, e0, e1);
+  block_lower_bound2(A.src_i, E, (int64_t)a0, (int64_t)a0 + n, e0, e1);
   const bool too_big = n > PL_MAXN;
   if (too_big && tid == 0) *A.status = 1;
   // The molecules' ranges [e0, e1) share their ends (the same key, the same search), so they tile [e0 of the first, e1 of
   // the last): an edge list that is not grouped by molecule in batch order leaves edges in front of or behind that span -
   // visited by no block, their slots would keep the previous step's data - or inside a wrong molecule's
   // range (caught below).
-  if (tid == 0 && ((m == 0 && e0 != 0) || (m == (int)gridDim.x - 1 && e1 != A.E))) *A.status = 1;
+  if (tid == 0 && ((m == 0 && e0 != 0) || (m == (int)gridDim.x - 1 && e1 != E))) *A.status = 1;
   const int nn = too_big ? 0 : n;  // (a molecule above the limit gets empty lists; the status word reports it)
-  const int N = A.N, E = A.E;
+  const int N = A.N;
   for (int i = tid; i < 2 * 4 * PL_MAXN; i += 256) (&cnt[0][0][0])[i] = 0;
   __syncthreads();
   // the wave's quarter of the molecule's edges
@@ -257,18 +270,45 @@ __global__ __launch_bounds__(256) void k_painn_edge_layout(PainnLayoutArgs A) {
 
 extern "C" int64_t geossl_painn_group_capacity(int64_t E2, int64_t N2) { return E2 / 4 + N2 + 1; }
 
-extern "C" int geossl_painn_edge_layout(const int64_t* src_i, const int64_t* src_j, int64_t E, const int32_t* mol_ptr,
-                                        int64_t N, int64_t B, int64_t N2cap, int64_t* idx_i2, int64_t* idx_j2,
-                                        int64_t* iptr_i, int32_t* ilist_i, int64_t* iptr_j, int32_t* ilist_j,
-                                        int32_t* row_edge, int32_t* grp_atom, int32_t* mol_grp, int32_t* mol_grp_end,
-                                        int32_t* status, hipStream_t stream) {
+namespace {
+
+int launch_edge_layout(const int64_t* src_i, const int64_t* src_j, int64_t E, const int32_t* dyn_E, const int32_t* mol_ptr,
+                       int64_t N, int64_t B, int64_t N2cap, int64_t* idx_i2, int64_t* idx_j2, int64_t* iptr_i,
+                       int32_t* ilist_i, int64_t* iptr_j, int32_t* ilist_j, int32_t* row_edge, int32_t* grp_atom,
+                       int32_t* mol_grp, int32_t* mol_grp_end, int32_t* status, hipStream_t stream) {
   if (B <= 0) return 0;
   if (2 * E >= ((int64_t)1 << 30) || 2 * N >= ((int64_t)1 << 30) || N2cap < 2 * N) return (int)hipErrorInvalidValue;
   PainnLayoutArgs A{};
   A.src_i = src_i; A.src_j = src_j; A.mol_ptr = mol_ptr; A.E = (int)E; A.N = (int)N; A.B = (int)B; A.N2cap = (int)N2cap;
   A.idx_i2 = idx_i2; A.idx_j2 = idx_j2; A.iptr_i = iptr_i; A.ilist_i = ilist_i; A.iptr_j = iptr_j; A.ilist_j = ilist_j;
   A.row_edge = row_edge; A.grp_atom = grp_atom; A.mol_grp = mol_grp; A.mol_grp_end = mol_grp_end; A.status = status;
-  hipLaunchKernelGGL(k_painn_edge_layout, dim3((unsigned)B), dim3(256), 0, stream, A);
+  A.dyn_E = dyn_E;
+  if (dyn_E != nullptr)
+    hipLaunchKernelGGL(k_painn_edge_layout<true>, dim3((unsigned)B), dim3(256), 0, stream, A);
+  else
+    hipLaunchKernelGGL(k_painn_edge_layout<false>, dim3((unsigned)B), dim3(256), 0, stream, A);
   GEOSSL_CHECK_LAUNCH();
   return 0;
+}
+
+}  // namespace
+
+extern "C" int geossl_painn_edge_layout(const int64_t* src_i, const int64_t* src_j, int64_t E, const int32_t* mol_ptr,
+                                        int64_t N, int64_t B, int64_t N2cap, int64_t* idx_i2, int64_t* idx_j2,
+                                        int64_t* iptr_i, int32_t* ilist_i, int64_t* iptr_j, int32_t* ilist_j,
+                                        int32_t* row_edge, int32_t* grp_atom, int32_t* mol_grp, int32_t* mol_grp_end,
+                                        int32_t* status, hipStream_t stream) {
+  return launch_edge_layout(src_i, src_j, E, nullptr, mol_ptr, N, B, N2cap, idx_i2, idx_j2, iptr_i, ilist_i, iptr_j,
+                            ilist_j, row_edge, grp_atom, mol_grp, mol_grp_end, status, stream);
+}
+
+extern "C" int geossl_painn_edge_layout_dyn(const int64_t* src_i, const int64_t* src_j, int64_t E_cap,
+                                            const int32_t* dyn_E, const int32_t* mol_ptr, int64_t N, int64_t B,
+                                            int64_t N2cap, int64_t* idx_i2, int64_t* idx_j2, int64_t* iptr_i,
+                                            int32_t* ilist_i, int64_t* iptr_j, int32_t* ilist_j, int32_t* row_edge,
+                                            int32_t* grp_atom, int32_t* mol_grp, int32_t* mol_grp_end, int32_t* status,
+                                            hipStream_t stream) {
+  if (dyn_E == nullptr || E_cap < 0) return (int)hipErrorInvalidValue;
+  return launch_edge_layout(src_i, src_j, E_cap, dyn_E, mol_ptr, N, B, N2cap, idx_i2, idx_j2, iptr_i, ilist_i, iptr_j,
+                            ilist_j, row_edge, grp_atom, mol_grp, mol_grp_end, status, stream);
 }

@@ -488,11 +488,13 @@ class StepGraphs:
         return g
 
     def _edges(self, batch):
-        """Edges of the batch's radius_edge_index (PaiNN; a tensor shape: no read-back), else None."""
+        """Edges of the batch's radius_edge_index (PaiNN; a tensor shape or a host-side count / bound: no read-back),
+        else None."""
         if self.model_3d != "painn":
             return None
         if getattr(batch, "_dataset", None) is not None:
-            return batch.n_edges   # (the dataset's host-side edge counts)
+            from . import bucket as bk
+            return bk.handle_edges(batch)   # (the dataset's host-side edge counts; a masked handle: their upper bound)
         return int(batch.radius_edge_index.size(1))
 
     def capture_now(self, batch):

@@ -25,3 +25,10 @@ def env(name, default=None):
         key = _KEYS[name] = _ENCODE(name)
     value = _DATA.get(key)
     return default if value is None else _DECODE(value)
+
+
+def masked_painn_buckets():
+    """``GEOSSL_MASKED_PAINN_BUCKETS`` (default on): masked PaiNN handles of a ``DeviceLoader`` go through a capacity
+    bucket, their surviving radius edges counted on the device.  ``0``: they are collated - a count launch and a read-back
+    of the B counts - and run on their own tensors, the routing before the bucket took them (A/B timing)."""
+    return env("GEOSSL_MASKED_PAINN_BUCKETS", "1") != "0"

@@ -601,6 +601,13 @@ int geossl_ddm_loss_bwd_fused2_dyn(const GeosslNcsnHeadBwd* heads, const int64_t
  *   (row_edge [4 G], grp_atom [G], G = geossl_painn_group_capacity(2 E_cap, N2cap)) with the groups of molecule m in
  *   [mol_grp[m], mol_grp_end[m]); *status is set to 1 on an edge that leaves its molecule (or a molecule above 256
  *   atoms) - such edges are left out.  Molecules of at most 256 atoms.
+ * geossl_painn_edge_layout_dyn: the namesake with the edge count read from device memory (*dyn_E, one view's edges; a
+ *   masked batch of a device-resident dataset, whose surviving edges are counted on the device:
+ *   geossl_masked_edge_offsets): the same kernel body - the offset of view 1, the end 2E of the lists, mol_grp[2B], the
+ *   bound of the search for a molecule's edge range and the check that the molecules' ranges tile [0, E) all use the
+ *   device value - with outputs sized for E_cap edges per view.  The host-side range check is on E_cap; *dyn_E outside
+ *   [0, E_cap] is clamped into it and sets *status.  Given the same E through memory it writes what the by-value entry
+ *   point writes, bit for bit.
  * geossl_painn_interaction_fwd_mma_dyn: the namesake with mol_grp_end (NULL: groups lie back to back).
  * The element-wise launches take the real row / edge count from device memory like the other `_dyn` entry points.   */
 int64_t geossl_painn_group_capacity(int64_t E2, int64_t N2);
@@ -608,6 +615,11 @@ int geossl_painn_edge_layout(const int64_t* src_i, const int64_t* src_j, int64_t
                              int64_t B, int64_t N2cap, int64_t* idx_i2, int64_t* idx_j2, int64_t* iptr_i,
                              int32_t* ilist_i, int64_t* iptr_j, int32_t* ilist_j, int32_t* row_edge, int32_t* grp_atom,
                              int32_t* mol_grp, int32_t* mol_grp_end, int32_t* status, hipStream_t stream);
+int geossl_painn_edge_layout_dyn(const int64_t* src_i, const int64_t* src_j, int64_t E_cap, const int32_t* dyn_E,
+                                 const int32_t* mol_ptr, int64_t N, int64_t B, int64_t N2cap, int64_t* idx_i2,
+                                 int64_t* idx_j2, int64_t* iptr_i, int32_t* ilist_i, int64_t* iptr_j, int32_t* ilist_j,
+                                 int32_t* row_edge, int32_t* grp_atom, int32_t* mol_grp, int32_t* mol_grp_end,
+                                 int32_t* status, hipStream_t stream);
 int geossl_painn_edge_geom_dyn(const float* pos, const int64_t* idx_i, const int64_t* idx_j, int64_t E, float cutoff,
                                const float* offsets, const float* widths, int R, float* dir, float* fcut, float* phi,
                                const int32_t* dyn_E, hipStream_t stream);
@@ -745,8 +757,8 @@ int geossl_gather_molecules(const GeosslGather* g, int64_t B, hipStream_t stream
  * empty, the draw(n - t)-th unvisited atom in ascending order, else the draw(|frontier|)-th frontier atom in ascending
  * order.  With e_count != NULL the launch only decides the kept lists, writes keep_out (required then) and counts the
  * surviving radius edges of every molecule into e_count - the survivor count depends on the draw, so a gather with
- * radius edges is a count launch, a read-back of B counts (the caller's e_ptr) and a gather launch with keep_in = the
- * count launch's keep_out.  Refused (hipErrorInvalidValue): max_n > 2048, bond_ptr / bond_dst NULL when drawing.
+ * radius edges is a count launch, a read-back of B counts (the caller's e_ptr; or geossl_masked_edge_offsets, which
+ * makes e_ptr on the device) and a gather launch with keep_in = the count launch's keep_out.  Refused (hipErrorInvalidValue): max_n > 2048, bond_ptr / bond_dst NULL when drawing.
  * Molecules with n > 2048 or k outside [1, n] are skipped; kept atoms of keep_in outside [0, n) read atom 0.          */
 typedef struct GeosslMask {
   const int32_t* bond_ptr;  /* [Ntot+1] over DATASET atoms: the successors of atom s are bond_dst[bond_ptr[s] ..
@@ -763,6 +775,17 @@ typedef struct GeosslMask {
   int32_t pad_;
 } GeosslMask;
 int geossl_gather_masked_molecules(const GeosslGather* g, const GeosslMask* mask, int64_t B, hipStream_t stream);
+
+/* geossl_masked_edge_offsets: the read-back of the B counts done on the device instead (a masked PaiNN batch on a
+ * capacity bucket, whose captured step reads its edge count from device memory).  From e_count [B] (the count launch's
+ * survivors per molecule) one block writes e_ptr [B + 1] = their exclusive prefix (e_ptr[B] = E, the edges of one
+ * view: what the gather launch takes as g->e_ptr and geossl_painn_edge_layout_dyn as dyn_E) and *dyn_E2 = views * E
+ * (views 1 or 2: the edge count of the batch the backbone sees).  B is scanned in chunks of the block's threads with a
+ * carry.  Every offset is clamped to E_cap, so the launches behind it stay inside buffers of that capacity; *status
+ * (nullable) is set to 1 when the total exceeds E_cap or a count is negative.  Integer work, plain stores, no atomics.
+ * Refused (hipErrorInvalidValue): B outside [1, 2^24], 2 E_cap >= 2^30, views other than 1 or 2, a NULL array.     */
+int geossl_masked_edge_offsets(const int32_t* e_count, int64_t B, int64_t E_cap, int views, int32_t* e_ptr,
+                               int32_t* dyn_E2, int32_t* status, hipStream_t stream);
 
 /* ---- contrastive heads: pretrain_GeoSSL.py --GeoSSL_option=InfoNCE / EBM_NCE (:103-176) -----------------------------
  * X, Y [B][F]: the readouts of the two views (row-major fp32).  No atomics: the same inputs give the same bits.
