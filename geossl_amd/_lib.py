@@ -285,6 +285,12 @@ PROTOTYPES = {
     "geossl_property_bwd_dyn": (i32, [i64, i32, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp, i32, vp, vp, vp, vp,
                                       vp, vp, i32, vp, vp]),
     "geossl_property_targets": (i32, [vp, i64, i32, i32, vp, vp, i64, vp, vp]),
+    # LEP pair head (csrc/pair_head.hip)
+    "geossl_pair_head_width_ok": (i32, [i32]),
+    "geossl_pair_head_workspace_floats": (i64, [i64]),
+    "geossl_pair_head_fwd": (i32, [vp, i64, i32, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "geossl_pair_head_predict": (i32, [vp, i64, i32, vp, i64, i32, vp, vp, vp, vp]),
+    "geossl_pair_head_bwd": (i32, [i64, i32, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
     # angle-prediction head on atom triples, the angle producer and the triple gather (csrc/torsion_head.hip)
     "geossl_torsion_head_width_ok": (i32, [i32]),
     "geossl_torsion_head_fwd_workspace_floats": (i64, [i64]),

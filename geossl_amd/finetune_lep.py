@@ -1,0 +1,351 @@
+"""Step API of ``examples/finetune_lep.py`` (ligand efficacy prediction: a binary label per protein-ligand pair seen in
+its active and its inactive conformation) on the HIP path.
+
+``do_LEP(args, batch, model, graph_pred_linear, criterion)`` is the body of ``train()``, :31-45, as one call -> the fp32
+loss.  The reference runs the backbone twice per step, once per conformation; here both go through it ONCE, as one batch
+of 2B structures ``[active 0 .. B-1 | inactive 0 .. B-1]`` (``fused_batch``: built once per batch object from the sizes
+the collation keeps on the host), and the fused head of csrc/pair_head.hip forms the two readouts, the logit of
+``Linear(2F, 1)`` and the mean BCE-with-logits.  Every backbone weight is thus used once on 2B structures where the
+reference uses it twice and lets autograd add: the gradients agree to rounding, not bit for bit.  A side above 255 atoms
+puts the whole fused batch on the sparse pair list (geossl_amd/layout.py), as for LBA.  The loss supports the
+reference's own ``optimizer.zero_grad(); loss.backward(); optimizer.step()`` with a stock ``torch.optim.Adam``.
+
+Anything the kernels do not serve runs the reference's own ATen lines on our backbone, two passes - B = 1 included, where
+the reference's ``.squeeze()`` makes ``pred`` 0-d against a ``[1]`` target and ``BCEWithLogitsLoss`` raises ValueError.
+``predict_LEP`` / ``eval_LEP`` mirror ``eval()``, :66-101, with the two rank metrics in numpy (sklearn's definitions).
+``LEPTrainer`` is the ``train()`` body on the fused step with backbone and head in one flat buffer.
+"""
+from collections import OrderedDict
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import ops
+from .pretrain_Supervised import model_width, readout_of
+from .step import Objective, StepTrainer, backbone_latent, engine_for
+from .switches import env as _env
+
+
+# ---------------------------------------------------------------------------------------------------- what is served
+def _stock_bce(criterion):
+    """nn.BCEWithLogitsLoss() as the script builds it (:226): mean, no weight, no pos_weight, not a subclass."""
+    return (type(criterion) is nn.BCEWithLogitsLoss and criterion.weight is None and criterion.pos_weight is None
+            and criterion.reduction == "mean")
+
+
+def head_params(head):
+    """(weight, bias) of a head the kernels serve - nn.Linear(2F, 1) with a bias, fp32 CUDA parameters, F a served
+    width - or None."""
+    if type(head) is not nn.Linear or head.out_features != 1 or head.bias is None or head.in_features % 2:
+        return None
+    ps = (head.weight, head.bias)
+    if not all(p.is_cuda and p.dtype == torch.float32 for p in ps):
+        return None
+    return ps if ops.pair_head_width_ok(head.in_features // 2) else None
+
+
+def modules_ok(model, graph_pred_linear):
+    """Backbone and head run on the fused pair head: an unscaled mean / add readout at a width F the kernels take and
+    Linear(2F, 1)."""
+    ps = head_params(graph_pred_linear)
+    return ps is not None and readout_of(model) is not None and model_width(model) * 2 == ps[0].size(1)
+
+
+def _fused_batch_ok(batch):
+    need = ("x_active", "positions_active", "batch_active", "x_inactive", "positions_inactive", "batch_inactive", "y")
+    ts = [getattr(batch, k, None) for k in need]
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in ts):
+        return False
+    xa, pa, ba, xi, pi, bi, y = ts
+    if not (pa.dtype == torch.float32 and pi.dtype == torch.float32 and not pa.requires_grad and not pi.requires_grad
+            and ba.dtype == torch.long and bi.dtype == torch.long and ba.numel() > 0 and bi.numel() > 0
+            and xa.dim() == xi.dim() and not y.requires_grad):
+        return False
+    B = _n_pairs(batch)
+    return B >= 2 and y.dim() == 1 and y.numel() == B
+
+
+def _n_pairs(batch):
+    sizes = getattr(batch, "_sizes_active", None)
+    return len(sizes) if sizes is not None else int(batch.num_graphs)
+
+
+# ------------------------------------------------------------------------------------------------- the one-pass batch
+_BATCH_VECTORS = OrderedDict()   # (device, both size sequences) -> the fused batch vector
+
+
+def _fused_batch_vector(batch, sizes):
+    """cat(batch_active, batch_inactive + B).  It is a function of the two size sequences, so batches that agree in them
+    get the SAME tensor object: the layout cached on it is built once, and a step graph - which identifies such a batch
+    by its index tensors (pretrain_GeoSSL.structure_fingerprint) - serves them all."""
+    key = (batch.batch_active.device, sizes.tobytes())
+    vec = _BATCH_VECTORS.get(key)
+    if vec is None:
+        B = len(sizes) // 2
+        vec = _BATCH_VECTORS[key] = torch.cat([batch.batch_active, batch.batch_inactive + B])
+        from .layout import prepare_batch
+        prepare_batch(vec, None, sizes.tolist(), lazy=True)   # (the host sizes: a layout without a device read-back)
+        while len(_BATCH_VECTORS) > 64:
+            _BATCH_VECTORS.popitem(last=False)
+    else:
+        _BATCH_VECTORS.move_to_end(key)
+    return vec
+
+
+def _host_sizes(batch, side):
+    sizes = getattr(batch, "_sizes_" + side, None)
+    if sizes is None:   # (a batch built by hand: one read-back, then kept)
+        sizes = torch.bincount(getattr(batch, "batch_" + side), minlength=int(batch.num_graphs)).cpu().numpy()
+        setattr(batch, "_sizes_" + side, sizes)
+    return np.asarray(sizes, dtype=np.int64)
+
+
+def fused_batch(batch):
+    """The two conformations as ONE batch of 2B structures [active 0 .. B-1 | inactive 0 .. B-1] - a plain
+    ``pretrain_GeoSSL.Batch`` without tuples - built once per batch object and kept on it.  PaiNN: the inactive side's
+    edges are shifted by the TOTAL active atom count (the loader has already applied the per-side running counts).
+    ``y`` is the batch's label tensor as float32, taken anew at every call."""
+    from .pretrain_GeoSSL import Batch
+    if isinstance(batch, Batch):
+        return batch
+    fb = batch.__dict__.get("_geossl_fused")
+    if fb is None:
+        sizes = np.concatenate([_host_sizes(batch, "active"), _host_sizes(batch, "inactive")])
+        rei = None
+        if getattr(batch, "radius_edge_index_active", None) is not None:
+            n_active = int(batch.batch_active.numel())
+            rei = torch.cat([batch.radius_edge_index_active, batch.radius_edge_index_inactive + n_active], dim=1)
+        fb = Batch(torch.cat([batch.x_active, batch.x_inactive]),
+                   torch.cat([batch.positions_active, batch.positions_inactive]), _fused_batch_vector(batch, sizes),
+                   None, radius_edge_index=rei, num_graphs=len(sizes), sizes=sizes)
+        batch.__dict__["_geossl_fused"] = fb
+    y = batch.y
+    fb.y = y if y.dtype == torch.float32 else y.float()   # (:43)
+    return fb
+
+
+# --------------------------------------------------------------------------------------------------------- steps
+def _forward_aten(args, batch, model, graph_pred_linear):
+    """:33-42 as the reference writes them, on our backbone."""
+    if args.model_3d == "schnet":
+        active_mol_repr = model(batch.x_active, batch.positions_active, batch.batch_active)
+        inactive_mol_repr = model(batch.x_inactive, batch.positions_inactive, batch.batch_inactive)
+    elif args.model_3d == "painn":
+        active_mol_repr = model(batch.x_active, batch.positions_active, batch.radius_edge_index_active,
+                                batch.batch_active)
+        inactive_mol_repr = model(batch.x_inactive, batch.positions_inactive, batch.radius_edge_index_inactive,
+                                  batch.batch_inactive)
+    else:
+        raise Exception("3D model {} not included.".format(args.model_3d))
+
+    molecule_3D_repr = torch.cat((active_mol_repr, inactive_mol_repr), dim=1)
+
+    pred = graph_pred_linear(molecule_3D_repr).squeeze()
+    return pred
+
+
+def lep_step_aten(args, batch, model, graph_pred_linear, criterion):
+    """:33-45 as the reference writes them, on our backbone (two passes)."""
+    pred = _forward_aten(args, batch, model, graph_pred_linear)
+    actual = batch.y.float()
+
+    loss = criterion(pred, actual)
+    return loss
+
+
+def lep_step_fused(model_3d, fb, model, graph_pred_linear, y):
+    """The step as eager launches on the one-pass batch ``fb``: the backbone's latent of the 2B structures, then the
+    fused pair head with the readout in it -> (loss fp32 scalar, logits [B]).  y [B]: the labels as float32."""
+    h, lay, _ = backbone_latent(model_3d, fb, model, x=fb.x, what="LEP", layout=True)
+    w, b = head_params(graph_pred_linear)
+    return ops.pair_head(h, w, b, lay, readout_of(model), y)
+
+
+class _StepArgs:
+    """What the replayed step reads: the backbone kind (and the graph mode of its StepGraphs)."""
+
+    def __init__(self, model_3d, mode="auto"):
+        self.model_3d, self.step_graph_mode = model_3d, mode
+
+
+# (no draws: the labels, the graph's static input "target", are the one per-step input beside the structures - data of a
+# graph, not structure: batches that agree in their index tensors share a graph whatever their labels)
+LEP = Objective(
+    "LEP",
+    lambda eng, args, mu, sigma, batch, noise: lep_step_fused(args.model_3d, batch, eng.model, eng.n1, noise["target"])[0],
+    noise_keys=lambda args: ("target",),
+    capture_inputs=lambda eng, args, batch, mu, sigma, noise, device_noise: {"target": batch.y},
+    write_inputs=lambda eng, args, sg, g, batch, mu, sigma, noise, device_noise: g["noise"]["target"].copy_(batch.y))
+
+
+def do_LEP(args, batch, model, graph_pred_linear, criterion=None, graph=None):
+    """examples/finetune_lep.py:31-45 -> the fp32 loss.  args.model_3d picks the backbone call ("schnet" / "painn");
+    criterion None means the script's nn.BCEWithLogitsLoss(); batch.y may be integer (:43).  The fused one-pass step runs
+    for a stock mean BCEWithLogitsLoss, graph_pred_linear = Linear(2F, 1) with a bias, an unscaled backbone with a
+    mean / add readout at F = 32 / 64 / 128, and CUDA batches of B >= 2 pairs with one label per pair; anything else runs
+    the reference's ATen lines (two passes) - at B = 1 they raise ValueError, as the reference does.  graph: replay HIP
+    graphs of forward + backward (default: ``args.step_graph`` if present, else on unless GEOSSL_NO_STEP_GRAPH is set);
+    a batch gets its graph at the second sighting of its index tensors."""
+    if criterion is None:
+        criterion = nn.BCEWithLogitsLoss()
+    if args.model_3d not in ("schnet", "painn"):
+        raise Exception("3D model {} not included.".format(args.model_3d))
+    if not (_stock_bce(criterion) and modules_ok(model, graph_pred_linear) and _fused_batch_ok(batch)):
+        return lep_step_aten(args, batch, model, graph_pred_linear, criterion)
+    fb = fused_batch(batch)
+    if graph is None:
+        graph = getattr(args, "step_graph", _env("GEOSSL_NO_STEP_GRAPH") is None)
+    if graph and torch.is_grad_enabled() and not torch.cuda.is_current_stream_capturing():
+        eng = engine_for(model, "_geossl_lep_step", LEP, graph_pred_linear)
+        loss = eng.run(_StepArgs(args.model_3d, getattr(args, "step_graph_mode", "auto")), fb, 0.0, 0.0, None, False)
+        if loss is not None:
+            return loss
+    return lep_step_fused(args.model_3d, fb, model, graph_pred_linear, fb.y)[0]
+
+
+@torch.no_grad()
+def predict_LEP(args, batch, model, graph_pred_linear):
+    """eval()'s forward for one batch, :77-85 -> the logits [B] (a 0-d tensor at B = 1, on the ATen lines)."""
+    if args.model_3d not in ("schnet", "painn"):
+        raise Exception("3D model {} not included.".format(args.model_3d))
+    if not (modules_ok(model, graph_pred_linear) and _fused_batch_ok(batch)):
+        return _forward_aten(args, batch, model, graph_pred_linear)
+    fb = fused_batch(batch)
+    h, lay, _ = backbone_latent(args.model_3d, fb, model, x=fb.x, what="LEP", layout=True)
+    w, b = head_params(graph_pred_linear)
+    return ops.pair_predict(h, w, b, lay, readout_of(model))
+
+
+# ------------------------------------------------------------------------------------------------------- metrics
+def _binary(y_true):
+    y = np.asarray(y_true).reshape(-1)
+    classes = np.unique(y)
+    if classes.size > 2:
+        raise ValueError("binary labels expected, got %d classes" % classes.size)
+    return y == classes[-1] if classes.size == 2 else y == 1, classes.size
+
+
+def _threshold_counts(y_true, y_score):
+    """Cumulative true / false positives at every DISTINCT score, scores descending (tied scores form one threshold)."""
+    pos, n_classes = _binary(y_true)
+    score = np.asarray(y_score, dtype=np.float64).reshape(-1)
+    if score.size != pos.size:
+        raise ValueError("y_true and y_score differ in length")
+    order = np.argsort(-score, kind="mergesort")
+    score, pos = score[order], pos[order]
+    last = np.r_[np.nonzero(np.diff(score))[0], score.size - 1] if score.size else np.zeros(0, dtype=np.int64)
+    tps = np.cumsum(pos, dtype=np.float64)[last]
+    fps = (1.0 + last) - tps
+    return tps, fps, n_classes
+
+
+def roc_auc(y_true, y_score):
+    """sklearn.metrics.roc_auc_score for binary labels: the trapezoidal area under (FPR, TPR) over the distinct
+    thresholds.  One class present: ValueError, as sklearn raises."""
+    tps, fps, n_classes = _threshold_counts(y_true, y_score)
+    if n_classes != 2:
+        raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
+    tpr, fpr = np.r_[0.0, tps] / tps[-1], np.r_[0.0, fps] / fps[-1]
+    return float(np.sum(np.diff(fpr) * (tpr[1:] + tpr[:-1]) / 2.0))
+
+
+def average_precision(y_true, y_score):
+    """sklearn.metrics.average_precision_score for binary labels: the step-wise sum over the distinct thresholds of
+    (R_k - R_{k-1}) P_k."""
+    tps, fps, _ = _threshold_counts(y_true, y_score)
+    if tps.size == 0 or tps[-1] == 0:
+        return 0.0   # (no positive label: sklearn warns and returns 0)
+    precision, recall = tps / (tps + fps), tps / tps[-1]
+    return float(np.sum(np.diff(np.r_[0.0, recall]) * precision))
+
+
+@torch.no_grad()
+def eval_LEP(args, loader, model, graph_pred_linear):
+    """examples/finetune_lep.py eval(), :66-101 -> (sqrt(sum_b loss_b B_b / total), roc, pr, y_true, y_pred) with the
+    script's nn.BCEWithLogitsLoss().  Batches are moved to the backbone's device."""
+    model.eval()
+    if graph_pred_linear is not None:
+        graph_pred_linear.eval()
+    device = next(model.parameters()).device
+    criterion = nn.BCEWithLogitsLoss()
+
+    loss_all, total = 0, 0
+    y_true, y_pred = [], []
+
+    for batch in loader:
+        batch = batch.to(device)
+        output = predict_LEP(args, batch, model, graph_pred_linear)
+        y = batch.y.float()
+
+        B = y.size()[0]
+
+        loss = criterion(output, y)
+        loss_all += loss.item() * B
+        total += B
+        y_true.extend(y.detach().cpu().tolist())
+        y_pred.extend(output.detach().cpu().tolist())
+
+    y_true = np.array(y_true)
+    y_pred = np.array(y_pred)
+    roc = roc_auc(y_true, y_pred)
+    pr = average_precision(y_true, y_pred)
+
+    return np.sqrt(loss_all / total), roc, pr, y_true, y_pred
+
+
+# -------------------------------------------------------------------------------------------------------- trainer
+class LEPTrainer(StepTrainer):
+    """The body of ``train()`` (finetune_lep.py:17-62) on the one-pass step: backbone latent of the 2B structures, fused
+    pair head with the readout in it, backward, gradient all-reduce, Adam - backbone and graph_pred_linear in one flat
+    buffer (one fused Adam launch: both of the reference's groups run at args.lr), no host sync inside ``step``.
+    ``step(batch) -> loss`` on the device; ``set_lr(lr)`` between epochs is how a schedule is applied.
+    ``use_graph=True``: forward + backward are captured into HIP graphs and replayed, one graph per structure of the
+    fused batch (``graph_mode="auto"``: from its second sighting on; capacity buckets do not take paired batches); the
+    labels are a static input of the graph."""
+
+    def __init__(self, model, graph_pred_linear, lr=5e-4, weight_decay=0.0, model_3d="schnet", use_graph=False,
+                 max_graphs=256, graph_mode="auto"):
+        if not modules_ok(model, graph_pred_linear):
+            raise ValueError("LEPTrainer needs graph_pred_linear = Linear(2F, 1) with a bias at F = 32, 64 or 128 on the "
+                             "GPU and a backbone of width F with an unscaled mean / add readout; use do_LEP for "
+                             "anything else")
+        if model_3d not in ("schnet", "painn"):
+            raise Exception("3D model {} not included.".format(model_3d))
+        self.head, self.model_3d = graph_pred_linear, model_3d
+        super().__init__([model, graph_pred_linear], model_3d, lr, weight_decay, use_graph, max_graphs, graph_mode,
+                         noise_keys=("target",), views=1)
+
+    @property
+    def lr(self):
+        return self.opt.lr
+
+    def set_lr(self, lr):
+        """The learning rate of the following steps (an epoch-level scheduler: optim.cosine_annealing_lr)."""
+        self.opt.lr = float(lr)
+
+    def _forward(self, fb, noise):
+        return lep_step_fused(self.model_3d, fb, self.model, self.head, noise["target"] if noise is not None else fb.y)[0]
+
+    def _capture_inputs(self, fb, noise):
+        return {"target": fb.y}
+
+    def _write_inputs(self, g, fb, noise):
+        g["noise"]["target"].copy_(fb.y)
+
+    def _one_pass(self, batch):
+        from .pretrain_GeoSSL import Batch
+        if not isinstance(batch, Batch) and not _fused_batch_ok(batch):
+            raise ValueError("LEPTrainer needs CUDA batches of B >= 2 pairs with one label per pair; use do_LEP for "
+                             "anything else")
+        return fused_batch(batch)
+
+    def _eager(self, batch, noise=None):
+        return super()._eager(self._one_pass(batch), noise)
+
+    def _graph_fwd_bwd(self, batch, noise=None):
+        return super()._graph_fwd_bwd(self._one_pass(batch), noise)
+
+    def predict(self, batch):
+        """eval()'s logits of one batch with the trainer's parameters."""
+        return predict_LEP(_StepArgs(self.model_3d), batch, self.model, self.head)

@@ -1266,3 +1266,100 @@ def property_targets(y, task_id, mol_off, src_off, B, out):
     call("geossl_property_targets", ptr(y), y.size(0), y.size(1), int(task_id), ptr(mol_off), src_off, int(B), ptr(out),
          stream())
     return out
+
+
+# ---- LEP pair head (csrc/pair_head.hip) ---------------------------------------------------------------------------------
+class _PairHead(torch.autograd.Function):
+    """The LEP step after the backbone (finetune_lep.py:40-45) on csrc/pair_head.hip -> (loss fp32 scalar, z [B] fp32
+    logits, non-differentiable).  h is the latent of the 2B-structure batch [active | inactive], (w, b) the parameters
+    of Linear(2F, 1).  The backward returns dh (the readout's backward in it) and the head's gradients through autograd,
+    or, inside _lib.direct_grads() with dense fp32 .grad tensors, adds the head's gradients into them."""
+
+    @staticmethod
+    def forward(ctx, h, y, layout, readout, w, b):
+        h = _f32(h)
+        N, F = h.shape
+        B = int(layout.B) // 2
+        f32 = dict(dtype=torch.float32, device=h.device)
+        wd, bd = w.detach().contiguous(), b.detach().contiguous()
+        m = torch.empty(2 * B, F, **f32)
+        z = torch.empty(B, **f32)
+        ws = torch.empty(int(_lib.load().geossl_pair_head_workspace_floats(B)), **f32)
+        loss = torch.empty((), **f32)
+        call("geossl_pair_head_fwd", ptr(h), N, F, ptr(layout.mol_ptr), B, PROPERTY_READOUTS[readout], ptr(wd), ptr(bd),
+             ptr(y), ptr(m), ptr(z), ptr(ws), ptr(loss), stream())
+        ctx.save_for_backward(m, z, y, wd)
+        ctx.lay, ctx.readout, ctx.params, ctx.N = layout, readout, (w, b), N
+        ctx.mark_non_differentiable(z)
+        ctx.set_materialize_grads(False)
+        return loss, z
+
+    @staticmethod
+    def backward(ctx, gout, _gz):
+        if gout is None:
+            return (None,) * 6
+        m, z, y, wd = ctx.saved_tensors
+        F = m.size(1)
+        B = z.numel()
+        dev = m.device
+        dh = torch.empty(ctx.N, F, dtype=torch.float32, device=dev)
+        ws = torch.empty(int(_lib.load().geossl_pair_head_workspace_floats(B)), dtype=torch.float32, device=dev)
+        g = gout.to(torch.float32).contiguous()
+        params = ctx.params
+        live = [p for p in params if p.requires_grad]
+        direct = bool(live) and _lib.direct_grads_enabled(live)
+        grads = [None, None]
+        for i, p in enumerate(params):
+            if direct:
+                grads[i] = p.grad if p.requires_grad else None
+            elif ctx.needs_input_grad[4 + i]:
+                grads[i] = torch.empty_like(p, dtype=torch.float32)
+        call("geossl_pair_head_bwd", ctx.N, F, ptr(ctx.lay.mol_ptr), B, PROPERTY_READOUTS[ctx.readout], ptr(wd), ptr(m),
+             ptr(z), ptr(y), ptr(g), ptr(dh), ptr(grads[0]), ptr(grads[1]), ptr(ws), 1 if direct else 0, stream())
+        if direct:
+            grads = [None, None]
+        return (dh, None, None, None) + tuple(grads)
+
+
+def pair_head_width_ok(F):
+    """The backbone widths the fused pair head serves: F = 32, 64 or 128 (a head of 64 / 128 / 256 inputs)."""
+    return bool(_lib.load().geossl_pair_head_width_ok(int(F)))
+
+
+def _check_pair_head(h, layout, readout, w, b):
+    _lib.require_cuda(h, layout.mol_ptr, w, b)
+    F = h.size(1) if h.dim() == 2 else -1
+    if h.dim() != 2 or not pair_head_width_ok(F):
+        raise ValueError("pair head: h [N, F] with F in (32, 64, 128), got %s" % (tuple(h.shape),))
+    if (tuple(w.shape), tuple(b.shape)) != ((1, 2 * F), (1,)) or w.dtype != torch.float32 or b.dtype != torch.float32:
+        raise ValueError("pair head: float32 Linear(2F, 1) parameters, got %s, %s" % (tuple(w.shape), tuple(b.shape)))
+    if readout not in PROPERTY_READOUTS:
+        raise ValueError("pair head: readout is 'mean', 'add' or 'sum', got %r" % (readout,))
+    if int(layout.B) < 2 or int(layout.B) % 2 or int(layout.N) != h.size(0):
+        raise ValueError("pair head: the layout of 2B structures [active | inactive] over the rows of h, got B = %d, "
+                         "N = %d for %d rows" % (layout.B, layout.N, h.size(0)))
+
+
+def pair_head(h, w, b, layout, readout, y):
+    """The LEP loss with the readout inside the head -> (loss, z): h [N, F] per-atom latent of the 2B structures
+    [active 0 .. B-1 | inactive 0 .. B-1] (atoms sorted by structure), (w [1, 2F], b [1]) of Linear(2F, 1), layout: the
+    MolLayout of the 2B structures, readout "mean" / "add" ("sum"), y [B] float32 labels.  loss is the mean
+    BCE-with-logits of z_b = b + <w[0:F], m_b> + <w[F:2F], m_{B+b}>; z [B] the logits."""
+    _check_pair_head(h, layout, readout, w, b)
+    B = int(layout.B) // 2
+    _lib.require_cuda(y)
+    if y.dim() != 1 or y.numel() != B or y.dtype != torch.float32 or not y.is_contiguous():
+        raise ValueError("pair head: y is a contiguous float32 [B], B = %d, got %s %s" % (B, y.dtype, tuple(y.shape)))
+    return _PairHead.apply(h, y, layout, readout, w, b)
+
+
+def pair_predict(h, w, b, layout, readout):
+    """eval() of finetune_lep.py:77-85 after the backbone: the logits [B] (no autograd)."""
+    _check_pair_head(h, layout, readout, w, b)
+    h = _f32(h.detach())
+    N, F = h.shape
+    B = int(layout.B) // 2
+    z = torch.empty(B, dtype=torch.float32, device=h.device)
+    call("geossl_pair_head_predict", ptr(h), N, F, ptr(layout.mol_ptr), B, PROPERTY_READOUTS[readout],
+         ptr(w.detach().contiguous()), ptr(b.detach().contiguous()), ptr(z), stream())
+    return z

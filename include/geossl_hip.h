@@ -965,6 +965,29 @@ int geossl_property_bwd_dyn(int64_t N, int F, const int32_t* mol_ptr, int64_t B,
 int geossl_property_targets(const float* y, int64_t M, int T, int task_id, const int64_t* mol_off,
                             const int32_t* src_off, int64_t B, float* out, hipStream_t stream);
 
+/* ---- LEP pair head: examples/finetune_lep.py:33-45 (train), :77-90 (eval) (csrc/pair_head.hip)
+ * h [N][F] per-atom latent (F = 32, 64 or 128: geossl_pair_head_width_ok) of a batch of 2B structures
+ * [active 0 .. B-1 | inactive 0 .. B-1], mol_ptr [2B + 1] int32 atom offsets (atoms sorted by structure), B >= 1 pairs.
+ * readout: 0 "add", 1 "mean" (sum / max(n_s, 1), the arithmetic of geossl_segment_reduce_fwd).  w [2F], b [1]: the
+ * parameters of Linear(2F, 1); y [B] float32 labels.  No atomics: the same inputs give the same bits.
+ * Forward: m [2B][F] (out) the readouts, z [B] (out) = b + <w[0:F], m_b> + <w[F:2F], m_{B+b}>, loss [1] (out) = mean_b of
+ *   max(z_b, 0) - z_b y_b + log1p(exp(-|z_b|)) (fp64 terms added in pair order, stored as fp32).
+ *   workspace: geossl_pair_head_workspace_floats(B) floats, 8-byte aligned.
+ * Predict: z [B] only.
+ * Backward with gout[0]: dz_b = gout (sigmoid(z_b) - y_b) / B; dh [N][F] (out) = dz_b w[side F + j] (/ max(n_s, 1) for
+ *   "mean") on every atom row of both structures of pair b, each written once; dw [2F] / db [1] (out; NULL: skipped) =
+ *   sum_b dz_b m[side B + b][j] / sum_b dz_b in pair order, added to what is there when accumulate != 0. */
+int geossl_pair_head_width_ok(int F);
+int64_t geossl_pair_head_workspace_floats(int64_t B);
+int geossl_pair_head_fwd(const float* h, int64_t N, int F, const int32_t* mol_ptr, int64_t B, int readout, const float* w,
+                         const float* b, const float* y, float* m, float* z, float* workspace, float* loss,
+                         hipStream_t stream);
+int geossl_pair_head_predict(const float* h, int64_t N, int F, const int32_t* mol_ptr, int64_t B, int readout,
+                             const float* w, const float* b, float* z, hipStream_t stream);
+int geossl_pair_head_bwd(int64_t N, int F, const int32_t* mol_ptr, int64_t B, int readout, const float* w, const float* m,
+                         const float* z, const float* y, const float* gout, float* dh, float* dw, float* db,
+                         float* workspace, int accumulate, hipStream_t stream);
+
 /* ---- angle prediction on atom triples: examples/pretrain_TorsionAnglePrediction.py:16-27,64-78 (csrc/torsion_head.hip)
  * h [N][F] node features (F = 64, 128, 256 or 512: geossl_torsion_head_width_ok), W [3F] = predictor.weight =
  * [w_u | w_v | w_w], bias [1], triples (tri0[t], tri1[t], tri2[t]) = (u_t, v_t, w_t), t < T (batch atom ids), angle [T] the
