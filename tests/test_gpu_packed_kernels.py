@@ -24,12 +24,14 @@ from conftest import REPO
 sys.path.insert(0, os.path.join(REPO, "tools"))
 
 import packed_opsel_registry as reg  # noqa: E402
+from elementwise import (REPEATS, assert_repeatable, assert_sees_a_dropped_term, assert_within, flagged,  # noqa: E402,F401
+                         pick_term)
 from filter_twin import _filter_ref_and_bound  # noqa: E402
+from ncsn_twin import KEYS as _NCSN_KEYS, _ncsn_ref_and_bound  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 U22, U24 = 2.0 ** -22, 2.0 ** -24
-REPEATS = 8
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -58,50 +60,6 @@ def assert_occupancy(symbol, label, lds=None, grid=None):
     got = sp.waves_per_simd(_RES[k], block, lds, grid)
     assert got == waves, (symbol, label, got, waves)
     return waves
-
-
-def flagged(got, ref, S, c, u, extra=None):
-    """Elements outside |got - ref| <= c u S (+ extra): a boolean tensor of got's shape (NaN and inf are outside)."""
-    bound = c * u * S
-    if extra is not None:
-        bound = bound + extra
-    err = (got.double() - ref).abs()
-    return ~(err <= bound)
-
-
-def assert_within(got, ref, S, c, u, what, extra=None):
-    bad = flagged(got, ref, S, c, u, extra)
-    n = int(bad.sum())
-    if n:
-        idx = bad.nonzero()[:8]
-        rows = [(tuple(int(v) for v in i), float(got[tuple(i)]), float(ref[tuple(i)]), float(S[tuple(i)])) for i in idx]
-        pytest.fail("%s: %d of %d elements outside %g u S (index, got, ref, S): %s" % (what, n, bad.numel(), c, rows))
-
-
-def assert_sees_a_dropped_term(got, ref, S, c, u, index, term, what, extra=None):
-    """Remove `term` from ref[index]: the checker must flag exactly that element."""
-    ref2 = ref.clone()
-    ref2[index] -= term
-    bad = flagged(got, ref2, S, c, u, extra)
-    hit = [tuple(int(v) for v in i) for i in bad.nonzero()[:4]]
-    assert hit == [tuple(int(v) for v in index)] and int(bad.sum()) == 1, (what, index, float(term), hit)
-
-
-def pick_term(terms, bound, where):
-    """Among the candidate terms (`where` True), the one largest against the bound of its element: (flat position,
-    ratio).  A term under twice its bound cannot be told apart from rounding: the test then fails."""
-    ratio = torch.where(where & (bound > 0), terms.abs() / bound, torch.zeros_like(terms))
-    k = int(ratio.argmax())
-    return k, float(ratio.reshape(-1)[k])
-
-
-def assert_repeatable(launch, first, what):
-    """Seven more launches, each compared with the first element by element."""
-    for rep in range(REPEATS - 1):
-        again = launch()
-        for a, b in zip(first, again):
-            n = int((a != b).sum()) + int((a.isnan() != b.isnan()).sum())
-            assert n == 0, (what, rep, "%d elements differ between launches" % n)
 
 
 # ----------------------------------------------------------------------------------------------- filter backward
@@ -187,43 +145,6 @@ def _ncsn_problem(F, seed=5, K=50):
     P = ncsn_oracle_params(F, K)
     return dict(h=h.to(DEV), dist=dist.to(DEV), nl=nl.to(DEV), dn=dn.to(DEV), batch=batch.to(DEV), sei0=sei[0].contiguous().to(DEV),
                 sei1=sei[1].contiguous().to(DEV), P={k: v.detach().to(DEV) for k, v in P.items()}, S=S)
-
-
-_NCSN_KEYS = ("input_distance_mlp.layers.0.weight", "input_distance_mlp.layers.0.bias",
-              "input_distance_mlp.layers.1.weight", "input_distance_mlp.layers.1.bias",
-              "output_mlp.layers.0.weight", "output_mlp.layers.0.bias", "output_mlp.layers.1.weight",
-              "output_mlp.layers.1.bias", "output_mlp.layers.2.weight", "output_mlp.layers.2.bias")
-
-
-def _ncsn_ref_and_bound(p, power):
-    """loss_e (NCSN.py:183-209) in fp64 and its S: every layer's magnitude M = |W| M_in + |b| (relu is 1-Lipschitz),
-    the scores' S = M / sigma, the target's S = (|d| + |dn| sigma) / sigma^2, loss_e's S = |s - t| (S_s + S_t) sigma^p +
-    loss_e.  Also the last layer's terms, for the dropped-term check."""
-    P = {k: v.double() for k, v in p["P"].items()}
-    e2g = p["batch"][p["sei0"]]
-    sig = P["sigmas"][p["nl"]][e2g].unsqueeze(-1)
-    d, dn = p["dist"].double(), p["dn"].double()
-    pert = d + dn * sig
-    Mp = d.abs() + (dn * sig).abs()
-    lin = lambda x, k: x @ P[k + ".weight"].t() + P[k + ".bias"]
-    mag = lambda m, k: m @ P[k + ".weight"].abs().t() + P[k + ".bias"].abs()
-    z = lin(pert, "input_distance_mlp.layers.0")
-    m = mag(Mp, "input_distance_mlp.layers.0")
-    emb = lin(torch.relu(z), "input_distance_mlp.layers.1")
-    memb = mag(m, "input_distance_mlp.layers.1")
-    h = p["h"].double()
-    x = torch.cat([h[p["sei0"]] + h[p["sei1"]], emb], -1)
-    mx = torch.cat([h.abs()[p["sei0"]] + h.abs()[p["sei1"]], memb], -1)
-    for k in ("output_mlp.layers.0", "output_mlp.layers.1"):
-        x, mx = torch.relu(lin(x, k)), mag(mx, k)
-    w3 = P["output_mlp.layers.2.weight"][0]
-    s = (lin(x, "output_mlp.layers.2") / sig).view(-1)
-    Ss = (mag(mx, "output_mlp.layers.2") / sig).view(-1)
-    t = (-1.0 / sig ** 2 * (pert - d)).view(-1)
-    St = (Mp / sig ** 2).view(-1)
-    sp = sig.view(-1) ** power
-    loss = 0.5 * (s - t) ** 2 * sp
-    return loss, (s - t).abs() * (Ss + St) * sp + loss, dict(s=s, t=t, sp=sp, last=x * w3[None, :] / sig)
 
 
 @pytest.mark.parametrize("heads", [1, 2])
