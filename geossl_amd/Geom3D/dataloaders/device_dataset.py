@@ -71,8 +71,8 @@ class _Staging:
 class DeviceDataset:
     def __init__(self, x, positions, sizes, device, option="combination", radius=None, max_num_neighbors=32,
                  bond_index=None, bond_counts=None, y=None, triples=None, triple_counts=None, triple_angle=None):
-        """x [Ntot, C] int64, positions [Ntot, 3] float32 (numpy or tensors; molecule after molecule), sizes [M] atoms
-        per molecule.  option: the AtomTupleExtractor enumeration of the batches drawn from it.  radius: also build the
+        """x [Ntot, C] int64 (or [Ntot]: one column), positions [Ntot, 3] float32 (numpy or tensors; molecule after
+        molecule), sizes [M] atoms per molecule.  option: the AtomTupleExtractor enumeration of the batches drawn from it.  radius: also build the
         per-molecule radius_edge_index (PaiNN) on this geometry.  bond_index [2, Etot] (local atom indices, molecule
         after molecule) with bond_counts [M]: the bond graph (``data.edge_index``) that atom masking walks.  y [M, T]
         (or [M]): per-molecule targets, kept in device memory as float32 (the Supervised / fine-tuning steps).
@@ -93,6 +93,8 @@ class DeviceDataset:
         self.off = np.zeros(M + 1, dtype=np.int64)
         np.cumsum(self.sizes, out=self.off[1:])
         self.x, self.positions = as_t(x, torch.int64), as_t(positions, torch.float32)
+        if self.x.dim() == 1:   # (DatasetLBA's records: the atomic numbers alone - one column)
+            self.x = self.x.reshape(-1, 1)
         if self.x.dim() != 2 or self.positions.dim() != 2 or self.positions.size(1) != 3:
             raise ValueError("x is [Ntot, C], positions [Ntot, 3]")
         Nt = int(self.off[-1])

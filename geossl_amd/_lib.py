@@ -305,6 +305,8 @@ PROTOTYPES = {
     # sparse pair list (csrc/sparse_pairs.hip)
     "geossl_sparse_pairs_build": (i32, [vp, vp, i64, i64, i32, f32, i32, f32, i64] + [vp] * 13),
     "geossl_cfconv_aggregate_sparse": (i32, [vp, vp, vp, vp, vp, i64, i32, i32, vp, vp]),
+    "geossl_sparse_pairs_build_dyn": (i32, [vp, vp, i64, i64, i32, f32, i32, f32, i64] + [vp] * 14),
+    "geossl_cfconv_aggregate_sparse_dyn": (i32, [vp, vp, vp, vp, vp, i64, i32, i32, vp, vp, vp]),
     "geossl_pair_position_grad_sparse": (i32, [vp, vp, vp, vp, vp, vp, i64, i64, i32, vp, vp]),
     "geossl_pair_geometry_live": (i32, [vp, vp, vp, i64, i32, f32, i32, f32, vp, vp, vp, vp, vp]),
     "geossl_gather_live_rows": (i32, [vp, vp, vp, i64, i32, i32, vp, vp]),

@@ -17,6 +17,11 @@ aggregation; the number of molecules is the loader's batch size) and turns every
   include/geossl_hip.h, which take their grid from the capacity and their row count from ``dims``: rows past the real
   count are never read or written.
 
+A SPARSE bucket (option ``SPARSE``; one view, SchNet; structures of up to 1024 atoms) has no pair slots at all: the
+backbone builds the compacted pair list from the positions inside the captured step (geossl_sparse_pairs_build_dyn),
+at the capacity ``P_cap = 33 N_cap`` that every batch which fits the atoms fits too.  Its fill uploads mol_ptr and the
+counts and gathers the atom rows: nothing else of the batch is read.
+
 Layout of the fused two-view batch in a bucket: ``[view 0 atoms | view 1 atoms | unused]`` - view 1 starts right behind
 the REAL atoms of view 0 (``dims[N]``), so the molecule CSR stays contiguous.
 """
@@ -127,6 +132,58 @@ def sizes_array(batch):
 
 
 TRIPLES = "triples"   # the "tuple option" of a bucket whose step reads atom triples and no pair tuples (angle prediction)
+# ... and of a one-view SchNet bucket on the sparse pair list, for a step that reads neither (Supervised): no pair slots,
+# no pair tuples, no aggregation work list; molecules of up to layout.SPARSE_MAX_N atoms
+SPARSE = "sparse"
+SPARSE_MAX_N_CLASSES = (256, 512, 1024)   # its bound on the molecule size (LDS of the list's build: up to 139 KB)
+
+
+def sparse_max_n_class(hi, prev=None):
+    """The sparse bucket's bound on the molecule size for a batch whose largest molecule has `hi` atoms (the classes
+    double: the head room is in the class itself); never below a previous bucket's."""
+    for c in SPARSE_MAX_N_CLASSES:
+        if hi <= c and (prev is None or c >= prev):
+            return c
+    return SPARSE_MAX_N_CLASSES[-1]
+
+
+def sparse_capacities(N, B, prev=None, sizes=None):
+    """(N_cap, P_cap, 0, 0) of a sparse bucket: the atoms with the slack of `capacities`, the pair list at
+    SPARSE_EDGES_PER_ATOM rows per atom of the capacity - layout.sparse_pair_capacity(sizes) <= 33 sum(sizes), so a
+    batch that fits the atoms fits the list."""
+    from .layout import SPARSE_EDGES_PER_ATOM
+    N_cap = capacities(N, 0, 0, 0, B, prev=prev, sizes=sizes)[0]
+    return (N_cap, SPARSE_EDGES_PER_ATOM * N_cap, 0, 0)
+
+
+def sparse_tensors_ok(batch):
+    """What a sparse bucket's fill copies of a collated batch: int64 x [N] or [N, c] and float32 positions [N, 3] on the
+    device, contiguous, N the sum of the sizes (the batch vector is generated, pair tuples are not read)."""
+    x, pos = getattr(batch, "x", None), getattr(batch, "positions", None)
+    if not (torch.is_tensor(x) and torch.is_tensor(pos)):
+        return False
+    N = int(sizes_array(batch).sum())
+    return (pos.is_cuda and pos.dtype == torch.float32 and pos.dim() == 2 and pos.size(1) == 3 and pos.is_contiguous()
+            and pos.size(0) == N and not pos.requires_grad
+            and x.is_cuda and x.dtype == torch.long and x.dim() in (1, 2) and x.is_contiguous() and x.size(0) == N
+            and x.device == pos.device)
+
+
+def sparse_eligible(batch):
+    """Can this batch go through a SPARSE bucket?  Molecule sizes known on the host, 1 .. 1024 atoms, and a layout of
+    them would be sparse (layout.want_sparse: a structure above 255 atoms, or GEOSSL_SPARSE_PAIRS=1).  A collated batch:
+    tensors as `sparse_tensors_ok`; a handle on a device-resident dataset: unmasked, pair-tuple dataset (its tuple option
+    is not read)."""
+    from .layout import SPARSE_MAX_N, want_sparse
+    sizes = getattr(batch, "_sizes", None)
+    if sizes is None or not len(sizes):
+        return False
+    lo, hi = size_range(batch)
+    if lo < 1 or hi > SPARSE_MAX_N or not want_sparse(hi):
+        return False
+    if getattr(batch, "_dataset", None) is not None:
+        return getattr(batch, "_mask", None) is None and not getattr(batch, "_triples", False)
+    return not getattr(batch, "_triples", False) and sparse_tensors_ok(batch)
 
 
 def option_of(batch):
@@ -145,7 +202,10 @@ def n_triples(batch):
 
 def batch_counts(sizes, option, views=2):
     """(atoms N, pair slots P, super-edges S, aggregation work items W of the `views`-view batch) of molecules `sizes`.
-    option "triples": no pair tuples (S = 0)."""
+    option "triples": no pair tuples (S = 0); "sparse": atoms only (N, 0, 0, 0)."""
+    if option == SPARSE:
+        n = sizes if isinstance(sizes, np.ndarray) else np.asarray(sizes, dtype=np.int64)
+        return int(n.sum()), 0, 0, 0
     global _PARTS
     if _PARTS is None:
         _PARTS = _parts_table()
@@ -360,12 +420,17 @@ def host_plan(sizes, option, views=2):
     (largest first, stable; 27 .. 33-atom molecules as 2 or 4 items, larger ones one item per atom: molecule | part << 24;
     over the B molecules of view 0 only when views = 1); the divisor of NCSN.py:210-212
     (last molecule with a super-edge, + 1); inc_ptr [N + 1] (an atom of an n-atom molecule lies on n - 1 tuples of the
-    "combination" enumeration, 2 (n - 1) of "permutation")."""
+    "combination" enumeration, 2 (n - 1) of "permutation").  option "sparse": counts (N, 0, 0, 0) and ``mol_ptr``
+    [B + 1] of the one view - no pair, tuple or work entry exists."""
+    n = sizes if isinstance(sizes, np.ndarray) else np.asarray(sizes, dtype=np.int64)
+    B = n.shape[0]
+    if option == SPARSE:
+        mp = np.zeros(B + 1, dtype=np.int64)
+        np.cumsum(n, out=mp[1:])
+        return dict(counts=(int(mp[-1]), 0, 0, 0), mol_ptr=mp)
     global _PARTS
     if _PARTS is None:
         _PARTS = _parts_table()
-    n = sizes if isinstance(sizes, np.ndarray) else np.asarray(sizes, dtype=np.int64)
-    B = n.shape[0]
     N, P, S, W = batch_counts(n, option, views)
     mult = 1 if option == "combination" else (0 if option == TRIPLES else 2)
     mp = np.zeros(B + 1, dtype=np.int64)
@@ -393,7 +458,11 @@ class Bucket:
     views = 1 (a step with no second view: Distance Prediction): the backbone's layout `lay2` and the counts in `dims`
     describe view 0 alone - B molecules, its aggregation work list, its pair slots and edges.  The gather and the PaiNN
     edge layout still write the two-view structures (view 1 lands in buffer space this step never reads); view 0 comes
-    first in every one of them, so its slices are the one-view structures."""
+    first in every one of them, so its slices are the one-view structures.
+
+    option "sparse" (kind "schnet", views = 1): `lay2` is a SPARSE layout at capacity - N = N_cap, P = P_cap (rows of the
+    pair list the backbone builds per step), max_n a class of SPARSE_MAX_N_CLASSES, mol_ptr the B real offsets, no pair
+    slots, no work list; `caps` = sparse_capacities(...)."""
 
     def __init__(self, device, B, caps, option, x_cols=2, max_n=SMALL_N, kind="schnet", E_cap=0, n_rbf=20, views=2,
                  T_cap=0):
@@ -408,6 +477,9 @@ class Bucket:
         self.T_cap = int(T_cap) if option == TRIPLES else 0
         if option == TRIPLES and views != 1:
             raise ValueError("a triples bucket holds one view")
+        sparse = option == SPARSE
+        if sparse and (views != 1 or kind != "schnet"):
+            raise ValueError("a sparse bucket holds one view of a SchNet batch")
         self.N_cap, self.P_cap, self.S_cap, self.W_cap = (int(c) for c in caps[:4])
         B, Nc, Pc, Sc, Wc = self.B, self.N_cap, self.P_cap, self.S_cap, self.W_cap
         i32 = dict(dtype=torch.int32, device=device)
@@ -420,7 +492,7 @@ class Bucket:
         o["work"] = o["se_ptr"] + B + 1
         o["stats"] = _round_up(o["work"] + Wc, 2)
         o["inc_ptr"] = o["stats"] + 4
-        o["big0"] = o["inc_ptr"] + 2 * (Nc + 1)
+        o["big0"] = o["inc_ptr"] + (0 if sparse else 2 * (Nc + 1))   # (sparse: no tuples, no incidence lists of them)
         # PaiNN, molecules above the stage caps of the molecule-staged interaction kernels: their atoms (two lists)
         self.big_caps = ()
         if kind == "painn" and self.max_n > 0:
@@ -462,7 +534,11 @@ class Bucket:
         if self.big_caps:
             lay.big = {c: (self.blob[o["big%d" % k]:o["big%d" % k] + 2 * Nc], 2 * Nc, self.dyn.n_big[k])
                        for k, c in enumerate(self.big_caps)}
-        if kind == "schnet":
+        lay.sparse = sparse
+        if sparse:
+            lay.pair_i = lay.pair_j = None
+            lay.pair_capacity = Pc
+        elif kind == "schnet":
             lay.pair_i = torch.zeros(2 * Pc, **i32)
             lay.pair_j = torch.zeros(2 * Pc, **i32)
             lay.agg_work = self.blob[o["work"]:o["work"] + Wc]
@@ -503,7 +579,7 @@ class Bucket:
         sel.S, sel.N, sel.B = Sc, Nc, B
         sel.se_ptr = self.blob[o["se_ptr"]:o["se_ptr"] + B + 1]
         sel.stats = self.blob[o["stats"]:o["stats"] + 4].view(torch.int64)
-        sel.inc_ptr = self.blob[o["inc_ptr"]:o["inc_ptr"] + 2 * (Nc + 1)].view(torch.int64)
+        sel.inc_ptr = self.blob[o["inc_ptr"]:o["inc_ptr"] + (0 if sparse else 2 * (Nc + 1))].view(torch.int64)
         sel.inc_idx = torch.zeros(2 * Sc, **i32)
         sel.dyn = self.dyn
         sel._versions = (self.batch_vec._version, self.sei._version)
@@ -537,7 +613,9 @@ class Bucket:
         launches geossl_gather_masked_molecules instead: the BFS and the gather are that one launch.  A masked PaiNN
         handle is four launches - count (BFS + survivors per molecule), geossl_masked_edge_offsets (e_ptr and
         dims[D_E2] on the device), gather, geossl_painn_edge_layout_dyn - and nothing is read back: the host only
-        checks the handle's upper bound on the edges against E_cap."""
+        checks the handle's upper bound on the edges against E_cap.  A sparse bucket: `_fill_sparse`."""
+        if self.option == SPARSE:
+            return self._fill_sparse(batch, counts, zero)
         global _PARTS
         if _PARTS is None:
             _PARTS = _parts_table()
@@ -691,4 +769,54 @@ class Bucket:
             self.el_status.arm(every=8)
         self.real = (N, P, S, W)
         self.real_E = None if masked_edges else E   # (a masked PaiNN fill: only the device knows; blob[e_ptr + B])
+        return self.real
+
+    def _fill_sparse(self, batch, counts=None, zero=None):
+        """`fill` of a sparse bucket: counts, mol_ptr and (a dataset handle) the molecules' offsets in the dataset in one
+        pinned upload, then geossl_gather_molecules with no pair, tuple or incidence pointers - atom rows, positions, the
+        batch vector and the cleared buffer.  A collated batch's 1-D x (DatasetLBA's atomic numbers) is its one column;
+        a dataset's tuple option is not read."""
+        B, o = self.B, self.off
+        n = sizes_array(batch)
+        if n.shape[0] != B:
+            raise ValueError("bucket of %d molecules got a batch of %d" % (B, n.shape[0]))
+        hp = host_plan(n, SPARSE, 1)
+        N = hp["counts"][0]
+        ds = getattr(batch, "_dataset", None)
+        if getattr(batch, "_mask", None) is not None or getattr(batch, "_triples", False):
+            raise ValueError("a sparse bucket takes unmasked batches of whole molecules")
+        if int(n.min()) < 1 or not self.fits((N, 0, 0, 0), int(n.max())):
+            raise ValueError("batch exceeds the bucket's capacity")
+        if ds is not None:
+            if ds.x_cols != self.x.size(1) or ds.device != self.x.device:
+                raise ValueError("dataset and bucket disagree (x columns or device)")
+        elif (not sparse_tensors_ok(batch) or batch.x.numel() != N * self.x.size(1)
+              or batch.x.device != self.x.device):
+            raise ValueError("bucket fill expects contiguous collated int64 / float32 tensors of the sizes' shapes")
+        slot = self._host[self._slot]
+        self._slot = (self._slot + 1) % len(self._host)
+        if slot[1] is not None:
+            slot[1].synchronize()   # the upload that last read this staging buffer (three steps ago)
+        h = slot[0].numpy()
+        h[0:8] = (N, N, 0, 0, 0, B, 3 * N, 0)
+        h[o["mol_ptr"]:o["mol_ptr"] + B + 1] = hp["mol_ptr"]
+        if ds is not None:
+            h[o["src_off"]:o["src_off"] + B] = ds.off[batch.ids]
+        self.blob.copy_(slot[0], non_blocking=True)
+        slot[1] = torch.cuda.Event()
+        slot[1].record()
+        base = self.blob.data_ptr()
+        g = _lib.Gather()
+        g.option, g.x_cols = 0, self.x.size(1)
+        g.mol_ptr = base + 4 * o["mol_ptr"]
+        g.x_dst, g.pos_dst, g.batch_dst = ptr(self.x), ptr(self.positions), ptr(self.batch_vec)
+        if ds is not None:
+            g.x_src, g.pos_src, g.src_off = ptr(ds.x), ptr(ds.positions), base + 4 * o["src_off"]
+        else:
+            g.x_src, g.pos_src, g.src_off = ptr(batch.x), ptr(batch.positions), g.mol_ptr
+        if zero is not None:
+            g.zero, g.zero_count = ptr(zero), zero.numel()
+        call("geossl_gather_molecules", C.byref(g), B, stream())
+        self.real = (N, 0, 0, 0)
+        self.real_E = None
         return self.real

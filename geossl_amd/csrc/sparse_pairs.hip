@@ -54,6 +54,10 @@ __device__ __forceinline__ SpLds sp_carve(unsigned char* raw, int max_n) {
   return L;
 }
 
+// LDS holds max_n atoms: a molecule above the bound (the host checks it: layout.max_n, Bucket.fits) is given no pairs
+// instead of a walk past the arrays
+__device__ __forceinline__ int sp_mol_atoms(int n, int max_n) { return n <= max_n ? n : 0; }
+
 // positions and the bit matrix of molecule [a0, a0 + n) into LDS: a wave per target atom (radius_adj.h says which
 // edges exist)
 __device__ __forceinline__ void sp_adjacency(const float* __restrict__ pos, int a0, int n, int ws, float r2, int cap,
@@ -77,7 +81,7 @@ __global__ __launch_bounds__(SP_THREADS) void k_sparse_count(const float* __rest
   const int m = blockIdx.x;
   if (m >= B) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int a0 = mol_ptr[m], n = mol_ptr[m + 1] - a0, ws = sp_stride(max_n);
+  const int a0 = mol_ptr[m], n = sp_mol_atoms(mol_ptr[m + 1] - a0, max_n), ws = sp_stride(max_n);
   const SpLds L = sp_carve(smem_raw, max_n);
   int* s_tot = L.s_a;
   sp_adjacency(pos, a0, n, ws, r2, cap, L);
@@ -124,12 +128,12 @@ __global__ __launch_bounds__(SP_THREADS) void k_sparse_fill(
     const int32_t* __restrict__ lo_cnt, int Pcap, int32_t* __restrict__ pair_i, int32_t* __restrict__ pair_j,
     float* __restrict__ pair_d, float* __restrict__ pair_c, uint8_t* __restrict__ pair_flag,
     int32_t* __restrict__ inc_ptr, int32_t* __restrict__ inc_pair, uint32_t* __restrict__ inc_src,
-    int32_t* __restrict__ n_pairs) {
+    int32_t* __restrict__ n_pairs, const int32_t* __restrict__ dyn_N) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int m = blockIdx.x;
   if (m >= B) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int a0 = mol_ptr[m], n = mol_ptr[m + 1] - a0, ws = sp_stride(max_n);
+  const int a0 = mol_ptr[m], n_all = mol_ptr[m + 1] - a0, n = sp_mol_atoms(n_all, max_n), ws = sp_stride(max_n);
   const SpLds L = sp_carve(smem_raw, max_n);
   int* s_a = L.s_a;
   int* s_b = L.s_b;
@@ -156,7 +160,9 @@ __global__ __launch_bounds__(SP_THREADS) void k_sparse_fill(
   const int base = s_a[0], total = min(s_b[0], Pcap);
   __syncthreads();
   if (m == 0 && tid == 0) n_pairs[0] = total;
-  if (m == B - 1 && tid == 0) inc_ptr[N] = 2 * total;
+  if (m == B - 1 && tid == 0) inc_ptr[dyn_count(N, dyn_N)] = 2 * total;  // (N real atoms: mol_ptr[B])
+  if (n != n_all)  // (a molecule above the LDS bound: empty incidence lists)
+    for (int a = tid; a < n_all; a += SP_THREADS) inc_ptr[a0 + a] = 2 * base;
   // rows past the real ones: harmless to a kernel that only knows the capacity (never a zero distance)
   for (int p = total + m * SP_THREADS + tid; p < Pcap; p += B * SP_THREADS) {
     pair_i[p] = 0;
@@ -365,20 +371,22 @@ __global__ __launch_bounds__(256) void k_gather_live_rows(const float* __restric
 // partner, separate multiply and add: the rounding sequence of k_aggregate.  One wave per target atom, a lane owns VW
 // adjacent columns; the entries of a target are read 64 at a time (one per lane), the rows of the ones that count four at
 // a time (four filter rows and four x rows in flight).  Workgroup b runs on XCD b mod 8: the targets are dealt so that
-// an XCD gets a contiguous range of atoms and a molecule's x rows stay in one L2.  Every row of out is written.
+// an XCD gets a contiguous range of atoms and a molecule's x rows stay in one L2.  Every row of out is written
+// (`_dyn`: every row below the real count *dyn_N; N is then the capacity the grid was sized by).
 template <int VW>
 __global__ __launch_bounds__(SP_THREADS) void k_aggregate_sparse(const float* __restrict__ x,
                                                                  const float* __restrict__ Wf,
                                                                  const int32_t* __restrict__ inc_ptr,
                                                                  const int32_t* __restrict__ inc_pair,
                                                                  const uint32_t* __restrict__ inc_src, int N, int F,
-                                                                 int swap, float* __restrict__ out) {
+                                                                 int swap, float* __restrict__ out,
+                                                                 const int32_t* __restrict__ dyn_N) {
 #pragma clang fp contract(off)
   typedef float V __attribute__((ext_vector_type(VW)));
   const int per = gridDim.x / 8;
   const int blk = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
   const int t = blk * SP_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (t >= N) return;
+  if (t >= dyn_count(N, dyn_N)) return;  // (a capacity launch: rows at and past the real count are not touched)
   const bool col = VW * lane < F;
   const int f = col ? VW * lane : 0;
   const int k0 = inc_ptr[t], k1 = inc_ptr[t + 1];
@@ -448,11 +456,11 @@ __global__ __launch_bounds__(64) void k_pair_position_grad_sparse(const float* _
 
 }  // namespace
 
-extern "C" int geossl_sparse_pairs_build(const float* pos, const int32_t* mol_ptr, int64_t B, int64_t N, int max_n,
-                                         float r2, int cap, float cutoff, int64_t capacity, int32_t* mol_cnt,
-                                         int32_t* up_cnt, int32_t* lo_cnt, int32_t* pair_i, int32_t* pair_j,
-                                         float* pair_d, float* pair_c, uint8_t* pair_flag, int32_t* inc_ptr,
-                                         int32_t* inc_pair, uint32_t* inc_src, int32_t* n_pairs, hipStream_t stream) {
+static int sparse_pairs_build(const float* pos, const int32_t* mol_ptr, int64_t B, int64_t N, int max_n, float r2,
+                              int cap, float cutoff, int64_t capacity, int32_t* mol_cnt, int32_t* up_cnt,
+                              int32_t* lo_cnt, int32_t* pair_i, int32_t* pair_j, float* pair_d, float* pair_c,
+                              uint8_t* pair_flag, int32_t* inc_ptr, int32_t* inc_pair, uint32_t* inc_src,
+                              int32_t* n_pairs, const int32_t* dyn_N, hipStream_t stream) {
   if (max_n < 1 || max_n > GEOSSL_RADIUS_MAX_N || B <= 0 || N <= 0 || capacity < 0 || capacity > (1ll << 29))
     return (int)hipErrorInvalidValue;
   const size_t lds = sp_lds_bytes(max_n);
@@ -463,9 +471,29 @@ extern "C" int geossl_sparse_pairs_build(const float* pos, const int32_t* mol_pt
   GEOSSL_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_sparse_fill, dim3((unsigned)B), dim3(SP_THREADS), lds, stream, pos, mol_ptr, (int)B, (int)N, max_n,
                      r2, cap, cutoff, mol_cnt, up_cnt, lo_cnt, (int)capacity, pair_i, pair_j, pair_d, pair_c, pair_flag,
-                     inc_ptr, inc_pair, inc_src, n_pairs);
+                     inc_ptr, inc_pair, inc_src, n_pairs, dyn_N);
   GEOSSL_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int geossl_sparse_pairs_build(const float* pos, const int32_t* mol_ptr, int64_t B, int64_t N, int max_n,
+                                         float r2, int cap, float cutoff, int64_t capacity, int32_t* mol_cnt,
+                                         int32_t* up_cnt, int32_t* lo_cnt, int32_t* pair_i, int32_t* pair_j,
+                                         float* pair_d, float* pair_c, uint8_t* pair_flag, int32_t* inc_ptr,
+                                         int32_t* inc_pair, uint32_t* inc_src, int32_t* n_pairs, hipStream_t stream) {
+  return sparse_pairs_build(pos, mol_ptr, B, N, max_n, r2, cap, cutoff, capacity, mol_cnt, up_cnt, lo_cnt, pair_i, pair_j,
+                            pair_d, pair_c, pair_flag, inc_ptr, inc_pair, inc_src, n_pairs, nullptr, stream);
+}
+
+extern "C" int geossl_sparse_pairs_build_dyn(const float* pos, const int32_t* mol_ptr, int64_t B, int64_t N, int max_n,
+                                             float r2, int cap, float cutoff, int64_t capacity, int32_t* mol_cnt,
+                                             int32_t* up_cnt, int32_t* lo_cnt, int32_t* pair_i, int32_t* pair_j,
+                                             float* pair_d, float* pair_c, uint8_t* pair_flag, int32_t* inc_ptr,
+                                             int32_t* inc_pair, uint32_t* inc_src, int32_t* n_pairs,
+                                             const int32_t* dyn_N, hipStream_t stream) {
+  if (dyn_N == nullptr) return (int)hipErrorInvalidValue;
+  return sparse_pairs_build(pos, mol_ptr, B, N, max_n, r2, cap, cutoff, capacity, mol_cnt, up_cnt, lo_cnt, pair_i, pair_j,
+                            pair_d, pair_c, pair_flag, inc_ptr, inc_pair, inc_src, n_pairs, dyn_N, stream);
 }
 
 extern "C" int geossl_live_pairs_build(const float* pair_d, const float* pair_c, const uint8_t* pair_flag,
@@ -493,20 +521,33 @@ extern "C" int geossl_gather_live_rows(const float* src, const int32_t* row_slot
   return 0;
 }
 
-extern "C" int geossl_cfconv_aggregate_sparse(const float* x, const float* Wf, const int32_t* inc_ptr,
-                                              const int32_t* inc_pair, const uint32_t* inc_src, int64_t N, int F,
-                                              int swap, float* out, hipStream_t stream) {
+static int aggregate_sparse(const float* x, const float* Wf, const int32_t* inc_ptr, const int32_t* inc_pair,
+                            const uint32_t* inc_src, int64_t N, int F, int swap, float* out, const int32_t* dyn_N,
+                            hipStream_t stream) {
   if (N <= 0) return 0;
-  if (F != 32 && F != 64 && F != 128) return (int)hipErrorInvalidValue;
+  if ((F != 32 && F != 64 && F != 128) || N > (1ll << 30)) return (int)hipErrorInvalidValue;
   const unsigned blocks = (unsigned)((N + SP_WAVES - 1) / SP_WAVES), grid = 8 * ((blocks + 7) / 8);
   if (F == 128)
     hipLaunchKernelGGL(k_aggregate_sparse<2>, dim3(grid), dim3(SP_THREADS), 0, stream, x, Wf, inc_ptr, inc_pair, inc_src,
-                       (int)N, F, swap, out);
+                       (int)N, F, swap, out, dyn_N);
   else
     hipLaunchKernelGGL(k_aggregate_sparse<1>, dim3(grid), dim3(SP_THREADS), 0, stream, x, Wf, inc_ptr, inc_pair, inc_src,
-                       (int)N, F, swap, out);
+                       (int)N, F, swap, out, dyn_N);
   GEOSSL_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int geossl_cfconv_aggregate_sparse(const float* x, const float* Wf, const int32_t* inc_ptr,
+                                              const int32_t* inc_pair, const uint32_t* inc_src, int64_t N, int F,
+                                              int swap, float* out, hipStream_t stream) {
+  return aggregate_sparse(x, Wf, inc_ptr, inc_pair, inc_src, N, F, swap, out, nullptr, stream);
+}
+
+extern "C" int geossl_cfconv_aggregate_sparse_dyn(const float* x, const float* Wf, const int32_t* inc_ptr,
+                                                  const int32_t* inc_pair, const uint32_t* inc_src, int64_t N, int F,
+                                                  int swap, float* out, const int32_t* dyn_N, hipStream_t stream) {
+  if (dyn_N == nullptr) return (int)hipErrorInvalidValue;
+  return aggregate_sparse(x, Wf, inc_ptr, inc_pair, inc_src, N, F, swap, out, dyn_N, stream);
 }
 
 extern "C" int geossl_pair_position_grad_sparse(const float* pos, const float* pair_d, const float* dd,

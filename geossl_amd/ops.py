@@ -145,10 +145,11 @@ class SparsePairs:
     partner | edge partner -> t << 30 | edge t -> partner << 31).  ``P`` is the CAPACITY every array is sized by (from
     host sizes, layout.sparse_pair_capacity); ``n_pairs`` (int32 [1], device) the real number of rows, which nothing
     here reads back - the filter kernels take its address as their dyn_P.  Rows past it hold flag 0, pair_i = pair_j = 0,
-    pair_c = 0, pair_d = cutoff."""
+    pair_c = 0, pair_d = cutoff.  ``dyn_N``: None, or - the list of a capacity bucket's layout, where ``N`` is a
+    capacity too - the device address of the real atom count, which the aggregation's capacity launch reads."""
 
     __slots__ = ("P", "N", "pair_i", "pair_j", "pair_d", "pair_c", "pair_flag", "inc_ptr", "inc_pair", "inc_src",
-                 "n_pairs")
+                 "n_pairs", "dyn_N")
 
     @property
     def dyn_P(self):
@@ -156,7 +157,9 @@ class SparsePairs:
 
 
 def sparse_pair_geometry(pos, layout, cutoff, max_num_neighbors=32):
-    """Radius graph as a sparse pair list -> SparsePairs.  No device-to-host read."""
+    """Radius graph as a sparse pair list -> SparsePairs.  No device-to-host read.  A capacity bucket's layout (it
+    carries ``dyn``): N, P and max_n are capacities, mol_ptr holds the real offsets and the real atom count is read on
+    the device (geossl_sparse_pairs_build_dyn)."""
     if not getattr(layout, "sparse", False):
         raise _lib.GeosslHipError("sparse_pair_geometry needs a sparse layout (GEOSSL_SPARSE_PAIRS=1 makes any layout one)")
     _check_graph_size(layout)
@@ -176,21 +179,31 @@ def sparse_pair_geometry(pos, layout, cutoff, max_num_neighbors=32):
     sp.n_pairs = torch.empty(1, **i32)
     work = torch.empty(layout.B + 2 * N, **i32)
     r2 = float(torch.tensor(float(cutoff) * float(cutoff), dtype=torch.float32))
-    call("geossl_sparse_pairs_build", ptr(pos), ptr(layout.mol_ptr), layout.B, N, layout.max_n, r2,
-         radius_cap(max_num_neighbors), float(cutoff), P, ptr(work), ptr(work[layout.B:]), ptr(work[layout.B + N:]),
-         ptr(sp.pair_i), ptr(sp.pair_j), ptr(sp.pair_d), ptr(sp.pair_c), ptr(sp.pair_flag), ptr(sp.inc_ptr),
-         ptr(sp.inc_pair), ptr(sp.inc_src), ptr(sp.n_pairs), stream())
+    sp.dyn_N = _dyn(getattr(layout, "dyn", None), "n_atoms2")
+    args = (ptr(pos), ptr(layout.mol_ptr), layout.B, N, layout.max_n, r2,
+            radius_cap(max_num_neighbors), float(cutoff), P, ptr(work), ptr(work[layout.B:]), ptr(work[layout.B + N:]),
+            ptr(sp.pair_i), ptr(sp.pair_j), ptr(sp.pair_d), ptr(sp.pair_c), ptr(sp.pair_flag), ptr(sp.inc_ptr),
+            ptr(sp.inc_pair), ptr(sp.inc_src), ptr(sp.n_pairs))
+    if sp.dyn_N is None:
+        call("geossl_sparse_pairs_build", *args, stream())
+    else:
+        call("geossl_sparse_pairs_build_dyn", *args, sp.dyn_N, stream())
     return sp
 
 
 def aggregate_sparse(x, Wf_l, pairs, swap=False, out=None):
     """Neighbour aggregation over a sparse pair list: x, out [N, F]; Wf_l [P, F] rows of the list.  swap: the transposed
-    graph (the backward).  Bit-identical to `aggregate` on the same filter rows."""
+    graph (the backward).  Bit-identical to `aggregate` on the same filter rows.  The list of a capacity bucket
+    (``pairs.dyn_N``): rows at and past the real atom count are neither read nor written."""
     N, F = x.shape
     if out is None:
         out = torch.empty_like(x)
-    call("geossl_cfconv_aggregate_sparse", ptr(x), ptr(Wf_l), ptr(pairs.inc_ptr), ptr(pairs.inc_pair), ptr(pairs.inc_src),
-         N, F, 1 if swap else 0, ptr(out), stream())
+    args = (ptr(x), ptr(Wf_l), ptr(pairs.inc_ptr), ptr(pairs.inc_pair), ptr(pairs.inc_src), N, F, 1 if swap else 0,
+            ptr(out))
+    if pairs.dyn_N is None:
+        call("geossl_cfconv_aggregate_sparse", *args, stream())
+    else:
+        call("geossl_cfconv_aggregate_sparse_dyn", *args, pairs.dyn_N, stream())
     return out
 
 
@@ -242,7 +255,8 @@ class PairGraph:
 
 def pair_graph(pos, layout, cutoff, want_rows, want_pos):
     """-> PairGraph.  A SPARSE layout (a structure above 255 atoms, layout.want_sparse) gets the compacted list of the
-    pairs that carry an edge: P is then the list's capacity and its real row count stays on the device.  A dense layout
+    pairs that carry an edge: P is then the list's capacity and its real row count stays on the device (the sparse
+    layout of a capacity bucket, bucket.SPARSE: the atom count is a capacity as well, read on the device).  A dense layout
     gets its pair slots, and - unless GEOSSL_LIVE_PAIRS=0 - the list of the slots that carry an edge (93 % of them in
     QM9-sized molecules at 5 A, fewer in extended ones; `live_pairs`, one launch) for the filter network to run on: with
     parameter gradients (want_rows) or without a position gradient (want_pos).  The position gradient reads T and Wf by
@@ -252,8 +266,6 @@ def pair_graph(pos, layout, cutoff, want_rows, want_pos):
     g.layout, g.sparse = layout, bool(getattr(layout, "sparse", False))
     dyn = getattr(layout, "dyn", None)
     if g.sparse:
-        if dyn is not None:
-            raise _lib.GeosslHipError("capacity buckets hold molecules of at most 255 atoms (bucket.MAX_N)")
         g.slots = g.rows = sparse_pair_geometry(pos, layout, cutoff)
         g.fwd_on_rows, g.loop_flag = False, None
         return g

@@ -19,7 +19,7 @@ from collections import OrderedDict
 
 import numpy as np
 import torch
-from .switches import env as _env
+from .switches import env as _env, sparse_buckets
 
 from . import _lib, ops
 from ._lib import call, ptr, stream
@@ -411,6 +411,10 @@ class StepGraphs:
       tuples, batches built by hand): one graph per ``structure_fingerprint`` - the size sequence, or the tensor objects;
       a structure that only a fingerprint identifies is captured on its SECOND sighting (a loader that never repeats one
       never pays for a capture);
+    * a batch with a SPARSE layout (a structure of 256 to 1024 atoms - LBA's pockets - or GEOSSL_SPARSE_PAIRS=1) in a
+      one-view SchNet step that reads no pair tuples (``pair_tuples=False``: Supervised): one graph per number of
+      structures in a sparse bucket (``bucket.SPARSE``) - by default the handles of a DeviceLoader, with
+      ``GEOSSL_SPARSE_BUCKETS=1`` collated batches too (``=0``: neither; such a batch is served as the first entry says);
     * every other SchNet batch - ragged molecules in shuffled order, the reference's loader (pretrain_GeoSSL.py:301) - one
       graph per (molecules in the batch, tuple option) at a CAPACITY (``geossl_amd/bucket.py``): the graph's kernels read
       the batch's real atom / pair-slot / super-edge counts and every index structure from device memory, so ONE graph
@@ -421,7 +425,7 @@ class StepGraphs:
     batches that come back every epoch)."""
 
     def __init__(self, fwd_bwd, model_3d, max_graphs=256, split=None, mode="auto", normalize=False, modules=None,
-                 noise_keys=None, views=2):
+                 noise_keys=None, views=2, pair_tuples=True):
         # split = (fwd(batch, noise) -> loss with its autograd graph, bwd(loss)): forward and backward captured as TWO
         # graphs (same pool, same capture stream; replayed in this order) - the forward's loss is then on the device
         # before the backward runs, and the backward can run on a side stream while the host goes on (_AutogradStep)
@@ -432,6 +436,9 @@ class StepGraphs:
         self.noise_keys = _NOISE_KEYS if noise_keys is None else tuple(noise_keys)
         # views of the molecules the backbone sees in a bucket (1: the Distance / Charge Prediction steps)
         self.views = views
+        # the step reads the batch's pair tuples (step.Objective.pair_tuples); False: a one-view SchNet step whose
+        # batches with a sparse layout go through a sparse bucket
+        self.pair_tuples = pair_tuples
         self.graphs, self.pool = OrderedDict(), None
         self.enabled = True
         self.captures = 0
@@ -450,8 +457,14 @@ class StepGraphs:
     def bucket_key(self, batch):
         """("bucket", molecules, option) when the batch goes through a capacity bucket, else None."""
         from . import bucket as bk
-        if (self.mode != "auto" or not self.bucket_ok or _env("GEOSSL_NO_BUCKETS")
-                or not bk.eligible(batch, self.model_3d, self.normalize)
+        if (self.mode != "auto" or not self.bucket_ok or _env("GEOSSL_NO_BUCKETS") or self.modules is None):
+            return None
+        # a sparse layout (a structure above 255 atoms, or GEOSSL_SPARSE_PAIRS=1) in a step that reads no pair tuples: the
+        # sparse bucket - no other bucket takes such a layout, and every other step keeps its routing
+        if (not self.pair_tuples and self.views == 1 and self.model_3d == "schnet"
+                and sparse_buckets(getattr(batch, "_dataset", None) is not None) and bk.sparse_eligible(batch)):
+            return ("bucket", len(batch._sizes), bk.SPARSE) if self._modules_ok() else None
+        if (not bk.eligible(batch, self.model_3d, self.normalize)
                 or (self.model_3d != "painn" and bk.is_uniform(batch))   # (PaiNN: the edge list differs batch by batch anyway)
                 or self.modules is None or not self._modules_ok()):
             return None
@@ -560,9 +573,14 @@ class StepGraphs:
         old = self.graphs.pop(key, None)
         option = key[2]
         counts = bk.batch_counts(bk.sizes_array(batch), option, self.views)
-        caps = bk.capacities(*counts, B=len(batch._sizes), prev=None if old is None else old["bucket"].caps(),
-                             sizes=bk.sizes_array(batch))
-        max_n = bk.max_n_class(bk.size_range(batch)[1], None if old is None else old["bucket"].max_n, self.model_3d)
+        if option == bk.SPARSE:
+            caps = bk.sparse_capacities(counts[0], len(batch._sizes), None if old is None else old["bucket"].caps(),
+                                        sizes=bk.sizes_array(batch))
+            max_n = bk.sparse_max_n_class(bk.size_range(batch)[1], None if old is None else old["bucket"].max_n)
+        else:
+            caps = bk.capacities(*counts, B=len(batch._sizes), prev=None if old is None else old["bucket"].caps(),
+                                 sizes=bk.sizes_array(batch))
+            max_n = bk.max_n_class(bk.size_range(batch)[1], None if old is None else old["bucket"].max_n, self.model_3d)
         E_cap = 0
         if self.model_3d == "painn":
             E_cap = bk.edge_capacity(self._edges(batch), len(batch._sizes), None if old is None else old["bucket"].E_cap,
@@ -576,7 +594,7 @@ class StepGraphs:
         dev = batch.device if from_ds else batch.positions.device
         try:
             bkt = bk.Bucket(dev, len(batch._sizes), caps, option,
-                            x_cols=batch.x_cols if from_ds else batch.x.size(1), max_n=max_n,
+                            x_cols=batch.x_cols if from_ds else (batch.x.size(1) if batch.x.dim() == 2 else 1), max_n=max_n,
                             n_rbf=getattr(getattr(self.modules[0], "radial_basis", None), "n_rbf", 20),
                             kind=self.model_3d, E_cap=E_cap, views=self.views, T_cap=T_cap)
             bkt.fill(batch, counts)
@@ -1064,7 +1082,8 @@ class _AutogradStep:
                                                mode=getattr(args, "step_graph_mode", "auto"),
                                                normalize=obj.normalize and bool(getattr(args, "normalize", False)),
                                                modules=(self.model, self.n1, self.n2),
-                                               noise_keys=obj.noise_keys(args), views=obj.views)
+                                               noise_keys=obj.noise_keys(args), views=obj.views,
+                                               pair_tuples=obj.pair_tuples)
             sg.zero_with_refresh = self.gflat
         if not sg.enabled:
             return None

@@ -208,7 +208,8 @@ SUPERVISED = Objective(
     capture_inputs=lambda eng, args, batch, mu, sigma, noise, device_noise:
         {"target": target_column(batch, args.task_id)},
     write_inputs=lambda eng, args, sg, g, batch, mu, sigma, noise, device_noise:
-        write_targets(g, batch, args.task_id))
+        write_targets(g, batch, args.task_id),
+    pair_tuples=False)
 
 
 def _raise_like_squeeze(B):
@@ -282,8 +283,10 @@ class SupervisedTrainer(StepTrainer):
     ``step(batch) -> loss`` on the device.  ``set_lr(lr)`` between epochs is how a schedule is applied
     (``optim.cosine_annealing_lr`` is CosineAnnealingLR's), ``set_stats(mean, std)`` changes the target normalisation
     without a recapture.  ``use_graph=True``: forward + backward are captured into HIP graphs and replayed (ragged SchNet /
-    PaiNN batches and DeviceLoader handles share one ONE-view capacity-bucket graph per batch size at width 128; anything
-    else one graph per structure); the target column is a static input of the graph."""
+    PaiNN batches and DeviceLoader handles share one ONE-view capacity-bucket graph per batch size at width 128 - SchNet
+    handles with structures of 256 to 1024 atoms, LBA's pockets, through the sparse bucket of geossl_amd/bucket.py, and
+    collated batches of such structures with GEOSSL_SPARSE_BUCKETS=1; anything else one graph per structure); the target
+    column is a static input of the graph."""
 
     def __init__(self, model, graph_pred_linear, TRAIN_mean, TRAIN_std, task_id=6, loss="mae", lr=5e-4,
                  weight_decay=0.0, model_3d="schnet", use_graph=False, max_graphs=256, graph_mode="auto"):
@@ -297,7 +300,7 @@ class SupervisedTrainer(StepTrainer):
         self.head = graph_pred_linear
         self.model_3d, self.loss_kind, self.task_id = model_3d, loss, int(task_id)
         super().__init__([model, graph_pred_linear], model_3d, lr, weight_decay, use_graph, max_graphs, graph_mode,
-                         noise_keys=("target",))
+                         noise_keys=("target",), pair_tuples=False)
         self.stats = _Stats(self.flat.grad.device)
         self.stats.set(TRAIN_mean, TRAIN_std)
         self.args = _StepArgs(model_3d, loss, task_id, self.stats.t)

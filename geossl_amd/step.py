@@ -32,6 +32,9 @@ class Objective:
     name            first entry of the default graph key
     views           views of the molecules the backbone sees in a capacity bucket (1 or 2)
     normalize       ``args.normalize`` keeps a batch off capacity buckets (DDM only: its row normalisation is over atoms)
+    pair_tuples     the step reads the batch's pair tuples (``super_edge_index``); False (Supervised): a batch whose
+                    layout is sparse - a structure above 255 atoms - may go through a sparse bucket (bucket.SPARSE), which
+                    enumerates none
     head_params     head module -> the parameters the step reaches
     graph_key       args -> the key of the engine's StepGraphs (what a graph binds by value)
     noise_keys      args -> names of the per-step static inputs of a graph (StepGraphs.noise_keys)
@@ -44,8 +47,9 @@ class Objective:
     """
 
     def __init__(self, name, forward, views=1, normalize=False, head_params=None, graph_key=None, noise_keys=None,
-                 step_args=None, capture_inputs=_no_inputs, write_inputs=None, result=None):
+                 step_args=None, capture_inputs=_no_inputs, write_inputs=None, result=None, pair_tuples=True):
         self.name, self.forward, self.views, self.normalize = name, forward, views, normalize
+        self.pair_tuples = pair_tuples
         self.head_params = head_params or (lambda h: list(h.parameters()))
         self.graph_key = graph_key or (lambda args: (name, args.model_3d))
         self.noise_keys = noise_keys or (lambda args: ())
@@ -133,7 +137,7 @@ class StepTrainer:
     with_extra = False   # a replayed step returns (loss, the graph's extra static outputs)
 
     def __init__(self, modules, model_3d, lr, weight_decay, use_graph, max_graphs, graph_mode, noise_keys=(), views=1,
-                 one_dtype=torch.float32):
+                 one_dtype=torch.float32, pair_tuples=True):
         from .pretrain_GeoSSL import StepGraphs
         self.model = modules[0]
         self.flat = FlatParams(modules)
@@ -142,10 +146,11 @@ class StepTrainer:
         self.use_graph = use_graph
         # graph_mode "auto": ragged batches share one capacity-bucket graph per batch size, equal-sized molecules one
         # graph per size, anything else one per structure from its second sighting on; "structure": one graph per
-        # structure fingerprint, captured at first sight (StepGraphs)
+        # structure fingerprint, captured at first sight (StepGraphs).  pair_tuples=False: the step reads no pair tuples
+        # (Objective.pair_tuples) - its batches above 255 atoms per structure share a sparse bucket graph too
         self.step_graphs = StepGraphs(self._fwd_bwd, model_3d, max_graphs, mode=graph_mode,
                                       modules=tuple((list(modules) + [None, None])[:3]), noise_keys=noise_keys,
-                                      views=views)
+                                      views=views, pair_tuples=pair_tuples)
         self.step_graphs.zero_with_refresh = self.flat.grad
         self._one = torch.ones((), dtype=one_dtype, device=self.flat.grad.device)
 

@@ -32,3 +32,17 @@ def masked_painn_buckets():
     bucket, their surviving radius edges counted on the device.  ``0``: they are collated - a count launch and a read-back
     of the B counts - and run on their own tensors, the routing before the bucket took them (A/B timing)."""
     return env("GEOSSL_MASKED_PAINN_BUCKETS", "1") != "0"
+
+
+def sparse_buckets(handle):
+    """``GEOSSL_SPARSE_BUCKETS``: the batches of a step that reads no pair tuples (Supervised) whose layout is sparse - a
+    structure above 255 atoms, or ``GEOSSL_SPARSE_PAIRS=1`` - replay one capacity-bucket graph per batch size
+    (``bucket.SPARSE``).  ``1``: every such batch; ``0``: none - the routing before that bucket existed: a per-structure
+    graph from the second sighting on, eager launches before.  Unset: ``handle`` - the handles of a ``DeviceLoader`` do,
+    collated batches do not (measured on shuffled pockets, DESIGN section 5: the handles' step is 9 - 13 % shorter through
+    the bucket; a collated batch's step is bound by the device and the host's collation either way, and the bucket's
+    replay did not beat the eager launches there)."""
+    v = env("GEOSSL_SPARSE_BUCKETS")
+    if v == "0":
+        return False
+    return True if v == "1" else bool(handle)

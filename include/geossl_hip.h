@@ -1052,6 +1052,15 @@ int geossl_sparse_pairs_build(const float* pos, const int32_t* mol_ptr, int64_t 
                               int32_t* lo_cnt, int32_t* pair_i, int32_t* pair_j, float* pair_d, float* pair_c,
                               uint8_t* pair_flag, int32_t* inc_ptr, int32_t* inc_pair, uint32_t* inc_src,
                               int32_t* n_pairs, hipStream_t stream);
+/* The build for a capacity bucket: N is the CAPACITY of the per-atom arrays (up_cnt / lo_cnt [N], inc_ptr [N + 1]) and
+ * dyn_N (device, not null) the batch's real atom count; mol_ptr holds the B real offsets (B is exact).  No atom row at
+ * or past the real count is read; inc_ptr[0 .. N_real] is written; max_n is a bound on the largest molecule that only
+ * sizes LDS (the list does not depend on it).  Everything else as geossl_sparse_pairs_build, bit for bit.          */
+int geossl_sparse_pairs_build_dyn(const float* pos, const int32_t* mol_ptr, int64_t B, int64_t N, int max_n, float r2,
+                                  int cap, float cutoff, int64_t capacity, int32_t* mol_cnt, int32_t* up_cnt,
+                                  int32_t* lo_cnt, int32_t* pair_i, int32_t* pair_j, float* pair_d, float* pair_c,
+                                  uint8_t* pair_flag, int32_t* inc_ptr, int32_t* inc_pair, uint32_t* inc_src,
+                                  int32_t* n_pairs, const int32_t* dyn_N, hipStream_t stream);
 
 /* ---- live-pair list of a dense layout (csrc/sparse_pairs.hip, csrc/graph.hip) -------------------------------------
  * The filter network has work only for the pair slots that carry an edge (pair_flag != 0).
@@ -1087,6 +1096,11 @@ int geossl_gather_live_rows(const float* src, const int32_t* row_slot, const int
 int geossl_cfconv_aggregate_sparse(const float* x, const float* Wf, const int32_t* inc_ptr, const int32_t* inc_pair,
                                    const uint32_t* inc_src, int64_t N, int F, int swap, float* out,
                                    hipStream_t stream);
+/* The same launch at a capacity: the grid comes from N, a wave whose atom is at or past *dyn_N (device, not null)
+ * returns - those rows of x and out are neither read nor written.  Same arithmetic, bit for bit.                    */
+int geossl_cfconv_aggregate_sparse_dyn(const float* x, const float* Wf, const int32_t* inc_ptr,
+                                       const int32_t* inc_pair, const uint32_t* inc_src, int64_t N, int F, int swap,
+                                       float* out, const int32_t* dyn_N, hipStream_t stream);
 /* geossl_pair_position_grad through the incidence lists: dd is [L, P] (P = capacity) from geossl_cfconv_filter_dpos. */
 int geossl_pair_position_grad_sparse(const float* pos, const float* pair_d, const float* dd, const int32_t* inc_ptr,
                                      const int32_t* inc_pair, const uint32_t* inc_src, int64_t N, int64_t P, int L,
