@@ -19,9 +19,9 @@ from collections import OrderedDict
 
 import numpy as np
 import torch
-from .switches import env as _env, sparse_buckets
+from .switches import env as _env
 
-from . import _lib, ops
+from . import _lib, bucket as bk, ops
 from ._lib import call, ptr, stream
 from .layout import MolLayout
 from .step import Objective, StepTrainer, _OWN_CAPTURE, engine_for, latent, own_capture_open, with_counts  # noqa: F401
@@ -455,25 +455,17 @@ class StepGraphs:
 
     # ---- which graph
     def bucket_key(self, batch):
-        """("bucket", molecules, option) when the batch goes through a capacity bucket, else None."""
-        from . import bucket as bk
+        """("bucket", molecules, option) when the batch goes through a capacity bucket (bucket.route), else None."""
         if (self.mode != "auto" or not self.bucket_ok or _env("GEOSSL_NO_BUCKETS") or self.modules is None):
             return None
-        # a sparse layout (a structure above 255 atoms, or GEOSSL_SPARSE_PAIRS=1) in a step that reads no pair tuples: the
-        # sparse bucket - no other bucket takes such a layout, and every other step keeps its routing
-        if (not self.pair_tuples and self.views == 1 and self.model_3d == "schnet"
-                and sparse_buckets(getattr(batch, "_dataset", None) is not None) and bk.sparse_eligible(batch)):
-            return ("bucket", len(batch._sizes), bk.SPARSE) if self._modules_ok() else None
-        if (not bk.eligible(batch, self.model_3d, self.normalize)
-                or (self.model_3d != "painn" and bk.is_uniform(batch))   # (PaiNN: the edge list differs batch by batch anyway)
-                or self.modules is None or not self._modules_ok()):
+        option = bk.route(batch, self.model_3d, self.views, self.pair_tuples, self.normalize)
+        if option is None or not self._modules_ok():
             return None
-        return ("bucket", len(batch._sizes), bk.option_of(batch))
+        return ("bucket", len(batch._sizes), option)
 
     def _modules_ok(self):
         """bucket.modules_ok of this engine's modules, remembered per state of the switches it reads (the modules of a
         StepGraphs are fixed: a replaced parameter rebuilds the engine, _AutogradStep.unchanged / DDMTrainer)."""
-        from . import bucket as bk
         env = tuple(_env(k) for k in bk.MODULE_SWITCHES + bk.PAINN_SWITCHES)
         if self._mod_ok is None or self._mod_ok[0] != env:
             self._mod_ok = (env, bk.modules_ok(*self.modules))
@@ -483,13 +475,9 @@ class StepGraphs:
         """The graph that serves this batch (None: not captured yet, or its bucket is too small)."""
         key = self.bucket_key(batch)
         if key is not None:
-            from . import bucket as bk
             g = self.graphs.get(key)
-            if g is None:
-                return None
-            counts = bk.batch_counts(bk.sizes_array(batch), key[2], self.views)
-            if not g["bucket"].fits(counts, bk.size_range(batch)[1], self._edges(batch),
-                                    bk.n_triples(batch) if key[2] == bk.TRIPLES else None):
+            counts = None if g is None else g["bucket"].fits_batch(batch)
+            if counts is None:
                 return None
             g["counts"] = counts
             self.graphs.move_to_end(key)
@@ -500,23 +488,12 @@ class StepGraphs:
             self.graphs.move_to_end(fp)
         return g
 
-    def _edges(self, batch):
-        """Edges of the batch's radius_edge_index (PaiNN; a tensor shape or a host-side count / bound: no read-back),
-        else None."""
-        if self.model_3d != "painn":
-            return None
-        if getattr(batch, "_dataset", None) is not None:
-            from . import bucket as bk
-            return bk.handle_edges(batch)   # (the dataset's host-side edge counts; a masked handle: their upper bound)
-        return int(batch.radius_edge_index.size(1))
-
     def capture_now(self, batch):
         """Should a batch without a graph be captured at this sighting?  Buckets and equal-sized molecules: yes (their
         graph serves every later batch of the kind); a structure known by fingerprint only: from its second sighting on
         (mode "structure": always)."""
         if self.mode != "auto" or self.bucket_key(batch) is not None:
             return True
-        from . import bucket as bk
         if bk.is_uniform(batch) and getattr(batch, "_canonical", None) is not None and self.model_3d == "schnet":
             return True
         return self.seen_before(batch)
@@ -569,52 +546,20 @@ class StepGraphs:
         return g
 
     def _capture_bucket(self, key, batch, noise):
-        from . import bucket as bk
         old = self.graphs.pop(key, None)
-        option = key[2]
-        counts = bk.batch_counts(bk.sizes_array(batch), option, self.views)
-        if option == bk.SPARSE:
-            caps = bk.sparse_capacities(counts[0], len(batch._sizes), None if old is None else old["bucket"].caps(),
-                                        sizes=bk.sizes_array(batch))
-            max_n = bk.sparse_max_n_class(bk.size_range(batch)[1], None if old is None else old["bucket"].max_n)
-        else:
-            caps = bk.capacities(*counts, B=len(batch._sizes), prev=None if old is None else old["bucket"].caps(),
-                                 sizes=bk.sizes_array(batch))
-            max_n = bk.max_n_class(bk.size_range(batch)[1], None if old is None else old["bucket"].max_n, self.model_3d)
-        E_cap = 0
-        if self.model_3d == "painn":
-            E_cap = bk.edge_capacity(self._edges(batch), len(batch._sizes), None if old is None else old["bucket"].E_cap,
-                                     sizes=bk.sizes_array(batch))
-        T_cap = 0
-        if option == bk.TRIPLES:
-            T_cap = bk.triple_capacity(bk.n_triples(batch), len(batch._sizes), None if old is None else old["bucket"].T_cap)
+        prev = None if old is None else old["bucket"].sizes()
         del old  # (its graph and static buffers go before the larger ones are made)
         self._evict()
-        from_ds = getattr(batch, "_dataset", None) is not None
-        dev = batch.device if from_ds else batch.positions.device
+        args = bk.Bucket.sizing(batch, key[2], self.model_3d, self.views,
+                                getattr(getattr(self.modules[0], "radial_basis", None), "n_rbf", 20), prev)
         try:
-            bkt = bk.Bucket(dev, len(batch._sizes), caps, option,
-                            x_cols=batch.x_cols if from_ds else (batch.x.size(1) if batch.x.dim() == 2 else 1), max_n=max_n,
-                            n_rbf=getattr(getattr(self.modules[0], "radial_basis", None), "n_rbf", 20),
-                            kind=self.model_3d, E_cap=E_cap, views=self.views, T_cap=T_cap)
-            bkt.fill(batch, counts)
+            bkt = bk.Bucket(**args)
+            counts = bkt.fill(batch)
         except (ValueError, RuntimeError) as e:
             warnings.warn("capacity bucket not usable for this batch (%s); per-structure graphs from now on" % e)
             self.bucket_ok = False
             return None
-        N, P, S, W = counts
-        B = len(batch._sizes)
-        f32 = dict(dtype=torch.float32, device=dev)
-        sn = {"pos_noise": torch.zeros(bkt.N_cap, 3, **f32), "dist_noise_1": torch.zeros(bkt.S_cap, 1, **f32),
-              "dist_noise_2": torch.zeros(bkt.S_cap, 1, **f32),
-              "noise_level_1": torch.zeros(B, dtype=torch.long, device=dev),
-              "noise_level_2": torch.zeros(B, dtype=torch.long, device=dev),
-              # Charge Prediction's mask input: the device draw's seed, or the host-drawn list (k <= N entries)
-              "mask_seed": torch.zeros(1, dtype=torch.long, device=dev),
-              "mask_idx": torch.zeros(max(bkt.N_cap, 1), dtype=torch.long, device=dev),
-              # the Supervised step's target column (B exact)
-              "target": torch.zeros(B, **f32)}
-        sn = {k: sn[k] for k in self.noise_keys}
+        sn = bkt.static_noise(self.noise_keys)
         g0 = dict(bucket=bkt, noise=sn, counts=counts)
         self.copy_noise(g0, noise)
         g = self._capture(bkt.batch, sn)
@@ -700,10 +645,9 @@ class StepGraphs:
         if bkt is None:
             return g["noise"]
         N, P, S, W = g["counts"]
-        sn = g["noise"]
         # (the noise levels are per molecule: B is exact; a mask list holds k <= N entries, copy_noise writes k)
-        rows = {"pos_noise": N, "dist_noise_1": S, "dist_noise_2": S, "mask_idx": N}
-        return {k: (v[:rows[k]] if k in rows else v) for k, v in sn.items()}
+        real = {"N": N, "S": S}
+        return {k: (v[:real[r]] if (r := bk.NOISE_SHAPES[k][0]) in real else v) for k, v in g["noise"].items()}
 
     @staticmethod
     def copy_noise(g, noise):

@@ -305,10 +305,7 @@ def test_set_c_at_10_angstrom_through_the_bucket_graph_vs_oracle():
     # the same launches eagerly on a bucket of the same capacity
     te = _trainer(cfg, use_graph=False)
     eb = bk.Bucket(torch.device(DEV), B, bkt.caps(), "combination", max_n=bkt.max_n)
-    f32 = dict(dtype=torch.float32, device=DEV)
-    sn = {"pos_noise": torch.zeros(eb.N_cap, 3, **f32), "dist_noise_1": torch.zeros(eb.S_cap, 1, **f32),
-          "dist_noise_2": torch.zeros(eb.S_cap, 1, **f32), "noise_level_1": torch.zeros(B, dtype=torch.long, device=DEV),
-          "noise_level_2": torch.zeros(B, dtype=torch.long, device=DEV)}
+    sn = eb.static_noise(pg._NOISE_KEYS)
     for i, (b_, nz_) in enumerate(zip(raws, nzs)):
         N, P, S, W = eb.fill(pg.Batch.from_numpy(b_, DEV))
         sn["pos_noise"][:N].copy_(t(nz_["pos_noise"], DEV))
@@ -446,10 +443,7 @@ def test_painn_bucket_replays_on_different_edge_lists_bit_for_bit_and_matches_th
     # ---- the same launches eagerly on a bucket of the same capacity
     te = trainer(False)
     eb = bk.Bucket(torch.device(DEV), B, bkt.caps(), "combination", max_n=bkt.max_n, kind="painn", E_cap=bkt.E_cap)
-    f32 = dict(dtype=torch.float32, device=DEV)
-    sn = {"pos_noise": torch.zeros(eb.N_cap, 3, **f32), "dist_noise_1": torch.zeros(eb.S_cap, 1, **f32),
-          "dist_noise_2": torch.zeros(eb.S_cap, 1, **f32), "noise_level_1": torch.zeros(B, dtype=torch.long, device=DEV),
-          "noise_level_2": torch.zeros(B, dtype=torch.long, device=DEV)}
+    sn = eb.static_noise(pg._NOISE_KEYS)
     for i, (bt, nz) in enumerate(zip(bts, nzs)):
         N, P, S, W = eb.fill(bt)
         sn["pos_noise"][:N].copy_(t(nz["pos_noise"], DEV))
@@ -681,10 +675,7 @@ def test_painn_bucket_with_oversized_molecules_replays_bit_for_bit(fwd_split, mo
     assert bkt.max_n == 128 and bkt.big_caps == ((44, 73) if fwd_split else (73,)) and int(bkt.el.status) == 0
     te = trainer(False)
     eb = bk.Bucket(torch.device(DEV), B, bkt.caps(), "combination", max_n=bkt.max_n, kind="painn", E_cap=bkt.E_cap)
-    f32 = dict(dtype=torch.float32, device=DEV)
-    sn = {"pos_noise": torch.zeros(eb.N_cap, 3, **f32), "dist_noise_1": torch.zeros(eb.S_cap, 1, **f32),
-          "dist_noise_2": torch.zeros(eb.S_cap, 1, **f32), "noise_level_1": torch.zeros(B, dtype=torch.long, device=DEV),
-          "noise_level_2": torch.zeros(B, dtype=torch.long, device=DEV)}
+    sn = eb.static_noise(pg._NOISE_KEYS)
     tp = trainer(False)
     for i, (bt, nz) in enumerate(zip(bts, nzs)):
         N, P, S, W = eb.fill(bt)

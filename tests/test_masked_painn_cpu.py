@@ -90,15 +90,15 @@ def test_masked_painn_handle_is_eligible_with_edges_and_the_switch_turns_it_off(
 
 
 def test_step_graphs_size_a_masked_painn_bucket_by_the_bound():
-    """StepGraphs._edges hands the bound to edge_capacity / Bucket.fits for a masked handle and the count otherwise."""
-    from geossl_amd import pretrain_GeoSSL as pg
+    """bucket.batch_edges - what StepGraphs sizes a bucket by and Bucket.fits_batch checks - hands the bound to
+    edge_capacity / Bucket.fits for a masked handle and the count otherwise."""
+    from geossl_amd import bucket as bk
     from geossl_amd.Geom3D.dataloaders import masking
     from geossl_amd.Geom3D.dataloaders.device_dataset import DatasetBatch
     sizes = np.array([4, 18, 1, 30, 7], dtype=np.int64)
     ds = _stub(sizes, sizes * (sizes - 1))
-    sg = pg.StepGraphs(lambda b, n: None, "painn")
     hb = DatasetBatch(ds, np.array([1, 3, 4]), masking.MaskDraw(0.5, seed=2))
     k = masking.kept_count(sizes[[1, 3, 4]], 0.5)
-    assert sg._edges(hb) == int((k * (k - 1)).sum()) == hb.n_edges_bound
-    assert sg._edges(DatasetBatch(ds, np.array([1, 3, 4]))) == int((sizes * (sizes - 1))[[1, 3, 4]].sum())
-    assert pg.StepGraphs(lambda b, n: None, "schnet")._edges(hb) is None
+    assert bk.batch_edges(hb, "painn") == int((k * (k - 1)).sum()) == hb.n_edges_bound
+    assert bk.batch_edges(DatasetBatch(ds, np.array([1, 3, 4])), "painn") == int((sizes * (sizes - 1))[[1, 3, 4]].sum())
+    assert bk.batch_edges(hb, "schnet") is None
