@@ -19,7 +19,7 @@ import torch
 from ...switches import env as _env
 from torch.nn import Embedding, Linear, ModuleList, Sequential
 
-from ... import _lib, ops
+from ... import _lib, ops, switches
 from ..._lib import call, ptr, stream
 from ...layout import get_layout
 from ._atomic_mass import atomic_masses
@@ -170,7 +170,15 @@ class _SchNetCore(torch.autograd.Function):
         if cfg["debug"]:
             status.check()
         # radius graph + edge length + envelope (schnet.py:91-93,186): pair slots, a sparse list or a live-pair list
-        graph = ops.pair_graph(pos, lay, cfg["cutoff"], want_params, ctx.needs_input_grad[1])
+        # (with the image of the Gaussian fragments for the weight-gradient launch, where that launch copies them:
+        # GEOSSL_RBF_IMAGE, and the forms that keep their own Gaussians - three bf16 pieces, hidden rows rebuilt - excepted)
+        keep_T = training and (ctx.needs_input_grad[1] or not _env("GEOSSL_FILTER_RECOMPUTE_T")
+                               or bool(_env("GEOSSL_FILTER_BWD_BF16X3"))
+                               or bool(_env("GEOSSL_ARITH_24BIT")))
+        use_image = (want_params and keep_T and not _env("GEOSSL_FILTER_BWD_BF16X3") and not _env("GEOSSL_ARITH_24BIT")
+                     and switches.rbf_image(torch.cuda.is_current_stream_capturing()))
+        graph = ops.pair_graph(pos, lay, cfg["cutoff"], want_params, ctx.needs_input_grad[1],
+                               rbf=(cfg["offset"], cfg["coeff"]) if use_image else None)
         P = lay.P
         # continuous-filter network of every block in one launch (schnet.py:94,187)
         fw = _filter_weights(layers)
@@ -182,9 +190,6 @@ class _SchNetCore(torch.autograd.Function):
         # within 0.1 % either way, 21 % less HBM traffic.  Equal speed is not a win: saving stays the default, the
         # rebuild is there for when memory is what is short.  The position gradient
         # (geossl_cfconv_filter_dpos) and the three-bf16-piece backward read the saved rows.
-        keep_T = training and (ctx.needs_input_grad[1] or not _env("GEOSSL_FILTER_RECOMPUTE_T")
-                               or bool(_env("GEOSSL_FILTER_BWD_BF16X3"))
-                               or bool(_env("GEOSSL_ARITH_24BIT")))
         T = torch.empty(L, P, F, dtype=torch.float32, device=dev) if keep_T else None
         if graph.fwd_on_rows:
             # Wf at the dense slot - what the aggregation walks address - and T at the list's row, which is what the
@@ -365,9 +370,13 @@ class _SchNetCore(torch.autograd.Function):
                 nfl = _lib.load().geossl_cfconv_filter_bwd_workspace_floats(P, L, F, G)
                 ws2 = torch.empty(nfl, dtype=torch.float32, device=dev)
                 r = graph.rows
-                call("geossl_cfconv_filter_bwd_dyn", ptr(r.pair_d), ptr(r.pair_c), ptr(r.pair_flag), ptr(r.pair_i),
-                     ptr(r.pair_j), P, N, C.byref(fw), C.byref(gin), L, F, G, ptr(cfg["offset"]), cfg["coeff"],
-                     ptr(graph.T_for_rows(sv["T"])), C.byref(gout), ptr(ws2), accum, r.dyn_P, dN2, st)
+                args = (ptr(r.pair_d), ptr(r.pair_c), ptr(r.pair_flag), ptr(r.pair_i), ptr(r.pair_j), P, N, C.byref(fw),
+                        C.byref(gin), L, F, G, ptr(cfg["offset"]), cfg["coeff"], ptr(graph.T_for_rows(sv["T"])),
+                        C.byref(gout), ptr(ws2), accum, r.dyn_P, dN2)
+                if graph.rbf_image is not None and sv["T"] is not None:  # the Gaussian fragments from the step's image
+                    call("geossl_cfconv_filter_bwd_frag_dyn", *args, ptr(graph.rbf_image), st)
+                else:
+                    call("geossl_cfconv_filter_bwd_dyn", *args, st)
             elif not direct:
                 for gl in g_layers:
                     for k in range(4):

@@ -207,6 +207,14 @@ PROTOTYPES = {
     "geossl_cfconv_filter_fwd_dyn": (i32, [vp, vp, i64, P(FilterWeights), i32, i32, i32, vp, f32, vp, vp, vp, vp]),
     "geossl_cfconv_filter_bwd_dyn": (i32, [vp, vp, vp, vp, vp, i64, i64, P(FilterWeights), P(FilterGradIn), i32, i32, i32,
                                            vp, f32, vp, P(FilterGradOut), vp, i32, vp, vp, vp]),
+    "geossl_rbf_fragments_bytes": (i64, [i64]),
+    "geossl_rbf_fragments": (i32, [vp, i64, i32, vp, f32, vp, vp]),
+    "geossl_rbf_fragments_dyn": (i32, [vp, i64, i32, vp, f32, vp, vp, vp]),
+    "geossl_rbf_fragment_items": (i32, [vp, i64, i32, vp, f32, vp, vp, vp]),
+    "geossl_cfconv_filter_bwd_frag": (i32, [vp, vp, vp, vp, vp, i64, i64, P(FilterWeights), P(FilterGradIn), i32, i32,
+                                            i32, vp, f32, vp, P(FilterGradOut), vp, i32, vp, vp]),
+    "geossl_cfconv_filter_bwd_frag_dyn": (i32, [vp, vp, vp, vp, vp, i64, i64, P(FilterWeights), P(FilterGradIn), i32,
+                                                i32, i32, vp, f32, vp, P(FilterGradOut), vp, i32, vp, vp, vp, vp]),
     "geossl_cfconv_aggregate_work_dyn": (i32, [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp]),
     "geossl_cfconv_aggregate_targets_dyn": (i32, [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp]),
     "geossl_linear_chain_dyn": (i32, [vp, i32, P(Chain), i64, i32, vp, vp]),

@@ -26,6 +26,7 @@
 // tiles of a block; one partial per block, fixed-order reduction afterwards (no atomics).
 #include "common.h"
 #include "geossl_hip.h"
+#include "rbf_frag.h"
 #include "split.h"
 #include "tn.h"
 
@@ -546,6 +547,11 @@ struct BwdLdsH {
 // one K = 64 product per tile against the wave's W1 slice (held as B fragments), the Gaussians as A fragments in
 // registers - the forward kernel's arithmetic with the operand roles swapped (rows on M, hidden units on N), which
 // leaves t in the C layout the rest of the tile wants (lane = hidden unit, register = pair row).
+//
+// img != nullptr (a block-uniform branch of the form that reads the saved hidden rows; one kernel either way): the Gaussian
+// fragments are not built here - the same words for every layer of the launch - but copied from the per-step image
+// (rbf_frag.h, k_rbf_fragments): a role-B lane requests the two 16-byte words of its item of the NEXT tile at the start
+// of a tile's MFMA phase and stores them to L.rbf where the build stores them otherwise.
 template <int NW, bool ROLE_A, bool RECOMP>
 __device__ __forceinline__ void filter_bwd_body_h(const float* __restrict__ pair_d, const float* __restrict__ pair_c,
                                                 const uint8_t* __restrict__ pair_flag,
@@ -555,9 +561,11 @@ __device__ __forceinline__ void filter_bwd_body_h(const float* __restrict__ pair
                                                 const float* __restrict__ offset, float coeff,
                                                 const float* __restrict__ T, float* __restrict__ partial_w1,
                                                 float* __restrict__ partial_b1, float* __restrict__ partial_w2,
-                                                float* __restrict__ partial_b2, int Pstride) {
+                                                float* __restrict__ partial_b2, int Pstride,
+                                                const u32x4* __restrict__ img) {
   constexpr int F = 32 * NW, NT = 128 * NW, KC = F / 16, CB = F / 32, AS = BwdLdsH<F>::AS, Q = F / 4;
   static_assert(TR * (F / 8) == NT, "one dOr fragment lane per thread");
+  static_assert(TR == RBF_TILE_ROWS && RBF_TILE_ITEMS % (64 * NW) == 0, "whole items per role-B lane");
   extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
   const BwdLdsH<F> L(smem_raw);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, kh = lane >> 5;
@@ -770,6 +778,25 @@ __device__ __forceinline__ void filter_bwd_body_h(const float* __restrict__ pair
       for (int r = 0; r < 16; ++r) tc[r] = ssp(fmaf(au[r], inv1, b1v));
     }
   };
+  // IMG, role B: the words of this lane's items of tile tt's Gaussian fragments, from the image
+  constexpr bool IMG = !RECOMP;  // (the form that rebuilds the hidden rows keeps its own Gaussians)
+  const bool use_img = IMG && img != nullptr;
+  constexpr int NIT = (IMG && !ROLE_A) ? RBF_TILE_ITEMS / (64 * NW) : 1;
+  u32x4 gfh[NIT], gfl[NIT];
+#pragma unroll
+  for (int u = 0; u < NIT; ++u) gfh[u] = gfl[u] = u32x4{0u, 0u, 0u, 0u};
+  auto request_rbf = [&](int tt) {
+    if constexpr (IMG && !roleA) {
+      if (!use_img) return;
+      const u32x4* __restrict__ src = img + (size_t)tt * RBF_TILE_WORDS;  // (uniform base, 32-bit lane offsets)
+#pragma unroll
+      for (int u = 0; u < NIT; ++u) {
+        const int w = rbf_item_word(64 * hs + lane + 64 * NW * u);
+        gfh[u] = src[w];
+        gfl[u] = src[w + 64];
+      }
+    }
+  };
   // publish what was requested earlier as tile tt's staging buffer: role B the atom window (and its largest magnitudes),
   // the first role-A wave the row descriptors (role B is the longer path of the phase)
   auto publish = [&](int tt) {
@@ -836,6 +863,7 @@ __device__ __forceinline__ void filter_bwd_body_h(const float* __restrict__ pair
     alo_a = pair_i[t_begin * TR];
     request_rows(t_begin);
     decide(alo_a);
+    request_rbf(t_begin);
     request_atoms(t_begin, alo_a);
     request_t(t_begin);
     if constexpr (RECOMP) {
@@ -954,30 +982,31 @@ __device__ __forceinline__ void filter_bwd_body_h(const float* __restrict__ pair
     }
     // Gaussian fragments: by the role-B waves (role A also splits its saved activations in this phase; with the sticky
     // window role B has the shorter build)
+    // (rbf_frag.h: B[k = row = 16ks + kperm(e, kh)][n = g], fixed scale 2^14, a column of ones at g = 63 when G < 64 -
+    // db1 by the matrix pipe with the rest of dW1 instead of sixteen vector adds per role-A wave and tile)
+    if (use_img) {
+      if constexpr (IMG && !roleA) {  // this tile's words were requested one MFMA phase ago
+#pragma unroll
+        for (int u = 0; u < NIT; ++u) {
+          u32x4* dst = L.rbf + rbf_item_word(64 * hs + lane + 64 * NW * u);
+          dst[0] = gfh[u];
+          dst[64] = gfl[u];
+        }
+      }
+    } else {
 #ifndef FBH_RBF_BY_A
     if (!roleA) {
-      for (int it = 64 * hs + lane; it < 2 * 2 * 64; it += 64 * NW) {  // rbf: B[k = row = 16ks + kperm(e, kh)][n = g]
+      for (int it = 64 * hs + lane; it < RBF_TILE_ITEMS; it += 64 * NW) {
 #else
     if (NW == 1 ? roleA : (roleA ? hs < NW / 2 : hs >= NW / 2)) {
-      for (int it = 64 * hs + lane; it < 2 * 2 * 64; it += 64 * (NW == 1 ? 1 : NW)) {
+      for (int it = 64 * hs + lane; it < RBF_TILE_ITEMS; it += 64 * (NW == 1 ? 1 : NW)) {
 #endif
-        const int ln = it & 63, ks = (it >> 6) & 1, gb = it >> 7;
-        const int gg = 32 * gb + (ln & 31);
-        const float off = gg < G ? offset[gg] : 0.0f;
-        // column 63 (free whenever G < 64) is a column of ONES: dW1[:, 63] = sum over the rows of dU = db1, formed by the
-        // matrix pipe with the rest of dW1 instead of sixteen vector adds per role-A wave and tile
-        const float pad = (gg == 63 && G < 64) ? 1.0f : 0.0f;
-        float u8[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float diff = L.tdd(bsel)[16 * ks + kperm(e, ln >> 5)] - off;
-          u8[e] = gg < G ? exp_neg(coeff * (diff * diff)) : pad;
-        }
-        const Frag2 f = split8h_scaled(u8, 16384.0f);  // Gaussians are <= 1: fixed scale 2^14
-        u32x4* dst = L.rbf + (size_t)((gb * 2 + ks) * 2) * 64 + ln;
+        const Frag2 f = rbf_fragment_item(it, [&](int r) { return L.tdd(bsel)[r]; }, offset, coeff, G);
+        u32x4* dst = L.rbf + rbf_item_word(it);
         dst[0] = f.h;
         dst[64] = f.l;
       }
+    }
     }
     float tcur[16];
 #pragma unroll
@@ -996,6 +1025,7 @@ __device__ __forceinline__ void filter_bwd_body_h(const float* __restrict__ pair
       if (blockIdx.x == 3 && blockIdx.y == 0 && lane == 0 && (wave == 0 || wave == NW) && t - t_begin < 64)
         fb_dbg2[(wave == 0 ? 0 : 1) * 64 + (t - t_begin)] = clock64();
 #endif
+      request_rbf(t + 1);  // first: nothing requested in this phase is waited for before these words are
       publish(t + 1);
       FBH_MARK(7);
       if (t + 2 < t_end) {
@@ -1192,16 +1222,38 @@ __global__ __launch_bounds__(128 * NW) void k_filter_bwd_h(const float* __restri
                                                          float* __restrict__ partial_w2,
                                                          float* __restrict__ partial_b2,
                                                          const int32_t* __restrict__ dyn_P,
-                                                         const int32_t* __restrict__ dyn_N) {
+                                                         const int32_t* __restrict__ dyn_N,
+                                                         const u32x4* __restrict__ img) {
   const int Pstride = P;
   P = dyn_count(P, dyn_P);
   N = dyn_count(N, dyn_N);
   if ((int)(threadIdx.x >> 6) < NW)
-    filter_bwd_body_h<NW, true, RECOMP>(pair_d, pair_c, pair_flag, pair_i, pair_j, P, N, w, g, G, offset, coeff, T, partial_w1,
-                              partial_b1, partial_w2, partial_b2, Pstride);
+    filter_bwd_body_h<NW, true, RECOMP>(pair_d, pair_c, pair_flag, pair_i, pair_j, P, N, w, g, G, offset, coeff, T,
+                                             partial_w1, partial_b1, partial_w2, partial_b2, Pstride, img);
   else
-    filter_bwd_body_h<NW, false, RECOMP>(pair_d, pair_c, pair_flag, pair_i, pair_j, P, N, w, g, G, offset, coeff, T, partial_w1,
-                               partial_b1, partial_w2, partial_b2, Pstride);
+    filter_bwd_body_h<NW, false, RECOMP>(pair_d, pair_c, pair_flag, pair_i, pair_j, P, N, w, g, G, offset, coeff, T,
+                                              partial_w1, partial_b1, partial_w2, partial_b2, Pstride, img);
+}
+
+// The per-step image of the Gaussian fragments (rbf_frag.h): one block per 32-row tile of the CAPACITY P, one item per
+// thread.  Distances as the tile build above reads them: row r of the list at r < n, the last real row's past it (tail
+// tile and every tile past the real count n = dyn_count(P, dyn_P): finite words - their dO is exactly zero, which an
+// unwritten word could still turn into NaN).  No real row at all: zeros.
+__global__ __launch_bounds__(RBF_TILE_ITEMS) void k_rbf_fragments(const float* __restrict__ pair_d, int P, int G,
+                                                                  const float* __restrict__ offset, float coeff,
+                                                                  u32x4* __restrict__ image,
+                                                                  const int32_t* __restrict__ dyn_P) {
+  const int n = dyn_count(P, dyn_P);
+  const int r0 = blockIdx.x * TR, it = threadIdx.x;
+  u32x4* __restrict__ dst = image + (size_t)blockIdx.x * RBF_TILE_WORDS + rbf_item_word(it);
+  if (n <= 0) {
+    dst[0] = u32x4{0u, 0u, 0u, 0u};
+    dst[64] = u32x4{0u, 0u, 0u, 0u};
+    return;
+  }
+  const Frag2 f = rbf_fragment_item(it, [&](int r) { return pair_d[min(r0 + r, n - 1)]; }, offset, coeff, G);
+  dst[0] = f.h;
+  dst[64] = f.l;
 }
 
 inline int blocks_per_layer(int L, int ntiles) {
@@ -1241,12 +1293,14 @@ extern "C" int geossl_cfconv_filter_bwd(const float* pair_d, const float* pair_c
                                       workspace, accumulate, nullptr, nullptr, stream);
 }
 
-extern "C" int geossl_cfconv_filter_bwd_dyn(const float* pair_d, const float* pair_c, const uint8_t* pair_flag,
-                                            const int32_t* pair_i, const int32_t* pair_j, int64_t P, int64_t N,
-                                            const GeosslFilterWeights* w, const GeosslFilterGradIn* g, int L, int F,
-                                            int G, const float* offset, float coeff, const float* T,
-                                            const GeosslFilterGradOut* out, float* workspace, int accumulate,
-                                            const int32_t* dyn_P, const int32_t* dyn_N, hipStream_t stream) {
+namespace {
+
+// every entry point of the weight-gradient launch; image: the Gaussian fragments of geossl_rbf_fragments, or nullptr
+int filter_bwd_launch(const float* pair_d, const float* pair_c, const uint8_t* pair_flag, const int32_t* pair_i,
+                      const int32_t* pair_j, int64_t P, int64_t N, const GeosslFilterWeights* w,
+                      const GeosslFilterGradIn* g, int L, int F, int G, const float* offset, float coeff, const float* T,
+                      const GeosslFilterGradOut* out, float* workspace, int accumulate, const int32_t* dyn_P,
+                      const int32_t* dyn_N, const void* image, hipStream_t stream) {
   if (P <= 0 || L <= 0) return 0;
   // (G < 1: the kernels clamp the padded Gaussian index to G - 1, which would read in front of w1 and offset)
   if (L > GEOSSL_MAX_L || (F != 32 && F != 64 && F != 128) || G > 64 || G < 1) return (int)hipErrorInvalidValue;
@@ -1271,14 +1325,16 @@ extern "C" int geossl_cfconv_filter_bwd_dyn(const float* pair_d, const float* pa
       allow_big_lds(&k_filter_bwd_h<NW, true>);                                                                    \
       hipLaunchKernelGGL((k_filter_bwd_h<NW, true>), grid, dim3(128 * NW), lds, stream, pair_d, pair_c, pair_flag, \
                          pair_i, pair_j, (int)P, (int)N, *w, *g, G, offset, coeff, T, pw1, pb1, pw2, pb2, dyn_P,   \
-                         dyn_N);                                                                                   \
+                         dyn_N, nullptr);                                                                          \
     } else {                                                                                                       \
       allow_big_lds(&k_filter_bwd_h<NW, false>);                                                                   \
       hipLaunchKernelGGL((k_filter_bwd_h<NW, false>), grid, dim3(128 * NW), lds, stream, pair_d, pair_c, pair_flag,\
                          pair_i, pair_j, (int)P, (int)N, *w, *g, G, offset, coeff, T, pw1, pb1, pw2, pb2, dyn_P,   \
-                         dyn_N);                                                                                   \
+                         dyn_N, img);                                                                              \
     }                                                                                                              \
   } while (0)
+  // (the three-piece form and the form that rebuilds the hidden rows keep the in-kernel Gaussians: an image is ignored)
+  const u32x4* img = static_cast<const u32x4*>(image);
   const bool bf16x3 = getenv("GEOSSL_FILTER_BWD_BF16X3") != nullptr || getenv("GEOSSL_ARITH_24BIT") != nullptr;  // (read per call: bench.py times both forms in one process)
   if (bf16x3 && T == nullptr) return (int)hipErrorInvalidValue;  // (the three-piece form reads the saved hidden rows)
   if (!bf16x3) {
@@ -1295,6 +1351,85 @@ extern "C" int geossl_cfconv_filter_bwd_dyn(const float* pair_d, const float* pa
   rm.add(pw2, F * F, F, F, 1, out->dw2, L);
   rm.add(pb2, F, F, F, 1, out->db2, L);
   hipLaunchKernelGGL(k_reduce_multi, dim3(rm.blocks(), L), dim3(256), 0, stream, rm, nb, accumulate);
+  GEOSSL_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int geossl_cfconv_filter_bwd_dyn(const float* pair_d, const float* pair_c, const uint8_t* pair_flag,
+                                            const int32_t* pair_i, const int32_t* pair_j, int64_t P, int64_t N,
+                                            const GeosslFilterWeights* w, const GeosslFilterGradIn* g, int L, int F,
+                                            int G, const float* offset, float coeff, const float* T,
+                                            const GeosslFilterGradOut* out, float* workspace, int accumulate,
+                                            const int32_t* dyn_P, const int32_t* dyn_N, hipStream_t stream) {
+  return filter_bwd_launch(pair_d, pair_c, pair_flag, pair_i, pair_j, P, N, w, g, L, F, G, offset, coeff, T, out, workspace,
+                           accumulate, dyn_P, dyn_N, nullptr, stream);
+}
+
+extern "C" int geossl_cfconv_filter_bwd_frag(const float* pair_d, const float* pair_c, const uint8_t* pair_flag,
+                                             const int32_t* pair_i, const int32_t* pair_j, int64_t P, int64_t N,
+                                             const GeosslFilterWeights* w, const GeosslFilterGradIn* g, int L, int F,
+                                             int G, const float* offset, float coeff, const float* T,
+                                             const GeosslFilterGradOut* out, float* workspace, int accumulate,
+                                             const void* image, hipStream_t stream) {
+  return geossl_cfconv_filter_bwd_frag_dyn(pair_d, pair_c, pair_flag, pair_i, pair_j, P, N, w, g, L, F, G, offset, coeff, T,
+                                           out, workspace, accumulate, nullptr, nullptr, image, stream);
+}
+
+extern "C" int geossl_cfconv_filter_bwd_frag_dyn(const float* pair_d, const float* pair_c, const uint8_t* pair_flag,
+                                                 const int32_t* pair_i, const int32_t* pair_j, int64_t P, int64_t N,
+                                                 const GeosslFilterWeights* w, const GeosslFilterGradIn* g, int L, int F,
+                                                 int G, const float* offset, float coeff, const float* T,
+                                                 const GeosslFilterGradOut* out, float* workspace, int accumulate,
+                                                 const int32_t* dyn_P, const int32_t* dyn_N, const void* image,
+                                                 hipStream_t stream) {
+  if (image == nullptr) return (int)hipErrorInvalidValue;
+  return filter_bwd_launch(pair_d, pair_c, pair_flag, pair_i, pair_j, P, N, w, g, L, F, G, offset, coeff, T, out, workspace,
+                           accumulate, dyn_P, dyn_N, image, stream);
+}
+
+// (tests: the items of rbf_frag.h one after the other - [tile][item 256][piece 2] - with the distances of k_rbf_fragments)
+namespace {
+__global__ __launch_bounds__(RBF_TILE_ITEMS) void k_rbf_fragment_items(const float* __restrict__ pair_d, int P, int G,
+                                                                       const float* __restrict__ offset, float coeff,
+                                                                       u32x4* __restrict__ items,
+                                                                       const int32_t* __restrict__ dyn_P) {
+  const int n = dyn_count(P, dyn_P);
+  const int r0 = blockIdx.x * TR, it = threadIdx.x;
+  if (n <= 0) return;
+  const Frag2 f = rbf_fragment_item(it, [&](int r) { return pair_d[min(r0 + r, n - 1)]; }, offset, coeff, G);
+  u32x4* __restrict__ dst = items + ((size_t)blockIdx.x * RBF_TILE_ITEMS + it) * 2;
+  dst[0] = f.h;
+  dst[1] = f.l;
+}
+}  // namespace
+
+extern "C" int geossl_rbf_fragment_items(const float* pair_d, int64_t P, int G, const float* offset, float coeff,
+                                         void* items, const int32_t* dyn_P, hipStream_t stream) {
+  if (P <= 0) return 0;
+  if (G > 64 || G < 1 || P > INT32_MAX) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_rbf_fragment_items, dim3((unsigned)((P + TR - 1) / TR)), dim3(RBF_TILE_ITEMS), 0, stream, pair_d,
+                     (int)P, G, offset, coeff, static_cast<u32x4*>(items), dyn_P);
+  GEOSSL_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int64_t geossl_rbf_fragments_bytes(int64_t P) {
+  return P > 0 ? (P + TR - 1) / TR * (int64_t)RBF_TILE_WORDS * 16 : 0;
+}
+
+extern "C" int geossl_rbf_fragments(const float* pair_d, int64_t P, int G, const float* offset, float coeff, void* image,
+                                    hipStream_t stream) {
+  return geossl_rbf_fragments_dyn(pair_d, P, G, offset, coeff, image, nullptr, stream);
+}
+
+extern "C" int geossl_rbf_fragments_dyn(const float* pair_d, int64_t P, int G, const float* offset, float coeff,
+                                        void* image, const int32_t* dyn_P, hipStream_t stream) {
+  if (P <= 0) return 0;
+  if (G > 64 || G < 1 || P > INT32_MAX) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_rbf_fragments, dim3((unsigned)((P + TR - 1) / TR)), dim3(RBF_TILE_ITEMS), 0, stream, pair_d, (int)P,
+                     G, offset, coeff, static_cast<u32x4*>(image), dyn_P);
   GEOSSL_CHECK_LAUNCH();
   return 0;
 }

@@ -225,9 +225,10 @@ class PairGraph:
     ``rows``: the arrays the filter weight-gradient launch walks - the LivePairs (with ``row_slot`` and dyn_P = n_live)
     where a live-pair list was built, else ``slots`` itself;
     ``fwd_on_rows``: the filter forward runs on ``rows`` through the row map (T compact, Wf per slot), not on ``slots``;
-    ``loop_flag``: the pair_flag the layer loop walks, None where it may not be used (dense layouts with pairs only)."""
+    ``loop_flag``: the pair_flag the layer loop walks, None where it may not be used (dense layouts with pairs only);
+    ``rbf_image``: the Gaussian fragments of the filter weight-gradient launch over ``rows`` (`rbf_fragments`), or None."""
 
-    __slots__ = ("layout", "sparse", "slots", "rows", "fwd_on_rows", "loop_flag")
+    __slots__ = ("layout", "sparse", "slots", "rows", "fwd_on_rows", "loop_flag", "rbf_image")
 
     def T_for_rows(self, T):
         """T [L, P, F] as the forward stored it -> T at the rows of ``rows`` (regrouped if it was stored per slot)."""
@@ -253,7 +254,21 @@ class PairGraph:
         return out
 
 
-def pair_graph(pos, layout, cutoff, want_rows, want_pos):
+def rbf_fragments(rows, P, offset, coeff, out=None):
+    """The Gaussian fragments of every 32-row tile of ``rows`` (a LivePairs, a SparsePairs or the dense slots; P = its
+    capacity) as the filter weight-gradient kernel multiplies them (csrc/rbf_frag.h) -> uint8 [8 KB per tile].  One
+    launch, sized by the capacity, every tile written; geossl_cfconv_filter_bwd_frag(_dyn) reads it."""
+    nbytes = _lib.load().geossl_rbf_fragments_bytes(P)
+    if out is None:
+        out = torch.empty(nbytes, dtype=torch.uint8, device=rows.pair_d.device)
+    elif out.numel() != nbytes:
+        raise ValueError("the image given as `out` was made for another capacity")
+    call("geossl_rbf_fragments_dyn", ptr(rows.pair_d), P, offset.numel(), ptr(offset), float(coeff), ptr(out), rows.dyn_P,
+         stream())
+    return out
+
+
+def pair_graph(pos, layout, cutoff, want_rows, want_pos, rbf=None):
     """-> PairGraph.  A SPARSE layout (a structure above 255 atoms, layout.want_sparse) gets the compacted list of the
     pairs that carry an edge: P is then the list's capacity and its real row count stays on the device (the sparse
     layout of a capacity bucket, bucket.SPARSE: the atom count is a capacity as well, read on the device).  A dense layout
@@ -261,13 +276,20 @@ def pair_graph(pos, layout, cutoff, want_rows, want_pos):
     QM9-sized molecules at 5 A, fewer in extended ones; `live_pairs`, one launch) for the filter network to run on: with
     parameter gradients (want_rows) or without a position gradient (want_pos).  The position gradient reads T and Wf by
     one index, so with it the forward keeps the dense rows and the backward regroups T (`T_for_rows`): the filter
-    weight gradients are then those of the path without it, bit for bit."""
+    weight gradients are then those of the path without it, bit for bit.
+    ``rbf`` = (offset, coeff) of the model's Gaussian smearing: with want_rows the graph also gets the image of the
+    Gaussian fragments over ``rows`` (`rbf_fragments`), built right behind the list it is made from - once per forward,
+    for all layers of the weight-gradient launch."""
     g = PairGraph()
     g.layout, g.sparse = layout, bool(getattr(layout, "sparse", False))
+    g.rbf_image = None
     dyn = getattr(layout, "dyn", None)
+    want_image = rbf is not None and want_rows and layout.P > 0
     if g.sparse:
         g.slots = g.rows = sparse_pair_geometry(pos, layout, cutoff)
         g.fwd_on_rows, g.loop_flag = False, None
+        if want_image:
+            g.rbf_image = rbf_fragments(g.rows, layout.P, *rbf)
         return g
     use_live = layout.P > 0 and live_pairs_enabled() and (want_rows or not want_pos)
     mol_live = torch.empty(layout.B, dtype=torch.int32, device=pos.device) if use_live else None
@@ -278,6 +300,8 @@ def pair_graph(pos, layout, cutoff, want_rows, want_pos):
         g.rows = live_pairs(pair_d, pair_c, pair_flag, layout, mol_live, cutoff)
     g.fwd_on_rows = use_live and not want_pos
     g.loop_flag = pair_flag if layout.P > 0 else None
+    if want_image:
+        g.rbf_image = rbf_fragments(g.rows, layout.P, *rbf)
     return g
 
 

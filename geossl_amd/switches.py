@@ -34,6 +34,17 @@ def masked_painn_buckets():
     return env("GEOSSL_MASKED_PAINN_BUCKETS", "1") != "0"
 
 
+def rbf_image(capturing):
+    """``GEOSSL_RBF_IMAGE``: the Gaussian fragments of the filter weight-gradient kernel come from a per-step image
+    (``ops.rbf_fragments``, one launch behind the pair list) instead of being rebuilt by every layer's blocks.  ``1``:
+    always; ``0``: never - the launches before the image existed (A/B timing); unset: ``capturing`` - like the layer loop,
+    the image belongs to captured steps, where its launch costs its kernel time only.  The same bits either way."""
+    v = env("GEOSSL_RBF_IMAGE")
+    if v == "0":
+        return False
+    return True if v == "1" else bool(capturing)
+
+
 def sparse_buckets(handle):
     """``GEOSSL_SPARSE_BUCKETS``: the batches of a step that reads no pair tuples (Supervised) whose layout is sparse - a
     structure above 255 atoms, or ``GEOSSL_SPARSE_PAIRS=1`` - replay one capacity-bucket graph per batch size

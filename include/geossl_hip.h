@@ -572,6 +572,34 @@ int geossl_cfconv_filter_bwd_dyn(const float* pair_d, const float* pair_c, const
                                  const float* offset, float coeff, const float* T, const GeosslFilterGradOut* out,
                                  float* workspace, int accumulate, const int32_t* dyn_P, const int32_t* dyn_N,
                                  hipStream_t stream);
+/* The Gaussian-smearing fragments of the filter backward's dW1 product as a per-step image (csrc/rbf_frag.h): for every
+ * 32-row tile of the pair list the words the kernel otherwise builds in LDS for every layer again -
+ * [tile][gb 2][ks 2][piece 2][64 lanes] of 16-byte words, 8 KB per tile, geossl_rbf_fragments_bytes(P) in all.  They
+ * depend on the row's distance, offset / coeff and G only.  P is the list's CAPACITY: every tile of it is written (rows at
+ * and past the real count *dyn_P with the last real row's distance, as the kernel's tile build substitutes), so no
+ * word of the image is ever unwritten.  geossl_cfconv_filter_bwd_frag(_dyn): geossl_cfconv_filter_bwd(_dyn) copying
+ * the fragments from `image` (built from the same pair_d, P, G, offset, coeff, dyn_P) - the same bits.  The forms
+ * that keep their own Gaussians (three bf16 pieces, T == NULL) ignore the image.                                   */
+int64_t geossl_rbf_fragments_bytes(int64_t P);
+int geossl_rbf_fragments(const float* pair_d, int64_t P, int G, const float* offset, float coeff, void* image,
+                         hipStream_t stream);
+int geossl_rbf_fragments_dyn(const float* pair_d, int64_t P, int G, const float* offset, float coeff, void* image,
+                             const int32_t* dyn_P, hipStream_t stream);
+/* (for tests) the same items in plain order, [tile][item 256][piece 2] of 16-byte words, geossl_rbf_fragments_bytes(P);
+ * item it = (gb * 2 + ks) * 64 + lane sits at word (it >> 6) * 128 + piece * 64 + (it & 63) of its tile in the image */
+int geossl_rbf_fragment_items(const float* pair_d, int64_t P, int G, const float* offset, float coeff, void* items,
+                              const int32_t* dyn_P, hipStream_t stream);
+int geossl_cfconv_filter_bwd_frag(const float* pair_d, const float* pair_c, const uint8_t* pair_flag,
+                                  const int32_t* pair_i, const int32_t* pair_j, int64_t P, int64_t N,
+                                  const GeosslFilterWeights* w, const GeosslFilterGradIn* g, int L, int F, int G,
+                                  const float* offset, float coeff, const float* T, const GeosslFilterGradOut* out,
+                                  float* workspace, int accumulate, const void* image, hipStream_t stream);
+int geossl_cfconv_filter_bwd_frag_dyn(const float* pair_d, const float* pair_c, const uint8_t* pair_flag,
+                                      const int32_t* pair_i, const int32_t* pair_j, int64_t P, int64_t N,
+                                      const GeosslFilterWeights* w, const GeosslFilterGradIn* g, int L, int F, int G,
+                                      const float* offset, float coeff, const float* T, const GeosslFilterGradOut* out,
+                                      float* workspace, int accumulate, const int32_t* dyn_P, const int32_t* dyn_N,
+                                      const void* image, hipStream_t stream);
 /* work items [0, *dyn_nwork) of the list */
 int geossl_cfconv_aggregate_work_dyn(const float* x, const float* Wf, const uint8_t* pair_flag, const int32_t* mol_ptr,
                                      const int32_t* pair_ptr, const int32_t* work, int64_t nwork, int max_n, int F,
