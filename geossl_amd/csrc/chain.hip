@@ -980,14 +980,17 @@ int launch_chain(const GeosslChain& ch, const float* X, int ldx, int64_t R, hipS
   static const bool four_waves = getenv("GEOSSL_CHAIN4") != nullptr;  // the four-wave form, kept for A/B runs
   static const bool eight_waves = getenv("GEOSSL_CHAIN8") != nullptr;  // the streaming eight-wave form, for A/B runs
   // weight-stationary form: F = 128 (its images are in the two-fp16-piece format: no other kernel reads them); every
-  // row-piece offset must fit the 32-bit range of a buffer descriptor: longer inputs run as two launches of half the rows
+  // row-piece offset must fit the 32-bit range of a buffer descriptor: longer inputs run as two launches of half the rows.
+  // The eight-wave form (F = 64 / 32) forms its row-piece offsets in 32 bits as well (k_row_chain8: load_x, ro): same split.
   const bool cu_form = KS == 8;
+  const bool offsets32 = cu_form || !four_waves;
   bool same_input = false, silu = false;
   for (int s2 = 0; s2 < ch.nstage; ++s2) silu |= (ch.st[s2].flags & (GEOSSL_EPI_SILU | GEOSSL_EPI_MUL_DSILU)) != 0;
   if (ch.nstage > 3) silu = true;  // chains of four and five stages are instantiated in that form only
   if (silu && !cu_form) return (int)hipErrorInvalidValue;  // silu epilogues, long chains: weight-stationary form only
   for (int s2 = 0; s2 < ch.nstage; ++s2) {
-    if (cu_form && ((int64_t)R * ch.st[s2].ld * 4 >= (int64_t)0xFFFFFF00u || (int64_t)R * ldx * 4 >= (int64_t)0xFFFFFF00u)) {
+    if (offsets32 && ((int64_t)R * ch.st[s2].ld * 4 >= (int64_t)0xFFFFFF00u || (int64_t)R * ldx * 4 >= (int64_t)0xFFFFFF00u ||
+                      (int64_t)R * ch.st[s2].ldxin * 4 >= (int64_t)0xFFFFFF00u)) {
       if (dyn_R != nullptr) return (int)hipErrorInvalidValue;  // (two launches of half the rows: by-value counts only)
       const int64_t r0 = ((R / 2 + 31) / 32) * 32;
       GeosslChain hi = ch;
