@@ -31,6 +31,10 @@ step at the reference's batch size).  Here the molecules are uploaded once:
   handle takes a count launch and a read-back of B counts before the gather; a PaiNN capacity bucket (``bucket.Bucket.
   fill``) keeps the counts on the device instead (``geossl_masked_edge_offsets``) and is sized by the handle's host-side
   bound ``n_edges_bound``.
+* ``PairedDeviceDataset``: LEP's protein-ligand pairs (Geom3D/dataloaders/dataloaders_LEP.py) - ONE ``DeviceDataset``
+  over the 2M structures, active m at id m and inactive m at id M + m, with the labels ``y [M]`` beside it.  The loader
+  yields ``PairedBatch`` handles; the batch of 2B structures ``[active | inactive]`` that the one-pass step runs on
+  (finetune_lep.fused_batch) is a plain ``DatasetBatch`` of that dataset, so every gather above serves it.
 """
 import ctypes as C
 
@@ -279,6 +283,7 @@ class DeviceDataset:
 
     # ---- batches
     def batch(self, ids):
+        """The handle of these molecules (what an unmasked DeviceLoader yields)."""
         return DatasetBatch(self, ids)
 
     def __getitem__(self, ids):
@@ -556,9 +561,143 @@ class DatasetBatch:
         return fp
 
 
+class PairedDeviceDataset:
+    """M protein-ligand pairs - each in its ACTIVE and its INACTIVE conformation, with a label - resident in HBM: what
+    ``DataLoaderLEP`` collates per step (dataloaders_LEP.py), uploaded once.  The 2M structures are one ``DeviceDataset``
+    (``structures``): active m at id m, inactive m at id M + m; ``y [M]`` float32 on the device beside it."""
+
+    def __init__(self, x_active, positions_active, sizes_active, x_inactive, positions_inactive, sizes_inactive, y,
+                 device):
+        """x_* [Ntot_*] int64 (or [Ntot_*, C]), positions_* [Ntot_*, 3] float32, sizes_* [M] atoms per structure (numpy
+        or tensors; structure after structure); y [M], integer or float: stored as float32 (finetune_lep.py:43)."""
+        as_t = lambda a: a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+        xa, xi = as_t(x_active).cpu(), as_t(x_inactive).cpu()
+        pa, pi = as_t(positions_active).cpu().float(), as_t(positions_inactive).cpu().float()
+        if xa.dim() != xi.dim() or xa.shape[1:] != xi.shape[1:]:
+            raise ValueError("x_active and x_inactive have the same columns")
+        # the reference's two asserts (dataloaders_LEP.py:49-52): a position row that sums to 0 marks a padded / missing atom
+        assert (pa.sum(1) == 0).sum() == 0
+        assert (pi.sum(1) == 0).sum() == 0
+        sa, si = (np.asarray(as_t(n_).cpu().numpy() if torch.is_tensor(n_) else n_, dtype=np.int64).reshape(-1)
+                  for n_ in (sizes_active, sizes_inactive))
+        if sa.shape != si.shape:
+            raise ValueError("one active and one inactive structure per pair: got %d and %d" % (sa.size, si.size))
+        M = int(sa.size)
+        self.x_1d = xa.dim() == 1   # (DatasetLEP's records: the atom types alone - the backbone gets them as they are)
+        self.structures = DeviceDataset(torch.cat([xa, xi]), torch.cat([pa, pi]), np.concatenate([sa, si]), device)
+        self.device, self.x_cols = self.structures.device, self.structures.x_cols
+        self.sizes = self.structures.sizes            # [2M]: active | inactive
+        self.sizes_active, self.sizes_inactive = self.sizes[:M], self.sizes[M:]
+        yt = as_t(y).reshape(-1)
+        if yt.numel() != M:
+            raise ValueError("y holds one label per pair: [%d], got %s" % (M, tuple(as_t(y).shape)))
+        self.y = yt.to(self.device, torch.float32).contiguous()
+        self._M = M
+
+    @classmethod
+    def from_data_list(cls, items, device):
+        """From the reference's LEP records (``x_active``, ``positions_active``, ``x_inactive``, ``positions_inactive``,
+        ``y``: what ``DataLoaderLEP`` consumes): concatenated once, uploaded once."""
+        cat = lambda k: torch.cat([torch.as_tensor(getattr(d, k)) for d in items], dim=0)
+        n = lambda k: [int(torch.as_tensor(getattr(d, k)).size(0)) for d in items]
+        y = torch.cat([torch.as_tensor(d.y).reshape(-1) for d in items])
+        return cls(cat("x_active"), cat("positions_active"), n("x_active"), cat("x_inactive"),
+                   cat("positions_inactive"), n("x_inactive"), y, device)
+
+    def __len__(self):
+        return self._M
+
+    def batch(self, ids):
+        return PairedBatch(self, ids)
+
+    def __getitem__(self, ids):
+        return PairedBatch(self, [int(ids)] if isinstance(ids, (int, np.integer)) else ids)
+
+
+class PairedBatch:
+    """``batch_size`` pairs of a ``PairedDeviceDataset`` by id.  Host side only: the pair ids, the ids and sizes of the 2B
+    fused structures ``[active 0 .. B-1 | inactive 0 .. B-1]`` (the batch the one-pass LEP step runs on:
+    ``fused()``, a ``DatasetBatch`` of the dataset's ``structures``), and ``y [B]`` on the device.  Whoever asks for the
+    attributes of a collated ``BatchLEP`` (``x_active``, ``positions_active``, ``batch_active``, the three inactive ones)
+    gets them from ONE gather launch on the device - bit for bit ``BatchLEP.from_data_list`` of the same records - so the
+    reference's lines, the eager step and ``eval_LEP`` take a handle unchanged."""
+
+    _mask, _triples, _canonical = None, False, None   # (whole structures; the LEP step reads no tuples)
+
+    def __init__(self, dataset, ids):
+        self._dataset = dataset
+        self.ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int64))
+        M = len(dataset)
+        if self.ids.ndim != 1 or not self.ids.size:
+            raise ValueError("a batch is a non-empty list of pair ids")
+        if self.ids.min() < 0 or self.ids.max() >= M:
+            raise IndexError("pair id out of range")
+        B = int(self.ids.size)
+        self.fused_ids = np.concatenate([self.ids, self.ids + M])
+        self._sizes = dataset.sizes[self.fused_ids]
+        self._sizes_active, self._sizes_inactive = self._sizes[:B], self._sizes[B:]
+        self.num_graphs = B
+        self.n_atoms = int(self._sizes.sum())
+        self.device, self.x_cols = dataset.device, dataset.x_cols
+        self._fused, self._batch = None, None
+
+    def fused(self):
+        """The 2B structures as a handle on the dataset's ``structures`` (made once)."""
+        if self._fused is None:
+            self._fused = _FusedPairs(self)
+        return self._fused
+
+    @property
+    def y(self):
+        got = self.__dict__.get("_y")
+        if got is None:
+            ds = self._dataset
+            got = self.__dict__["_y"] = ds.y.index_select(0, torch.from_numpy(self.ids).to(ds.device))
+        return got
+
+    def materialize(self):
+        """The collated tensors of both sides: views of the fused handle's gathered x / positions / batch vector."""
+        if self._batch is None:
+            fb, B, na = self.fused().materialize(), self.num_graphs, int(self._sizes_active.sum())
+            x = fb.x[:, 0] if self._dataset.x_1d else fb.x
+            self._batch = dict(x_active=x[:na], x_inactive=x[na:], positions_active=fb.positions[:na],
+                               positions_inactive=fb.positions[na:], batch_active=fb.batch[:na],
+                               batch_inactive=fb.batch[na:] - B)
+        return self._batch
+
+    x_active = property(lambda self: self.materialize()["x_active"])
+    x_inactive = property(lambda self: self.materialize()["x_inactive"])
+    positions_active = property(lambda self: self.materialize()["positions_active"])
+    positions_inactive = property(lambda self: self.materialize()["positions_inactive"])
+    batch_active = property(lambda self: self.materialize()["batch_active"])
+    batch_inactive = property(lambda self: self.materialize()["batch_inactive"])
+
+    def to(self, device, **kw):
+        """``batch.to(device)`` of the reference's loop: the structures are there already."""
+        dev = torch.device(device)
+        if dev.type != self.device.type or (dev.index is not None and dev.index != self.device.index):
+            raise _lib.GeosslHipError("a PairedBatch lives on %s (its structures are gathered there; there is no copy to "
+                                      "another device)" % self.device)
+        return self
+
+
+class _FusedPairs(DatasetBatch):
+    """The 2B structures of a ``PairedBatch`` as a handle on the paired dataset's ``structures``: what a bucket fill, a
+    per-structure graph's refresh and the eager step gather from.  No pair tuples are enumerated (``n_super`` = 0:
+    the LEP step reads none, and 2B pockets would have millions), and no tuple option routes it to a dense bucket."""
+
+    def __init__(self, pairs):
+        super().__init__(pairs._dataset.structures, pairs.fused_ids)
+        self._canonical, self.n_super = None, 0
+        self.pairs = pairs
+
+    y = property(lambda self: self.pairs.y)
+
+
 class DeviceLoader:
     """``DataLoaderAtomTuple(dataset, batch_size, shuffle)`` (dataloaders_AtomTuple.py:81-88) over a ``DeviceDataset``:
-    iterating yields ``DatasetBatch`` handles.  With ``shuffle=True`` the molecules are visited in the order
+    iterating yields the dataset's handles (``dataset.batch(ids)``: ``DatasetBatch``, or ``PairedBatch`` over a
+    ``PairedDeviceDataset``).  With ``shuffle=True`` the molecules are visited in the order
     ``torch.utils.data.RandomSampler`` produces under the same global torch seed (one ``torch.randperm`` per epoch from
     a generator seeded by one draw of the default generator), so a run is reproducible against the reference's loader."""
 
@@ -577,6 +716,9 @@ class DeviceLoader:
             raise ValueError("mask_rng is 'device' or 'numpy'")
         self.mask_rng = mask_rng
         if self.mask_ratio > 0:
+            if isinstance(dataset, PairedDeviceDataset):
+                raise ValueError("mask_ratio > 0 with a paired dataset is not supported: the reference's LEP loader "
+                                 "masks nothing")
             if getattr(dataset, "triples", None) is not None:
                 raise ValueError("mask_ratio > 0 with a triple dataset is not supported: the sampled triples name atoms "
                                  "by index, and masking renumbers them")
@@ -605,7 +747,7 @@ class DeviceLoader:
         r = self.mask_ratio
         if r == 0:
             for k in range(len(self)):
-                yield DatasetBatch(self.dataset, order[k * bs:(k + 1) * bs])
+                yield self.dataset.batch(order[k * bs:(k + 1) * bs])
             return
         ds = self.dataset
         seed = int(np.random.randint(0, 2 ** 63 - 1, dtype=np.int64)) if self.mask_rng == "device" else None

@@ -299,6 +299,9 @@ PROTOTYPES = {
     "geossl_pair_head_fwd": (i32, [vp, i64, i32, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
     "geossl_pair_head_predict": (i32, [vp, i64, i32, vp, i64, i32, vp, vp, vp, vp]),
     "geossl_pair_head_bwd": (i32, [i64, i32, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
+    "geossl_pair_head_fwd_dyn": (i32, [vp, i64, i32, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "geossl_pair_head_predict_dyn": (i32, [vp, i64, i32, vp, i64, i32, vp, vp, vp, vp, vp]),
+    "geossl_pair_head_bwd_dyn": (i32, [i64, i32, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]),
     # angle-prediction head on atom triples, the angle producer and the triple gather (csrc/torsion_head.hip)
     "geossl_torsion_head_width_ok": (i32, [i32]),
     "geossl_torsion_head_fwd_workspace_floats": (i64, [i64]),

@@ -345,7 +345,8 @@ def modules_ok(model, n1=None, n2=None):
     One DistancePredictor of width 2 * 128 / ChargePredictor of width 128 / Discriminator of width 128 / property head of
     width 128 (n2 = None): the Distance / Charge Prediction, 3D InfoGraph and Supervised steps on a one-view bucket
     (InfoGraph's and the property head's readouts read view 0's B real molecule offsets: exact counts); one
-    TorsionAnglePredictor of width 3 * 128: the angle-prediction step on a one-view "triples" bucket."""
+    TorsionAnglePredictor of width 3 * 128: the angle-prediction step on a one-view "triples" bucket; Linear(2 * 128, 1):
+    LEP's pair head, whose 2B structures [active | inactive] are the B_bucket molecules of a sparse bucket."""
     from .Geom3D.models.painn import PaiNN
     from .Geom3D.models.schnet import SchNet
     from .NCSN import NCSN_version_03, _head_params
@@ -380,6 +381,9 @@ def modules_ok(model, n1=None, n2=None):
         return infograph_head_ok(n1) and n1.weight.size(0) == 128 and readout_of(model) is not None
     from .pretrain_Supervised import head_width, readout_of as property_readout_of
     if isinstance(n1, (torch.nn.Linear, torch.nn.Sequential)) and n2 is None:
+        if type(n1) is torch.nn.Linear and n1.in_features == 2 * 128:   # LEP's pair head on a width-128 backbone
+            from .finetune_lep import head_params as pair_head_params
+            return pair_head_params(n1) is not None and property_readout_of(model) is not None
         return head_width(n1) == 128 and property_readout_of(model) is not None
     if not (isinstance(n1, NCSN_version_03) and isinstance(n2, NCSN_version_03)) or n1 is n2 \
             or n1.emb_dim != 128 or n2.emb_dim != 128:
@@ -760,7 +764,7 @@ NOISE_SHAPES = {"pos_noise": ("N", (3,), torch.float32), "dist_noise_1": ("S", (
                 "noise_level_2": ("B", (), torch.long),
                 # Charge Prediction's mask input: the device draw's seed, or the host-drawn list (k <= N entries)
                 "mask_seed": (1, (), torch.long), "mask_idx": ("N", (), torch.long),
-                # the Supervised step's target column
+                # the Supervised step's target column; LEP's labels - one per pair, the leading half of the 2B rows
                 "target": ("B", (), torch.float32)}
 
 

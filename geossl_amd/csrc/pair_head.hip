@@ -20,6 +20,9 @@
 //     two structures of pair b - every atom row is written exactly once.
 //   k_pair_vgrad (one thread per column): dw[side F + j] = sum_b dz_b m[side B + b][j], db = sum_b dz_b, in pair order.
 // Every sum has a fixed order and there are no atomics: the same inputs give the same bits.
+// Capacity launches (`_dyn`): N is a capacity and the real atom count is read from dyn_N; mol_ptr [2B + 1] holds the real
+// offsets (B is exact).  No atom row at or past the real count is read or written.  The exact forms are the same kernels
+// with dyn_N = nullptr: the clamp is to N, as before.
 #include "common.h"
 #include "geossl_hip.h"
 
@@ -32,7 +35,8 @@ constexpr int kTile = 4;   // pairs per block of k_pair_fwd / k_pair_bwd
 enum Readout { kAdd = 0, kMean = 1 };
 
 template <int F>
-__global__ __launch_bounds__(F < 64 ? 64 : F) void k_pair_fwd(const float* __restrict__ h, int N,
+__global__ __launch_bounds__(F < 64 ? 64 : F) void k_pair_fwd(const float* __restrict__ h, int N_cap,
+                                                              const int32_t* __restrict__ dyn_N,
                                                               const int32_t* __restrict__ mol_ptr, int B, int readout,
                                                               const float* __restrict__ w, const float* __restrict__ bias,
                                                               const float* __restrict__ y, float* __restrict__ m_out,
@@ -43,6 +47,7 @@ __global__ __launch_bounds__(F < 64 ? 64 : F) void k_pair_fwd(const float* __res
   const int j = threadIdx.x, lane = j & 63, wave = j >> 6;
   const int b0 = blockIdx.x * kTile;
   const bool live = j < F;
+  const int N = dyn_count(N_cap, dyn_N);
   const float w0 = live ? w[j] : 0.0f, w1 = live ? w[F + j] : 0.0f;
 #pragma unroll
   for (int t = 0; t < kTile; ++t) {
@@ -97,13 +102,15 @@ __global__ __launch_bounds__(256) void k_pair_loss(const double* __restrict__ pa
 }
 
 template <int F>
-__global__ __launch_bounds__(F < 64 ? 64 : F) void k_pair_bwd(int N, const int32_t* __restrict__ mol_ptr, int B,
+__global__ __launch_bounds__(F < 64 ? 64 : F) void k_pair_bwd(int N_cap, const int32_t* __restrict__ dyn_N,
+                                                              const int32_t* __restrict__ mol_ptr, int B,
                                                               int readout, const float* __restrict__ w,
                                                               const float* __restrict__ z, const float* __restrict__ y,
                                                               const float* __restrict__ gout, float* __restrict__ dh,
                                                               float* __restrict__ dz_out) {
   const int j = threadIdx.x;
   const int b0 = blockIdx.x * kTile;
+  const int N = dyn_count(N_cap, dyn_N);
   const float g = gout[0];
 #pragma unroll
   for (int t = 0; t < kTile; ++t) {
@@ -151,16 +158,16 @@ inline bool args_ok(int64_t N, int F, int64_t B, int readout) {
 
 int fwd_impl(const float* h, int64_t N, int F, const int32_t* mol_ptr, int64_t B, int readout, const float* w,
              const float* b, const float* y, float* m, float* z, float* workspace, float* loss, bool predict,
-             hipStream_t stream) {
+             const int32_t* dyn_N, hipStream_t stream) {
   if (!args_ok(N, F, B, readout) || mol_ptr == nullptr || w == nullptr || b == nullptr || z == nullptr ||
       (N > 0 && h == nullptr) || (!predict && (y == nullptr || m == nullptr || workspace == nullptr || loss == nullptr)))
     return (int)hipErrorInvalidValue;
   double* part = predict ? nullptr : reinterpret_cast<double*>(workspace);
   const dim3 tiles((unsigned)((B + kTile - 1) / kTile));
   switch (F) {
-    case 32: hipLaunchKernelGGL(k_pair_fwd<32>, tiles, dim3(64), 0, stream, h, (int)N, mol_ptr, (int)B, readout, w, b, y, m, z, part); break;
-    case 64: hipLaunchKernelGGL(k_pair_fwd<64>, tiles, dim3(64), 0, stream, h, (int)N, mol_ptr, (int)B, readout, w, b, y, m, z, part); break;
-    default: hipLaunchKernelGGL(k_pair_fwd<128>, tiles, dim3(128), 0, stream, h, (int)N, mol_ptr, (int)B, readout, w, b, y, m, z, part); break;
+    case 32: hipLaunchKernelGGL(k_pair_fwd<32>, tiles, dim3(64), 0, stream, h, (int)N, dyn_N, mol_ptr, (int)B, readout, w, b, y, m, z, part); break;
+    case 64: hipLaunchKernelGGL(k_pair_fwd<64>, tiles, dim3(64), 0, stream, h, (int)N, dyn_N, mol_ptr, (int)B, readout, w, b, y, m, z, part); break;
+    default: hipLaunchKernelGGL(k_pair_fwd<128>, tiles, dim3(128), 0, stream, h, (int)N, dyn_N, mol_ptr, (int)B, readout, w, b, y, m, z, part); break;
   }
   GEOSSL_CHECK_LAUNCH();
   if (!predict) {
@@ -176,29 +183,42 @@ extern "C" int geossl_pair_head_width_ok(int F) { return width_ok(F) ? 1 : 0; }
 
 extern "C" int64_t geossl_pair_head_workspace_floats(int64_t B) { return 2 * (B > 0 ? B : 1); }
 
+extern "C" int geossl_pair_head_fwd_dyn(const float* h, int64_t N, int F, const int32_t* mol_ptr, int64_t B, int readout,
+                                        const float* w, const float* b, const float* y, float* m, float* z,
+                                        float* workspace, float* loss, const int32_t* dyn_N, hipStream_t stream) {
+  return fwd_impl(h, N, F, mol_ptr, B, readout, w, b, y, m, z, workspace, loss, false, dyn_N, stream);
+}
+
 extern "C" int geossl_pair_head_fwd(const float* h, int64_t N, int F, const int32_t* mol_ptr, int64_t B, int readout,
                                     const float* w, const float* b, const float* y, float* m, float* z,
                                     float* workspace, float* loss, hipStream_t stream) {
-  return fwd_impl(h, N, F, mol_ptr, B, readout, w, b, y, m, z, workspace, loss, false, stream);
+  return geossl_pair_head_fwd_dyn(h, N, F, mol_ptr, B, readout, w, b, y, m, z, workspace, loss, nullptr, stream);
+}
+
+extern "C" int geossl_pair_head_predict_dyn(const float* h, int64_t N, int F, const int32_t* mol_ptr, int64_t B,
+                                            int readout, const float* w, const float* b, float* z,
+                                            const int32_t* dyn_N, hipStream_t stream) {
+  return fwd_impl(h, N, F, mol_ptr, B, readout, w, b, nullptr, nullptr, z, nullptr, nullptr, true, dyn_N, stream);
 }
 
 extern "C" int geossl_pair_head_predict(const float* h, int64_t N, int F, const int32_t* mol_ptr, int64_t B,
                                         int readout, const float* w, const float* b, float* z, hipStream_t stream) {
-  return fwd_impl(h, N, F, mol_ptr, B, readout, w, b, nullptr, nullptr, z, nullptr, nullptr, true, stream);
+  return geossl_pair_head_predict_dyn(h, N, F, mol_ptr, B, readout, w, b, z, nullptr, stream);
 }
 
-extern "C" int geossl_pair_head_bwd(int64_t N, int F, const int32_t* mol_ptr, int64_t B, int readout, const float* w,
-                                    const float* m, const float* z, const float* y, const float* gout, float* dh,
-                                    float* dw, float* db, float* workspace, int accumulate, hipStream_t stream) {
+extern "C" int geossl_pair_head_bwd_dyn(int64_t N, int F, const int32_t* mol_ptr, int64_t B, int readout, const float* w,
+                                        const float* m, const float* z, const float* y, const float* gout, float* dh,
+                                        float* dw, float* db, float* workspace, int accumulate, const int32_t* dyn_N,
+                                        hipStream_t stream) {
   if (!args_ok(N, F, B, readout) || mol_ptr == nullptr || w == nullptr || m == nullptr || z == nullptr ||
       y == nullptr || gout == nullptr || (N > 0 && dh == nullptr) || workspace == nullptr)
     return (int)hipErrorInvalidValue;
   const dim3 tiles((unsigned)((B + kTile - 1) / kTile));
   float* dz = workspace;
   switch (F) {
-    case 32: hipLaunchKernelGGL(k_pair_bwd<32>, tiles, dim3(64), 0, stream, (int)N, mol_ptr, (int)B, readout, w, z, y, gout, dh, dz); break;
-    case 64: hipLaunchKernelGGL(k_pair_bwd<64>, tiles, dim3(64), 0, stream, (int)N, mol_ptr, (int)B, readout, w, z, y, gout, dh, dz); break;
-    default: hipLaunchKernelGGL(k_pair_bwd<128>, tiles, dim3(128), 0, stream, (int)N, mol_ptr, (int)B, readout, w, z, y, gout, dh, dz); break;
+    case 32: hipLaunchKernelGGL(k_pair_bwd<32>, tiles, dim3(64), 0, stream, (int)N, dyn_N, mol_ptr, (int)B, readout, w, z, y, gout, dh, dz); break;
+    case 64: hipLaunchKernelGGL(k_pair_bwd<64>, tiles, dim3(64), 0, stream, (int)N, dyn_N, mol_ptr, (int)B, readout, w, z, y, gout, dh, dz); break;
+    default: hipLaunchKernelGGL(k_pair_bwd<128>, tiles, dim3(128), 0, stream, (int)N, dyn_N, mol_ptr, (int)B, readout, w, z, y, gout, dh, dz); break;
   }
   GEOSSL_CHECK_LAUNCH();
   if (dw != nullptr || db != nullptr) {
@@ -207,4 +227,11 @@ extern "C" int geossl_pair_head_bwd(int64_t N, int F, const int32_t* mol_ptr, in
     GEOSSL_CHECK_LAUNCH();
   }
   return 0;
+}
+
+extern "C" int geossl_pair_head_bwd(int64_t N, int F, const int32_t* mol_ptr, int64_t B, int readout, const float* w,
+                                    const float* m, const float* z, const float* y, const float* gout, float* dh,
+                                    float* dw, float* db, float* workspace, int accumulate, hipStream_t stream) {
+  return geossl_pair_head_bwd_dyn(N, F, mol_ptr, B, readout, w, m, z, y, gout, dh, dw, db, workspace, accumulate, nullptr,
+                                  stream);
 }

@@ -14,6 +14,16 @@ Anything the kernels do not serve runs the reference's own ATen lines on our bac
 the reference's ``.squeeze()`` makes ``pred`` 0-d against a ``[1]`` target and ``BCEWithLogitsLoss`` raises ValueError.
 ``predict_LEP`` / ``eval_LEP`` mirror ``eval()``, :66-101, with the two rank metrics in numpy (sklearn's definitions).
 ``LEPTrainer`` is the ``train()`` body on the fused step with backbone and head in one flat buffer.
+
+On shuffled pairs no two batches share both size sequences, so a graph keyed by them is never replayed.  The step reads
+no pair tuples (``LEP.pair_tuples`` is False): a SchNet batch whose layout is sparse - a structure of either side above
+255 atoms, or GEOSSL_SPARSE_PAIRS=1 - goes through ONE sparse capacity bucket (``bucket.SPARSE``) of 2B structures per
+batch size, with the pair head's ``_dyn`` forms reading the real atom count on the device.  The switch is
+GEOSSL_SPARSE_BUCKETS (switches.sparse_buckets): unset, the pair handles of a ``DeviceLoader`` over a
+``PairedDeviceDataset`` take the bucket and collated ``BatchLEP`` batches keep their routing; 1: both; 0: neither.
+A handle's fill is one pinned upload, one gather launch over the 2B structures and one launch that writes the labels
+from the dataset's ``y`` on the device; nothing is read back and nothing is concatenated per step.  A batch whose
+structures are all <= 255 atoms, a structure above 1024 atoms and PaiNN keep the per-structure graph or eager launches.
 """
 from collections import OrderedDict
 
@@ -52,7 +62,19 @@ def modules_ok(model, graph_pred_linear):
     return ps is not None and readout_of(model) is not None and model_width(model) * 2 == ps[0].size(1)
 
 
+def _is_handle(batch):
+    """A PairedBatch of a DeviceLoader over a PairedDeviceDataset (or its fused 2B-structure handle)."""
+    return getattr(batch, "_dataset", None) is not None
+
+
+def _check_handle(batch, model_3d):
+    if model_3d == "painn" and _is_handle(batch):
+        raise ValueError("a PairedDeviceDataset holds no radius edges: PaiNN pairs are collated by DataLoaderLEP")
+
+
 def _fused_batch_ok(batch):
+    if _is_handle(batch):   # float32 / int64 tensors on its device, one label per pair, by construction
+        return batch.device.type == "cuda" and _n_pairs(batch) >= 2
     need = ("x_active", "positions_active", "batch_active", "x_inactive", "positions_inactive", "batch_inactive", "y")
     ts = [getattr(batch, k, None) for k in need]
     if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in ts):
@@ -107,8 +129,10 @@ def fused_batch(batch):
     edges are shifted by the TOTAL active atom count (the loader has already applied the per-side running counts).
     ``y`` is the batch's label tensor as float32, taken anew at every call."""
     from .pretrain_GeoSSL import Batch
-    if isinstance(batch, Batch):
+    if isinstance(batch, Batch) or hasattr(batch, "pairs"):
         return batch
+    if _is_handle(batch):   # a PairedBatch: the 2B structures are a handle on the dataset's structures - no host cat
+        return batch.fused()
     fb = batch.__dict__.get("_geossl_fused")
     if fb is None:
         sizes = np.concatenate([_host_sizes(batch, "active"), _host_sizes(batch, "inactive")])
@@ -156,10 +180,36 @@ def lep_step_aten(args, batch, model, graph_pred_linear, criterion):
 
 def lep_step_fused(model_3d, fb, model, graph_pred_linear, y):
     """The step as eager launches on the one-pass batch ``fb``: the backbone's latent of the 2B structures, then the
-    fused pair head with the readout in it -> (loss fp32 scalar, logits [B]).  y [B]: the labels as float32."""
-    h, lay, _ = backbone_latent(model_3d, fb, model, x=fb.x, what="LEP", layout=True)
+    fused pair head with the readout in it -> (loss fp32 scalar, logits [B]).  y: the labels as float32 - the leading B
+    entries are read (the static "target" of a bucket graph has one row per structure).  ``fb`` may be the static batch
+    of a sparse bucket of 2B structures: the head then reads the real atom count on the device (``dims``)."""
+    h, lay, dyn = backbone_latent(model_3d, fb, model, x=_x_of(model_3d, fb), what="LEP", layout=True)
     w, b = head_params(graph_pred_linear)
-    return ops.pair_head(h, w, b, lay, readout_of(model), y)
+    return ops.pair_head(h, w, b, lay, readout_of(model), y[:int(lay.B) // 2], dyn=dyn)
+
+
+def _x_of(model_3d, fb):
+    """The backbone's first argument: the atom types as the records hold them (1-D), which a DeviceDataset and a bucket
+    keep as one column."""
+    return fb.x[:, 0] if model_3d == "schnet" and fb.x.dim() == 2 else fb.x
+
+
+def write_labels(g, fb):
+    """The batch's labels into the leading B entries of the graph's static "target": a collated batch's by one copy;
+    a handle's by one launch over the dataset's labels, from the structure offsets the step's gather has just uploaded
+    (the bucket's blob, or the dataset's staging buffer of a per-structure graph) - the active structure of pair m is
+    structure m of the dataset.  Nothing is read back."""
+    dst, B = g["noise"]["target"], int(fb.num_graphs) // 2
+    pairs = getattr(fb, "pairs", None)
+    if pairs is None:
+        dst[:B].copy_(fb.y)
+        return
+    pds, bkt = pairs._dataset, g.get("bucket")
+    if bkt is not None:
+        src = bkt.blob.data_ptr() + 4 * bkt.off["src_off"]
+    else:
+        src = pds.structures.__dict__["_src_off_dev"].data_ptr()
+    ops.property_targets(pds.y.view(-1, 1), 0, pds.structures.mol_off(), src, B, dst)
 
 
 class _StepArgs:
@@ -170,13 +220,15 @@ class _StepArgs:
 
 
 # (no draws: the labels, the graph's static input "target", are the one per-step input beside the structures - data of a
-# graph, not structure: batches that agree in their index tensors share a graph whatever their labels)
+# graph, not structure: batches that agree in their index tensors share a graph whatever their labels; no pair tuples
+# are read, so a batch with a sparse layout - a structure above 255 atoms - may go through a sparse bucket of 2B structures)
 LEP = Objective(
     "LEP",
     lambda eng, args, mu, sigma, batch, noise: lep_step_fused(args.model_3d, batch, eng.model, eng.n1, noise["target"])[0],
     noise_keys=lambda args: ("target",),
     capture_inputs=lambda eng, args, batch, mu, sigma, noise, device_noise: {"target": batch.y},
-    write_inputs=lambda eng, args, sg, g, batch, mu, sigma, noise, device_noise: g["noise"]["target"].copy_(batch.y))
+    write_inputs=lambda eng, args, sg, g, batch, mu, sigma, noise, device_noise: write_labels(g, batch),
+    pair_tuples=False)
 
 
 def do_LEP(args, batch, model, graph_pred_linear, criterion=None, graph=None):
@@ -184,13 +236,16 @@ def do_LEP(args, batch, model, graph_pred_linear, criterion=None, graph=None):
     criterion None means the script's nn.BCEWithLogitsLoss(); batch.y may be integer (:43).  The fused one-pass step runs
     for a stock mean BCEWithLogitsLoss, graph_pred_linear = Linear(2F, 1) with a bias, an unscaled backbone with a
     mean / add readout at F = 32 / 64 / 128, and CUDA batches of B >= 2 pairs with one label per pair; anything else runs
-    the reference's ATen lines (two passes) - at B = 1 they raise ValueError, as the reference does.  graph: replay HIP
-    graphs of forward + backward (default: ``args.step_graph`` if present, else on unless GEOSSL_NO_STEP_GRAPH is set);
-    a batch gets its graph at the second sighting of its index tensors."""
+    the reference's ATen lines (two passes) - at B = 1 they raise ValueError, as the reference does.  batch: a collated
+    ``BatchLEP`` or a ``DeviceLoader`` pair handle (``PairedBatch``; SchNet).  graph: replay HIP graphs of forward +
+    backward (default: ``args.step_graph`` if present, else on unless GEOSSL_NO_STEP_GRAPH is set): the sparse bucket
+    graph of ``LEPTrainer``'s routing where that serves the batch, else a graph of its own at the second sighting of its
+    index tensors."""
     if criterion is None:
         criterion = nn.BCEWithLogitsLoss()
     if args.model_3d not in ("schnet", "painn"):
         raise Exception("3D model {} not included.".format(args.model_3d))
+    _check_handle(batch, args.model_3d)
     if not (_stock_bce(criterion) and modules_ok(model, graph_pred_linear) and _fused_batch_ok(batch)):
         return lep_step_aten(args, batch, model, graph_pred_linear, criterion)
     fb = fused_batch(batch)
@@ -209,12 +264,13 @@ def predict_LEP(args, batch, model, graph_pred_linear):
     """eval()'s forward for one batch, :77-85 -> the logits [B] (a 0-d tensor at B = 1, on the ATen lines)."""
     if args.model_3d not in ("schnet", "painn"):
         raise Exception("3D model {} not included.".format(args.model_3d))
+    _check_handle(batch, args.model_3d)
     if not (modules_ok(model, graph_pred_linear) and _fused_batch_ok(batch)):
         return _forward_aten(args, batch, model, graph_pred_linear)
     fb = fused_batch(batch)
-    h, lay, _ = backbone_latent(args.model_3d, fb, model, x=fb.x, what="LEP", layout=True)
+    h, lay, dyn = backbone_latent(args.model_3d, fb, model, x=_x_of(args.model_3d, fb), what="LEP", layout=True)
     w, b = head_params(graph_pred_linear)
-    return ops.pair_predict(h, w, b, lay, readout_of(model))
+    return ops.pair_predict(h, w, b, lay, readout_of(model), dyn=dyn)
 
 
 # ------------------------------------------------------------------------------------------------------- metrics
@@ -300,9 +356,13 @@ class LEPTrainer(StepTrainer):
     pair head with the readout in it, backward, gradient all-reduce, Adam - backbone and graph_pred_linear in one flat
     buffer (one fused Adam launch: both of the reference's groups run at args.lr), no host sync inside ``step``.
     ``step(batch) -> loss`` on the device; ``set_lr(lr)`` between epochs is how a schedule is applied.
-    ``use_graph=True``: forward + backward are captured into HIP graphs and replayed, one graph per structure of the
-    fused batch (``graph_mode="auto"``: from its second sighting on; capacity buckets do not take paired batches); the
-    labels are a static input of the graph."""
+    ``use_graph=True``: forward + backward are captured into HIP graphs and replayed; the labels are a static input of
+    the graph.  ``graph_mode="auto"``: SchNet batches with a sparse layout (a structure of either side above 255 atoms, up
+    to 1024; or GEOSSL_SPARSE_PAIRS=1) at width 128 share ONE sparse capacity-bucket graph of 2B structures per batch
+    size - the pair handles of a ``DeviceLoader`` over a ``PairedDeviceDataset`` by default, collated ``BatchLEP``
+    batches with GEOSSL_SPARSE_BUCKETS=1 (``=0``: neither); anything else - all structures <= 255 atoms, PaiNN, other
+    widths - one graph per structure of the fused batch, from its second sighting on.  ``step`` takes a collated
+    ``BatchLEP`` or a pair handle (SchNet; a handle holds no radius edges)."""
 
     def __init__(self, model, graph_pred_linear, lr=5e-4, weight_decay=0.0, model_3d="schnet", use_graph=False,
                  max_graphs=256, graph_mode="auto"):
@@ -314,7 +374,7 @@ class LEPTrainer(StepTrainer):
             raise Exception("3D model {} not included.".format(model_3d))
         self.head, self.model_3d = graph_pred_linear, model_3d
         super().__init__([model, graph_pred_linear], model_3d, lr, weight_decay, use_graph, max_graphs, graph_mode,
-                         noise_keys=("target",), views=1)
+                         noise_keys=("target",), views=1, pair_tuples=False)
 
     @property
     def lr(self):
@@ -331,11 +391,12 @@ class LEPTrainer(StepTrainer):
         return {"target": fb.y}
 
     def _write_inputs(self, g, fb, noise):
-        g["noise"]["target"].copy_(fb.y)
+        write_labels(g, fb)
 
     def _one_pass(self, batch):
         from .pretrain_GeoSSL import Batch
-        if not isinstance(batch, Batch) and not _fused_batch_ok(batch):
+        _check_handle(batch, self.model_3d)
+        if not isinstance(batch, Batch) and not hasattr(batch, "pairs") and not _fused_batch_ok(batch):
             raise ValueError("LEPTrainer needs CUDA batches of B >= 2 pairs with one label per pair; use do_LEP for "
                              "anything else")
         return fused_batch(batch)

@@ -1309,10 +1309,12 @@ class _PairHead(torch.autograd.Function):
     """The LEP step after the backbone (finetune_lep.py:40-45) on csrc/pair_head.hip -> (loss fp32 scalar, z [B] fp32
     logits, non-differentiable).  h is the latent of the 2B-structure batch [active | inactive], (w, b) the parameters
     of Linear(2F, 1).  The backward returns dh (the readout's backward in it) and the head's gradients through autograd,
-    or, inside _lib.direct_grads() with dense fp32 .grad tensors, adds the head's gradients into them."""
+    or, inside _lib.direct_grads() with dense fp32 .grad tensors, adds the head's gradients into them.  dyn
+    (bucket.DynDims, or None): the rows of h are a capacity - the `_dyn` entry points, which are the exact ones with the
+    real atom count read on the device."""
 
     @staticmethod
-    def forward(ctx, h, y, layout, readout, w, b):
+    def forward(ctx, h, y, layout, readout, dyn, w, b):
         h = _f32(h)
         N, F = h.shape
         B = int(layout.B) // 2
@@ -1322,10 +1324,10 @@ class _PairHead(torch.autograd.Function):
         z = torch.empty(B, **f32)
         ws = torch.empty(int(_lib.load().geossl_pair_head_workspace_floats(B)), **f32)
         loss = torch.empty((), **f32)
-        call("geossl_pair_head_fwd", ptr(h), N, F, ptr(layout.mol_ptr), B, PROPERTY_READOUTS[readout], ptr(wd), ptr(bd),
-             ptr(y), ptr(m), ptr(z), ptr(ws), ptr(loss), stream())
+        call("geossl_pair_head_fwd_dyn", ptr(h), N, F, ptr(layout.mol_ptr), B, PROPERTY_READOUTS[readout], ptr(wd),
+             ptr(bd), ptr(y), ptr(m), ptr(z), ptr(ws), ptr(loss), _dyn(dyn, "n_atoms"), stream())
         ctx.save_for_backward(m, z, y, wd)
-        ctx.lay, ctx.readout, ctx.params, ctx.N = layout, readout, (w, b), N
+        ctx.lay, ctx.readout, ctx.params, ctx.N, ctx.dyn = layout, readout, (w, b), N, dyn
         ctx.mark_non_differentiable(z)
         ctx.set_materialize_grads(False)
         return loss, z
@@ -1333,7 +1335,7 @@ class _PairHead(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout, _gz):
         if gout is None:
-            return (None,) * 6
+            return (None,) * 7
         m, z, y, wd = ctx.saved_tensors
         F = m.size(1)
         B = z.numel()
@@ -1348,13 +1350,14 @@ class _PairHead(torch.autograd.Function):
         for i, p in enumerate(params):
             if direct:
                 grads[i] = p.grad if p.requires_grad else None
-            elif ctx.needs_input_grad[4 + i]:
+            elif ctx.needs_input_grad[5 + i]:
                 grads[i] = torch.empty_like(p, dtype=torch.float32)
-        call("geossl_pair_head_bwd", ctx.N, F, ptr(ctx.lay.mol_ptr), B, PROPERTY_READOUTS[ctx.readout], ptr(wd), ptr(m),
-             ptr(z), ptr(y), ptr(g), ptr(dh), ptr(grads[0]), ptr(grads[1]), ptr(ws), 1 if direct else 0, stream())
+        call("geossl_pair_head_bwd_dyn", ctx.N, F, ptr(ctx.lay.mol_ptr), B, PROPERTY_READOUTS[ctx.readout], ptr(wd),
+             ptr(m), ptr(z), ptr(y), ptr(g), ptr(dh), ptr(grads[0]), ptr(grads[1]), ptr(ws), 1 if direct else 0,
+             _dyn(ctx.dyn, "n_atoms"), stream())
         if direct:
             grads = [None, None]
-        return (dh, None, None, None) + tuple(grads)
+        return (dh, None, None, None, None) + tuple(grads)
 
 
 def pair_head_width_ok(F):
@@ -1376,26 +1379,27 @@ def _check_pair_head(h, layout, readout, w, b):
                          "N = %d for %d rows" % (layout.B, layout.N, h.size(0)))
 
 
-def pair_head(h, w, b, layout, readout, y):
+def pair_head(h, w, b, layout, readout, y, dyn=None):
     """The LEP loss with the readout inside the head -> (loss, z): h [N, F] per-atom latent of the 2B structures
     [active 0 .. B-1 | inactive 0 .. B-1] (atoms sorted by structure), (w [1, 2F], b [1]) of Linear(2F, 1), layout: the
     MolLayout of the 2B structures, readout "mean" / "add" ("sum"), y [B] float32 labels.  loss is the mean
-    BCE-with-logits of z_b = b + <w[0:F], m_b> + <w[F:2F], m_{B+b}>; z [B] the logits."""
+    BCE-with-logits of z_b = b + <w[0:F], m_b> + <w[F:2F], m_{B+b}>; z [B] the logits.  dyn (bucket.DynDims): the rows of
+    h are a capacity and the real atom count is read on the device (layout.mol_ptr holds the real offsets)."""
     _check_pair_head(h, layout, readout, w, b)
     B = int(layout.B) // 2
     _lib.require_cuda(y)
     if y.dim() != 1 or y.numel() != B or y.dtype != torch.float32 or not y.is_contiguous():
         raise ValueError("pair head: y is a contiguous float32 [B], B = %d, got %s %s" % (B, y.dtype, tuple(y.shape)))
-    return _PairHead.apply(h, y, layout, readout, w, b)
+    return _PairHead.apply(h, y, layout, readout, dyn, w, b)
 
 
-def pair_predict(h, w, b, layout, readout):
-    """eval() of finetune_lep.py:77-85 after the backbone: the logits [B] (no autograd)."""
+def pair_predict(h, w, b, layout, readout, dyn=None):
+    """eval() of finetune_lep.py:77-85 after the backbone: the logits [B] (no autograd); dyn as in `pair_head`."""
     _check_pair_head(h, layout, readout, w, b)
     h = _f32(h.detach())
     N, F = h.shape
     B = int(layout.B) // 2
     z = torch.empty(B, dtype=torch.float32, device=h.device)
-    call("geossl_pair_head_predict", ptr(h), N, F, ptr(layout.mol_ptr), B, PROPERTY_READOUTS[readout],
-         ptr(w.detach().contiguous()), ptr(b.detach().contiguous()), ptr(z), stream())
+    call("geossl_pair_head_predict_dyn", ptr(h), N, F, ptr(layout.mol_ptr), B, PROPERTY_READOUTS[readout],
+         ptr(w.detach().contiguous()), ptr(b.detach().contiguous()), ptr(z), _dyn(dyn, "n_atoms"), stream())
     return z

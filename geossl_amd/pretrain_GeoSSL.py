@@ -412,8 +412,8 @@ class StepGraphs:
       a structure that only a fingerprint identifies is captured on its SECOND sighting (a loader that never repeats one
       never pays for a capture);
     * a batch with a SPARSE layout (a structure of 256 to 1024 atoms - LBA's pockets - or GEOSSL_SPARSE_PAIRS=1) in a
-      one-view SchNet step that reads no pair tuples (``pair_tuples=False``: Supervised): one graph per number of
-      structures in a sparse bucket (``bucket.SPARSE``) - by default the handles of a DeviceLoader, with
+      one-view SchNet step that reads no pair tuples (``pair_tuples=False``: Supervised, and LEP with its 2B structures
+      [active | inactive]): one graph per number of structures in a sparse bucket (``bucket.SPARSE``) - by default the handles of a DeviceLoader, with
       ``GEOSSL_SPARSE_BUCKETS=1`` collated batches too (``=0``: neither; such a batch is served as the first entry says);
     * every other SchNet batch - ragged molecules in shuffled order, the reference's loader (pretrain_GeoSSL.py:301) - one
       graph per (molecules in the batch, tuple option) at a CAPACITY (``geossl_amd/bucket.py``): the graph's kernels read
@@ -654,7 +654,9 @@ class StepGraphs:
         into = StepGraphs.noise_views(g)
         for k in into:   # (the graph's own draws: all five of a DDM step)
             dst = into[k]
-            if k == "mask_idx":   # (the leading k entries: the kernel reads as many as the batch's k)
+            # (the leading k entries: the mask kernel reads as many as the batch's k; a paired step - LEP - has one
+            # label per PAIR, the leading half of a bucket's structure count)
+            if k == "mask_idx" or (k == "target" and noise[k].numel() * 2 == dst.numel()):
                 dst = dst[:noise[k].numel()]
             dst.copy_(noise[k].view_as(dst))
 

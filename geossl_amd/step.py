@@ -32,7 +32,7 @@ class Objective:
     name            first entry of the default graph key
     views           views of the molecules the backbone sees in a capacity bucket (1 or 2)
     normalize       ``args.normalize`` keeps a batch off capacity buckets (DDM only: its row normalisation is over atoms)
-    pair_tuples     the step reads the batch's pair tuples (``super_edge_index``); False (Supervised): a batch whose
+    pair_tuples     the step reads the batch's pair tuples (``super_edge_index``); False (Supervised, LEP): a batch whose
                     layout is sparse - a structure above 255 atoms - may go through a sparse bucket (bucket.SPARSE), which
                     enumerates none
     head_params     head module -> the parameters the step reaches

@@ -46,13 +46,14 @@ def rbf_image(capturing):
 
 
 def sparse_buckets(handle):
-    """``GEOSSL_SPARSE_BUCKETS``: the batches of a step that reads no pair tuples (Supervised) whose layout is sparse - a
+    """``GEOSSL_SPARSE_BUCKETS``: the batches of a step that reads no pair tuples (Supervised, LEP) whose layout is sparse - a
     structure above 255 atoms, or ``GEOSSL_SPARSE_PAIRS=1`` - replay one capacity-bucket graph per batch size
     (``bucket.SPARSE``).  ``1``: every such batch; ``0``: none - the routing before that bucket existed: a per-structure
     graph from the second sighting on, eager launches before.  Unset: ``handle`` - the handles of a ``DeviceLoader`` do,
     collated batches do not (measured on shuffled pockets, DESIGN section 5: the handles' step is 9 - 13 % shorter through
     the bucket; a collated batch's step is bound by the device and the host's collation either way, and the bucket's
-    replay did not beat the eager launches there)."""
+    replay did not beat the eager launches there.  LEP's pair handles, same section: 5 - 13 % below the fastest route of
+    collated pairs; collated pairs through the bucket gain at 8 pairs and nothing at 32)."""
     v = env("GEOSSL_SPARSE_BUCKETS")
     if v == "0":
         return False

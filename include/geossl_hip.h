@@ -1004,7 +1004,10 @@ int geossl_property_targets(const float* y, int64_t M, int T, int task_id, const
  * Predict: z [B] only.
  * Backward with gout[0]: dz_b = gout (sigmoid(z_b) - y_b) / B; dh [N][F] (out) = dz_b w[side F + j] (/ max(n_s, 1) for
  *   "mean") on every atom row of both structures of pair b, each written once; dw [2F] / db [1] (out; NULL: skipped) =
- *   sum_b dz_b m[side B + b][j] / sum_b dz_b in pair order, added to what is there when accumulate != 0. */
+ *   sum_b dz_b m[side B + b][j] / sum_b dz_b in pair order, added to what is there when accumulate != 0.
+ * `_dyn`: N is a capacity and dyn_N (nullable) points at the real atom count; mol_ptr [2B + 1] holds the real offsets
+ *   (B is exact).  No atom row of h / dh at or past the real count is read or written; the arithmetic and the order of
+ *   every sum are those of the exact forms (the same inputs give the same bits as they do). */
 int geossl_pair_head_width_ok(int F);
 int64_t geossl_pair_head_workspace_floats(int64_t B);
 int geossl_pair_head_fwd(const float* h, int64_t N, int F, const int32_t* mol_ptr, int64_t B, int readout, const float* w,
@@ -1015,6 +1018,14 @@ int geossl_pair_head_predict(const float* h, int64_t N, int F, const int32_t* mo
 int geossl_pair_head_bwd(int64_t N, int F, const int32_t* mol_ptr, int64_t B, int readout, const float* w, const float* m,
                          const float* z, const float* y, const float* gout, float* dh, float* dw, float* db,
                          float* workspace, int accumulate, hipStream_t stream);
+int geossl_pair_head_fwd_dyn(const float* h, int64_t N, int F, const int32_t* mol_ptr, int64_t B, int readout,
+                             const float* w, const float* b, const float* y, float* m, float* z, float* workspace,
+                             float* loss, const int32_t* dyn_N, hipStream_t stream);
+int geossl_pair_head_predict_dyn(const float* h, int64_t N, int F, const int32_t* mol_ptr, int64_t B, int readout,
+                                 const float* w, const float* b, float* z, const int32_t* dyn_N, hipStream_t stream);
+int geossl_pair_head_bwd_dyn(int64_t N, int F, const int32_t* mol_ptr, int64_t B, int readout, const float* w,
+                             const float* m, const float* z, const float* y, const float* gout, float* dh, float* dw,
+                             float* db, float* workspace, int accumulate, const int32_t* dyn_N, hipStream_t stream);
 
 /* ---- angle prediction on atom triples: examples/pretrain_TorsionAnglePrediction.py:16-27,64-78 (csrc/torsion_head.hip)
  * h [N][F] node features (F = 64, 128, 256 or 512: geossl_torsion_head_width_ok), W [3F] = predictor.weight =
