@@ -320,6 +320,12 @@ class _PaiNNCore(torch.autograd.Function):
         # k_painn_interaction_bwd_mol<R, true>).  Forces (edge gradients read mu) and GEOSSL_PAINN_NO_MU_ZERO keep the tensor.
         mu_is_zero = (use_mma and big_f is None and not ctx.needs_input_grad[1] and R in (8, 16, 20)
                       and not _env("GEOSSL_PAINN_NO_MU_ZERO"))
+        # Structures of hundreds of atoms fit neither staged form: the atom-tile kernels (painn_tile.hip) then take ALL
+        # atoms in one launch per block - no staged launch, no lists (layout.painn_tile_route; GEOSSL_PAINN_TILE).
+        from ...layout import painn_tile_route
+        use_tile = bool(cfg["mma"]) and painn_tile_route(lay, F_, R, E, dyn)
+        if use_tile:
+            mu_is_zero = not ctx.needs_input_grad[1] and not _env("GEOSSL_PAINN_NO_MU_ZERO")
         mu = None if mu_is_zero else torch.zeros(N, 3, F_, **f32)            # :249
         for l in range(L):
             c0w, c0b, c1w, c1b = inter[l]
@@ -338,7 +344,11 @@ class _PaiNNCore(torch.autograd.Function):
                         _split3(xc, F_))                                     # Dense(F, 3F)
             q2, mu2 = torch.empty_like(q), torch.empty(N, 3, F_, **f32)
             # one block per molecule: the rows its edges read are staged in LDS once
-            if use_mma:  # filter on the matrix pipe (painn_mma.hip); LDS: 3.5 KB per atom + 3 KB
+            if use_tile:  # atom tiles: the filter on the matrix pipe, source rows from L2
+                call("geossl_painn_interaction_fwd_tile", ptr(q), ptr(mu), ptr(xc), ptr(el.idx_j), ptr(inc_ptr),
+                     ptr(inc_idx), ptr(phi), ptr(fcut), ptr(dirv), ptr(fw[l * 3 * F_:(l + 1) * 3 * F_]),
+                     ptr(fb[l * 3 * F_:(l + 1) * 3 * F_]), None, N, None, F_, R, ptr(q2), ptr(mu2), st)   # :54-64
+            elif use_mma:  # filter on the matrix pipe (painn_mma.hip); LDS: 3.5 KB per atom + 3 KB
                 row_edge, grp_atom, _, mol_grp = el.groups("i", lay.mol_ptr)
                 call("geossl_painn_interaction_fwd_mma_dyn", ptr(q), ptr(mu), ptr(xc), ptr(el.idx_j), ptr(row_edge),
                      ptr(grp_atom), ptr(mol_grp), ptr(phi), ptr(fcut), ptr(dirv), ptr(fw[l * 3 * F_:(l + 1) * 3 * F_]),
@@ -392,6 +402,7 @@ class _PaiNNCore(torch.autograd.Function):
             ctx.pos, ctx.want_params = pos, want_params
             ctx.geom = (dirv, fcut, phi)
             ctx.saved = saved
+            ctx.use_tile = use_tile
         return q
 
     @staticmethod
@@ -477,12 +488,16 @@ class _PaiNNCore(torch.autograd.Function):
                 stages[-1]["res"] = res
             return ops.linear_chain(xs_list[0], stages, dyn_rows=dN if xs_list[0].size(0) == N else dN3)[-1]
 
-        nfl = _lib.load().geossl_painn_interaction_bwd_mol_workspace_floats(N, lay.B, F_, R)
+        use_tile = bool(getattr(ctx, "use_tile", False))   # the forward's route (atom tiles: painn_tile.hip)
+        if use_tile:
+            nfl = _lib.load().geossl_painn_interaction_bwd_tile_workspace_floats(N, F_, R)
+        else:
+            nfl = _lib.load().geossl_painn_interaction_bwd_mol_workspace_floats(N, lay.B, F_, R)
         ws = torch.empty(max(int(nfl), 1), **f32)
         # molecules above the LDS rows of the molecule-staged backward: skipped there, covered by the per-atom kernel
         from ...layout import painn_stage_caps
         cap_b = painn_stage_caps(F_, R)[1]
-        big_b = lay.big_atoms(cap_b) if (0 < cap_b < lay.max_n and F_ in (64, 128)) else None
+        big_b = lay.big_atoms(cap_b) if (0 < cap_b < lay.max_n and F_ in (64, 128) and not use_tile) else None
         keep = []
         E = el.E
         if want_pos:  # dL/d(phi, fcut, dir) per edge, summed over the blocks (painn_force.hip)
@@ -543,11 +558,15 @@ class _PaiNNCore(torch.autograd.Function):
                 mu_l = torch.zeros(N, 3, F_, **f32)
             # (the first interaction's mu is identically zero and its gradient is nobody's input: NULL for both)
             dxc, dmu_in = torch.empty(N, 3 * F_, **f32), (None if mu_l is None else torch.empty(N, 3, F_, **f32))
-            call("geossl_painn_interaction_bwd_mol" if big_b is None else "geossl_painn_interaction_bwd_mol_skip",
-                 ptr(dq2), ptr(dmu2), ptr(mu_l), ptr(sv["xc"]), ptr(el.idx_i),
-                 ptr(inc_ptr), ptr(inc_idx), ptr(phi), ptr(fcut), ptr(dirv), ptr(ps[1][l * 3 * F_:(l + 1) * 3 * F_]),
-                 ptr(ps[2][l * 3 * F_:(l + 1) * 3 * F_]), ptr(lay.mol_ptr), lay.B, lay.max_n, N, F_, R, ptr(dxc), ptr(dmu_in),
-                 ptr(g_fw[l * 3 * F_:(l + 1) * 3 * F_]), ptr(g_fb[l * 3 * F_:(l + 1) * 3 * F_]), ptr(ws), acc, st)
+            args = (ptr(dq2), ptr(dmu2), ptr(mu_l), ptr(sv["xc"]), ptr(el.idx_i), ptr(inc_ptr), ptr(inc_idx), ptr(phi),
+                    ptr(fcut), ptr(dirv), ptr(ps[1][l * 3 * F_:(l + 1) * 3 * F_]), ptr(ps[2][l * 3 * F_:(l + 1) * 3 * F_]))
+            outs = (ptr(dxc), ptr(dmu_in), ptr(g_fw[l * 3 * F_:(l + 1) * 3 * F_]), ptr(g_fb[l * 3 * F_:(l + 1) * 3 * F_]),
+                    ptr(ws), acc, st)
+            if use_tile:  # all atoms in one launch (atom_list NULL)
+                call("geossl_painn_interaction_bwd_tile", *args, None, N, None, F_, R, *outs)
+            else:
+                call("geossl_painn_interaction_bwd_mol" if big_b is None else "geossl_painn_interaction_bwd_mol_skip",
+                     *args, ptr(lay.mol_ptr), lay.B, lay.max_n, N, F_, R, *outs)
             if big_b is not None and big_b[1] > 0:
                 call("geossl_painn_interaction_bwd_atoms", ptr(dq2), ptr(dmu2), ptr(mu_l), ptr(sv["xc"]), ptr(el.idx_i),
                      ptr(inc_ptr), ptr(inc_idx), ptr(phi), ptr(fcut), ptr(dirv), ptr(ps[1][l * 3 * F_:(l + 1) * 3 * F_]),

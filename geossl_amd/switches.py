@@ -58,3 +58,22 @@ def sparse_buckets(handle):
     if v == "0":
         return False
     return True if v == "1" else bool(handle)
+
+
+# What the unset GEOSSL_PAINN_TILE means for a layout with a structure above 255 atoms: the outcome of the measurement in
+# profiles/painn_tile_bench.json by the rule stated there.
+PAINN_TILE_DEFAULT = True
+
+
+def painn_tile(max_n):
+    """``GEOSSL_PAINN_TILE``: PaiNN's fused F = 128 interaction runs on the atom-tile kernels (``painn_tile.hip``: one
+    launch per interaction block and pass, over all atoms).  ``1``: every layout those kernels serve - how tests and A/B
+    runs reach them on small molecules; ``0``: never - the molecule-staged and per-atom kernels, call for call.  Unset:
+    layouts whose largest structure is above 255 atoms (``bucket.MAX_N``), if the measurement supports it
+    (``PAINN_TILE_DEFAULT``)."""
+    v = env("GEOSSL_PAINN_TILE")
+    if v == "0":
+        return False
+    if v == "1":
+        return True
+    return PAINN_TILE_DEFAULT and max_n > 255

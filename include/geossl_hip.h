@@ -692,6 +692,30 @@ int geossl_painn_mix_post_bwd_dyn(const float* dq_new, const float* dmu_new, con
 int geossl_painn_mix_pre_bwd_dyn(const float* dq_new, const float* dctx, const float* ctx, const float* mm, int64_t N,
                                  int F, float* dq_in, float* dmm, const int32_t* dyn_N, hipStream_t stream);
 
+/* ---- PaiNN interaction on atom tiles (painn_tile.hip): structures of hundreds of atoms -------------------------------
+ * The filter on the matrix pipe with no molecule in LDS: an atom's incidence list is walked in tiles of 32 rows (one
+ * MFMA tile), the rows of the atoms at the other end come from L2.  F = 128, R in {8, 16, 20} (geossl_painn_tile_ok;
+ * anything else: hipErrorInvalidValue).  The argument lists are those of geossl_painn_interaction_fwd_atoms /
+ * _bwd_atoms, with two extensions: atom_list == NULL means atoms 0 .. nlist-1, and mu == NULL means mu is identically
+ * zero (the first interaction: no mu rows are gathered; the backward then requires dmu_in == NULL).  min(nlist,
+ * *dyn_nlist) entries are real when dyn_nlist is given; the grid depends on nlist alone.  Bit-reproducible, and an
+ * atom's outputs do not depend on its place in the list.  The backward leaves one filter-gradient partial per block
+ * in `workspace` (geossl_painn_interaction_bwd_tile_workspace_floats(nlist, F, R)) and sums them in block order into
+ * dWf / dbf (accumulate = 1: onto what is there).                                                                        */
+int geossl_painn_tile_ok(int F, int R);
+int geossl_painn_interaction_fwd_tile(const float* q, const float* mu, const float* xc, const int64_t* idx_j,
+                                      const int64_t* inc_ptr, const int32_t* inc_idx, const float* phi,
+                                      const float* fcut, const float* dir, const float* Wf, const float* bf,
+                                      const int32_t* atom_list, int64_t nlist, const int32_t* dyn_nlist, int F, int R,
+                                      float* q_out, float* mu_out, hipStream_t stream);
+int64_t geossl_painn_interaction_bwd_tile_workspace_floats(int64_t nlist, int F, int R);
+int geossl_painn_interaction_bwd_tile(const float* dq_out, const float* dmu_out, const float* mu, const float* xc,
+                                      const int64_t* idx_i, const int64_t* inc_ptr, const int32_t* inc_idx,
+                                      const float* phi, const float* fcut, const float* dir, const float* Wf,
+                                      const float* bf, const int32_t* atom_list, int64_t nlist,
+                                      const int32_t* dyn_nlist, int F, int R, float* dxc, float* dmu_in, float* dWf,
+                                      float* dbf, float* workspace, int accumulate, hipStream_t stream);
+
 /* ---- Second-order route (training on forces): the primitives of geossl_amd/tape.py that are not dense products --------
  * Replaces, on the route that differentiates a force again (examples/finetune_md17.py:46-54: pred_force =
  * -grad(E, pos, create_graph=True); loss.backward()), the ATen element-wise / index kernels autograd would launch for
