@@ -530,6 +530,7 @@ extern "C" int geossl_linear_wgrad_dyn(const GeosslTnBatch* batch, int nprob, in
   if (lda < M || ldb < N || ldw < N || (lda & 3) || (ldb & 3) || (M & 3) || (N & 3)) return (int)hipErrorInvalidValue;
   if (nprob <= 0 || R <= 0) return 0;
   if (nprob > GEOSSL_TN_MAX) return (int)hipErrorInvalidValue;
+  if (R > INT_MAX) return (int)hipErrorInvalidValue;  // (the kernel counts rows in 32 bits)
   {
     const int NCM = (M + 31) / 32, NCN = (N + 31) / 32;
     PlainOps ops;

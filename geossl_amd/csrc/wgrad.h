@@ -297,6 +297,7 @@ int launch_wgrad_split(const Ops& ops, int nprob, int64_t R, int M, int N, const
                        float* workspace, int accumulate, hipStream_t stream, const int32_t* dyn_R = nullptr) {
   if (nprob <= 0 || R <= 0) return 0;
   if (nprob > GEOSSL_TN_MAX) return (int)hipErrorInvalidValue;
+  if (R > INT_MAX) return (int)hipErrorInvalidValue;  // (the kernel counts rows in 32 bits)
   int chunk, nblk;
   geossl_tn_plan(R, nprob, &chunk, &nblk);
   float* partial = workspace;
