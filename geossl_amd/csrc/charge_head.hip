@@ -13,8 +13,8 @@
 //
 // Head forward (k_charge_fwd: one wave per masked row, W in LDS): logits = h[idx_j] W^T + b, a max-subtracted
 //   log-softmax, term_j = lse_j - logit_j[y_j]; the softmax rows are kept for the backward; per-block fp64 sums of the
-//   terms in row order, then one block adds them in block order and divides by k (k = 0: 0 / 0 = NaN, the mean of an
-//   empty tensor).  A row whose atom index is outside [0, N) or whose label is outside [0, C) reads nothing, its term is
+//   terms in row order, then one block adds them in block order and divides by k (k_head_loss of head_common.h; k = 0:
+//   0 / 0 = NaN, the mean of an empty tensor).  A row whose atom index is outside [0, N) or whose label is outside [0, C) reads nothing, its term is
 //   NaN, its softmax row 0, and bit 0 of the status word is set (nn.CrossEntropyLoss raises for such a label).
 // Head backward, with g = gout[0] / k (fp32): d_j = (p_j - onehot(y_j)) g;
 //   dh = 0 on every atom row, then dh[idx_j] = d_j W for the masked rows (k_charge_bwd_rows);
@@ -24,8 +24,8 @@
 // order), so the same inputs and seed give the same bits.
 // Capacity launches (`_dyn`): N and K are capacities that size grids and buffers; the real N is read from dyn_N and
 // the real k from k_dev (written by the mask launch).  Rows at and past them are neither read nor written.
-#include "common.h"
 #include "geossl_hip.h"
+#include "head_common.h"
 
 using namespace geossl;
 
@@ -284,22 +284,6 @@ __global__ __launch_bounds__(kFwdBlock) void k_charge_fwd(const float* __restric
   }
 }
 
-// One block: loss = (the block partials added in block order per thread, then a tree) / k.
-__global__ __launch_bounds__(256) void k_charge_loss(const double* __restrict__ partial, int nblk, int K_cap,
-                                                     const int32_t* __restrict__ k_dev, float* __restrict__ loss) {
-  const int k = dyn_count(K_cap, k_dev);
-  double acc = 0.0;
-  for (int b = threadIdx.x; b < nblk; b += 256) acc += partial[b];
-  __shared__ double red[256];
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) loss[0] = (float)(red[0] / (double)k);
-}
-
 __global__ void k_charge_zero_rows(float* __restrict__ dh, int N_cap, int F, const int32_t* __restrict__ dyn_N) {
   const int64_t n = (int64_t)dyn_count(N_cap, dyn_N) * F / 4;   // (F is a multiple of 64)
   float4* p = reinterpret_cast<float4*>(dh);
@@ -392,7 +376,7 @@ __global__ __launch_bounds__(256) void k_charge_wgrad(const float* __restrict__ 
   *o = accumulate ? *o + s : s;
 }
 
-inline bool width_ok(int F, int C) { return (F == 64 || F == 128 || F == 256 || F == 512) && C >= 2 && C <= kMaxC; }
+inline bool width_ok(int F, int C) { return wave_row_width_ok(F) && C >= 2 && C <= kMaxC; }
 inline int fwd_blocks(int64_t K) {
   return (int)std::max<int64_t>(1, std::min<int64_t>((K + kFwdBlock / 64 - 1) / (kFwdBlock / 64), kFwdMaxBlocks));
 }
@@ -442,16 +426,13 @@ extern "C" int geossl_charge_head_fwd_dyn(const float* h, int64_t N, int F, cons
   double* partial = reinterpret_cast<double*>(workspace);
   const int nb = fwd_blocks(K);
   if (K > 0) {
-    const dim3 grid(nb), block(kFwdBlock);
-    switch (F) {
-      case 64: hipLaunchKernelGGL(k_charge_fwd<1>, grid, block, 0, stream, h, (int)N, dyn_N, W, bias, C, idx, labels, (int)K, k_dev, prob, partial, status); break;
-      case 128: hipLaunchKernelGGL(k_charge_fwd<2>, grid, block, 0, stream, h, (int)N, dyn_N, W, bias, C, idx, labels, (int)K, k_dev, prob, partial, status); break;
-      case 256: hipLaunchKernelGGL(k_charge_fwd<4>, grid, block, 0, stream, h, (int)N, dyn_N, W, bias, C, idx, labels, (int)K, k_dev, prob, partial, status); break;
-      default: hipLaunchKernelGGL(k_charge_fwd<8>, grid, block, 0, stream, h, (int)N, dyn_N, W, bias, C, idx, labels, (int)K, k_dev, prob, partial, status); break;
-    }
+    dispatch_int<1, 2, 4, 8>(F / 64, [&](auto v) {
+      hipLaunchKernelGGL(k_charge_fwd<decltype(v)::value>, dim3(nb), dim3(kFwdBlock), 0, stream, h, (int)N, dyn_N, W, bias,
+                         C, idx, labels, (int)K, k_dev, prob, partial, status);
+    });
     GEOSSL_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(k_charge_loss, dim3(1), dim3(256), 0, stream, partial, K > 0 ? nb : 0, (int)K, k_dev, loss);
+  hipLaunchKernelGGL(k_head_loss<0>, dim3(1), dim3(kLossBlock), 0, stream, partial, K > 0 ? nb : 0, (int)K, k_dev, loss);
   GEOSSL_CHECK_LAUNCH();
   return 0;
 }

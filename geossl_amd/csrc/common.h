@@ -60,6 +60,10 @@ __device__ __forceinline__ float add_rn(float a, float b) {
 #pragma clang fp contract(off)
   return a + b;
 }
+__device__ __forceinline__ float sub_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a - b;
+}
 // fl32(fl32(fl32(x*x) + fl32(y*y)) + fl32(z*z))
 __device__ __forceinline__ float norm2_rn(float x, float y, float z) {
 #pragma clang fp contract(off)
@@ -190,6 +194,38 @@ __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+
+// The scalar functions of the loss heads (the *_head.hip files and contrastive.hip), each defined here once.
+__device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + expf(-v)); }
+__device__ __forceinline__ float siluf_(float v) { return v / (1.0f + expf(-v)); }
+// log(1 + exp(z)), stable
+__device__ __forceinline__ double softplus_d(double z) { return fmax(z, 0.0) + log1p(exp(-fabs(z))); }
+__device__ __forceinline__ double sigmoid_d(double z) { return 1.0 / (1.0 + exp(-z)); }
+
+// The backbone's readout over the atom rows [a0, a1) of one molecule, written once: k_segment_reduce_fwd / _bwd
+// (schnet.hip) and the readouts inside the property, pair and InfoGraph heads all call these two, so a head's readout has
+// the backbone's bits.  kExternal (InfoGraph only): the caller brings the readout.
+enum Readout { kAdd = 0, kMean = 1, kExternal = 2 };
+
+// column j of the readout: the rows added in atom order, "mean": that sum / max(n, 1)
+__device__ __forceinline__ float readout_col(const float* __restrict__ h, int F, int j, int a0, int a1, bool mean) {
+  float acc = 0.0f;
+  for (int a = a0; a < a1; ++a) acc += h[(size_t)a * F + j];
+  return mean ? acc / fmaxf((float)(a1 - a0), 1.0f) : acc;
+}
+// its backward: what every atom row of the molecule receives from the readout's gradient g ...
+__device__ __forceinline__ float readout_grad(float g, int a0, int a1, bool mean) {
+  return mean ? g / fmaxf((float)(a1 - a0), 1.0f) : g;
+}
+// ... stored to (or, with accumulate, added to) column j of those rows
+__device__ __forceinline__ void scatter_readout_col(float* __restrict__ dh, int F, int j, int a0, int a1, float g,
+                                                    bool mean, bool accumulate = false) {
+  const float gv = readout_grad(g, a0, a1, mean);
+  for (int a = a0; a < a1; ++a) {
+    const size_t o = (size_t)a * F + j;
+    dh[o] = accumulate ? dh[o] + gv : gv;
+  }
 }
 
 }  // namespace geossl

@@ -284,8 +284,6 @@ __device__ __forceinline__ float wave_dot(const float* __restrict__ a, const flo
   return p;
 }
 
-__device__ __forceinline__ double softplus_d(double x) { return fmax(x, 0.0) + log1p(exp(-fabs(x))); }
-__device__ __forceinline__ double sigmoid_d(double x) { return 1.0 / (1.0 + exp(-x)); }
 __device__ __forceinline__ int wrap(int64_t v, int B) { return (int)(((v % B) + B) % B); }
 
 // a wave per molecule i: pred[i][0] = <x_i, y_i>, pred[i][k] = <x_i, y_{(i+k) mod B}> (cycle_index, examples/util.py:19-22)

@@ -5,13 +5,14 @@
 //
 // Forward
 //   k_ig_summary (kTile molecules per block, thread j = feature j): m_b = readout of the atom rows of molecule b
-//     ("add": a sum in atom order, "mean": that sum / max(n_b, 1) - the arithmetic of k_segment_reduce_fwd, so the head's
-//     readout has the backbone's bits) or the caller's m_b (external readout); s_b = sigmoid(m_b); h_b = s_b W with a
+//     ("add": a sum in atom order, "mean": that sum / max(n_b, 1) - readout_col of common.h, the function
+//     k_segment_reduce_fwd calls, so the head's readout has the backbone's bits) or the caller's m_b (external readout);
+//     s_b = sigmoid(m_b); h_b = s_b W with a
 //     fp32 fma chain over k in index order (W read once per block for its kTile molecules).
 //   k_ig_scores (one block per molecule, one wave per atom): pos_i = <x_i, h_b>, neg_i = <x_i, h_{(b+1) mod B}> (fp32
 //     lane partials, then a fixed xor tree); per molecule the fp64 sums of softplus(-pos_i) and softplus(neg_i) and the
 //     integer counts #(pos_i > 0), #(neg_i < 0) in atom order per wave, waves added in order.
-//   k_ig_loss (one block): the per-molecule sums added in a fixed order; loss = S_pos / N + S_neg / N (two means over N
+//   k_ig_loss (one block): the per-molecule sums added in a fixed order (block_sum of head_common.h); loss = S_pos / N + S_neg / N (two means over N
 //     atoms, fp64, stored as fp32; N = 0: NaN, the mean of an empty tensor), counts = the two totals.
 // Backward, with c = gout[0] / N (fp32): g_pos_i = -c / (1 + exp(pos_i)) (= (sigmoid(pos_i) - 1) c),
 //   g_neg_i = c / (1 + exp(-neg_i)) (= sigmoid(neg_i) c).  k_ig_bwd (kTile molecules per block, thread j = feature j):
@@ -24,8 +25,8 @@
 // Capacity launches (`_dyn`): N is a capacity (the row stride of `scores`); the real atom count is read from dyn_N.
 // The molecule offsets mol_ptr [B + 1] are the real ones (B is exact), so rows past the real count are neither read nor
 // written.
-#include "common.h"
 #include "geossl_hip.h"
+#include "head_common.h"
 
 using namespace geossl;
 
@@ -34,14 +35,6 @@ namespace {
 constexpr int kTile = 4;             // molecules per block of k_ig_summary / k_ig_bwd
 constexpr int kScoreBlock = 256;     // k_ig_scores: 4 waves, one atom per wave at a time
 constexpr int kScoreWaves = kScoreBlock / 64;
-
-enum Readout { kAdd = 0, kMean = 1, kExternal = 2 };
-
-__device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + expf(-v)); }
-
-__device__ __forceinline__ double softplus_d(double z) {   // log(1 + exp(z)), stable
-  return fmax(z, 0.0) + log1p(exp(-fabs(z)));
-}
 
 template <int F>
 __global__ __launch_bounds__(F) void k_ig_summary(const float* __restrict__ x, const int32_t* __restrict__ mol_ptr,
@@ -59,10 +52,7 @@ __global__ __launch_bounds__(F) void k_ig_summary(const float* __restrict__ x, c
       if (readout == kExternal) {
         v = m_in[(size_t)b * F + j];
       } else {
-        const int a0 = mol_ptr[b], a1 = mol_ptr[b + 1];
-        float acc = 0.0f;
-        for (int a = a0; a < a1; ++a) acc += x[(size_t)a * F + j];
-        v = readout == kMean ? acc / fmaxf((float)(a1 - a0), 1.0f) : acc;
+        v = readout_col(x, F, j, mol_ptr[b], mol_ptr[b + 1], readout == kMean);
       }
       v = sigmoidf_(v);
       s_out[(size_t)b * F + j] = v;
@@ -145,40 +135,33 @@ __global__ __launch_bounds__(kScoreBlock) void k_ig_scores(const float* __restri
   }
 }
 
+// The four totals of the loss step, reduced by one tree.
+struct IgSums {
+  double pos, neg;   // sums of softplus(-pos_i), softplus(neg_i)
+  int hit_pos, hit_neg;
+  __device__ IgSums& operator+=(const IgSums& o) {
+    pos += o.pos;
+    neg += o.neg;
+    hit_pos += o.hit_pos;
+    hit_neg += o.hit_neg;
+    return *this;
+  }
+};
+
 // One block: thread t adds the molecules t, t + 256, ... in order, then a tree over the threads.
-__global__ __launch_bounds__(256) void k_ig_loss(const double* __restrict__ part, const int32_t* __restrict__ hits,
-                                                 int B, int N_cap, const int32_t* __restrict__ dyn_N,
-                                                 float* __restrict__ loss, int32_t* __restrict__ counts) {
-  __shared__ double rp[256], rn[256];
-  __shared__ int cp[256], cn[256];
-  const int t = threadIdx.x;
-  double sp = 0.0, sn = 0.0;
-  int ip = 0, in = 0;
-  for (int b = t; b < B; b += 256) {
-    sp += part[2 * (size_t)b];
-    sn += part[2 * (size_t)b + 1];
-    ip += hits[2 * (size_t)b];
-    in += hits[2 * (size_t)b + 1];
-  }
-  rp[t] = sp;
-  rn[t] = sn;
-  cp[t] = ip;
-  cn[t] = in;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (t < o) {
-      rp[t] += rp[t + o];
-      rn[t] += rn[t + o];
-      cp[t] += cp[t + o];
-      cn[t] += cn[t + o];
-    }
-    __syncthreads();
-  }
-  if (t == 0) {
+__global__ __launch_bounds__(kLossBlock) void k_ig_loss(const double* __restrict__ part, const int32_t* __restrict__ hits,
+                                                        int B, int N_cap, const int32_t* __restrict__ dyn_N,
+                                                        float* __restrict__ loss, int32_t* __restrict__ counts) {
+  __shared__ IgSums red[kLossBlock];
+  IgSums acc = {0.0, 0.0, 0, 0};
+  for (int b = threadIdx.x; b < B; b += kLossBlock)
+    acc += IgSums{part[2 * (size_t)b], part[2 * (size_t)b + 1], hits[2 * (size_t)b], hits[2 * (size_t)b + 1]};
+  const IgSums s = block_sum<kLossBlock>(acc, red);
+  if (threadIdx.x == 0) {
     const double n = (double)dyn_count(N_cap, dyn_N);
-    loss[0] = (float)(rp[0] / n + rn[0] / n);
-    counts[0] = cp[0];
-    counts[1] = cn[0];
+    loss[0] = (float)(s.pos / n + s.neg / n);
+    counts[0] = s.hit_pos;
+    counts[1] = s.hit_neg;
   }
 }
 
@@ -238,7 +221,7 @@ __global__ __launch_bounds__(F) void k_ig_bwd(const float* __restrict__ x, int N
     if (readout == kExternal)
       dm_out[(size_t)b * F + j] = dm;
     else
-      dr = readout == kMean ? dm / fmaxf((float)(a1 - a0), 1.0f) : dm;
+      dr = readout_grad(dm, a0, a1, readout == kMean);
     const float hb = h[(size_t)b * F + j], hbn = h[(size_t)bn * F + j];
     for (int a = a0; a < a1; ++a) {
       const float gp = -c / (1.0f + expf(pos[a]));
@@ -269,20 +252,18 @@ extern "C" int geossl_infograph_fwd_dyn(const float* x, int64_t N, int F, const 
   double* part = reinterpret_cast<double*>(workspace);
   int32_t* hits = reinterpret_cast<int32_t*>(workspace + 4 * B);
   const dim3 tiles((unsigned)((B + kTile - 1) / kTile));
-  switch (F) {
-    case 64: hipLaunchKernelGGL(k_ig_summary<64>, tiles, dim3(64), 0, stream, x, mol_ptr, (int)B, readout, m_in, W, s, h); break;
-    case 128: hipLaunchKernelGGL(k_ig_summary<128>, tiles, dim3(128), 0, stream, x, mol_ptr, (int)B, readout, m_in, W, s, h); break;
-    default: hipLaunchKernelGGL(k_ig_summary<256>, tiles, dim3(256), 0, stream, x, mol_ptr, (int)B, readout, m_in, W, s, h); break;
-  }
+  dispatch_int<64, 128, 256>(F, [&](auto f) {
+    hipLaunchKernelGGL(k_ig_summary<decltype(f)::value>, tiles, dim3(F), 0, stream, x, mol_ptr, (int)B, readout, m_in, W,
+                       s, h);
+  });
   GEOSSL_CHECK_LAUNCH();
   const dim3 mols((unsigned)B), block(kScoreBlock);
-  switch (F) {
-    case 64: hipLaunchKernelGGL(k_ig_scores<1>, mols, block, 0, stream, x, (int)N, mol_ptr, (int)B, h, scores, part, hits); break;
-    case 128: hipLaunchKernelGGL(k_ig_scores<2>, mols, block, 0, stream, x, (int)N, mol_ptr, (int)B, h, scores, part, hits); break;
-    default: hipLaunchKernelGGL(k_ig_scores<4>, mols, block, 0, stream, x, (int)N, mol_ptr, (int)B, h, scores, part, hits); break;
-  }
+  dispatch_int<1, 2, 4>(F / 64, [&](auto v) {
+    hipLaunchKernelGGL(k_ig_scores<decltype(v)::value>, mols, block, 0, stream, x, (int)N, mol_ptr, (int)B, h, scores,
+                       part, hits);
+  });
   GEOSSL_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_ig_loss, dim3(1), dim3(256), 0, stream, part, hits, (int)B, (int)N, dyn_N, loss, counts);
+  hipLaunchKernelGGL(k_ig_loss, dim3(1), dim3(kLossBlock), 0, stream, part, hits, (int)B, (int)N, dyn_N, loss, counts);
   GEOSSL_CHECK_LAUNCH();
   return 0;
 }
@@ -300,11 +281,10 @@ extern "C" int geossl_infograph_bwd_dyn(const float* x, int64_t N, int F, const 
                                         hipStream_t stream) {
   if (!args_ok(N, F, B, readout, dm)) return (int)hipErrorInvalidValue;
   const dim3 tiles((unsigned)((B + kTile - 1) / kTile));
-  switch (F) {
-    case 64: hipLaunchKernelGGL(k_ig_bwd<64>, tiles, dim3(64), 0, stream, x, (int)N, dyn_N, W, mol_ptr, (int)B, readout, s, h, scores, gout, dx, dm, dh); break;
-    case 128: hipLaunchKernelGGL(k_ig_bwd<128>, tiles, dim3(128), 0, stream, x, (int)N, dyn_N, W, mol_ptr, (int)B, readout, s, h, scores, gout, dx, dm, dh); break;
-    default: hipLaunchKernelGGL(k_ig_bwd<256>, tiles, dim3(256), 0, stream, x, (int)N, dyn_N, W, mol_ptr, (int)B, readout, s, h, scores, gout, dx, dm, dh); break;
-  }
+  dispatch_int<64, 128, 256>(F, [&](auto f) {
+    hipLaunchKernelGGL(k_ig_bwd<decltype(f)::value>, tiles, dim3(F), 0, stream, x, (int)N, dyn_N, W, mol_ptr, (int)B,
+                       readout, s, h, scores, gout, dx, dm, dh);
+  });
   GEOSSL_CHECK_LAUNCH();
   return 0;
 }

@@ -8,31 +8,31 @@
 //
 // Forward, k_pair_fwd (kTile pairs per block, thread j = feature j; F = 32 runs in a 64-thread block whose upper
 // lanes add zeros):
-//   m_s = readout of the atom rows of structure s ("add": a sum in atom order, "mean": that sum / max(n_s, 1) - the
-//     arithmetic of k_segment_reduce_fwd, so the head's readout has the backbone's bits);
+//   m_s = readout of the atom rows of structure s ("add": a sum in atom order, "mean": that sum / max(n_s, 1) -
+//     readout_col of common.h, the function k_segment_reduce_fwd calls, so the head's readout has the backbone's bits);
 //   z_b = (sum over the waves of <w[0:F], m_b>, then of <w[F:2F], m_{B+b}>) + b: lane products, a fixed xor tree per
 //     wave, the waves added in order, the active side first;
 //   per pair the BCE-with-logits term in the overflow-safe form max(z, 0) - z y + log1p(exp(-|z|)), evaluated in fp64
 //     from the fp32 logit, into an fp64 slot.  Predict mode writes z only.
-//   k_pair_loss (one block): the B slots added in a fixed order, / B, stored as fp32.
+//   k_head_loss<1> (head_common.h, one block; the property head's): the B slots added in a fixed order, / B, stored as
+//     fp32.
 // Backward: dz_b = gout[0] (sigmoid(z_b) - y_b) / B.
 //   k_pair_bwd (kTile pairs per block): dh_i = dz_b w[side F + j] (/ max(n_s, 1) for "mean") for every atom i of the
 //     two structures of pair b - every atom row is written exactly once.
-//   k_pair_vgrad (one thread per column): dw[side F + j] = sum_b dz_b m[side B + b][j], db = sum_b dz_b, in pair order.
+//   k_head_vgrad (head_common.h, one thread per column): dw[side F + j] = sum_b dz_b m[side B + b][j], db = sum_b dz_b,
+//     in pair order.
 // Every sum has a fixed order and there are no atomics: the same inputs give the same bits.
 // Capacity launches (`_dyn`): N is a capacity and the real atom count is read from dyn_N; mol_ptr [2B + 1] holds the real
 // offsets (B is exact).  No atom row at or past the real count is read or written.  The exact forms are the same kernels
 // with dyn_N = nullptr: the clamp is to N, as before.
-#include "common.h"
 #include "geossl_hip.h"
+#include "head_common.h"
 
 using namespace geossl;
 
 namespace {
 
 constexpr int kTile = 4;   // pairs per block of k_pair_fwd / k_pair_bwd
-
-enum Readout { kAdd = 0, kMean = 1 };
 
 template <int F>
 __global__ __launch_bounds__(F < 64 ? 64 : F) void k_pair_fwd(const float* __restrict__ h, int N_cap,
@@ -58,9 +58,7 @@ __global__ __launch_bounds__(F < 64 ? 64 : F) void k_pair_fwd(const float* __res
       if (b < B && live) {
         const int s = side * B + b;
         const int a0 = min(mol_ptr[s], N), a1 = min(mol_ptr[s + 1], N);
-        float acc = 0.0f;
-        for (int a = a0; a < a1; ++a) acc += h[(size_t)a * F + j];
-        v = readout == kMean ? acc / fmaxf((float)(a1 - a0), 1.0f) : acc;
+        v = readout_col(h, F, j, a0, a1, readout == kMean);
         if (m_out != nullptr) m_out[(size_t)s * F + j] = v;
       }
       const float p = wave_sum(mul_rn(side == 0 ? w0 : w1, v));
@@ -86,21 +84,6 @@ __global__ __launch_bounds__(F < 64 ? 64 : F) void k_pair_fwd(const float* __res
   }
 }
 
-// One block: thread t adds the pairs t, t + 256, ... in order, then a tree over the threads.
-__global__ __launch_bounds__(256) void k_pair_loss(const double* __restrict__ part, int B, float* __restrict__ loss) {
-  __shared__ double r[256];
-  const int t = threadIdx.x;
-  double s = 0.0;
-  for (int b = t; b < B; b += 256) s += part[b];
-  r[t] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (t < o) r[t] += r[t + o];
-    __syncthreads();
-  }
-  if (t == 0) loss[0] = (float)(r[0] / (double)B);
-}
-
 template <int F>
 __global__ __launch_bounds__(F < 64 ? 64 : F) void k_pair_bwd(int N_cap, const int32_t* __restrict__ dyn_N,
                                                               const int32_t* __restrict__ mol_ptr, int B,
@@ -116,38 +99,16 @@ __global__ __launch_bounds__(F < 64 ? 64 : F) void k_pair_bwd(int N_cap, const i
   for (int t = 0; t < kTile; ++t) {
     const int b = b0 + t;
     if (b >= B) break;
-    const float sg = 1.0f / (1.0f + expf(-z[b]));
-    const float dz = g * (sg - y[b]) / (float)B;
+    const float dz = g * (sigmoidf_(z[b]) - y[b]) / (float)B;
     if (j == 0) dz_out[b] = dz;
     if (j >= F) continue;
 #pragma unroll
     for (int side = 0; side < 2; ++side) {
       const int s = side * B + b;
       const int a0 = min(mol_ptr[s], N), a1 = min(mol_ptr[s + 1], N);
-      const float dm = mul_rn(dz, w[side * F + j]);
-      const float dr = readout == kMean ? dm / fmaxf((float)(a1 - a0), 1.0f) : dm;
-      for (int a = a0; a < a1; ++a) dh[(size_t)a * F + j] = dr;
+      scatter_readout_col(dh, F, j, a0, a1, mul_rn(dz, w[side * F + j]), readout == kMean);
     }
   }
-}
-
-// Column c < 2F: sum_b dz_b m[(c / F) B + b][c % F]; column 2F: sum_b dz_b.
-__global__ __launch_bounds__(256) void k_pair_vgrad(const float* __restrict__ m, int F, int B,
-                                                    const float* __restrict__ dz, float* __restrict__ dw,
-                                                    float* __restrict__ db, int accumulate) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c > 2 * F) return;
-  float* out = c < 2 * F ? dw : db;
-  if (out == nullptr) return;
-  float acc = 0.0f;
-  if (c < 2 * F) {
-    const float* col = m + (size_t)(c / F) * B * F + (c % F);
-    for (int b = 0; b < B; ++b) acc = fmaf(dz[b], col[(size_t)b * F], acc);
-  } else {
-    for (int b = 0; b < B; ++b) acc += dz[b];
-  }
-  const int o = c < 2 * F ? c : 0;
-  out[o] = accumulate ? out[o] + acc : acc;
 }
 
 inline bool width_ok(int F) { return F == 32 || F == 64 || F == 128; }
@@ -164,14 +125,13 @@ int fwd_impl(const float* h, int64_t N, int F, const int32_t* mol_ptr, int64_t B
     return (int)hipErrorInvalidValue;
   double* part = predict ? nullptr : reinterpret_cast<double*>(workspace);
   const dim3 tiles((unsigned)((B + kTile - 1) / kTile));
-  switch (F) {
-    case 32: hipLaunchKernelGGL(k_pair_fwd<32>, tiles, dim3(64), 0, stream, h, (int)N, dyn_N, mol_ptr, (int)B, readout, w, b, y, m, z, part); break;
-    case 64: hipLaunchKernelGGL(k_pair_fwd<64>, tiles, dim3(64), 0, stream, h, (int)N, dyn_N, mol_ptr, (int)B, readout, w, b, y, m, z, part); break;
-    default: hipLaunchKernelGGL(k_pair_fwd<128>, tiles, dim3(128), 0, stream, h, (int)N, dyn_N, mol_ptr, (int)B, readout, w, b, y, m, z, part); break;
-  }
+  dispatch_int<32, 64, 128>(F, [&](auto f) {
+    hipLaunchKernelGGL(k_pair_fwd<decltype(f)::value>, tiles, dim3(std::max(F, 64)), 0, stream, h, (int)N, dyn_N, mol_ptr,
+                       (int)B, readout, w, b, y, m, z, part);
+  });
   GEOSSL_CHECK_LAUNCH();
   if (!predict) {
-    hipLaunchKernelGGL(k_pair_loss, dim3(1), dim3(256), 0, stream, part, (int)B, loss);
+    hipLaunchKernelGGL(k_head_loss<1>, dim3(1), dim3(kLossBlock), 0, stream, part, 0, (int)B, nullptr, loss);
     GEOSSL_CHECK_LAUNCH();
   }
   return 0;
@@ -215,15 +175,15 @@ extern "C" int geossl_pair_head_bwd_dyn(int64_t N, int F, const int32_t* mol_ptr
     return (int)hipErrorInvalidValue;
   const dim3 tiles((unsigned)((B + kTile - 1) / kTile));
   float* dz = workspace;
-  switch (F) {
-    case 32: hipLaunchKernelGGL(k_pair_bwd<32>, tiles, dim3(64), 0, stream, (int)N, dyn_N, mol_ptr, (int)B, readout, w, z, y, gout, dh, dz); break;
-    case 64: hipLaunchKernelGGL(k_pair_bwd<64>, tiles, dim3(64), 0, stream, (int)N, dyn_N, mol_ptr, (int)B, readout, w, z, y, gout, dh, dz); break;
-    default: hipLaunchKernelGGL(k_pair_bwd<128>, tiles, dim3(128), 0, stream, (int)N, dyn_N, mol_ptr, (int)B, readout, w, z, y, gout, dh, dz); break;
-  }
+  dispatch_int<32, 64, 128>(F, [&](auto f) {
+    hipLaunchKernelGGL(k_pair_bwd<decltype(f)::value>, tiles, dim3(std::max(F, 64)), 0, stream, (int)N, dyn_N, mol_ptr,
+                       (int)B, readout, w, z, y, gout, dh, dz);
+  });
   GEOSSL_CHECK_LAUNCH();
   if (dw != nullptr || db != nullptr) {
-    hipLaunchKernelGGL(k_pair_vgrad, dim3((unsigned)((2 * F + 1 + 255) / 256)), dim3(256), 0, stream, m, F, (int)B, dz,
-                       dw, db, accumulate);
+    // column c < 2F is column c % F of the [B][F] readouts of side c / F
+    hipLaunchKernelGGL(k_head_vgrad<false>, dim3((unsigned)((2 * F + 1 + 255) / 256)), dim3(256), 0, stream, m, 2 * F, F,
+                       (int)B, dz, dw, db, accumulate);
     GEOSSL_CHECK_LAUNCH();
   }
   return 0;

@@ -6,25 +6,26 @@
 // Dense(F, F/2, silu) then Dense(F/2, 1) (W1 [F/2][F], b1 [F/2], w2 [F/2], b2 [1]).
 //
 // Forward, k_prop_fwd (kTile molecules per block, thread j = feature j):
-//   m_b = readout of the atom rows of molecule b ("add": a sum in atom order, "mean": that sum / max(n_b, 1) - the
-//     arithmetic of k_segment_reduce_fwd, so the head's readout has the backbone's bits);
+//   m_b = readout of the atom rows of molecule b ("add": a sum in atom order, "mean": that sum / max(n_b, 1) -
+//     readout_col of common.h, the function k_segment_reduce_fwd calls, so the head's readout has the backbone's bits);
 //   head 1: z_bk = b1_k + sum_j W1_kj m_bj (fp32 fma chain in j order), a_bk = silu(z_bk);
 //   pred_b = bias + <w, m_b> (head 0) or b2 + <w2, a_b> (head 1): lane products, a fixed xor tree per wave, the waves
 //     added in order;
 //   t_b = (y_b - mean) / std (fp32, a subtract then a divide, the two roundings ATen does); per molecule |pred_b - t_b|
 //     (L1) or (pred_b - t_b)^2 (MSE) into an fp64 slot.  Predict mode writes pred_b * std + mean instead (eval()).
-//   k_prop_loss (one block): the B slots added in a fixed order, / B, stored as fp32.
+//   k_head_loss<1> (head_common.h, one block): the B slots added in a fixed order, / B, stored as fp32.
 // Backward, c = gout[0] / B: dpred_b = c sign(pred_b - t_b) (sign(0) = 0, torch's sgn) or (2 / B) (pred_b - t_b) gout[0].
 //   k_prop_bwd (kTile molecules per block): dm_b = dpred_b w (head 0), or dz_bk = dpred_b w2_k silu'(z_bk) and
 //     dm_bj = sum_k dz_bk W1_kj (head 1); dh_i = dm_b (/ max(n_b, 1) for "mean") for every atom i of molecule b.
-//   k_prop_vgrad (one thread per column): dw = sum_b dpred_b m_b, db = sum_b dpred_b (head 0); dw2 = sum_b dpred_b a_b,
-//     db2 = sum_b dpred_b (head 1), in molecule order.  dW1 = dz^T m and db1 are the caller's (geossl_linear_wgrad).
+//   k_head_vgrad (head_common.h, one thread per column): dw = sum_b dpred_b m_b, db = sum_b dpred_b (head 0);
+//     dw2 = sum_b dpred_b a_b, db2 = sum_b dpred_b (head 1), in molecule order.  dW1 = dz^T m and db1 are the caller's
+//     (geossl_linear_wgrad).
 // Every sum has a fixed order and there are no atomics: the same inputs give the same bits.
 // mean and std are read from stats [2] in device memory, so a replayed graph picks up new values.
 // Capacity launches (`_dyn`): N is a capacity and the real atom count is read from dyn_N; mol_ptr [B + 1] holds the real
 // offsets (B is exact).  No atom row at or past the real count is read or written.
-#include "common.h"
 #include "geossl_hip.h"
+#include "head_common.h"
 
 using namespace geossl;
 
@@ -32,17 +33,8 @@ namespace {
 
 constexpr int kTile = 4;   // molecules per block of k_prop_fwd / k_prop_bwd
 
-enum Readout { kAdd = 0, kMean = 1 };
 enum Head { kLinear = 0, kMlp = 1 };
 enum Mode { kL1 = 0, kMse = 1, kPredict = 2 };
-
-__device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + expf(-v)); }
-__device__ __forceinline__ float siluf_(float v) { return v / (1.0f + expf(-v)); }
-
-__device__ __forceinline__ float sub_rn(float a, float b) {
-#pragma clang fp contract(off)
-  return a - b;
-}
 
 // t_b = (y_b - mean) / std with ATen's two roundings
 __device__ __forceinline__ float norm_target(float y, float mean, float sd) { return sub_rn(y, mean) / sd; }
@@ -78,9 +70,7 @@ __global__ __launch_bounds__(F) void k_prop_fwd(const float* __restrict__ h, int
     float v = 0.0f;
     if (b < B) {
       const int a0 = min(mol_ptr[b], n_real), a1 = min(mol_ptr[b + 1], n_real);
-      float acc = 0.0f;
-      for (int a = a0; a < a1; ++a) acc += h[(size_t)a * F + j];
-      v = readout == kMean ? acc / fmaxf((float)(a1 - a0), 1.0f) : acc;
+      v = readout_col(h, F, j, a0, a1, readout == kMean);
       if (m_out != nullptr) m_out[(size_t)b * F + j] = v;
     }
     sm[t][j] = v;
@@ -139,21 +129,6 @@ __global__ __launch_bounds__(F) void k_prop_fwd(const float* __restrict__ h, int
       }
     }
   }
-}
-
-// One block: thread t adds the molecules t, t + 256, ... in order, then a tree over the threads.
-__global__ __launch_bounds__(256) void k_prop_loss(const double* __restrict__ part, int B, float* __restrict__ loss) {
-  __shared__ double r[256];
-  const int t = threadIdx.x;
-  double s = 0.0;
-  for (int b = t; b < B; b += 256) s += part[b];
-  r[t] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (t < o) r[t] += r[t + o];
-    __syncthreads();
-  }
-  if (t == 0) loss[0] = (float)(r[0] / (double)B);
 }
 
 template <int F, bool MLP>
@@ -218,32 +193,8 @@ __global__ __launch_bounds__(F) void k_prop_bwd(int N_cap, const int32_t* __rest
     const int b = b0 + t;
     if (b >= B) break;
     const int a0 = min(mol_ptr[b], n_real), a1 = min(mol_ptr[b + 1], n_real);
-    const float dr = readout == kMean ? dm[t] / fmaxf((float)(a1 - a0), 1.0f) : dm[t];
-    for (int a = a0; a < a1; ++a) dh[(size_t)a * F + j] = dr;
+    scatter_readout_col(dh, F, j, a0, a1, dm[t], readout == kMean);
   }
-}
-
-// Column c < K: sum_b dpred_b v_b[c] (v = m for head 0, silu(z) for head 1); column K: sum_b dpred_b.
-template <bool MLP>
-__global__ __launch_bounds__(256) void k_prop_vgrad(const float* __restrict__ v, int K, int B,
-                                                    const float* __restrict__ dpred, float* __restrict__ dw,
-                                                    float* __restrict__ db, int accumulate) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c > K) return;
-  float* out = c < K ? dw : db;
-  if (out == nullptr) return;
-  float acc = 0.0f;
-  if (c < K) {
-#pragma unroll 8
-    for (int b = 0; b < B; ++b) {
-      const float x = v[(size_t)b * K + c];
-      acc = fmaf(dpred[b], MLP ? siluf_(x) : x, acc);
-    }
-  } else {
-    for (int b = 0; b < B; ++b) acc += dpred[b];
-  }
-  const int o = c < K ? c : 0;
-  out[o] = accumulate ? out[o] + acc : acc;
 }
 
 __global__ __launch_bounds__(256) void k_prop_targets(const float* __restrict__ y, int64_t M, int T, int task,
@@ -302,14 +253,13 @@ int fwd_impl(const float* h, int64_t N, int F, const int32_t* mol_ptr, int64_t B
     return (int)hipErrorInvalidValue;
   double* part = reinterpret_cast<double*>(workspace);
   const dim3 tiles((unsigned)((B + kTile - 1) / kTile));
-  switch (F) {
-    case 64: launch_fwd<64>(head, tiles, stream, h, (int)N, dyn_N, mol_ptr, (int)B, readout, W1, b1, W2, b2, y, y_stride, stats, mode, m, z, pred, part); break;
-    case 128: launch_fwd<128>(head, tiles, stream, h, (int)N, dyn_N, mol_ptr, (int)B, readout, W1, b1, W2, b2, y, y_stride, stats, mode, m, z, pred, part); break;
-    default: launch_fwd<256>(head, tiles, stream, h, (int)N, dyn_N, mol_ptr, (int)B, readout, W1, b1, W2, b2, y, y_stride, stats, mode, m, z, pred, part); break;
-  }
+  dispatch_int<64, 128, 256>(F, [&](auto f) {
+    launch_fwd<decltype(f)::value>(head, tiles, stream, h, (int)N, dyn_N, mol_ptr, (int)B, readout, W1, b1, W2, b2, y,
+                                   y_stride, stats, mode, m, z, pred, part);
+  });
   GEOSSL_CHECK_LAUNCH();
   if (mode != kPredict) {
-    hipLaunchKernelGGL(k_prop_loss, dim3(1), dim3(256), 0, stream, part, (int)B, loss);
+    hipLaunchKernelGGL(k_head_loss<1>, dim3(1), dim3(kLossBlock), 0, stream, part, 0, (int)B, nullptr, loss);
     GEOSSL_CHECK_LAUNCH();
   }
   return 0;
@@ -365,19 +315,19 @@ extern "C" int geossl_property_bwd_dyn(int64_t N, int F, const int32_t* mol_ptr,
     return (int)hipErrorInvalidValue;
   const dim3 tiles((unsigned)((B + kTile - 1) / kTile));
   float* dpred = workspace;
-  switch (F) {
-    case 64: launch_bwd<64>(head, tiles, stream, (int)N, dyn_N, mol_ptr, (int)B, readout, W1, W2, z, pred, y, y_stride, stats, loss_kind, gout, dh, dz, dpred); break;
-    case 128: launch_bwd<128>(head, tiles, stream, (int)N, dyn_N, mol_ptr, (int)B, readout, W1, W2, z, pred, y, y_stride, stats, loss_kind, gout, dh, dz, dpred); break;
-    default: launch_bwd<256>(head, tiles, stream, (int)N, dyn_N, mol_ptr, (int)B, readout, W1, W2, z, pred, y, y_stride, stats, loss_kind, gout, dh, dz, dpred); break;
-  }
+  dispatch_int<64, 128, 256>(F, [&](auto f) {
+    launch_bwd<decltype(f)::value>(head, tiles, stream, (int)N, dyn_N, mol_ptr, (int)B, readout, W1, W2, z, pred, y,
+                                   y_stride, stats, loss_kind, gout, dh, dz, dpred);
+  });
   GEOSSL_CHECK_LAUNCH();
   if (dw != nullptr || db != nullptr) {
     const int K = head == kMlp ? F / 2 : F;
     const dim3 cols((unsigned)((K + 1 + 255) / 256));
+    // v = silu(z) for head 1, m for head 0: one [B][K] block
     if (head == kMlp)
-      hipLaunchKernelGGL(k_prop_vgrad<true>, cols, dim3(256), 0, stream, z, K, (int)B, dpred, dw, db, accumulate);
+      hipLaunchKernelGGL(k_head_vgrad<true>, cols, dim3(256), 0, stream, z, K, K, (int)B, dpred, dw, db, accumulate);
     else
-      hipLaunchKernelGGL(k_prop_vgrad<false>, cols, dim3(256), 0, stream, m, K, (int)B, dpred, dw, db, accumulate);
+      hipLaunchKernelGGL(k_head_vgrad<false>, cols, dim3(256), 0, stream, m, K, K, (int)B, dpred, dw, db, accumulate);
     GEOSSL_CHECK_LAUNCH();
   }
   return 0;

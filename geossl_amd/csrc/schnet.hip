@@ -466,32 +466,21 @@ __global__ __launch_bounds__(256) void k_embedding_bwd_reduce(const float* __res
   }
 }
 // ----------------------------------------------------------------------------------------------- readout
+// (readout_col / scatter_readout_col of common.h: the loss heads' readouts are the same two functions)
 __global__ void k_segment_reduce_fwd(const float* __restrict__ h, const int32_t* __restrict__ mol_ptr, int B, int F,
                                      int mean, float* __restrict__ out) {
   const int m = blockIdx.x;
   if (m >= B) return;
   const int a0 = mol_ptr[m], a1 = mol_ptr[m + 1];
-  for (int f = threadIdx.x; f < F; f += blockDim.x) {
-    float s = 0.0f;
-    for (int a = a0; a < a1; ++a) s += h[(size_t)a * F + f];
-    if (mean) s = s / fmaxf((float)(a1 - a0), 1.0f);
-    out[(size_t)m * F + f] = s;
-  }
+  for (int f = threadIdx.x; f < F; f += blockDim.x) out[(size_t)m * F + f] = readout_col(h, F, f, a0, a1, mean != 0);
 }
 __global__ void k_segment_reduce_bwd(const float* __restrict__ dout, const int32_t* __restrict__ mol_ptr, int B, int F,
                                      int mean, float* __restrict__ dh, int accumulate) {
   const int m = blockIdx.x;
   if (m >= B) return;
   const int a0 = mol_ptr[m], a1 = mol_ptr[m + 1];
-  const float cnt = fmaxf((float)(a1 - a0), 1.0f);
-  for (int f = threadIdx.x; f < F; f += blockDim.x) {
-    float gv = dout[(size_t)m * F + f];
-    if (mean) gv = gv / cnt;
-    for (int a = a0; a < a1; ++a) {
-      const size_t o = (size_t)a * F + f;
-      dh[o] = accumulate ? dh[o] + gv : gv;
-    }
-  }
+  for (int f = threadIdx.x; f < F; f += blockDim.x)
+    scatter_readout_col(dh, F, f, a0, a1, dout[(size_t)m * F + f], mean != 0, accumulate != 0);
 }
 
 // ----------------------------------------------------------------------------------- F.normalize(h, dim=-1)

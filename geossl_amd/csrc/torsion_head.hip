@@ -6,13 +6,13 @@
 // A linear layer on a concatenation splits into per-atom projections: with W = [w_u | w_v | w_w],
 //   a_i = w_u . h_i,  b_i = w_v . h_i,  c_i = w_w . h_i,  pred_t = ((a_{u_t} + b_{v_t}) + c_{w_t}) + bias,
 // so the [T][3F] features of the reference are never formed.  Forward: one wave per atom computes (a_i, b_i, c_i)
-// (k_tor_project), one pass over the triples computes pred, res = pred - angle and per-block fp64 sums of res^2
-// (k_tor_triples), and one block adds the block sums in order and divides by T (k_tor_loss).
+// (k_cat_project<V, 3> of head_common.h), one pass over the triples computes pred, res = pred - angle and per-block fp64
+// sums of res^2 (k_tor_triples), and one block adds the block sums in order and divides by T (k_head_loss).
 // Backward, with d pred_t = (2 gout / T) res_t (MSELoss's mean and square backward):
 //   dA_i / dB_i / dC_i = the sums of d pred_t over the triples in which atom i is u / v / w, each in ascending triple order
 //   (k_tor_atom_grads); dh_i = dA_i w_u + dB_i w_v + dC_i w_w (written) and per block of atoms the partials of
-//   dW = [sum dA_i h_i | sum dB_i h_i | sum dC_i h_i] and db = sum dA_i (k_tor_dh); one launch adds the block partials in
-//   block order (k_tor_wgrad).
+//   dW = [sum dA_i h_i | sum dB_i h_i | sum dC_i h_i] and db = sum dA_i (k_cat_dh<3>); one launch adds the block partials
+//   in block order (k_cat_wgrad<3>).
 // How an atom finds its triples: the MOLECULE SCAN, not a three-sided incidence list.  The triples of a collated batch are
 // grouped by molecule in batch order, so molecule m's triples are one run [first t with u_t >= mol_ptr[m], first t with
 // u_t >= mol_ptr[m + 1]) that two binary searches find.  One block per molecule stages that run in LDS, kChunk triples at a
@@ -24,8 +24,8 @@
 // Capacity launches (`_dyn`): N and T are capacities that size the grids; the real counts are read from dyn_N / dyn_T.
 // Atoms and triples at and past them are never read or written, and the mean divides by the real T.  A triple with an
 // atom outside [0, N) reads nothing: its prediction is NaN (and so is the loss).
-#include "common.h"
 #include "geossl_hip.h"
+#include "head_common.h"
 
 #include <algorithm>
 #include <cmath>
@@ -34,51 +34,11 @@ using namespace geossl;
 
 namespace {
 
-constexpr int kProjBlock = 256;               // 4 waves, one atom per wave at a time
 constexpr int kTriBlock = 256;
 constexpr int kTriPerThread = 4;
 constexpr int kTriPerBlock = kTriBlock * kTriPerThread;
-constexpr int kAtomsPerBlock = 32;            // k_tor_dh: atoms per block (one partial row of dW / db per block)
 constexpr int kMolBlock = 256;                // k_tor_atom_grads: one thread per atom of the molecule (255 at most in a bucket)
 constexpr int kChunk = 1024;                  // ... triples staged in LDS at a time (16 KB)
-
-// (a_i, b_i, c_i): lane l holds features [l V, l V + V) of the row (F = 64 V), a butterfly over the wave adds the 64 lane
-// sums in a fixed order.
-template <int V>
-__global__ __launch_bounds__(kProjBlock) void k_tor_project(const float* __restrict__ h, int N_cap,
-                                                             const float* __restrict__ W, const int32_t* __restrict__ dyn_N,
-                                                             float* __restrict__ proj) {
-  constexpr int F = 64 * V;
-  const int N = dyn_count(N_cap, dyn_N);
-  const int l = threadIdx.x & 63;
-  float wu[V], wv[V], ww[V];
-#pragma unroll
-  for (int k = 0; k < V; ++k) {
-    wu[k] = W[l * V + k];
-    wv[k] = W[F + l * V + k];
-    ww[k] = W[2 * F + l * V + k];
-  }
-  const int waves = gridDim.x * (kProjBlock / 64);
-  for (int i = blockIdx.x * (kProjBlock / 64) + (threadIdx.x >> 6); i < N; i += waves) {
-    const float* row = h + (int64_t)i * F + l * V;
-    float a = 0.f, b = 0.f, c = 0.f;
-#pragma unroll
-    for (int k = 0; k < V; ++k) {
-      const float x = row[k];
-      a = fmaf(wu[k], x, a);
-      b = fmaf(wv[k], x, b);
-      c = fmaf(ww[k], x, c);
-    }
-    a = wave_sum(a);
-    b = wave_sum(b);
-    c = wave_sum(c);
-    if (l == 0) {
-      proj[3 * (int64_t)i] = a;
-      proj[3 * (int64_t)i + 1] = b;
-      proj[3 * (int64_t)i + 2] = c;
-    }
-  }
-}
 
 // Block k owns triples [k kTriPerBlock, (k + 1) kTriPerBlock); partial[k] = the sum of their res^2 in fp64 (per thread in
 // triple order, then a tree over the block).  Blocks at and past the real T write nothing.
@@ -110,32 +70,8 @@ __global__ __launch_bounds__(kTriBlock) void k_tor_triples(const float* __restri
       acc += (double)r * (double)r;
     }
   }
-  __shared__ double red[kTriBlock];
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = kTriBlock / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
-}
-
-// One block: loss = (sum of the block partials, in block order per thread, then a tree) / T.  T = 0: 0 / 0 = NaN, the
-// mean of an empty tensor.
-__global__ __launch_bounds__(256) void k_tor_loss(const double* __restrict__ partial, int T_cap,
-                                                  const int32_t* __restrict__ dyn_T, float* __restrict__ loss) {
-  const int T = dyn_count(T_cap, dyn_T);
-  const int nblk = (T + kTriPerBlock - 1) / kTriPerBlock;
-  double acc = 0.0;
-  for (int k = threadIdx.x; k < nblk; k += 256) acc += partial[k];
-  __shared__ double red[256];
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) loss[0] = (float)(red[0] / (double)T);
+  const double sum = block_sum_f64<kTriBlock>(acc);
+  if (threadIdx.x == 0) partial[blockIdx.x] = sum;
 }
 
 // first t in [0, T) with tri0[t] >= a (T when there is none): tri0 is non-decreasing over the molecules
@@ -202,52 +138,6 @@ __global__ __launch_bounds__(kMolBlock) void k_tor_atom_grads(const int64_t* __r
   }
 }
 
-// Block k owns atoms [k kAtomsPerBlock, ...): dh_i = dA_i w_u + dB_i w_v + dC_i w_w and the partial row
-// part[k] = [sum dA_i h_i (F) | sum dB_i h_i (F) | sum dC_i h_i (F) | sum dA_i (1)] over its atoms in ascending order.
-// Thread t: columns t, t + blockDim.x, ...
-__global__ void k_tor_dh(const float* __restrict__ h, int N_cap, int F, const float* __restrict__ W,
-                         const float* __restrict__ dABC, const int32_t* __restrict__ dyn_N, float* __restrict__ dh,
-                         float* __restrict__ part) {
-  const int N = dyn_count(N_cap, dyn_N);
-  const int i0 = blockIdx.x * kAtomsPerBlock;
-  if (i0 >= N) return;
-  const int i1 = min(N, i0 + kAtomsPerBlock);
-  float* prow = part + (int64_t)blockIdx.x * (3 * F + 1);
-  for (int f = threadIdx.x; f < F; f += blockDim.x) {
-    const float wu = W[f], wv = W[F + f], ww = W[2 * F + f];
-    float su = 0.f, sv = 0.f, sw = 0.f;
-    for (int i = i0; i < i1; ++i) {
-      const float dA = dABC[3 * (int64_t)i], dB = dABC[3 * (int64_t)i + 1], dC = dABC[3 * (int64_t)i + 2];
-      const float x = h[(int64_t)i * F + f];
-      dh[(int64_t)i * F + f] = fmaf(dC, ww, fmaf(dB, wv, mul_rn(dA, wu)));
-      su = fmaf(dA, x, su);
-      sv = fmaf(dB, x, sv);
-      sw = fmaf(dC, x, sw);
-    }
-    prow[f] = su;
-    prow[F + f] = sv;
-    prow[2 * F + f] = sw;
-  }
-  if (threadIdx.x == 0) {
-    float sb = 0.f;
-    for (int i = i0; i < i1; ++i) sb += dABC[3 * (int64_t)i];
-    prow[3 * F] = sb;
-  }
-}
-
-// dW[c] / db (+)= the partials of column c summed over the real blocks in block order (compensated).
-__global__ __launch_bounds__(256) void k_tor_wgrad(const float* __restrict__ part, int N_cap, int F,
-                                                   const int32_t* __restrict__ dyn_N, float* __restrict__ dW,
-                                                   float* __restrict__ db, int accumulate) {
-  const int N = dyn_count(N_cap, dyn_N);
-  const int nblk = (N + kAtomsPerBlock - 1) / kAtomsPerBlock;
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c > 3 * F) return;
-  const float s = kahan_sum_strided(part + c, 0, nblk, 3 * F + 1);
-  float* o = c < 3 * F ? dW + c : db;
-  *o = accumulate ? *o + s : s;
-}
-
 // angle_t at the middle atom v of (u, v, w): atan2(|a x b|, a . b), a = pos_u - pos_v, b = pos_w - pos_v; 0 for a zero arm.
 __global__ __launch_bounds__(256) void k_triple_angles(const float* __restrict__ pos, int64_t N,
                                                        const int64_t* __restrict__ tri0, const int64_t* __restrict__ tri1,
@@ -289,15 +179,8 @@ __global__ __launch_bounds__(256) void k_gather_triples(const int32_t* __restric
   }
 }
 
-inline int proj_blocks(int64_t N) {
-  const int64_t need = (N + kProjBlock / 64 - 1) / (kProjBlock / 64);
-  return (int)std::max<int64_t>(1, std::min<int64_t>(need, 2048));
-}
-
 inline int64_t tri_blocks(int64_t T) { return std::max<int64_t>(1, (T + kTriPerBlock - 1) / kTriPerBlock); }
-inline int64_t atom_blocks(int64_t N) { return std::max<int64_t>(1, (N + kAtomsPerBlock - 1) / kAtomsPerBlock); }
-
-inline bool width_ok(int F) { return F == 64 || F == 128 || F == 256 || F == 512; }
+inline bool width_ok(int F) { return wave_row_width_ok(F); }
 
 }  // namespace
 
@@ -316,14 +199,8 @@ extern "C" int geossl_torsion_head_fwd_dyn(const float* h, int64_t N, int F, con
                                            hipStream_t stream) {
   if (N < 0 || T < 0 || N >= (1 << 30) || T >= (1 << 30) || !width_ok(F)) return (int)hipErrorInvalidValue;
   if (N > 0) {
-    const dim3 grid(proj_blocks(N));
-    switch (F) {
-      case 64: hipLaunchKernelGGL(k_tor_project<1>, grid, dim3(kProjBlock), 0, stream, h, (int)N, W, dyn_N, proj); break;
-      case 128: hipLaunchKernelGGL(k_tor_project<2>, grid, dim3(kProjBlock), 0, stream, h, (int)N, W, dyn_N, proj); break;
-      case 256: hipLaunchKernelGGL(k_tor_project<4>, grid, dim3(kProjBlock), 0, stream, h, (int)N, W, dyn_N, proj); break;
-      default: hipLaunchKernelGGL(k_tor_project<8>, grid, dim3(kProjBlock), 0, stream, h, (int)N, W, dyn_N, proj); break;
-    }
-    GEOSSL_CHECK_LAUNCH();
+    const int e = launch_cat_project<3>(h, N, F, W, dyn_N, proj, stream);
+    if (e != 0) return e;
   }
   double* partial = reinterpret_cast<double*>(workspace);
   if (T > 0) {
@@ -331,7 +208,7 @@ extern "C" int geossl_torsion_head_fwd_dyn(const float* h, int64_t N, int F, con
                        tri2, angle, (int)N, (int)T, dyn_N, dyn_T, pred, res, partial);
     GEOSSL_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(k_tor_loss, dim3(1), dim3(256), 0, stream, partial, (int)T, dyn_T, loss);
+  hipLaunchKernelGGL(k_head_loss<kTriPerBlock>, dim3(1), dim3(kLossBlock), 0, stream, partial, 0, (int)T, dyn_T, loss);
   GEOSSL_CHECK_LAUNCH();
   return 0;
 }
@@ -358,14 +235,8 @@ extern "C" int geossl_torsion_head_bwd_dyn(const float* h, int64_t N, int F, con
     hipLaunchKernelGGL(k_tor_atom_grads, dim3((unsigned)B), dim3(kMolBlock), 0, stream, tri0, tri1, tri2, res, mol_ptr,
                        (int)N, (int)T, dyn_N, dyn_T, gout, dABC);
     GEOSSL_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_tor_dh, dim3((unsigned)atom_blocks(N)), dim3(std::min(F, 256)), 0, stream, h, (int)N, F, W,
-                       dABC, dyn_N, dh, part);
-    GEOSSL_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(k_tor_wgrad, dim3((unsigned)((3 * F + 1 + 255) / 256)), dim3(256), 0, stream, part, (int)N, F,
-                     dyn_N, dW, db, accumulate);
-  GEOSSL_CHECK_LAUNCH();
-  return 0;
+  return launch_cat_bwd<3>(h, N, F, W, dABC, part, dyn_N, dh, dW, db, accumulate, stream);
 }
 
 extern "C" int geossl_torsion_head_bwd(const float* h, int64_t N, int F, const float* W, const int64_t* tri0,

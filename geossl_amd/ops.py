@@ -792,6 +792,55 @@ def ebm_nce_loss(X, Y, num_neg=1):
     return _EBMNCELoss.apply(X, Y, num_neg)
 
 
+def _param_grads(params, needs=None):
+    """Where a head's backward writes its parameter gradients -> (direct, buffers), one buffer (or None) per parameter.
+    direct: inside _lib.direct_grads() with dense fp32 .grad tensors the kernels ADD into .grad (accumulate = 1) and
+    autograd gets None for the parameters; else the buffers are fresh and autograd gets them.
+    needs None (distance, torsion, charge: one launch writes every gradient): direct when all parameters own such a
+    .grad, and every parameter has a buffer.  needs = the parameters' slice of ctx.needs_input_grad (InfoGraph, property,
+    pair): only the parameters that require a gradient decide, and only they get a buffer."""
+    if needs is None:
+        direct = _lib.direct_grads_enabled(params)
+        return direct, [p.grad if direct else torch.empty_like(p) for p in params]
+    live = [p for p in params if p.requires_grad]
+    direct = bool(live) and _lib.direct_grads_enabled(live)
+    if direct:
+        return True, [p.grad if p.requires_grad else None for p in params]
+    return False, [torch.empty_like(p, dtype=torch.float32) if n else None for p, n in zip(params, needs)]
+
+
+def _cat_head_forward(ctx, name, dyn_field, h, W, b, sides, inputs, rows, dyn):
+    """Forward of a head that is Linear(sides F, 1) on a concatenation of atom rows (csrc/head_common.h: distance,
+    sides = 2; torsion, sides = 3): geossl_<name>_head_fwd_dyn on h, W, b, the head's own `inputs` and `rows` index rows
+    -> (Wd, residual, loss, pred).  residual [rows] is what the backward needs of the loss (sgn, or pred - target)."""
+    N, F = h.shape
+    f32 = dict(dtype=torch.float32, device=h.device)
+    Wd, bd = W.detach().contiguous().view(-1), b.detach().contiguous().view(-1)
+    proj = torch.empty(max(N, 1), sides, **f32)
+    pred, residual = torch.empty(rows, **f32), torch.empty(rows, **f32)
+    ws = torch.empty(int(getattr(_lib.load(), "geossl_%s_head_fwd_workspace_floats" % name)(rows)), **f32)
+    loss = torch.empty((), **f32)
+    call("geossl_%s_head_fwd_dyn" % name, ptr(h), N, F, ptr(Wd), ptr(bd), *[ptr(t) for t in inputs], rows, ptr(proj),
+         ptr(pred), ptr(residual), ptr(ws), ptr(loss), _dyn(dyn, "n_atoms"), _dyn(dyn, dyn_field), stream())
+    ctx.params, ctx.dyn = (W, b), dyn
+    ctx.mark_non_differentiable(pred)
+    return Wd, residual, loss, pred
+
+
+def _cat_head_backward(ctx, name, dyn_field, h, Wd, index_args, gout):
+    """Backward of the same heads: geossl_<name>_head_bwd_dyn with the head's own `index_args` between W and gout ->
+    the gradients of (h, W, b) followed by the six Nones of the other forward arguments."""
+    N, F = h.shape
+    direct, (dW, db) = _param_grads(ctx.params)
+    dh = torch.empty_like(h)
+    ws = torch.empty(int(getattr(_lib.load(), "geossl_%s_head_bwd_workspace_floats" % name)(N, F)), dtype=torch.float32,
+                     device=h.device)
+    g = gout.to(torch.float32).contiguous()
+    call("geossl_%s_head_bwd_dyn" % name, ptr(h), N, F, ptr(Wd), *index_args, ptr(g), ptr(dh), ptr(dW), ptr(db), ptr(ws),
+         1 if direct else 0, _dyn(ctx.dyn, "n_atoms"), _dyn(ctx.dyn, dyn_field), stream())
+    return (dh,) + ((None, None) if direct else (dW, db)) + (None,) * 6
+
+
 class _DistanceHead(torch.autograd.Function):
     """L1Loss(Linear(2F, 1)(cat(h_u, h_v)).squeeze(), |pos_u - pos_v|) (examples/pretrain_DistancePrediction.py:15-25,
     71-77) on csrc/distance_head.hip -> (loss fp32 scalar, pred [S]).  The backward returns dh through autograd; dW / db
@@ -799,42 +848,17 @@ class _DistanceHead(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, W, b, positions, sei0, sei1, inc_ptr, inc_idx, dyn):
-        h, pos = _f32(h), _f32(positions)
-        N, F = h.shape
-        S = sei0.numel()
-        dev = h.device
-        Wd, bd = W.detach().contiguous().view(-1), b.detach().contiguous().view(-1)
-        lib = _lib.load()
-        proj = torch.empty(max(N, 1), 2, dtype=torch.float32, device=dev)
-        pred = torch.empty(S, dtype=torch.float32, device=dev)
-        sgn = torch.empty(S, dtype=torch.float32, device=dev)
-        ws = torch.empty(int(lib.geossl_distance_head_fwd_workspace_floats(S)), dtype=torch.float32, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        call("geossl_distance_head_fwd_dyn", ptr(h), N, F, ptr(Wd), ptr(bd), ptr(pos), ptr(sei0), ptr(sei1), S,
-             ptr(proj), ptr(pred), ptr(sgn), ptr(ws), ptr(loss), _dyn(dyn, "n_atoms"), _dyn(dyn, "n_super"), stream())
+        h = _f32(h)
+        Wd, sgn, loss, pred = _cat_head_forward(ctx, "distance", "n_super", h, W, b, 2, (_f32(positions), sei0, sei1),
+                                                sei0.numel(), dyn)
         ctx.save_for_backward(h, Wd, sei0, sgn, inc_ptr, inc_idx)
-        ctx.params, ctx.dyn = (W, b), dyn
-        ctx.mark_non_differentiable(pred)
         return loss, pred
 
     @staticmethod
     def backward(ctx, gout, _gpred):
         h, Wd, sei0, sgn, inc_ptr, inc_idx = ctx.saved_tensors
-        W, b = ctx.params
-        N, F = h.shape
-        dev = h.device
-        direct = _lib.direct_grads_enabled((W, b))
-        dW, db = (W.grad, b.grad) if direct else (torch.empty_like(W), torch.empty_like(b))
-        dh = torch.empty_like(h)
-        ws = torch.empty(int(_lib.load().geossl_distance_head_bwd_workspace_floats(N, F)), dtype=torch.float32,
-                         device=dev)
-        g = gout.to(torch.float32).contiguous()
-        call("geossl_distance_head_bwd_dyn", ptr(h), N, F, ptr(Wd), ptr(sei0), sgn.numel(), ptr(sgn), ptr(inc_ptr),
-             ptr(inc_idx), ptr(g), ptr(dh), ptr(dW), ptr(db), ptr(ws), 1 if direct else 0, _dyn(ctx.dyn, "n_atoms"),
-             _dyn(ctx.dyn, "n_super"), stream())
-        if direct:
-            dW = db = None
-        return dh, dW, db, None, None, None, None, None, None
+        return _cat_head_backward(ctx, "distance", "n_super", h, Wd,
+                                  (ptr(sei0), sgn.numel(), ptr(sgn), ptr(inc_ptr), ptr(inc_idx)), gout)
 
 
 def distance_head_width_ok(F):
@@ -867,40 +891,17 @@ class _TorsionHead(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, W, b, tri0, tri1, tri2, angle, mol_ptr, dyn):
         h = _f32(h)
-        N, F = h.shape
-        T = tri0.numel()
-        dev = h.device
-        Wd, bd = W.detach().contiguous().view(-1), b.detach().contiguous().view(-1)
-        lib = _lib.load()
-        proj = torch.empty(max(N, 1), 3, dtype=torch.float32, device=dev)
-        pred = torch.empty(T, dtype=torch.float32, device=dev)
-        res = torch.empty(T, dtype=torch.float32, device=dev)
-        ws = torch.empty(int(lib.geossl_torsion_head_fwd_workspace_floats(T)), dtype=torch.float32, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        call("geossl_torsion_head_fwd_dyn", ptr(h), N, F, ptr(Wd), ptr(bd), ptr(tri0), ptr(tri1), ptr(tri2), ptr(angle), T,
-             ptr(proj), ptr(pred), ptr(res), ptr(ws), ptr(loss), _dyn(dyn, "n_atoms"), _dyn(dyn, "n_triples"), stream())
+        Wd, res, loss, pred = _cat_head_forward(ctx, "torsion", "n_triples", h, W, b, 3, (tri0, tri1, tri2, angle),
+                                                tri0.numel(), dyn)
         ctx.save_for_backward(h, Wd, tri0, tri1, tri2, res, mol_ptr)
-        ctx.params, ctx.dyn = (W, b), dyn
-        ctx.mark_non_differentiable(pred)
         return loss, pred
 
     @staticmethod
     def backward(ctx, gout, _gpred):
         h, Wd, tri0, tri1, tri2, res, mol_ptr = ctx.saved_tensors
-        W, b = ctx.params
-        N, F = h.shape
-        direct = _lib.direct_grads_enabled((W, b))
-        dW, db = (W.grad, b.grad) if direct else (torch.empty_like(W), torch.empty_like(b))
-        dh = torch.empty_like(h)
-        ws = torch.empty(int(_lib.load().geossl_torsion_head_bwd_workspace_floats(N, F)), dtype=torch.float32,
-                         device=h.device)
-        g = gout.to(torch.float32).contiguous()
-        call("geossl_torsion_head_bwd_dyn", ptr(h), N, F, ptr(Wd), ptr(tri0), ptr(tri1), ptr(tri2), res.numel(), ptr(res),
-             ptr(mol_ptr), mol_ptr.numel() - 1, ptr(g), ptr(dh), ptr(dW), ptr(db), ptr(ws), 1 if direct else 0,
-             _dyn(ctx.dyn, "n_atoms"), _dyn(ctx.dyn, "n_triples"), stream())
-        if direct:
-            dW = db = None
-        return dh, dW, db, None, None, None, None, None, None
+        return _cat_head_backward(ctx, "torsion", "n_triples", h, Wd,
+                                  (ptr(tri0), ptr(tri1), ptr(tri2), res.numel(), ptr(res), ptr(mol_ptr),
+                                   mol_ptr.numel() - 1), gout)
 
 
 def torsion_head_width_ok(F):
@@ -1010,11 +1011,9 @@ class _ChargeHead(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         h, Wd, idx, labels, k, prob = ctx.saved_tensors
-        W, b = ctx.params
         N, F = h.shape
         C, K = Wd.size(0), idx.numel()
-        direct = _lib.direct_grads_enabled((W, b))
-        dW, db = (W.grad, b.grad) if direct else (torch.empty_like(W), torch.empty_like(b))
+        direct, (dW, db) = _param_grads(ctx.params)
         dh = torch.empty_like(h)
         ws = torch.empty(max(int(_lib.load().geossl_charge_head_bwd_workspace_floats(K, F, C)), 1), dtype=torch.float32,
                          device=h.device)
@@ -1104,14 +1103,10 @@ class _InfoGraphHead(torch.autograd.Function):
         g = gout.to(torch.float32).contiguous()
         call("geossl_infograph_bwd_dyn", ptr(x), N, F, ptr(Wd), ptr(ctx.lay.mol_ptr), B, ctx.mode, ptr(s), ptr(h),
              ptr(scores), ptr(g), ptr(dx), ptr(dm), ptr(dh), _dyn(ctx.dyn, "n_atoms"), stream())
-        direct = W.requires_grad and _lib.direct_grads_enabled((W,))
-        dW = None
-        if direct:
-            _infograph_wgrad(s, dh, W.grad, True)
-        elif ctx.needs_input_grad[1]:
-            dW = torch.empty_like(Wd)
-            _infograph_wgrad(s, dh, dW, False)
-        return dx, dW, dm, None, None, None
+        direct, (dW,) = _param_grads((W,), ctx.needs_input_grad[1:2])
+        if dW is not None:
+            _infograph_wgrad(s, dh, dW, direct)
+        return dx, None if direct else dW, dm, None, None, None
 
 
 def infograph_width_ok(F):
@@ -1213,14 +1208,7 @@ class _PropertyHead(torch.autograd.Function):
         dz = torch.empty(B, F // 2, dtype=torch.float32, device=dev) if mlp else None
         ws = torch.empty(int(_lib.load().geossl_property_workspace_floats(B)), dtype=torch.float32, device=dev)
         g = gout.to(torch.float32).contiguous()
-        live = [p for p in params if p.requires_grad]
-        direct = bool(live) and _lib.direct_grads_enabled(live)
-        grads = [None] * len(params)
-        for i, p in enumerate(params):
-            if direct:
-                grads[i] = p.grad if p.requires_grad else None
-            elif ctx.needs_input_grad[7 + i]:
-                grads[i] = torch.empty_like(p, dtype=torch.float32)
+        direct, grads = _param_grads(params, ctx.needs_input_grad[7:])
         # the vector gradients of the launch: (w, b) of head 0, (w2, b2) of head 1
         vw, vb = (grads[2], grads[3]) if mlp else (grads[0], grads[1])
         call("geossl_property_bwd_dyn", ctx.N, F, ptr(ctx.lay.mol_ptr), B, PROPERTY_READOUTS[ctx.readout],
@@ -1343,15 +1331,7 @@ class _PairHead(torch.autograd.Function):
         dh = torch.empty(ctx.N, F, dtype=torch.float32, device=dev)
         ws = torch.empty(int(_lib.load().geossl_pair_head_workspace_floats(B)), dtype=torch.float32, device=dev)
         g = gout.to(torch.float32).contiguous()
-        params = ctx.params
-        live = [p for p in params if p.requires_grad]
-        direct = bool(live) and _lib.direct_grads_enabled(live)
-        grads = [None, None]
-        for i, p in enumerate(params):
-            if direct:
-                grads[i] = p.grad if p.requires_grad else None
-            elif ctx.needs_input_grad[5 + i]:
-                grads[i] = torch.empty_like(p, dtype=torch.float32)
+        direct, grads = _param_grads(ctx.params, ctx.needs_input_grad[5:])
         call("geossl_pair_head_bwd_dyn", ctx.N, F, ptr(ctx.lay.mol_ptr), B, PROPERTY_READOUTS[ctx.readout], ptr(wd),
              ptr(m), ptr(z), ptr(y), ptr(g), ptr(dh), ptr(grads[0]), ptr(grads[1]), ptr(ws), 1 if direct else 0,
              _dyn(ctx.dyn, "n_atoms"), stream())
