@@ -154,9 +154,11 @@ for _r in (8, 16, 20):
              _mol_launches("R=%d %s" % (_r, "mu0" if _mz else "general"), 512, lambda n, r=_r: painn_bwd_mol_lds(n, r),
                            lambda l: min(BENCH_MOLS, 256), [(2, None), (2, None)]))
     for _mz in (0, 1):   # the family of the round-6 finding: now built without packed fp32 ops, registered all the same
+        # (the general form, Lb0, by the test that runs it with LIVE mu; the two round-6 tests zero mu: they cover Lb1)
         _add("k_painn_fwd_mma", r"k_painn_fwd_mmaILi%dELb%dE" % (_r, _mz),
              ["test_gpu_round6::test_painn_first_interaction_with_mu_null_is_the_general_kernel_bit_for_bit",
-              "test_gpu_round6::test_painn_first_interaction_with_mu_null_at_more_batch_shapes"],
+              "test_gpu_round6::test_painn_first_interaction_with_mu_null_at_more_batch_shapes"] if _mz else
+             ["test_gpu_painn_mma::test_forward_with_live_mu_at_full_occupancy_vs_fp64"],
              _mol_launches("R=%d" % _r, 256, painn_mma_lds, lambda l: painn_mma_grid(BENCH_MOLS, l),
                            [(2, None), (1, MMA_SET_B)]))
 

@@ -33,12 +33,33 @@ the accumulator in at most four fp32-rounded steps (u each).
             bf16 pieces, the three dropped piece products <= 3 * 2^-24 = 0.75 u; 12 MFMAs per tile = 48 rounded steps;
             the compensated sum over the blocks' partials and its four slice sums: at most 6 more.
             C_WGRAD(T) = 2 + (48 T + 6) / 4      (T: most tiles any one block accumulates; one 70-edge atom -> 39.5)
-These come from the counts above, not from what the kernels return."""
+These come from the counts above, not from what the kernels return.
+
+The same forward is computed by two more kernels, and `forward` serves them with constants of their own (again counted
+in the sources, csrc/painn_mma.hip and csrc/painn.hip, never fitted to results; tests/test_gpu_painn_mma.py and
+tests/test_gpu_painn_atom.py print the worst measured ratio next to each):
+  k_painn_fwd_mma<R, MZ> (molecule-staged, groups of four rows per target atom, a tile = eight groups), u = 2^-22:
+            W: the same six chained 32x32x16 MFMAs on two fp16 pieces per operand as the tile kernels: 9 u.
+            kk fcut: kk = 2^(eW - 28) is a power of two: exact, no rounding.
+            (acc kf) xv: two rounded products; x1 d + x2 mu_j: at most three roundings (two products and their sum, one
+            less where the compiler contracts) = 5 roundings -> 1.25 u (q_out: 2, covered).
+            additions: a row is added to its group's sum (one rounded addition per edge: D), a group's sum to the
+            atom's running sum across groups and tiles (ceil(D / 4)), the residual (1); the exchange of the halves
+            moves values and rounds nothing.  Each is u / 4 of a partial sum of magnitudes <= S.
+            c_fwd_mma(D) = 9 + 1.25 + (D + ceil(D / 4) + 1) / 4        (D: largest in-degree; 17 -> 16, 43 -> 24)
+            The first addition of a group and of a run adds to an exact zero, so (D + ceil(D / 4) + 1) overcounts
+            by up to ceil(D / 4) + 1 additions - kept, as a bound.
+  k_painn_interaction_fwd<R> and k_painn_interaction_fwd_mol<R> (fp32 vector arithmetic), u = 2^-24 (U24):
+            W: the bias is the accumulator's exact starting value, then R fused multiply-adds, one rounding each: R;
+            W fcut, W x: 2; x1 d + x2 mu_j: at most 3; D sequential additions in incidence order; the residual: 1.
+            c_fwd_atom(R, D) = R + 2 + 3 + D + 1 = R + D + 6            (R = 20, D = 70 -> 96; R = 32 -> 108)
+            (the bias costs no rounding of its own: it is where the chain starts.)"""
 import math
 
 import torch
 
 U = 2.0 ** -22
+U24 = 2.0 ** -24
 
 
 def c_fwd(max_degree):
@@ -53,36 +74,48 @@ def c_wgrad(tiles):
     return 2.0 + (48 * tiles + 6) / 4.0
 
 
+def c_fwd_mma(max_degree):
+    """k_painn_fwd_mma, in units of U = 2^-22."""
+    return 9.0 + 1.25 + (max_degree + math.ceil(max_degree / 4) + 1) / 4.0
+
+
+def c_fwd_atom(R, max_degree):
+    """k_painn_interaction_fwd / _fwd_mol, in units of U24 = 2^-24."""
+    return float(R + 2 + 3 + max_degree + 1)
+
+
 MAX_DEGREE = 70                 # of the GPU test's edge list, either side
 C_FWD, C_BWD = c_fwd(MAX_DEGREE), c_bwd(MAX_DEGREE)
 C_WGRAD = c_wgrad(math.ceil(MAX_DEGREE / 32))   # one atom per block (96 atoms on 96 blocks)
 
 
-def _d(t):
-    return None if t is None else t.detach().double().cpu()
+def _d(t, device="cpu"):
+    return None if t is None else t.detach().double().to(device)
 
 
-def filters(phi, fcut, Wf, bf):
+def filters(phi, fcut, Wf, bf, device="cpu"):
     """-> W [E, 3F], Wabs [E, 3F]."""
-    phi, fcut, Wf, bf = _d(phi), _d(fcut), _d(Wf), _d(bf)
+    phi, fcut, Wf, bf = _d(phi, device), _d(fcut, device), _d(Wf, device), _d(bf, device)
     W = (phi @ Wf.t() + bf) * fcut[:, None]
     Wabs = (phi.abs() @ Wf.abs().t() + bf.abs()) * fcut.abs()[:, None]
     return W, Wabs
 
 
 def _scatter(terms, index, n):
-    out = torch.zeros((n,) + tuple(terms.shape[1:]), dtype=torch.float64)
+    out = torch.zeros((n,) + tuple(terms.shape[1:]), dtype=torch.float64, device=terms.device)
     return out.index_add_(0, index, terms)
 
 
-def forward(q, mu, xc, idx_i, idx_j, phi, fcut, dirv, Wf, bf):
-    """mu None: identically zero.  -> dict(q_out, mu_out: (ref, S), terms_q [E, F], terms_mu [E, 3, F], abs_q, abs_mu)."""
-    q, mu, xc, dirv = _d(q), _d(mu), _d(xc), _d(dirv)
+def forward(q, mu, xc, idx_i, idx_j, phi, fcut, dirv, Wf, bf, device="cpu"):
+    """mu None: identically zero.  -> dict(q_out, mu_out: (ref, S), terms_q [E, F], terms_mu [E, 3, F], abs_q, abs_mu,
+    and the two parts of terms_mu: terms_mu_r = W_1 x_1 dir, terms_mu_m = W_2 x_2 mu_j).  `device`: where the fp64
+    tensors live (the batches of a thousand molecules are evaluated on the device they are on, in one pass)."""
+    q, mu, xc, dirv = _d(q, device), _d(mu, device), _d(xc, device), _d(dirv, device)
     N, F = q.shape
     if mu is None:
-        mu = torch.zeros(N, 3, F, dtype=torch.float64)
-    i, j = idx_i.cpu().long(), idx_j.cpu().long()
-    W, Wabs = filters(phi, fcut, Wf, bf)
+        mu = torch.zeros(N, 3, F, dtype=torch.float64, device=device)
+    i, j = idx_i.to(device).long(), idx_j.to(device).long()
+    W, Wabs = filters(phi, fcut, Wf, bf, device)
     x = xc[j]                                                                  # [E, 3F]
     t_q = W[:, :F] * x[:, :F]
     a_q = Wabs[:, :F] * x[:, :F].abs()
@@ -93,7 +126,7 @@ def forward(q, mu, xc, idx_i, idx_j, phi, fcut, dirv, Wf, bf):
            (Wabs[:, 2 * F:] * x[:, 2 * F:].abs())[:, None, :] * mu[j].abs()
     return dict(q_out=(q + _scatter(t_q, i, N), q.abs() + _scatter(a_q, i, N)),
                 mu_out=(mu + _scatter(t_mu, i, N), mu.abs() + _scatter(a_mu, i, N)),
-                terms_q=t_q, terms_mu=t_mu, abs_q=a_q, abs_mu=a_mu)
+                terms_q=t_q, terms_mu=t_mu, abs_q=a_q, abs_mu=a_mu, terms_mu_r=r_part, terms_mu_m=m_part)
 
 
 def backward(dq_out, dmu_out, mu, xc, idx_i, idx_j, phi, fcut, dirv, Wf, bf, atoms=None):

@@ -132,9 +132,11 @@ def _dropped(got, ref, S, c_, terms, owner_index, what):
 
 PARAMS = [(20, True), (20, False), (8, True), (8, False)]
 IDS = ["R20-mu", "R20-mu0", "R8-mu", "R8-mu0"]
+PARAMS16 = PARAMS + [(16, True), (16, False)]          # (R = 16 is compiled and served: the element-wise tests run it too)
+IDS16 = IDS + ["R16-mu", "R16-mu0"]
 
 
-@pytest.mark.parametrize("R,mu_given", PARAMS, ids=IDS)
+@pytest.mark.parametrize("R,mu_given", PARAMS16, ids=IDS16)
 def test_forward_every_element_against_the_twin(R, mu_given):
     from geossl_amd import _lib
     c = _case(R, mu_given, False)
@@ -160,7 +162,7 @@ def test_forward_every_element_against_the_twin(R, mu_given):
     assert_repeatable(lambda: _fwd(c)[:2], (q_out, mu_out), "forward")
 
 
-@pytest.mark.parametrize("R,mu_given", PARAMS, ids=IDS)
+@pytest.mark.parametrize("R,mu_given", PARAMS16, ids=IDS16)
 def test_backward_every_element_against_the_twin(R, mu_given):
     c = _case(R, mu_given, True)
     j = c["el"].idx_j.cpu()
@@ -185,7 +187,7 @@ def test_backward_every_element_against_the_twin(R, mu_given):
     assert_repeatable(lambda: flat(_bwd(c, 1.0)), flat(first), "backward")
 
 
-@pytest.mark.parametrize("R,mu_given", PARAMS, ids=IDS)
+@pytest.mark.parametrize("R,mu_given", PARAMS16, ids=IDS16)
 def test_list_forms(R, mu_given):
     cf, cb = _case(R, mu_given, False), _case(R, mu_given, True)
     i32 = dict(dtype=torch.int32, device=DEV)

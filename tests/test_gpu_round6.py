@@ -483,7 +483,7 @@ _MU0_SIZES = {"setA": [18] * 1024, "setB": None, "setA2048": [18] * 2048,
               "ragged": [2, 26, 1, 7, 18, 1, 12, 25, 3, 20, 9, 33, 18, 18, 17, 19] * 64}
 
 
-@pytest.mark.parametrize("R", [20, 8])
+@pytest.mark.parametrize("R", [20, 8, 16])
 def test_painn_first_interaction_with_mu_null_is_the_general_kernel_bit_for_bit(R):
     """geossl_painn_interaction_fwd_mma with mu = NULL (the first interaction: mu identically zero, painn.py:249) against the
     same call with a tensor of zeros, at the bench size (1024 molecules, every CU holds two blocks): q_out and mu_out
@@ -494,7 +494,7 @@ def test_painn_first_interaction_with_mu_null_is_the_general_kernel_bit_for_bit(
 
 
 @pytest.mark.parametrize("sizes", ["setB", "setA2048", "ragged"])
-@pytest.mark.parametrize("R", [20, 8])
+@pytest.mark.parametrize("R", [20, 8, 16])
 def test_painn_first_interaction_with_mu_null_at_more_batch_shapes(R, sizes):
     """The same comparison (general kernel bit for bit, fp64 per element) on 1024 molecules of set B (one block per CU:
     33-atom molecules), 2048 x 18 atoms (four molecules per persistent block) and a ragged batch of 1024 molecules
