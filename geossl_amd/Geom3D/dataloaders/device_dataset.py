@@ -256,10 +256,14 @@ class DeviceDataset:
     def _build_edges(self, radius, max_num_neighbors):
         """radius_graph(positions, r) of every molecule (datasets_3D_Radius.py:120) in two launches over the whole
         dataset: [source ; target] with DATASET atom ids, target-major - a molecule's edges are one contiguous run."""
+        from ...layout import SPARSE_MAX_N
         from ...ops import radius_cap
         M, Nt, dev = len(self), int(self.off[-1]), self.device
         mol_ptr = torch.from_numpy(self.off.astype(np.int32)).to(dev)
         max_n = int(self.sizes.max()) if M else 0
+        if max_n > SPARSE_MAX_N:   # (the graph kernels keep a structure's positions and bit matrix in LDS)
+            raise ValueError("radius edges are built for structures of at most %d atoms (the largest here has %d)"
+                             % (SPARSE_MAX_N, max_n))
         r2 = float(torch.tensor(radius * radius, dtype=torch.float32))
         cap = radius_cap(max_num_neighbors)
         deg = torch.zeros(Nt, dtype=torch.int32, device=dev)
@@ -567,9 +571,10 @@ class PairedDeviceDataset:
     (``structures``): active m at id m, inactive m at id M + m; ``y [M]`` float32 on the device beside it."""
 
     def __init__(self, x_active, positions_active, sizes_active, x_inactive, positions_inactive, sizes_inactive, y,
-                 device):
+                 device, radius=None, max_num_neighbors=32):
         """x_* [Ntot_*] int64 (or [Ntot_*, C]), positions_* [Ntot_*, 3] float32, sizes_* [M] atoms per structure (numpy
-        or tensors; structure after structure); y [M], integer or float: stored as float32 (finetune_lep.py:43)."""
+        or tensors; structure after structure); y [M], integer or float: stored as float32 (finetune_lep.py:43).
+        radius: also build every structure's radius_edge_index (PaiNN) once on the device, as ``DeviceDataset`` does."""
         as_t = lambda a: a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
         xa, xi = as_t(x_active).cpu(), as_t(x_inactive).cpu()
         pa, pi = as_t(positions_active).cpu().float(), as_t(positions_inactive).cpu().float()
@@ -584,7 +589,8 @@ class PairedDeviceDataset:
             raise ValueError("one active and one inactive structure per pair: got %d and %d" % (sa.size, si.size))
         M = int(sa.size)
         self.x_1d = xa.dim() == 1   # (DatasetLEP's records: the atom types alone - the backbone gets them as they are)
-        self.structures = DeviceDataset(torch.cat([xa, xi]), torch.cat([pa, pi]), np.concatenate([sa, si]), device)
+        self.structures = DeviceDataset(torch.cat([xa, xi]), torch.cat([pa, pi]), np.concatenate([sa, si]), device,
+                                        radius=radius, max_num_neighbors=max_num_neighbors)
         self.device, self.x_cols = self.structures.device, self.structures.x_cols
         self.sizes = self.structures.sizes            # [2M]: active | inactive
         self.sizes_active, self.sizes_inactive = self.sizes[:M], self.sizes[M:]
@@ -595,14 +601,16 @@ class PairedDeviceDataset:
         self._M = M
 
     @classmethod
-    def from_data_list(cls, items, device):
+    def from_data_list(cls, items, device, radius=None, max_num_neighbors=32):
         """From the reference's LEP records (``x_active``, ``positions_active``, ``x_inactive``, ``positions_inactive``,
-        ``y``: what ``DataLoaderLEP`` consumes): concatenated once, uploaded once."""
+        ``y``: what ``DataLoaderLEP`` consumes): concatenated once, uploaded once.  radius: the structures' radius edges
+        are built on the device from these positions (the records' own ``radius_edge_index_*`` are not read)."""
         cat = lambda k: torch.cat([torch.as_tensor(getattr(d, k)) for d in items], dim=0)
         n = lambda k: [int(torch.as_tensor(getattr(d, k)).size(0)) for d in items]
         y = torch.cat([torch.as_tensor(d.y).reshape(-1) for d in items])
         return cls(cat("x_active"), cat("positions_active"), n("x_active"), cat("x_inactive"),
-                   cat("positions_inactive"), n("x_inactive"), y, device)
+                   cat("positions_inactive"), n("x_inactive"), y, device, radius=radius,
+                   max_num_neighbors=max_num_neighbors)
 
     def __len__(self):
         return self._M
@@ -663,6 +671,10 @@ class PairedBatch:
             self._batch = dict(x_active=x[:na], x_inactive=x[na:], positions_active=fb.positions[:na],
                                positions_inactive=fb.positions[na:], batch_active=fb.batch[:na],
                                batch_inactive=fb.batch[na:] - B)
+            rei = fb.radius_edge_index
+            if rei is not None:   # (a dataset built with radius=: each side's edges with its own running atom counts)
+                ea = int(self._dataset.structures.edge_cnt[self.ids].sum())
+                self._batch.update(radius_edge_index_active=rei[:, :ea], radius_edge_index_inactive=rei[:, ea:] - na)
         return self._batch
 
     x_active = property(lambda self: self.materialize()["x_active"])
@@ -671,6 +683,9 @@ class PairedBatch:
     positions_inactive = property(lambda self: self.materialize()["positions_inactive"])
     batch_active = property(lambda self: self.materialize()["batch_active"])
     batch_inactive = property(lambda self: self.materialize()["batch_inactive"])
+    # (None for a dataset built without radius=: the attribute a collated BatchLEP without edges does not have either)
+    radius_edge_index_active = property(lambda self: self.materialize().get("radius_edge_index_active"))
+    radius_edge_index_inactive = property(lambda self: self.materialize().get("radius_edge_index_inactive"))
 
     def to(self, device, **kw):
         """``batch.to(device)`` of the reference's loop: the structures are there already."""

@@ -324,6 +324,9 @@ class _PaiNNCore(torch.autograd.Function):
         # atoms in one launch per block - no staged launch, no lists (layout.painn_tile_route; GEOSSL_PAINN_TILE).
         from ...layout import painn_tile_route
         use_tile = bool(cfg["mma"]) and painn_tile_route(lay, F_, R, E, dyn)
+        if dyn is not None and getattr(lay, "sparse", False) and not use_tile:
+            raise _lib.GeosslHipError("a sparse capacity-bucket layout serves the atom-tile kernels only (F = 128, 8 / 16 / "
+                                      "20 radial functions, without GEOSSL_PAINN_VECTOR)")
         if use_tile:
             mu_is_zero = not ctx.needs_input_grad[1] and not _env("GEOSSL_PAINN_NO_MU_ZERO")
         mu = None if mu_is_zero else torch.zeros(N, 3, F_, **f32)            # :249
@@ -347,7 +350,8 @@ class _PaiNNCore(torch.autograd.Function):
             if use_tile:  # atom tiles: the filter on the matrix pipe, source rows from L2
                 call("geossl_painn_interaction_fwd_tile", ptr(q), ptr(mu), ptr(xc), ptr(el.idx_j), ptr(inc_ptr),
                      ptr(inc_idx), ptr(phi), ptr(fcut), ptr(dirv), ptr(fw[l * 3 * F_:(l + 1) * 3 * F_]),
-                     ptr(fb[l * 3 * F_:(l + 1) * 3 * F_]), None, N, None, F_, R, ptr(q2), ptr(mu2), st)   # :54-64
+                     ptr(fb[l * 3 * F_:(l + 1) * 3 * F_]), None, N, dN, F_, R, ptr(q2), ptr(mu2), st)   # :54-64
+                # (a sparse bucket: N is the atom capacity, the grid's; atoms 0 .. *dN - 1 are real)
             elif use_mma:  # filter on the matrix pipe (painn_mma.hip); LDS: 3.5 KB per atom + 3 KB
                 row_edge, grp_atom, _, mol_grp = el.groups("i", lay.mol_ptr)
                 call("geossl_painn_interaction_fwd_mma_dyn", ptr(q), ptr(mu), ptr(xc), ptr(el.idx_j), ptr(row_edge),
@@ -562,8 +566,8 @@ class _PaiNNCore(torch.autograd.Function):
                     ptr(fcut), ptr(dirv), ptr(ps[1][l * 3 * F_:(l + 1) * 3 * F_]), ptr(ps[2][l * 3 * F_:(l + 1) * 3 * F_]))
             outs = (ptr(dxc), ptr(dmu_in), ptr(g_fw[l * 3 * F_:(l + 1) * 3 * F_]), ptr(g_fb[l * 3 * F_:(l + 1) * 3 * F_]),
                     ptr(ws), acc, st)
-            if use_tile:  # all atoms in one launch (atom_list NULL)
-                call("geossl_painn_interaction_bwd_tile", *args, None, N, None, F_, R, *outs)
+            if use_tile:  # all atoms in one launch (atom_list NULL; a sparse bucket: the real ones, *dN of N)
+                call("geossl_painn_interaction_bwd_tile", *args, None, N, dN, F_, R, *outs)
             else:
                 call("geossl_painn_interaction_bwd_mol" if big_b is None else "geossl_painn_interaction_bwd_mol_skip",
                      *args, ptr(lay.mol_ptr), lay.B, lay.max_n, N, F_, R, *outs)

@@ -243,6 +243,9 @@ PROTOTYPES = {
     "geossl_painn_interaction_fwd_tile": (i32, [vp] * 12 + [i64, vp, i32, i32, vp, vp, vp]),
     "geossl_painn_interaction_bwd_tile_workspace_floats": (i64, [i64, i32, i32]),
     "geossl_painn_interaction_bwd_tile": (i32, [vp] * 13 + [i64, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp]),
+    "geossl_painn_incidence_layout_workspace_bytes": (i64, [i64, i64, i64]),
+    "geossl_painn_incidence_layout": (i32, [vp, vp, i64, vp, i64, i64, i32] + [vp] * 7),
+    "geossl_painn_incidence_layout_dyn": (i32, [vp, vp, i64, vp, vp, i64, i64, i32] + [vp] * 8),
     "geossl_painn_interaction_bwd_mol_skip": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i64, i32,
                                                     i32, vp, vp, vp, vp, vp, i32, vp]),
     "geossl_painn_mix_pre_fwd_dyn": (i32, [vp, vp, i64, i32, f32, vp, vp, vp, vp]),

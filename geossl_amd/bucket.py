@@ -26,7 +26,8 @@ atoms    always                         dims, mol_ptr, src_off         x, positi
 pairs    not sparse                     pair_ptr, stats; SchNet: work  SchNet: pair_i, pair_j, agg_targets
 tuples   "combination" / "permutation"  se_ptr, inc_ptr                sei, inc_idx
 triples  "triples" (views = 1)          dims[D_T], t_src_off, t_ptr    triples, triple_angle
-edges    PaiNN                          e_src_off, e_ptr, big0, big1   the _Edges buffers, the two status words
+edges    PaiNN, not sparse              e_src_off, e_ptr, big0, big1   the _Edges buffers, the two status words
+sedges   PaiNN, sparse                  e_src_off, e_ptr               radius_edge_index, both incidence lists, status
 ======== ============================== ============================== ==========================================
 
 (pairs also hands the gather the ADDRESS of se_ptr, which the gather takes in every dense bucket; the words of se_ptr
@@ -41,10 +42,14 @@ offsets are one running sum over the section table of ``BlobLayout``; a section 
 with length 0 (``dims`` .. ``stats`` exist in every bucket).  The pairs part is every dense bucket's: ``pair_ptr`` and the
 divisor are functions of the sizes that PaiNN and triples buckets carry too; the pair SLOTS are SchNet's.
 
-A SPARSE bucket (option ``SPARSE``; one view, SchNet; structures of up to 1024 atoms) is the bucket whose only part is
+A SPARSE bucket (option ``SPARSE``; one view; structures of up to 1024 atoms) is, for SchNet, the bucket whose only part is
 atoms: the backbone builds the compacted pair list from the positions inside the captured step
 (geossl_sparse_pairs_build_dyn), at the capacity ``P_cap = 33 N_cap`` that every batch which fits the atoms fits too.
 Its fill uploads mol_ptr and the counts and gathers the atom rows: nothing else of the batch is read.
+The sparse PaiNN bucket (kind "painn") adds the sparse edges part: the batch's ``radius_edge_index`` at ``E_cap`` (a
+handle's edges come with the gather launch, a collated batch's by a copy) and both incidence lists at capacity,
+rewritten per fill by one launch (geossl_painn_incidence_layout_dyn); the atom-tile interaction kernels read them under
+the device-side atom count.  No group arrays, no stage-cap atom lists, no size class of PAINN_MAX_N_CLASSES.
 
 Beside the class: which bucket a batch takes (``route``), how one is sized for a batch (``Bucket.sizing``, ``for_batch``), whether
 a batch still fits (``Bucket.fits_batch``), and the shapes of a step's static noise tensors (``NOISE_SHAPES``).
@@ -56,7 +61,7 @@ import ctypes as C
 
 import numpy as np
 import torch
-from .switches import env as _env, masked_painn_buckets, sparse_buckets
+from .switches import env as _env, masked_painn_buckets, painn_sparse_buckets, sparse_buckets
 
 from . import _lib
 from ._lib import call, ptr, stream
@@ -194,11 +199,12 @@ def sparse_tensors_ok(batch):
             and not batch.positions.requires_grad and batch.x.device == batch.positions.device)
 
 
-def sparse_eligible(batch):
+def sparse_eligible(batch, model_3d="schnet"):
     """Can this batch go through a SPARSE bucket?  Molecule sizes known on the host, 1 .. 1024 atoms, and a layout of
     them would be sparse (layout.want_sparse: a structure above 255 atoms, or GEOSSL_SPARSE_PAIRS=1).  A collated batch:
     tensors as `sparse_tensors_ok`; a handle on a device-resident dataset: unmasked, pair-tuple dataset (its tuple option
-    is not read)."""
+    is not read).  PaiNN: also radius edges on the device - a handle of a dataset built with ``radius=``, or a collated
+    int64 ``radius_edge_index`` [2, E]."""
     from .layout import SPARSE_MAX_N, want_sparse
     sizes = getattr(batch, "_sizes", None)
     if sizes is None or not len(sizes):
@@ -206,8 +212,12 @@ def sparse_eligible(batch):
     lo, hi = size_range(batch)
     if lo < 1 or hi > SPARSE_MAX_N or not want_sparse(hi):
         return False
+    painn = model_3d == "painn"
     if getattr(batch, "_dataset", None) is not None:
-        return getattr(batch, "_mask", None) is None and not getattr(batch, "_triples", False)
+        return (getattr(batch, "_mask", None) is None and not getattr(batch, "_triples", False)
+                and (not painn or batch.n_edges is not None))
+    if painn and not _rei_ok(getattr(batch, "radius_edge_index", None)):
+        return False
     return not getattr(batch, "_triples", False) and sparse_tensors_ok(batch)
 
 
@@ -277,6 +287,13 @@ def route(batch, model_3d, views, pair_tuples, normalize):
     PaiNN's edge list differs batch by batch anyway)."""
     if (not pair_tuples and views == 1 and model_3d == "schnet"
             and sparse_buckets(getattr(batch, "_dataset", None) is not None) and sparse_eligible(batch)):
+        return SPARSE
+    # PaiNN in such a step: the sparse bucket with an edges part, on the atom-tile kernels (a switch of its own:
+    # GEOSSL_PAINN_SPARSE_BUCKETS; GEOSSL_PAINN_TILE=0 / GEOSSL_PAINN_VECTOR leave no kernel that takes its layout)
+    if (not pair_tuples and views == 1 and model_3d == "painn" and not normalize
+            and painn_sparse_buckets(getattr(batch, "_dataset", None) is not None)
+            and _env("GEOSSL_PAINN_TILE") != "0" and not _env("GEOSSL_PAINN_VECTOR")
+            and sparse_eligible(batch, "painn")):
         return SPARSE
     if not eligible(batch, model_3d, normalize) or (model_3d != "painn" and is_uniform(batch)):
         return None
@@ -700,6 +717,61 @@ class _EdgesPart(_Part):
         b.el_status.arm(every=8)
 
 
+class _SparseEdgesPart(_Part):
+    """PaiNN on a sparse bucket (one view, structures of up to 1024 atoms): the batch's radius_edge_index in a static
+    [2, E_cap] buffer - a handle's edges gathered with their atom offsets by the gather launch, a collated batch's by
+    one copy - and both incidence lists at capacity, rewritten by ONE launch behind it
+    (geossl_painn_incidence_layout_dyn: the counts come from `dims`).  What the atom-tile interaction kernels read; no
+    group layout, no stage-cap lists."""
+
+    def __init__(self, lay):
+        o, B = lay.off, lay.B
+        self.B = B
+        self.src, self.ptr = slice(o["e_src_off"], o["e_src_off"] + B), slice(o["e_ptr"], o["e_ptr"] + B + 1)
+
+    def write_host(self, h, hp, n, N, P, S, E, T, masked_edges, src):
+        if src is not None:
+            h[self.src] = src[1]
+            ep = h[self.ptr]
+            ep[0] = 0
+            np.cumsum(src[2], out=ep[1:])
+
+    def attach(self, b):
+        self.b, dev = b, b.device
+        Nc, Ec = b.N_cap, max(b.E_cap, 1)
+        i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
+        b.rei = torch.zeros(2, Ec, **i64)
+        el = _Edges()
+        el.E, el.N, el.B = b.E_cap, Nc, b.B
+        el.idx_i, el.idx_j = b.rei[0], b.rei[1]   # (one view: the incidence lists index the edge list itself)
+        el.inc = {"i": (torch.zeros(Nc + 1, **i64), torch.zeros(Ec, **i32)),
+                  "j": (torch.zeros(Nc + 1, **i64), torch.zeros(Ec, **i32))}
+        b.el_status = _lib.StatusWord(dev, "radius_edge_index must be grouped by molecule in batch order with both "
+                                      "ends in the same molecule (collated MoleculeDataset3DRadius output is)")
+        el.status, el.dyn = b.el_status.word, b.dyn
+        b.el = el
+        b.e2 = torch.zeros(2, 1, **i64)   # placeholder for PaiNN.forward's radius_edge_index argument
+        self.src_ptr, self.e_ptr = b._base + 4 * self.src.start, b._base + 4 * self.ptr.start
+        self.rei = (ptr(b.rei[0]), ptr(b.rei[1]))
+        self.outs = (ptr(el.inc["i"][0]), ptr(el.inc["i"][1]), ptr(el.inc["j"][0]), ptr(el.inc["j"][1]), ptr(el.status))
+
+    def bind(self, g, batch, ds, E, masked_edges):
+        if ds is not None and E:
+            g.e0_src, g.e1_src, g.e_src_off, g.e_ptr = ptr(ds.edges[0]), ptr(ds.edges[1]), self.src_ptr, self.e_ptr
+            g.e0_dst, g.e1_dst = self.rei
+        else:
+            g.e0_src = g.e1_src = g.e_src_off = g.e_ptr = g.e0_dst = g.e1_dst = None
+
+    def after(self, batch, ds, N, E, T, masked_edges):
+        b = self.b
+        if ds is None and E:
+            b.rei[:, :E].copy_(batch.radius_edge_index)
+        _poll(b.el_status)
+        call("geossl_painn_incidence_layout_dyn", *self.rei, b.E_cap, b.dyn.n_edges2, b._g.mol_ptr, b.N_cap, self.B,
+             b.max_n, *self.outs, b.dyn.n_atoms, None, stream())
+        b.el_status.arm(every=8)
+
+
 def _poll(status):
     """A status word's late error as the ValueError a refused fill raises."""
     try:
@@ -718,7 +790,7 @@ class BlobLayout:
         Nc, Wc = int(caps[0]), int(caps[3])
         sparse, painn, triples = option == SPARSE, kind == "painn", option == TRIPLES
         self.big_caps = ()
-        if painn and max_n > 0:
+        if painn and max_n > 0 and not sparse:
             from .layout import painn_stage_caps
             # (the stage caps depend on the radial basis: 73 / 74 / 75 atoms for the backward at 20 / 16 / 8 functions -
             # lists made for another basis would never be found and the whole batch would fall back to the per-atom kernels)
@@ -739,7 +811,8 @@ class BlobLayout:
         self.words = at
         kinds = ((_Atoms,) + (() if sparse else (_Pairs,))
                  + ((_Tuples,) if option in ("combination", "permutation") else ())
-                 + ((_Triples,) if triples else ()) + ((_EdgesPart,) if painn else ()))
+                 + ((_Triples,) if triples else ())
+                 + (((_SparseEdgesPart if sparse else _EdgesPart),) if painn else ()))
         self.parts = tuple(kind_(self) for kind_ in kinds)
         self.writers = tuple(p.write_host for p in self.parts)
 
@@ -773,8 +846,8 @@ class Bucket:
     constructor (`BlobLayout.parts`; the table of the parts is in the module's docstring).
 
     `fill` is one path: check the batch, take a staging slot, `host_image` (every part's `write_host`), one upload, the
-    parts' `bind` on the bucket's `Gather` struct, the gather launch, the parts' `after`.  A sparse bucket (kind "schnet",
-    views = 1) is the bucket whose only part is atoms: `lay2` is a SPARSE layout at capacity - N = N_cap, P = P_cap (rows
+    parts' `bind` on the bucket's `Gather` struct, the gather launch, the parts' `after`.  A sparse bucket (views = 1;
+    kind "painn" adds the sparse edges part) is, for SchNet, the bucket whose only part is atoms: `lay2` is a SPARSE layout at capacity - N = N_cap, P = P_cap (rows
     of the pair list the backbone builds per step), max_n a class of SPARSE_MAX_N_CLASSES, mol_ptr the B real offsets.
 
     views = 1 (a step with no second view: Distance Prediction): the backbone's layout `lay2` and the counts in `dims`
@@ -789,8 +862,8 @@ class Bucket:
             raise ValueError("a bucket holds one or two views")
         if option == TRIPLES and views != 1:
             raise ValueError("a triples bucket holds one view")
-        if option == SPARSE and (views != 1 or kind != "schnet"):
-            raise ValueError("a sparse bucket holds one view of a SchNet batch")
+        if option == SPARSE and (views != 1 or kind not in ("schnet", "painn")):
+            raise ValueError("a sparse bucket holds one view of a SchNet or PaiNN batch")
         self.views = V = int(views)
         self.device, self.B, self.option, self.max_n = device, int(B), option, int(max_n)
         self.kind, self.E_cap, self.x_cols = kind, int(E_cap), int(x_cols)
@@ -901,7 +974,9 @@ class Bucket:
         painn, x_cols = self.kind == "painn", self.x.size(1)
         if opt == SPARSE:
             if mask is not None or getattr(batch, "_triples", False):
-                raise ValueError("a sparse bucket takes unmasked batches of whole molecules")
+                raise ValueError("a sparse bucket takes unmasked batches of whole molecules (a masked PaiNN batch is "
+                                 "served up to %d atoms per molecule, by the dense bucket)" % MAX_N if painn else
+                                 "a sparse bucket takes unmasked batches of whole molecules")
         elif option_of(batch) != opt:
             raise ValueError("batch and bucket disagree on the tuple option")
         if ds is not None:   # (a triples or sparse bucket does not read the dataset's tuple option)

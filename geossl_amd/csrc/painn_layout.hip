@@ -21,6 +21,7 @@
 // geossl_painn_edge_layout_dyn is the same launch with the edge count E read from device memory (a masked batch of a
 // device-resident dataset: its surviving edges are counted on the device, gather.hip); the outputs hold E_cap edges.
 #include "common.h"
+#include "edge_search.h"
 #include "geossl_hip.h"
 
 using namespace geossl;
@@ -47,47 +48,6 @@ struct PainnLayoutArgs {
   int32_t* status;        // set to 1 on an edge that leaves its molecule / a molecule above PL_MAXN atoms
   const int32_t* dyn_E;   // the `_dyn` entry point: the edge count in device memory (E above: the capacity it is clamped to)
 };
-
-// first e in [0, E) with src[e] >= key (src non-decreasing by molecule), for TWO keys at once, by all 256 threads of the
-// block (the two searches share their rounds: the probes of a round are in flight together)
-__device__ __forceinline__ void block_lower_bound2(const int64_t* __restrict__ src, int E, int64_t key0, int64_t key1,
-                                                   int& out0, int& out1) {
-  int lo[2] = {0, 0}, hi[2] = {E, E};
-  bool done[2] = {E == 0, E == 0};
-  const int64_t key[2] = {key0, key1};
-  while (!(done[0] && done[1])) {
-    int step[2], p[2];
-    bool below[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int len = hi[q] - lo[q];
-      step[q] = (len + 255) / 256;
-      p[q] = lo[q] + (int)threadIdx.x * step[q];
-      below[q] = !done[q] && p[q] < hi[q] && src[p[q]] < key[q];
-    }
-    const int c0 = __syncthreads_count(below[0] ? 1 : 0);
-    const int c1 = __syncthreads_count(below[1] ? 1 : 0);
-    const int c[2] = {c0, c1};
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      if (done[q]) continue;
-      if (c[q] == 0) {
-        hi[q] = lo[q];
-        done[q] = true;
-      } else if (step[q] == 1) {
-        lo[q] = hi[q] = lo[q] + c[q];
-        done[q] = true;
-      } else {
-        const int nlo = lo[q] + (c[q] - 1) * step[q] + 1, nhi = min(hi[q], lo[q] + c[q] * step[q]);
-        lo[q] = nlo;
-        hi[q] = nhi;
-        if (lo[q] >= hi[q]) done[q] = true;
-      }
-    }
-  }
-  out0 = lo[0];
-  out1 = lo[1];
-}
 
 // DYN: the edge count is read from device memory (a masked batch: the survivors are counted on the device) - a value
 // uniform over the grid, clamped to [0, A.E] (the capacity of the outputs) with the status word set when it was not

@@ -69,7 +69,10 @@ def _is_handle(batch):
 
 def _check_handle(batch, model_3d):
     if model_3d == "painn" and _is_handle(batch):
-        raise ValueError("a PairedDeviceDataset holds no radius edges: PaiNN pairs are collated by DataLoaderLEP")
+        ds = getattr(batch._dataset, "structures", batch._dataset)
+        if ds.edges is None:
+            raise ValueError("this PairedDeviceDataset holds no radius edges: build it with radius=..., or collate "
+                             "PaiNN pairs with DataLoaderLEP")
 
 
 def _fused_batch_ok(batch):
@@ -237,7 +240,7 @@ def do_LEP(args, batch, model, graph_pred_linear, criterion=None, graph=None):
     for a stock mean BCEWithLogitsLoss, graph_pred_linear = Linear(2F, 1) with a bias, an unscaled backbone with a
     mean / add readout at F = 32 / 64 / 128, and CUDA batches of B >= 2 pairs with one label per pair; anything else runs
     the reference's ATen lines (two passes) - at B = 1 they raise ValueError, as the reference does.  batch: a collated
-    ``BatchLEP`` or a ``DeviceLoader`` pair handle (``PairedBatch``; SchNet).  graph: replay HIP graphs of forward +
+    ``BatchLEP`` or a ``DeviceLoader`` pair handle (``PairedBatch``; PaiNN: of a dataset built with ``radius=``).  graph: replay HIP graphs of forward +
     backward (default: ``args.step_graph`` if present, else on unless GEOSSL_NO_STEP_GRAPH is set): the sparse bucket
     graph of ``LEPTrainer``'s routing where that serves the batch, else a graph of its own at the second sighting of its
     index tensors."""
@@ -360,9 +363,11 @@ class LEPTrainer(StepTrainer):
     the graph.  ``graph_mode="auto"``: SchNet batches with a sparse layout (a structure of either side above 255 atoms, up
     to 1024; or GEOSSL_SPARSE_PAIRS=1) at width 128 share ONE sparse capacity-bucket graph of 2B structures per batch
     size - the pair handles of a ``DeviceLoader`` over a ``PairedDeviceDataset`` by default, collated ``BatchLEP``
-    batches with GEOSSL_SPARSE_BUCKETS=1 (``=0``: neither); anything else - all structures <= 255 atoms, PaiNN, other
-    widths - one graph per structure of the fused batch, from its second sighting on.  ``step`` takes a collated
-    ``BatchLEP`` or a pair handle (SchNet; a handle holds no radius edges)."""
+    batches with GEOSSL_SPARSE_BUCKETS=1 (``=0``: neither); PaiNN batches the same way under
+    GEOSSL_PAINN_SPARSE_BUCKETS (pair handles of a ``PairedDeviceDataset(..., radius=r)``, collated batches with their
+    ``radius_edge_index_*``); anything else - all structures <= 255 atoms, other widths - one graph per structure of the
+    fused batch, from its second sighting on.  ``step`` takes a collated ``BatchLEP`` or a pair handle (PaiNN: of a
+    dataset built with ``radius=``)."""
 
     def __init__(self, model, graph_pred_linear, lr=5e-4, weight_decay=0.0, model_3d="schnet", use_graph=False,
                  max_graphs=256, graph_mode="auto"):

@@ -68,6 +68,45 @@ def radius_graph(pos, r, batch=None, loop=False, max_num_neighbors=32, layout=No
     return (edge_index, weight) if return_weight else edge_index
 
 
+def painn_incidence_layout(edge_index, mol_ptr, N, B, max_n, out=None, status=None, dyn_E=None, dyn_N=None):
+    """Both incidence lists of a collated one-view ``radius_edge_index`` (what layout.EdgeLayout.inc holds) in one launch
+    (geossl_painn_incidence_layout), structures of up to SPARSE_MAX_N atoms -> (iptr_i int64 [N + 1], ilist_i int32 [E],
+    iptr_j, ilist_j, status int32 [1]).  `max_n`: the largest structure, a host integer.  `out` / `status`: buffers to
+    write into (a bucket's, at capacity: `edge_index` then has E_cap columns and N is the atom capacity) with the real
+    counts in device memory (`dyn_E`, `dyn_N`: int32 tensors).  No allocation with `out` and `status` given, no read-back:
+    the status word (an edge that leaves its structure, a list not grouped by structure) is the caller's to read."""
+    _lib.require_cuda(edge_index, mol_ptr)
+    if edge_index.dtype != torch.long or edge_index.dim() != 2 or edge_index.size(0) != 2:
+        raise ValueError("radius_edge_index must be int64 [2, E]")
+    if mol_ptr.dtype != torch.int32 or mol_ptr.numel() != B + 1:
+        raise ValueError("mol_ptr must be int32 [B + 1]")
+    if max_n > SPARSE_MAX_N:
+        raise ValueError("the incidence lists take structures of at most %d atoms (the largest here has %d)"
+                         % (SPARSE_MAX_N, max_n))
+    if (dyn_E is None) != (dyn_N is None):
+        raise ValueError("dyn_E and dyn_N come together")
+    E, dev = int(edge_index.size(1)), edge_index.device
+    r0, r1 = edge_index[0], edge_index[1]
+    if not (r0.is_contiguous() and r1.is_contiguous()):
+        raise ValueError("radius_edge_index must have contiguous rows")
+    if out is None:
+        out = (torch.empty(N + 1, dtype=torch.int64, device=dev), torch.empty(max(E, 1), dtype=torch.int32, device=dev),
+               torch.empty(N + 1, dtype=torch.int64, device=dev), torch.empty(max(E, 1), dtype=torch.int32, device=dev))
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    iptr_i, ilist_i, iptr_j, ilist_j = out
+    if iptr_i.numel() < N + 1 or iptr_j.numel() < N + 1 or ilist_i.numel() < E or ilist_j.numel() < E:
+        raise ValueError("incidence buffers are smaller than (N + 1, E)")
+    tail = (ptr(iptr_i), ptr(ilist_i), ptr(iptr_j), ptr(ilist_j), ptr(status))
+    if dyn_E is not None:
+        call("geossl_painn_incidence_layout_dyn", ptr(r0), ptr(r1), E, ptr(dyn_E), ptr(mol_ptr), N, B, max(int(max_n), 1),
+             *tail, ptr(dyn_N), None, stream())
+    else:
+        call("geossl_painn_incidence_layout", ptr(r0), ptr(r1), E, ptr(mol_ptr), N, B, max(int(max_n), 1), *tail, None,
+             stream())
+    return iptr_i, ilist_i, iptr_j, ilist_j, status
+
+
 def pair_geometry(pos, layout, cutoff, max_num_neighbors=32, mol_live=None):
     """Radius graph in pair-slot form: (pair_d [P], pair_c [P], pair_flag [P] u8).  mol_live (int32 [B], optional)
     receives the number of slots with an edge per molecule (what `live_pairs` starts from)."""

@@ -415,6 +415,8 @@ class StepGraphs:
       one-view SchNet step that reads no pair tuples (``pair_tuples=False``: Supervised, and LEP with its 2B structures
       [active | inactive]): one graph per number of structures in a sparse bucket (``bucket.SPARSE``) - by default the handles of a DeviceLoader, with
       ``GEOSSL_SPARSE_BUCKETS=1`` collated batches too (``=0``: neither; such a batch is served as the first entry says);
+      a PaiNN step of that kind whose batch brings radius edges on the device (a dataset built with ``radius=``, or a
+      collated ``radius_edge_index``) takes the same bucket with an edges part, under ``GEOSSL_PAINN_SPARSE_BUCKETS``;
     * every other SchNet batch - ragged molecules in shuffled order, the reference's loader (pretrain_GeoSSL.py:301) - one
       graph per (molecules in the batch, tuple option) at a CAPACITY (``geossl_amd/bucket.py``): the graph's kernels read
       the batch's real atom / pair-slot / super-edge counts and every index structure from device memory, so ONE graph

@@ -285,8 +285,9 @@ class SupervisedTrainer(StepTrainer):
     without a recapture.  ``use_graph=True``: forward + backward are captured into HIP graphs and replayed (ragged SchNet /
     PaiNN batches and DeviceLoader handles share one ONE-view capacity-bucket graph per batch size at width 128 - SchNet
     handles with structures of 256 to 1024 atoms, LBA's pockets, through the sparse bucket of geossl_amd/bucket.py, and
-    collated batches of such structures with GEOSSL_SPARSE_BUCKETS=1; anything else one graph per structure); the target
-    column is a static input of the graph."""
+    collated batches of such structures with GEOSSL_SPARSE_BUCKETS=1; PaiNN handles of a dataset built with ``radius=``
+    likewise, collated PaiNN batches with GEOSSL_PAINN_SPARSE_BUCKETS=1; anything else one graph per structure); the
+    target column is a static input of the graph."""
 
     def __init__(self, model, graph_pred_linear, TRAIN_mean, TRAIN_std, task_id=6, loss="mae", lr=5e-4,
                  weight_decay=0.0, model_3d="schnet", use_graph=False, max_graphs=256, graph_mode="auto"):

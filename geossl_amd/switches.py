@@ -60,6 +60,26 @@ def sparse_buckets(handle):
     return True if v == "1" else bool(handle)
 
 
+# What the unset GEOSSL_PAINN_SPARSE_BUCKETS means for the handles of a DeviceLoader: the outcome of the measurement in
+# profiles/painn_bucket_bench.json by the rule stated there.
+PAINN_SPARSE_BUCKETS_DEFAULT = True
+
+
+def painn_sparse_buckets(handle):
+    """``GEOSSL_PAINN_SPARSE_BUCKETS``: PaiNN batches of a step that reads no pair tuples (Supervised, LEP) with a
+    structure above 255 atoms (or ``GEOSSL_SPARSE_PAIRS=1``) and radius edges on the device replay one capacity-bucket
+    graph per batch size (``bucket.SPARSE`` with an edges part; the atom-tile kernels under a device-side atom count).
+    ``1``: handles and collated batches; ``0``: neither - eager launches, a per-structure graph for a batch object that
+    comes back.  Unset: handles do (``PAINN_SPARSE_BUCKETS_DEFAULT``: on shuffled pockets their step through the bucket is
+    25 - 39 % shorter than the fastest route before it), collated batches do not (opt-in: their step
+    still pays the host's collation and upload).
+    ``GEOSSL_SPARSE_BUCKETS`` is SchNet's switch and does not open this bucket."""
+    v = env("GEOSSL_PAINN_SPARSE_BUCKETS")
+    if v == "0":
+        return False
+    return True if v == "1" else bool(handle) and PAINN_SPARSE_BUCKETS_DEFAULT
+
+
 # What the unset GEOSSL_PAINN_TILE means for a layout with a structure above 255 atoms: the outcome of the measurement in
 # profiles/painn_tile_bench.json by the rule stated there (DESIGN section 5).
 PAINN_TILE_DEFAULT = True

@@ -716,6 +716,36 @@ int geossl_painn_interaction_bwd_tile(const float* dq_out, const float* dmu_out,
                                       const int32_t* dyn_nlist, int F, int R, float* dxc, float* dmu_in, float* dWf,
                                       float* dbf, float* workspace, int accumulate, hipStream_t stream);
 
+/* ---- Incidence lists of a collated edge list, structures of up to 1024 atoms (painn_inc.hip) -------------------------
+ * What the atom-tile kernels above read as inc_ptr / inc_idx, for both sides, in ONE launch whose grid depends on
+ * (N, B, max_n) alone - what layout.EdgeLayout builds with five launches, two torch cumsums and a read-back per batch
+ * object.
+ * From the one-view edge list (rows src_i = radius_edge_index[0], src_j = [1], E edges grouped by structure in batch
+ * order, both ends in one structure) and the structure CSR (mol_ptr [B + 1], N atoms): iptr_i [N + 1] / ilist_i [E] =
+ * the edges by src_i, iptr_j / ilist_j = by src_j, an atom's edges in ascending edge order.  No two-view copies, no
+ * group layout.  max_n: the largest structure as a HOST integer (1 .. GEOSSL_PAINN_INC_MAX_N; anything else, E or N
+ * above INT_MAX: hipErrorInvalidValue) - the host cannot see mol_ptr, so it sizes the grid by max_n and refuses by it;
+ * a structure that has more atoms all the same gets no edges and sets *status.
+ * *status is set to 1 (never reset) on an edge that leaves its structure, on a list that is not grouped by structure
+ * in batch order and on a mol_ptr that does not end at N.  Such edges are left out; the lists are then not to be used
+ * (the slots left free hold an edge id of the same structure, so a kernel queued before the status is read stays inside
+ * the edge arrays).  Integer work only, bit-reproducible.
+ * geossl_painn_incidence_layout_dyn: the namesake with both counts read from device memory, outputs sized for
+ *   (E_cap, N_cap): atoms [*dyn_N, N_cap] get iptr = *dyn_E (empty lists), no list entry at or beyond *dyn_E is
+ *   written; a count outside [0, capacity] is clamped into it and sets *status.  Given the same counts through memory
+ *   it writes what the by-value entry writes, bit for bit.
+ * `workspace`: geossl_painn_incidence_layout_workspace_bytes(E_cap, N_cap, B) bytes - 0 with the present one-launch
+ *   decomposition (NULL is accepted).                                                                                  */
+#define GEOSSL_PAINN_INC_MAX_N 1024
+int64_t geossl_painn_incidence_layout_workspace_bytes(int64_t E_cap, int64_t N_cap, int64_t B);
+int geossl_painn_incidence_layout(const int64_t* src_i, const int64_t* src_j, int64_t E, const int32_t* mol_ptr,
+                                  int64_t N, int64_t B, int max_n, int64_t* iptr_i, int32_t* ilist_i, int64_t* iptr_j,
+                                  int32_t* ilist_j, int32_t* status, void* workspace, hipStream_t stream);
+int geossl_painn_incidence_layout_dyn(const int64_t* src_i, const int64_t* src_j, int64_t E_cap, const int32_t* dyn_E,
+                                      const int32_t* mol_ptr, int64_t N_cap, int64_t B, int max_n, int64_t* iptr_i,
+                                      int32_t* ilist_i, int64_t* iptr_j, int32_t* ilist_j, int32_t* status,
+                                      const int32_t* dyn_N, void* workspace, hipStream_t stream);
+
 /* ---- Second-order route (training on forces): the primitives of geossl_amd/tape.py that are not dense products --------
  * Replaces, on the route that differentiates a force again (examples/finetune_md17.py:46-54: pred_force =
  * -grad(E, pos, create_graph=True); loss.backward()), the ATen element-wise / index kernels autograd would launch for
