@@ -6,12 +6,9 @@ edge geometry / radial basis / cutoff, the filter-weighted message sum per targe
 edge from the 20 radial values, never stored), the element-wise parts of the mixing block, and the Dense layers
 on the MFMA row/column GEMMs — forward and backward, as one autograd node.  CUDA tensors only.
 """
-import ctypes as C
-import os
 from typing import Callable, Optional
 
 import torch
-from ...switches import env as _env
 import torch.nn as nn
 import torch.nn.functional as F
 from torch.nn.init import xavier_uniform_, zeros_
@@ -19,6 +16,7 @@ from torch.nn.init import xavier_uniform_, zeros_
 from ... import _lib, ops
 from ..._lib import call, ptr, stream
 from ...layout import get_edge_layout, get_layout
+from ...switches import env as _env
 
 
 class Dense(nn.Linear):
@@ -198,10 +196,6 @@ class PaiNN(nn.Module):
         return h
 
 
-def _split3(t, F_):
-    return [t[:, c * F_:(c + 1) * F_] for c in range(3)]
-
-
 class _PaiNNTapeCore(torch.autograd.Function):
     """painn.py:230-255 for the configurations the fused kernels do not take (any n_atom_basis / n_rbf, shared_filters,
     shared_interactions: painn.py:125-142,178-202,242-243): the backbone restated on the library's reverse-mode tape
@@ -234,30 +228,102 @@ class _PaiNNTapeCore(torch.autograd.Function):
         return (None, dpos, None, None) + tuple(grads)
 
 
+# The Dense layers of a block as F x F blocks (3F outputs = three, a 2F contraction = two), NB per block in this order:
+NB = 11
+CTX0 = 0     # interatomic context net, Dense(F, F, silu)
+CTX1 = 1     # ... its Dense(F, 3F): the three output thirds (1, 2, 3)
+MUMIX = 4    # mu_channel_mix, Dense(F, 2F): the two output halves (4, 5)
+INTRA0 = 6   # intra-atomic context net, Dense(2F, F, silu): the two input halves (6, 7)
+INTRA1 = 8   # ... its Dense(F, 3F): the three output thirds (8, 9, 10)
+
+
+def _filter_rows(t, l, F_):
+    """block l's 3F rows of the filter network's weight, bias or their gradients"""
+    return t[l * 3 * F_:(l + 1) * 3 * F_]
+
+
+def _unpack(ps, L):
+    """A flat list in PaiNN._params() order (the parameters, or their gradients) -> (embedding, filter weight, filter
+    bias, inter[l] = (c0w, c0b, c1w, c1b), mix[l] = (i0w, i0b, i1w, i1b, mw))."""
+    return (ps[0], ps[1], ps[2], [ps[3 + 4 * l: 7 + 4 * l] for l in range(L)],
+            [ps[3 + 4 * L + 5 * l: 8 + 4 * L + 5 * l] for l in range(L)])
+
+
+def _weight_blocks(inter, mix):
+    """The NB * L weight blocks, in place (views of the parameters)."""
+    blocks = []
+    for (c0w, _, c1w, _), (i0w, _, i1w, _, mw) in zip(inter, mix):
+        blocks += [c0w, *c1w.chunk(3), *mw.chunk(2), *i0w.chunk(2, dim=1), *i1w.chunk(3)]
+    return blocks
+
+
+class _RowGemms:
+    """The row GEMMs of one pass over the weight blocks: launches of the chained row kernel on the operand images `img`
+    (weights as fragments in registers, no per-launch weight formatting; one launch for several blocks at F = 128, else
+    one each), or - `img` None - one geossl_linear per block.  The rows are the atoms' (N) or the vector features' viewed
+    as [3 N, F]: a capacity bucket's launch is told where the real count of its kind lives (dN / dN3)."""
+
+    def __init__(self, blocks, img, transB, F_, N, dN, dN3):
+        self.blocks, self.img, self.transB, self.one_each = blocks, img, transB, img is None or F_ != 128
+        self.N, self.dN, self.dN3 = N, dN, dN3
+
+    def one(self, x, k, bias=None, res=None, out=None):
+        if self.img is None:
+            return ops.linear(x, self.blocks[k].contiguous(), bias=bias, res=res, transB=self.transB, out=out)
+        return ops.linear_chain(x, [dict(image=self.img[k], bias=bias, res=res, out=out)],
+                                dyn_rows=self.dN if x.size(0) == self.N else self.dN3)[0]
+
+    def fan(self, x, ks, biases, outs):
+        """several blocks of one wide Dense applied to the same rows"""
+        if self.one_each:
+            for k, b_, o_ in zip(ks, biases, outs):
+                self.one(x, k, bias=b_, out=o_)
+            return
+        ops.linear_chain(x, [dict(image=self.img[k], bias=b_, out=o_, same_input=(n_ > 0))
+                             for n_, (k, b_, o_) in enumerate(zip(ks, biases, outs))],
+                         dyn_rows=self.dN if x.size(0) == self.N else self.dN3)
+
+    def sum(self, xs, ks, bias=None, res=None):
+        """sum_c xs_c @ block_c (+ bias) (+ res): the F-wide passes of a contraction over a wide input (the split kernel
+        holds one K <= 128 weight image in LDS: a pass adds onto the one before it)"""
+        if self.one_each:
+            acc_ = self.one(xs[0], ks[0], bias=bias, res=res)
+            for x_, k_ in zip(xs[1:], ks[1:]):
+                self.one(x_, k_, res=acc_, out=acc_)
+            return acc_
+        stages = [dict(image=self.img[k_], store=False) for k_ in ks]
+        stages[0]["bias"] = bias
+        for sd, x_ in zip(stages[1:], xs[1:]):
+            sd.update(x=x_, add_prev=True)                   # (the stage brings its own input)
+        stages[-1].update(store=True, res=res)               # (the residual belongs to the stage that stores)
+        return ops.linear_chain(xs[0], stages, dyn_rows=self.dN if xs[0].size(0) == self.N else self.dN3)[-1]
+
+
 class _PaiNNCore(torch.autograd.Function):
-    """(atomic numbers, positions, radius_edge_index) -> scalar atom features q (painn.py:230-255)."""
+    """(atomic numbers, positions, radius_edge_index) -> scalar atom features q (painn.py:230-255).  Which interaction
+    kernels run (ops.PaiNNRoute) and what the GEOSSL_PAINN_* switches say is decided in the forward and kept on ctx: the
+    backward asks ctx."""
 
     @staticmethod
     def forward(ctx, z, pos, el, cfg, *params):
         F_, L, R = cfg["F"], cfg["L"], cfg["R"]
-        dev, N, E = pos.device, pos.size(0), el.E
-        st = stream()
-        want_params = any(ctx.needs_input_grad[4:])
-        training = want_params or ctx.needs_input_grad[1]  # positions: forces (finetune_md17.py:46)
+        dev, N, E, st = pos.device, pos.size(0), el.E, stream()
+        want_pos, want_params = ctx.needs_input_grad[1], any(ctx.needs_input_grad[4:])
+        training = want_params or want_pos  # positions: forces (finetune_md17.py:46)
         ps = [p.detach().contiguous() for p in params]
-        emb_w, fw, fb = ps[0], ps[1], ps[2]
-        inter = [ps[3 + 4 * l: 7 + 4 * l] for l in range(L)]
-        mix = [ps[3 + 4 * L + 5 * l: 8 + 4 * L + 5 * l] for l in range(L)]
+        emb_w, fw, fb, inter, mix = _unpack(ps, L)
         f32 = dict(dtype=torch.float32, device=dev)
+        no_chain, silu_kernels = bool(_env("GEOSSL_PAINN_NO_CHAIN")), bool(_env("GEOSSL_PAINN_SILU_KERNELS"))
         # the structures of a capacity bucket (geossl_amd/bucket.py) carry the device addresses of the batch's real counts:
         # N, E are then capacities and every count-driven launch below is told where the real count lives (rows of the
         # scalar features, rows of the vector features viewed as [3 N, F], edges)
         dyn = getattr(el, "dyn", None)
         dN, dN3, dE = (dyn.n_atoms2, dyn.n_atoms2x3, dyn.n_edges2) if dyn is not None else (None, None, None)
-        if dyn is not None and (ctx.needs_input_grad[1] or F_ != 128 or _env("GEOSSL_PAINN_NO_CHAIN")
-                                or _env("GEOSSL_PAINN_SILU_KERNELS")):
+        if dyn is not None and (want_pos or F_ != 128 or no_chain or silu_kernels):
             raise _lib.GeosslHipError("a capacity-bucket layout serves the F = 128 chain path without position gradients")
-        dirv, fcut, phi = torch.empty(max(E, 1), 3, **f32), torch.empty(max(E, 1), **f32), torch.empty(max(E, 1), R, **f32)
+        route = ops.painn_route(cfg["lay"], el, N, F_, R, cfg["mma"], training, want_pos, call)
+        geom = dirv, fcut, phi = (torch.empty(max(E, 1), 3, **f32), torch.empty(max(E, 1), **f32),
+                                  torch.empty(max(E, 1), R, **f32))
         call("geossl_painn_edge_geom_dyn", ptr(pos), ptr(el.idx_i), ptr(el.idx_j), E, cfg["cutoff"], ptr(cfg["offsets"]),
              ptr(cfg["widths"]), R, ptr(dirv), ptr(fcut), ptr(phi), dE, st)
         q = torch.empty(N, F_, **f32)
@@ -265,136 +331,52 @@ class _PaiNNCore(torch.autograd.Function):
              ptr(cfg["status"].word), dN, st)                               # painn.py:247 (row 0 is the zero padding row)
         if cfg["debug"]:
             cfg["status"].check()
-        inc_ptr, inc_idx = el.inc["i"]
         saved = []
-        # Every Dense layer here is a set of F x F row GEMMs (3F outputs = three, a 2F contraction = two with the
-        # residual operand): they run as one-stage launches of the chained row kernel (weights as fragments in
-        # registers, no per-launch weight formatting), on operand images built by one launch per pass.
-        blocks = []
+        blocks = _weight_blocks(inter, mix)
+        img = None if no_chain else ops.prepare_chain(blocks, transB=True)   # operand images: one launch per pass
+        rows = _RowGemms(blocks, img, True, F_, N, dN, dN3)
+        # silu inside the chained launches (F = 128): GEOSSL_PAINN_SILU_KERNELS keeps the separate silu launches (A/B runs)
+        fused = img is not None and F_ == 128 and not silu_kernels
+        # mu starts as zeros (:249).  Where one forward kernel covers every atom the first interaction is told so (NULL), not
+        # handed 3 N F zeros to stage and gather: its mu rows, the dmumu * mu_j products and - in the backward - the whole
+        # dmumu third of the filter are exact zeros (csrc: k_painn_fwd_mma<R, true>, k_painn_interaction_bwd_mol<R, true>)
+        mu = None if route.mu_is_zero else torch.zeros(N, 3, F_, **f32)
         for l in range(L):
             c0w, c0b, c1w, c1b = inter[l]
             i0w, i0b, i1w, i1b, mw = mix[l]
-            blocks += [c0w] + [c1w[c * F_:(c + 1) * F_] for c in range(3)] + [mw[:F_], mw[F_:]] + \
-                      [i0w[:, :F_], i0w[:, F_:]] + [i1w[c * F_:(c + 1) * F_] for c in range(3)]
-        img = ops.prepare_chain(blocks, transB=True) if not _env("GEOSSL_PAINN_NO_CHAIN") else None
-        NB = 11  # blocks per layer, in the order above
-        # silu inside the chained launches (F = 128): GEOSSL_PAINN_SILU_KERNELS keeps the separate silu launches (A/B runs)
-        fused = img is not None and F_ == 128 and not _env("GEOSSL_PAINN_SILU_KERNELS")
-
-        def lin_fan(x, ks, biases, outs):
-            """several F x F blocks of one wide Dense applied to the same rows: one launch (F = 128), else one each"""
-            if img is None or F_ != 128:
-                for k, b_, o_ in zip(ks, biases, outs):
-                    lin(x, None, k, bias=b_, out=o_)
-                return
-            ops.linear_chain(x, [dict(image=img[k], bias=b_, out=o_, same_input=(n_ > 0))
-                                 for n_, (k, b_, o_) in enumerate(zip(ks, biases, outs))],
-                             dyn_rows=dN if x.size(0) == N else dN3)
-
-        def lin(x, w, k, bias=None, res=None, out=None):
-            if img is None:
-                return ops.linear(x, blocks[k].contiguous(), bias=bias, res=res, out=out)
-            return ops.linear_chain(x, [dict(image=img[k], bias=bias, res=res, out=out)],
-                                    dyn_rows=dN if x.size(0) == N else dN3)[0]
-
-        # Which interaction kernel: the matrix-pipe form stages a molecule's rows in LDS (at most `cap_f` atoms).  A
-        # layout with larger molecules (Molecule3D with hydrogens) keeps that form for the molecules that fit and covers
-        # the atoms of the others with the per-atom kernel (`big_f`: their list) - one oversized molecule does not send
-        # the whole batch to the slower kernels.  Without host-side molecule sizes there is no list: one form for all.
-        lay = cfg["lay"]
-        lib = _lib.load()
-        use_mma = bool(cfg["mma"]) and E > 0
-        big_f, stage_f = None, lay.max_n      # the atoms left to the per-atom kernel; the molecule size the LDS rows are for
-        if use_mma:
-            from ...layout import painn_stage_caps
-            hard, split_cap = int(lib.geossl_painn_stage_cap(0, F_, R)), painn_stage_caps(F_, R)[0]
-            if 0 < split_cap < lay.max_n:
-                big_f = lay.big_atoms(split_cap)
-                if big_f is not None:
-                    stage_f = split_cap
-            if big_f is None and lay.max_n > hard:
-                use_mma = False
-        # mu starts as zeros (:249).  When the matrix-pipe kernel covers every atom, the first interaction is told so (NULL)
-        # instead of being handed 3 N F zeros to stage and gather: its mu rows, the dmumu * mu_j products and - in the
-        # backward - the whole dmumu third of the filter are exact zeros (csrc: k_painn_fwd_mma<R, true>,
-        # k_painn_interaction_bwd_mol<R, true>).  Forces (edge gradients read mu) and GEOSSL_PAINN_NO_MU_ZERO keep the tensor.
-        mu_is_zero = (use_mma and big_f is None and not ctx.needs_input_grad[1] and R in (8, 16, 20)
-                      and not _env("GEOSSL_PAINN_NO_MU_ZERO"))
-        # Structures of hundreds of atoms fit neither staged form: the atom-tile kernels (painn_tile.hip) then take ALL
-        # atoms in one launch per block - no staged launch, no lists (layout.painn_tile_route; GEOSSL_PAINN_TILE).
-        from ...layout import painn_tile_route
-        use_tile = bool(cfg["mma"]) and painn_tile_route(lay, F_, R, E, dyn)
-        if dyn is not None and getattr(lay, "sparse", False) and not use_tile:
-            raise _lib.GeosslHipError("a sparse capacity-bucket layout serves the atom-tile kernels only (F = 128, 8 / 16 / "
-                                      "20 radial functions, without GEOSSL_PAINN_VECTOR)")
-        if use_tile:
-            mu_is_zero = not ctx.needs_input_grad[1] and not _env("GEOSSL_PAINN_NO_MU_ZERO")
-        mu = None if mu_is_zero else torch.zeros(N, 3, F_, **f32)            # :249
-        for l in range(L):
-            c0w, c0b, c1w, c1b = inter[l]
             k0 = NB * l
             xc = torch.empty(N, 3 * F_, **f32)
             if fused:  # Dense(F, F, silu) and Dense(F, 3F) (:27-30,53) in one launch: u and silu(u) are both kept
                 u, s = torch.empty(N, F_, **f32), torch.empty(N, F_, **f32)
-                ops.linear_chain(q, [dict(image=img[k0], bias=c0b, out=u, out_act=s, flags=_lib.EPI_SILU)] +
-                                 [dict(image=img[k0 + 1 + c], bias=c1b[c * F_:(c + 1) * F_], out=o_, same_input=(c > 0))
-                                  for c, o_ in enumerate(_split3(xc, F_))], dyn_rows=dN)
+                ops.linear_chain(q, [dict(image=img[k0 + CTX0], bias=c0b, out=u, out_act=s, flags=_lib.EPI_SILU)] +
+                                 [dict(image=img[k0 + CTX1 + c], bias=b_, out=o_, same_input=(c > 0))
+                                  for c, (b_, o_) in enumerate(zip(c1b.chunk(3), xc.chunk(3, dim=1)))], dyn_rows=dN)
             else:
-                u = lin(q, c0w, k0, bias=c0b)                                # Dense(F, F, silu)      :27-30,53
+                u = rows.one(q, k0 + CTX0, bias=c0b)                         # Dense(F, F, silu)      :27-30,53
                 s = torch.empty_like(u)
                 call("geossl_silu_fwd", ptr(u), u.numel(), ptr(s), st)
-                lin_fan(s, [k0 + 1 + c for c in range(3)], [c1b[c * F_:(c + 1) * F_] for c in range(3)],
-                        _split3(xc, F_))                                     # Dense(F, 3F)
+                rows.fan(s, range(k0 + CTX1, k0 + CTX1 + 3), c1b.chunk(3), xc.chunk(3, dim=1))   # Dense(F, 3F)
             q2, mu2 = torch.empty_like(q), torch.empty(N, 3, F_, **f32)
-            # one block per molecule: the rows its edges read are staged in LDS once
-            if use_tile:  # atom tiles: the filter on the matrix pipe, source rows from L2
-                call("geossl_painn_interaction_fwd_tile", ptr(q), ptr(mu), ptr(xc), ptr(el.idx_j), ptr(inc_ptr),
-                     ptr(inc_idx), ptr(phi), ptr(fcut), ptr(dirv), ptr(fw[l * 3 * F_:(l + 1) * 3 * F_]),
-                     ptr(fb[l * 3 * F_:(l + 1) * 3 * F_]), None, N, dN, F_, R, ptr(q2), ptr(mu2), st)   # :54-64
-                # (a sparse bucket: N is the atom capacity, the grid's; atoms 0 .. *dN - 1 are real)
-            elif use_mma:  # filter on the matrix pipe (painn_mma.hip); LDS: 3.5 KB per atom + 3 KB
-                row_edge, grp_atom, _, mol_grp = el.groups("i", lay.mol_ptr)
-                call("geossl_painn_interaction_fwd_mma_dyn", ptr(q), ptr(mu), ptr(xc), ptr(el.idx_j), ptr(row_edge),
-                     ptr(grp_atom), ptr(mol_grp), ptr(phi), ptr(fcut), ptr(dirv), ptr(fw[l * 3 * F_:(l + 1) * 3 * F_]),
-                     ptr(fb[l * 3 * F_:(l + 1) * 3 * F_]), ptr(lay.mol_ptr), lay.B, stage_f, N, F_, R, ptr(q2),
-                     ptr(mu2), ptr(getattr(el, "mol_grp_end", None)), st)                 # :54-64
-                if big_f is not None and big_f[1] > 0:   # the atoms of the molecules above the staged rows
-                    call("geossl_painn_interaction_fwd_atoms", ptr(q), ptr(mu), ptr(xc), ptr(el.idx_j), ptr(inc_ptr),
-                         ptr(inc_idx), ptr(phi), ptr(fcut), ptr(dirv), ptr(fw[l * 3 * F_:(l + 1) * 3 * F_]),
-                         ptr(fb[l * 3 * F_:(l + 1) * 3 * F_]), ptr(big_f[0]), big_f[1], big_f[2], F_, R, ptr(q2), ptr(mu2), st)
-            else:
-                call("geossl_painn_interaction_fwd_mol", ptr(q), ptr(mu), ptr(xc), ptr(el.idx_j), ptr(inc_ptr),
-                     ptr(inc_idx), ptr(phi), ptr(fcut), ptr(dirv), ptr(fw[l * 3 * F_:(l + 1) * 3 * F_]),
-                     ptr(fb[l * 3 * F_:(l + 1) * 3 * F_]), ptr(lay.mol_ptr), lay.B, lay.max_n, N, F_, R, ptr(q2), ptr(mu2),
-                     st)                                                        # :54-64
-            i0w, i0b, i1w, i1b, mw = mix[l]
+            route.forward(q, mu, xc, geom, _filter_rows(fw, l, F_), _filter_rows(fb, l, F_), q2, mu2)    # :54-64
             mm = torch.empty(3 * N, 2 * F_, **f32)                           # mu_channel_mix        :100
-            lin_fan(mu2.view(3 * N, F_), [k0 + 4, k0 + 5], [None, None], [mm[:, :F_], mm[:, F_:]])
+            rows.fan(mu2.view(3 * N, F_), [k0 + MUMIX, k0 + MUMIX + 1], [None, None], [mm[:, :F_], mm[:, F_:]])
             cx, dot = torch.empty(N, 2 * F_, **f32), torch.empty(N, F_, **f32)
             call("geossl_painn_mix_pre_fwd_dyn", ptr(q2), ptr(mm), N, F_, cfg["eps"], ptr(cx), ptr(dot), dN, st)  # :101-104
-            # Dense(2F, F, silu) :105 - a contraction over 2F columns is two passes of the F-wide row GEMM (the split
-            # kernel holds one K <= 128 weight image in LDS): the second adds onto the first through the residual operand
             xx = torch.empty(N, 3 * F_, **f32)
-            if fused:  # both F-wide passes of Dense(2F, F, silu), then Dense(F, 3F) on silu of it: one launch
+            if fused:  # both F-wide passes of Dense(2F, F, silu) :105, then Dense(F, 3F) on silu of it: one launch
                 u1, s1 = torch.empty(N, F_, **f32), torch.empty(N, F_, **f32)
-                ops.linear_chain(cx[:, :F_], [dict(image=img[k0 + 6], bias=i0b, store=False),
-                                              dict(image=img[k0 + 7], x=cx[:, F_:], add_prev=True, out=u1, out_act=s1,
-                                                   flags=_lib.EPI_SILU)] +
-                                 [dict(image=img[k0 + 8 + c], bias=i1b[c * F_:(c + 1) * F_], out=o_, same_input=(c > 0))
-                                  for c, o_ in enumerate(_split3(xx, F_))], dyn_rows=dN)
+                ops.linear_chain(cx[:, :F_], [dict(image=img[k0 + INTRA0], bias=i0b, store=False),
+                                              dict(image=img[k0 + INTRA0 + 1], x=cx[:, F_:], add_prev=True, out=u1,
+                                                   out_act=s1, flags=_lib.EPI_SILU)] +
+                                 [dict(image=img[k0 + INTRA1 + c], bias=b_, out=o_, same_input=(c > 0))
+                                  for c, (b_, o_) in enumerate(zip(i1b.chunk(3), xx.chunk(3, dim=1)))], dyn_rows=dN)
             else:
-                if img is not None and F_ == 128:   # both F-wide passes in one launch (the second brings its own input)
-                    u1 = ops.linear_chain(cx[:, :F_], [dict(image=img[k0 + 6], bias=i0b, store=False),
-                                                       dict(image=img[k0 + 7], x=cx[:, F_:], add_prev=True)])[1]
-                else:
-                    u1 = lin(cx[:, :F_], None, k0 + 6, bias=i0b)
-                    lin(cx[:, F_:], None, k0 + 7, res=u1, out=u1)
+                u1 = rows.sum([cx[:, :F_], cx[:, F_:]], [k0 + INTRA0, k0 + INTRA0 + 1], bias=i0b)   # Dense(2F, F, silu) :105
                 s1 = torch.empty_like(u1)
                 call("geossl_silu_fwd", ptr(u1), u1.numel(), ptr(s1), st)
-                lin_fan(s1, [k0 + 8 + c for c in range(3)], [i1b[c * F_:(c + 1) * F_] for c in range(3)],
-                        _split3(xx, F_))                                     # Dense(F, 3F)
+                rows.fan(s1, range(k0 + INTRA1, k0 + INTRA1 + 3), i1b.chunk(3), xx.chunk(3, dim=1))   # Dense(F, 3F)
             # (the representation is q alone, :262-269: the LAST block's mu' is nobody's input and is not formed - NULL)
-            mu_dead = l == L - 1 and not _env("GEOSSL_PAINN_NO_MU_ZERO")
+            mu_dead = l == L - 1 and not route.keep_mu
             q3, mu3 = torch.empty_like(q), (None if mu_dead else torch.empty(N, 3, F_, **f32))
             call("geossl_painn_mix_post_fwd_dyn", ptr(q2), ptr(mu2), ptr(mm), ptr(xx), ptr(dot), N, F_, ptr(q3), ptr(mu3),
                  dN, st)
@@ -403,10 +385,8 @@ class _PaiNNCore(torch.autograd.Function):
             q, mu = q3, mu3
         if training:
             ctx.el, ctx.cfg, ctx.z, ctx.ps, ctx.params = el, cfg, z, ps, params
-            ctx.pos, ctx.want_params = pos, want_params
-            ctx.geom = (dirv, fcut, phi)
-            ctx.saved = saved
-            ctx.use_tile = use_tile
+            ctx.pos, ctx.want_params, ctx.geom, ctx.saved = pos, want_params, geom, saved
+            ctx.route, ctx.chain, ctx.fused = route, img is not None, fused
         return q
 
     @staticmethod
@@ -425,120 +405,63 @@ class _PaiNNCore(torch.autograd.Function):
     @staticmethod
     def fused_backward(ctx, dq, want_pos, want_params, allow_direct):
         """First-order gradients by the fused kernels -> (dpos or None, [one entry per parameter, None = not returned])."""
-        el, cfg, ps = ctx.el, ctx.cfg, ctx.ps
+        el, cfg, ps, route, fused = ctx.el, ctx.cfg, ctx.ps, ctx.route, ctx.fused
         F_, L, R = cfg["F"], cfg["L"], cfg["R"]
-        dirv, fcut, phi = ctx.geom
-        dev, N = dq.device, dq.size(0)
-        st = stream()
+        dirv, fcut, phi = geom = ctx.geom
+        dev, N, E, st = dq.device, dq.size(0), el.E, stream()
         f32 = dict(dtype=torch.float32, device=dev)
         # opt-in (DDMTrainer); otherwise gradients go through autograd
         direct = want_params and allow_direct and _lib.direct_grads_enabled(ctx.params)
         grads = [p.grad for p in ctx.params] if direct else [torch.zeros_like(p) for p in ps]
         acc = 1 if direct else 0
-        g_emb, g_fw, g_fb = grads[0], grads[1], grads[2]
-        inter = [ps[3 + 4 * l: 7 + 4 * l] for l in range(L)]
-        mix = [ps[3 + 4 * L + 5 * l: 8 + 4 * L + 5 * l] for l in range(L)]
-        g_inter = [grads[3 + 4 * l: 7 + 4 * l] for l in range(L)]
-        g_mix = [grads[3 + 4 * L + 5 * l: 8 + 4 * L + 5 * l] for l in range(L)]
-        inc_ptr, inc_idx = el.inc["j"]
+        emb_w, fw, fb, inter, mix = _unpack(ps, L)
+        g_emb, g_fw, g_fb, g_inter, g_mix = _unpack(grads, L)
         dyn = getattr(el, "dyn", None)
         dN, dN3 = (dyn.n_atoms2, dyn.n_atoms2x3) if dyn is not None else (None, None)
         if dyn is not None and want_pos:
             raise _lib.GeosslHipError("a capacity-bucket layout serves the step without position gradients")
         dq_cur = dq.contiguous()
         # d(last block's mu') = 0, as NULL: no 3 N F zeros written, read by two kernels and added as a residual
-        dmu_cur = torch.zeros(N, 3, F_, **f32) if _env("GEOSSL_PAINN_NO_MU_ZERO") else None
+        dmu_cur = torch.zeros(N, 3, F_, **f32) if route.keep_mu else None
         groups = {}  # (rows, lda, ldb, ldw) -> list of problems, all with M = N = F
 
-        def add(rows, lda, ldb, ldw, A, Bm, dW, db):
-            groups.setdefault((rows, lda, ldb, ldw), []).append((A, Bm, dW, db))
+        def add(rows_, lda, ldb, ldw, A, Bm, dW, db):
+            groups.setdefault((rows_, lda, ldb, ldw), []).append((A, Bm, dW, db))
 
-        blocks = []
-        for l in range(L):
-            c0w, c0b, c1w, c1b = inter[l]
-            i0w, i0b, i1w, i1b, mw = mix[l]
-            blocks += [c0w] + [c1w[c * F_:(c + 1) * F_] for c in range(3)] + [mw[:F_], mw[F_:]] + \
-                      [i0w[:, :F_], i0w[:, F_:]] + [i1w[c * F_:(c + 1) * F_] for c in range(3)]
-        img = ops.prepare_chain(blocks, transB=False) if not _env("GEOSSL_PAINN_NO_CHAIN") else None
-        NB = 11
-        fused = img is not None and F_ == 128 and not _env("GEOSSL_PAINN_SILU_KERNELS")
-
-        def lin_t(x, w, k, res=None, out=None):  # x @ w (the transposed use of a forward weight block)
-            if img is None:
-                return ops.linear(x, blocks[k].contiguous(), transB=False, res=res, out=out)
-            return ops.linear_chain(x, [dict(image=img[k], res=res, out=out)], dyn_rows=dN if x.size(0) == N else dN3)[0]
-
-        lay = cfg["lay"]
-        def lin_t_sum(xs_list, ks, res=None):
-            """sum_c xs_c @ W_c (+ res): the passes of a contraction over a wide input, one launch at F = 128"""
-            if img is None or F_ != 128:
-                acc_ = res
-                for x_, k_ in zip(xs_list, ks):
-                    acc_ = lin_t(x_, None, k_, res=acc_)
-                return acc_
-            stages = []
-            for n_, (x_, k_) in enumerate(zip(xs_list, ks)):
-                sd = dict(image=img[k_], store=(n_ == len(ks) - 1))
-                if n_ == 0:
-                    sd["res"] = res
-                    if res is not None and len(ks) > 1:
-                        sd["store"] = False
-                else:
-                    sd.update(x=x_, add_prev=True)
-                stages.append(sd)
-            if res is not None and len(ks) > 1:
-                # the residual belongs to the stage that stores: move it there (the row stride must be the output's)
-                stages[0].pop("res")
-                stages[-1]["res"] = res
-            return ops.linear_chain(xs_list[0], stages, dyn_rows=dN if xs_list[0].size(0) == N else dN3)[-1]
-
-        use_tile = bool(getattr(ctx, "use_tile", False))   # the forward's route (atom tiles: painn_tile.hip)
-        if use_tile:
-            nfl = _lib.load().geossl_painn_interaction_bwd_tile_workspace_floats(N, F_, R)
-        else:
-            nfl = _lib.load().geossl_painn_interaction_bwd_mol_workspace_floats(N, lay.B, F_, R)
-        ws = torch.empty(max(int(nfl), 1), **f32)
-        # molecules above the LDS rows of the molecule-staged backward: skipped there, covered by the per-atom kernel
-        from ...layout import painn_stage_caps
-        cap_b = painn_stage_caps(F_, R)[1]
-        big_b = lay.big_atoms(cap_b) if (0 < cap_b < lay.max_n and F_ in (64, 128) and not use_tile) else None
+        blocks = _weight_blocks(inter, mix)   # x @ w: the transposed use of a forward weight block
+        img = ops.prepare_chain(blocks, transB=False) if ctx.chain else None
+        rows = _RowGemms(blocks, img, False, F_, N, dN, dN3)
+        ws = route.workspace(dev)
         keep = []
-        E = el.E
         if want_pos:  # dL/d(phi, fcut, dir) per edge, summed over the blocks (painn_force.hip)
             dphi, dfc, ddir = torch.empty(max(E, 1), R, **f32), torch.empty(max(E, 1), **f32), torch.empty(max(E, 1), 3, **f32)
         for l in reversed(range(L)):
             sv = ctx.saved[l]
-            c0w, c0b, c1w, c1b = inter[l]
-            i0w, i0b, i1w, i1b, mw = mix[l]
             gc0w, gc0b, gc1w, gc1b = g_inter[l]
             gi0w, gi0b, gi1w, gi1b, gmw = g_mix[l]
+            fw_l, fb_l = _filter_rows(fw, l, F_), _filter_rows(fb, l, F_)
             k0 = NB * l
             # ---- mixing block
             dxx, dmm = torch.empty(N, 3 * F_, **f32), torch.empty(3 * N, 2 * F_, **f32)
             call("geossl_painn_mix_post_bwd_dyn", ptr(dq_cur), ptr(dmu_cur), ptr(sv["mm"]), ptr(sv["xx"]), ptr(sv["dot"]), N,
                  F_, ptr(dxx), ptr(dmm), dN, st)
-            for c, xs_ in enumerate(_split3(dxx, F_)):
-                add(N, 3 * F_, F_, F_, xs_, sv["s1"], gi1w[c * F_:(c + 1) * F_], gi1b[c * F_:(c + 1) * F_])
+            x3 = dxx.chunk(3, dim=1)
+            for xs_, gw_, gb_ in zip(x3, gi1w.chunk(3), gi1b.chunk(3)):
+                add(N, 3 * F_, F_, F_, xs_, sv["s1"], gw_, gb_)
             dctx = torch.empty(N, 2 * F_, **f32)                           # [N][2F] = du1 @ i0w
             if fused:  # (sum_c dxx_c W_c) * silu'(u1) = du1, then du1 @ i0w: one launch
                 du1 = torch.empty(N, F_, **f32)
-                x3 = _split3(dxx, F_)
-                ops.linear_chain(x3[0], [dict(image=img[k0 + 8], store=False),
-                                         dict(image=img[k0 + 9], x=x3[1], add_prev=True, store=False),
-                                         dict(image=img[k0 + 10], x=x3[2], add_prev=True, tprev=sv["u1"], out=du1,
+                ops.linear_chain(x3[0], [dict(image=img[k0 + INTRA1], store=False),
+                                         dict(image=img[k0 + INTRA1 + 1], x=x3[1], add_prev=True, store=False),
+                                         dict(image=img[k0 + INTRA1 + 2], x=x3[2], add_prev=True, tprev=sv["u1"], out=du1,
                                               flags=_lib.EPI_MUL_DSILU),
-                                         dict(image=img[k0 + 6], out=dctx[:, :F_]),
-                                         dict(image=img[k0 + 7], out=dctx[:, F_:], same_input=True)], dyn_rows=dN)
+                                         dict(image=img[k0 + INTRA0], out=dctx[:, :F_]),
+                                         dict(image=img[k0 + INTRA0 + 1], out=dctx[:, F_:], same_input=True)], dyn_rows=dN)
             else:
-                ds1 = lin_t_sum(_split3(dxx, F_), [k0 + 8 + c for c in range(3)])
+                ds1 = rows.sum(x3, range(k0 + INTRA1, k0 + INTRA1 + 3))
                 du1 = torch.empty_like(ds1)
                 call("geossl_silu_bwd", ptr(sv["u1"]), ptr(ds1), ds1.numel(), ptr(du1), st)
-                if img is not None and F_ == 128:
-                    ops.linear_chain(du1, [dict(image=img[k0 + 6], out=dctx[:, :F_]),
-                                           dict(image=img[k0 + 7], out=dctx[:, F_:], same_input=True)])
-                else:
-                    for c in range(2):
-                        lin_t(du1, i0w[:, c * F_:(c + 1) * F_], k0 + 6 + c, out=dctx[:, c * F_:(c + 1) * F_])
+                rows.fan(du1, [k0 + INTRA0, k0 + INTRA0 + 1], [None, None], [dctx[:, :F_], dctx[:, F_:]])
             for c in range(2):
                 add(N, F_, 2 * F_, 2 * F_, du1, sv["cx"][:, c * F_:(c + 1) * F_], gi0w[:, c * F_:(c + 1) * F_],
                     gi0b if c == 0 else None)
@@ -546,51 +469,35 @@ class _PaiNNCore(torch.autograd.Function):
             call("geossl_painn_mix_pre_bwd_dyn", ptr(dq_cur), ptr(dctx), ptr(sv["cx"]), ptr(sv["mm"]), N, F_, ptr(dq2),
                  ptr(dmm), dN, st)
             # d mu (after interaction): contraction over the 2F columns of dmm in two F-wide passes
-            dmu2 = lin_t_sum([dmm[:, :F_], dmm[:, F_:]], [k0 + 4, k0 + 5],
-                             res=None if dmu_cur is None else dmu_cur.view(3 * N, F_))
+            dmu2 = rows.sum([dmm[:, :F_], dmm[:, F_:]], [k0 + MUMIX, k0 + MUMIX + 1],
+                            res=None if dmu_cur is None else dmu_cur.view(3 * N, F_))
             for c in range(2):
                 add(3 * N, 2 * F_, F_, F_, dmm[:, c * F_:(c + 1) * F_], sv["mu2"].view(3 * N, F_),
                     gmw[c * F_:(c + 1) * F_], None)
             # ---- interaction block
             if want_pos:
                 call("geossl_painn_edge_grads", ptr(dq2), ptr(dmu2), ptr(sv["mu"]), ptr(sv["xc"]), ptr(el.idx_i),
-                     ptr(el.idx_j), ptr(phi), ptr(fcut), ptr(dirv), ptr(ps[1][l * 3 * F_:(l + 1) * 3 * F_]),
-                     ptr(ps[2][l * 3 * F_:(l + 1) * 3 * F_]), E, F_, R, ptr(dphi), ptr(dfc), ptr(ddir),
-                     0 if l == L - 1 else 1, st)
-            mu_l = sv["mu"]
-            if mu_l is None and big_b is not None:   # (cannot happen with today's stage caps: the forward's is the smaller)
-                mu_l = torch.zeros(N, 3, F_, **f32)
+                     ptr(el.idx_j), ptr(phi), ptr(fcut), ptr(dirv), ptr(fw_l), ptr(fb_l), E, F_, R, ptr(dphi), ptr(dfc),
+                     ptr(ddir), 0 if l == L - 1 else 1, st)
             # (the first interaction's mu is identically zero and its gradient is nobody's input: NULL for both)
-            dxc, dmu_in = torch.empty(N, 3 * F_, **f32), (None if mu_l is None else torch.empty(N, 3, F_, **f32))
-            args = (ptr(dq2), ptr(dmu2), ptr(mu_l), ptr(sv["xc"]), ptr(el.idx_i), ptr(inc_ptr), ptr(inc_idx), ptr(phi),
-                    ptr(fcut), ptr(dirv), ptr(ps[1][l * 3 * F_:(l + 1) * 3 * F_]), ptr(ps[2][l * 3 * F_:(l + 1) * 3 * F_]))
-            outs = (ptr(dxc), ptr(dmu_in), ptr(g_fw[l * 3 * F_:(l + 1) * 3 * F_]), ptr(g_fb[l * 3 * F_:(l + 1) * 3 * F_]),
-                    ptr(ws), acc, st)
-            if use_tile:  # all atoms in one launch (atom_list NULL; a sparse bucket: the real ones, *dN of N)
-                call("geossl_painn_interaction_bwd_tile", *args, None, N, dN, F_, R, *outs)
-            else:
-                call("geossl_painn_interaction_bwd_mol" if big_b is None else "geossl_painn_interaction_bwd_mol_skip",
-                     *args, ptr(lay.mol_ptr), lay.B, lay.max_n, N, F_, R, *outs)
-            if big_b is not None and big_b[1] > 0:
-                call("geossl_painn_interaction_bwd_atoms", ptr(dq2), ptr(dmu2), ptr(mu_l), ptr(sv["xc"]), ptr(el.idx_i),
-                     ptr(inc_ptr), ptr(inc_idx), ptr(phi), ptr(fcut), ptr(dirv), ptr(ps[1][l * 3 * F_:(l + 1) * 3 * F_]),
-                     ptr(ps[2][l * 3 * F_:(l + 1) * 3 * F_]), ptr(big_b[0]), big_b[1], big_b[2], F_, R, ptr(dxc), ptr(dmu_in),
-                     ptr(g_fw[l * 3 * F_:(l + 1) * 3 * F_]), ptr(g_fb[l * 3 * F_:(l + 1) * 3 * F_]), ptr(ws), 1, st)
-            for c, xs_ in enumerate(_split3(dxc, F_)):
-                add(N, 3 * F_, F_, F_, xs_, sv["s"], gc1w[c * F_:(c + 1) * F_], gc1b[c * F_:(c + 1) * F_])
+            dxc, dmu_in = torch.empty(N, 3 * F_, **f32), (None if sv["mu"] is None else torch.empty(N, 3, F_, **f32))
+            route.backward(dq2, dmu2, sv["mu"], sv["xc"], geom, fw_l, fb_l, dxc, dmu_in, _filter_rows(g_fw, l, F_),
+                           _filter_rows(g_fb, l, F_), ws, acc)
+            x3 = dxc.chunk(3, dim=1)
+            for xs_, gw_, gb_ in zip(x3, gc1w.chunk(3), gc1b.chunk(3)):
+                add(N, 3 * F_, F_, F_, xs_, sv["s"], gw_, gb_)
             if fused:  # (sum_c dxc_c W_c) * silu'(u) = du, then du @ c0w + dq2 (residual q2 = q + dq): one launch
                 du, dq_in = torch.empty(N, F_, **f32), torch.empty(N, F_, **f32)
-                x3 = _split3(dxc, F_)
-                ops.linear_chain(x3[0], [dict(image=img[k0 + 1], store=False),
-                                         dict(image=img[k0 + 2], x=x3[1], add_prev=True, store=False),
-                                         dict(image=img[k0 + 3], x=x3[2], add_prev=True, tprev=sv["u"], out=du,
+                ops.linear_chain(x3[0], [dict(image=img[k0 + CTX1], store=False),
+                                         dict(image=img[k0 + CTX1 + 1], x=x3[1], add_prev=True, store=False),
+                                         dict(image=img[k0 + CTX1 + 2], x=x3[2], add_prev=True, tprev=sv["u"], out=du,
                                               flags=_lib.EPI_MUL_DSILU),
-                                         dict(image=img[k0], res=dq2, out=dq_in)], dyn_rows=dN)
+                                         dict(image=img[k0 + CTX0], res=dq2, out=dq_in)], dyn_rows=dN)
             else:
-                ds = lin_t_sum(_split3(dxc, F_), [k0 + 1 + c for c in range(3)])
+                ds = rows.sum(x3, range(k0 + CTX1, k0 + CTX1 + 3))
                 du = torch.empty_like(ds)
                 call("geossl_silu_bwd", ptr(sv["u"]), ptr(ds), ds.numel(), ptr(du), st)
-                dq_in = lin_t(du, c0w, k0, res=dq2)                          # residual q2 = q + dq
+                dq_in = rows.one(du, k0 + CTX0, res=dq2)                     # residual q2 = q + dq
             add(N, F_, F_, F_, du, sv["q"], gc0w, gc0b)
             keep += [dxx, dmm, du1, dxc, du, dq2, dmu2]
             dq_cur, dmu_cur = dq_in, dmu_in
@@ -605,12 +512,11 @@ class _PaiNNCore(torch.autograd.Function):
                 call("geossl_painn_position_grad", ptr(dr), ptr(pi), ptr(ii), ptr(pj), ptr(ij), N, ptr(dpos), st)
         if not want_params:  # an evaluation of the forces alone (finetune_md17.py:85-105 with frozen weights)
             return dpos, [None] * len(grads)
-        for (rows, lda, ldb, ldw), probs in groups.items():
-            ops.linear_wgrad(probs, rows, F_, F_, accumulate=bool(acc), lda=lda, ldb=ldb, ldw=ldw,
-                             dyn_rows=dN if rows == N else dN3)
+        for (rows_, lda, ldb, ldw), probs in groups.items():
+            ops.linear_wgrad(probs, rows_, F_, F_, accumulate=bool(acc), lda=lda, ldb=ldb, ldw=ldw,
+                             dyn_rows=dN if rows_ == N else dN3)
         # embedding table; padding_idx = 0 keeps row 0 without gradient (painn.py:174)
         z = ctx.z
-        emb_w = ps[0]
         tmp = torch.empty_like(emb_w)
         wsf = torch.empty(int(_lib.load().geossl_embedding_bwd_workspace_floats(emb_w.size(0), F_)), **f32)
         call("geossl_embedding_bwd_dyn", ptr(z), z.stride(0) if z.numel() else 1, ptr(dq_cur), emb_w.size(0), N, F_, ptr(tmp),

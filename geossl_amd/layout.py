@@ -187,21 +187,6 @@ def painn_stage_caps(F=128, R=20):
     return cf, cb
 
 
-def painn_tile_route(lay, F, R, E, dyn=None):
-    """Whether PaiNN's fused interaction takes the atom-tile kernels (painn_tile.hip) for ALL atoms of this layout: one
-    launch per interaction block and pass, no molecule-staged launch and no atom lists.  The switch decides
-    (switches.painn_tile: by default only layouts with a structure above 255 atoms, which the staged kernels cannot hold);
-    the library says which shapes it serves.  Of the capacity buckets (`dyn`) the SPARSE one takes them - its layout has
-    structures of up to 1024 atoms and carries no group arrays or atom lists, so no other interaction kernel serves it
-    (bucket.route does not make one under GEOSSL_PAINN_TILE=0); the dense buckets keep their kernels."""
-    from .switches import painn_tile
-    if dyn is not None:
-        return bool(getattr(lay, "sparse", False)) and bool(_lib.load().geossl_painn_tile_ok(int(F), int(R)))
-    if E <= 0 or not painn_tile(lay.max_n):
-        return False
-    return bool(_lib.load().geossl_painn_tile_ok(int(F), int(R)))
-
-
 def big_atom_list(n, cap):
     """Atom indices (int32, ascending) of the molecules with more than `cap` atoms, for molecules of sizes `n` laid out
     back to back."""

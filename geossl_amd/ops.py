@@ -344,6 +344,111 @@ def pair_graph(pos, layout, cutoff, want_rows, want_pos, rbf=None):
     return g
 
 
+class PaiNNRoute:
+    """The interaction kernels of one PaiNN forward and of its backward (`painn_route` decides, once, in the forward):
+    ``form``: "tile" - the atom-tile kernels (painn_tile.hip): ALL atoms in one launch per block and pass, no staged launch
+    and no lists; "mma" - the matrix-pipe forward (painn_mma.hip), which stages the rows of a molecule of up to
+    ``stage_f`` atoms in LDS, with the per-atom kernel over ``big_f`` (the atoms of the larger molecules: list, entries,
+    device address of the real count) where there is such a list; "vector" - the molecule-staged vector forward;
+    ``big_b``: the atoms of the molecules above the LDS rows of the molecule-staged backward - skipped there
+    (``bwd_entry`` = ..._bwd_mol_skip) and covered by the per-atom kernel - or None (..._bwd_mol takes every molecule;
+    always with "tile");
+    ``mu_is_zero``: the first block's mu is NULL, not 3 N F zeros (and so is its gradient);
+    ``keep_mu``: GEOSSL_PAINN_NO_MU_ZERO as the forward read it (the last block forms its mu', d mu' starts as zeros);
+    ``call``: the node's `call` - its launches go the way of the node's other launches (whoever wraps painn.call sees them)."""
+
+    __slots__ = ("form", "lay", "el", "N", "F", "R", "dN", "stage_f", "big_f", "big_b", "bwd_entry", "mu_is_zero", "keep_mu",
+                 "call")
+
+    def forward(self, q, mu, xc, geom, fw, fb, q2, mu2):
+        """Block l, painn.py:54-64: (q, mu, xc) -> (q2, mu2) over geom = (dirv, fcut, phi); fw / fb: the block's 3F filter
+        rows.  One block per molecule (the rows its edges read are staged in LDS once), or per atom tile (rows from L2; a
+        sparse bucket: N is the atom capacity, the grid's, and atoms 0 .. *dN - 1 are real)."""
+        el, lay, N, F, R, st, call = self.el, self.lay, self.N, self.F, self.R, stream(), self.call
+        inc_ptr, inc_idx = el.inc["i"]
+        dirv, fcut, phi = geom
+        edge = (ptr(phi), ptr(fcut), ptr(dirv), ptr(fw), ptr(fb))
+        head = (ptr(q), ptr(mu), ptr(xc), ptr(el.idx_j))
+        if self.form == "tile":
+            call("geossl_painn_interaction_fwd_tile", *head, ptr(inc_ptr), ptr(inc_idx), *edge, None, N, self.dN, F, R,
+                 ptr(q2), ptr(mu2), st)
+        elif self.form == "mma":   # LDS: 3.5 KB per atom + 3 KB
+            row_edge, grp_atom, _, mol_grp = el.groups("i", lay.mol_ptr)
+            call("geossl_painn_interaction_fwd_mma_dyn", *head, ptr(row_edge), ptr(grp_atom), ptr(mol_grp), *edge,
+                 ptr(lay.mol_ptr), lay.B, self.stage_f, N, F, R, ptr(q2), ptr(mu2), ptr(getattr(el, "mol_grp_end", None)), st)
+            big = self.big_f
+            if big is not None and big[1] > 0:
+                call("geossl_painn_interaction_fwd_atoms", *head, ptr(inc_ptr), ptr(inc_idx), *edge, ptr(big[0]), big[1],
+                     big[2], F, R, ptr(q2), ptr(mu2), st)
+        else:
+            call("geossl_painn_interaction_fwd_mol", *head, ptr(inc_ptr), ptr(inc_idx), *edge, ptr(lay.mol_ptr), lay.B,
+                 lay.max_n, N, F, R, ptr(q2), ptr(mu2), st)
+
+    def workspace(self, device):
+        """The scratch of the backward launches of this form."""
+        lib = _lib.load()
+        n = lib.geossl_painn_interaction_bwd_tile_workspace_floats(self.N, self.F, self.R) if self.form == "tile" else \
+            lib.geossl_painn_interaction_bwd_mol_workspace_floats(self.N, self.lay.B, self.F, self.R)
+        return torch.empty(max(int(n), 1), dtype=torch.float32, device=device)
+
+    def backward(self, dq2, dmu2, mu, xc, geom, fw, fb, dxc, dmu_in, g_fw, g_fb, ws, acc):
+        """Block l backwards: (dq2, dmu2) -> (dxc, dmu_in; NULL with mu) and the block's filter gradients (acc: added)."""
+        el, lay, N, F, R, st, call = self.el, self.lay, self.N, self.F, self.R, stream(), self.call
+        inc_ptr, inc_idx = el.inc["j"]
+        dirv, fcut, phi = geom
+        args = (ptr(dq2), ptr(dmu2), ptr(mu), ptr(xc), ptr(el.idx_i), ptr(inc_ptr), ptr(inc_idx), ptr(phi), ptr(fcut),
+                ptr(dirv), ptr(fw), ptr(fb))
+        outs = (ptr(dxc), ptr(dmu_in), ptr(g_fw), ptr(g_fb), ptr(ws))
+        if self.form == "tile":   # (atom_list NULL: all atoms)
+            call("geossl_painn_interaction_bwd_tile", *args, None, N, self.dN, F, R, *outs, acc, st)
+            return
+        call(self.bwd_entry, *args, ptr(lay.mol_ptr), lay.B, lay.max_n, N, F, R, *outs, acc, st)
+        big = self.big_b
+        if big is not None and big[1] > 0:
+            call("geossl_painn_interaction_bwd_atoms", *args, ptr(big[0]), big[1], big[2], F, R, *outs, 1, st)
+
+
+def painn_route(lay, el, N, F, R, mma, training, want_pos, call=call):
+    """-> PaiNNRoute, from the layout, the library's limits and the switches (GEOSSL_PAINN_TILE, _MMA_CAP, _NO_SPLIT,
+    _NO_MU_ZERO), all read here.  `mma`: the configuration has matrix-pipe kernels and GEOSSL_PAINN_VECTOR is not set.
+    Tile: the switch decides (switches.painn_tile: by default only layouts with a structure above 255 atoms, which no staged
+    kernel holds), the library says which shapes it serves; of the capacity buckets (``el.dyn``) the SPARSE one takes them
+    (up to 1024 atoms, no group arrays or atom lists: no other kernel serves it), the dense ones keep their kernels.
+    Otherwise the matrix-pipe forward where every molecule fits its LDS rows; with larger ones (Molecule3D with hydrogens)
+    it keeps those that fit if layout.painn_stage_caps gives a forward cap and the layout an atom list (host-side sizes),
+    else the vector forward serves the whole batch.  The backward splits likewise at its own cap.  mu is NULL where one
+    forward kernel covers every atom, unless forces (the edge gradients read mu), a split backward or the switch keep it."""
+    from .layout import painn_stage_caps
+    from .switches import painn_tile
+    lib = _lib.load()
+    r = PaiNNRoute()
+    dyn = getattr(el, "dyn", None)
+    r.lay, r.el, r.N, r.F, r.R, r.dN, r.call = lay, el, N, F, R, _dyn(dyn, "n_atoms2"), call
+    r.form, r.stage_f, r.big_f, r.big_b = "vector", lay.max_n, None, None
+    bucket, sparse = dyn is not None, bool(getattr(lay, "sparse", False))
+    if mma and (sparse if bucket else (el.E > 0 and painn_tile(lay.max_n))) and lib.geossl_painn_tile_ok(int(F), int(R)):
+        r.form = "tile"
+    elif bucket and sparse:
+        raise _lib.GeosslHipError("a sparse capacity-bucket layout serves the atom-tile kernels only (F = 128, 8 / 16 / "
+                                  "20 radial functions, without GEOSSL_PAINN_VECTOR)")
+    else:
+        cap_f, cap_b = painn_stage_caps(F, R)
+        if mma and el.E > 0:
+            if 0 < cap_f < lay.max_n:
+                r.big_f = lay.big_atoms(cap_f)
+            if r.big_f is not None:
+                r.form, r.stage_f = "mma", cap_f
+            elif lay.max_n <= int(lib.geossl_painn_stage_cap(0, F, R)):
+                r.form = "mma"
+        if training and 0 < cap_b < lay.max_n and F in (64, 128):
+            r.big_b = lay.big_atoms(cap_b)
+    r.bwd_entry = "geossl_painn_interaction_bwd_mol" if r.big_b is None else "geossl_painn_interaction_bwd_mol_skip"
+    r.keep_mu = bool(_env("GEOSSL_PAINN_NO_MU_ZERO"))
+    covered = r.form == "tile" or (r.form == "mma" and r.big_f is None and R in (8, 16, 20) and r.big_b is None)
+    r.mu_is_zero = covered and not want_pos and not r.keep_mu
+    return r
+
+
 def gaussian_smearing(dist, offset, coeff):
     """GaussianSmearing.forward, schnet.py:205-207."""
     _lib.require_cuda(dist)

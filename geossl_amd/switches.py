@@ -1,6 +1,7 @@
 """Run-time switches (``GEOSSL_*`` environment variables) as plain dict lookups.
 
-The switches are read where they act, every call, so that a test or a bench line can flip one in the middle of a process.
+The switches are read where they act, every call, so that a test or a bench line can flip one in the middle of a process
+(a backward does not read again what its forward decided: PaiNN's node keeps its route and switches on ctx).
 ``os.environ.get`` encodes the key, looks it up and decodes the value on every call; a replayed step asks for a dozen of
 them.  ``env`` does the lookup in ``os.environ``'s own backing dict with keys encoded once (CPython on POSIX keeps the
 process environment as ``bytes -> bytes`` in ``os.environ._data``, updated by every ``os.environ[...] = ...`` /

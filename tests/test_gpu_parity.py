@@ -647,9 +647,12 @@ def _painn_model(cfg):
     return fill_module_(PaiNN(**cfg)).to(DEV)
 
 
-def test_painn_forward_and_grads_golden():
+@pytest.mark.parametrize("switch", [None, "GEOSSL_PAINN_NO_CHAIN", "GEOSSL_PAINN_SILU_KERNELS"])
+def test_painn_forward_and_grads_golden(switch, monkeypatch):
     """G7: hydrogen-containing batch (padding_idx row), perturbed geometry so that some precomputed edges lie
-    beyond the cutoff (mask path)."""
+    beyond the cutoff (mask path).  `switch`: the same values from one Linear per launch / from separate silu launches."""
+    if switch is not None:
+        monkeypatch.setenv(switch, "1")
     g = load_golden("g7_painn")
     cfg = cfg_of(g)
     assert int(g["n_beyond"]) > 0
