@@ -108,7 +108,7 @@ class AtomTupleExtractor:
             return self._from_batch_vector(data)
         data.super_edge_index = self._one(len(data.x))
         # the full enumeration is a function of the atom count: collated batches of such molecules can share step graphs
-        # (pretrain_GeoSSL.structure_fingerprint); a sampled subset (ratio < 1) is not
+        # (batch.structure_fingerprint); a sampled subset (ratio < 1) is not
         data._sei_canonical = self.option if self.ratio >= 1 else None
         return data
 

@@ -43,6 +43,7 @@ import torch
 
 from ... import _lib
 from ..._lib import call, ptr, stream
+from ...batch import Batch, TripleBatch
 from . import masking
 
 _OPTIONS = {"combination": 0, "permutation": 1}
@@ -364,7 +365,6 @@ class DeviceDataset:
     def collate(self, hb):
         """The collated batch of a handle as fresh device tensors - what ``BatchAtomTuple.from_data_list`` over these
         molecules followed by ``.to(device)`` holds (bit for bit) - with the host-side sizes attached."""
-        from ...pretrain_GeoSSL import Batch
         from ...layout import prepare_batch
         B, dev = hb.num_graphs, self.device
         N, S = hb.n_atoms, (0 if self.triples is not None else hb.n_super)   # (a triple dataset enumerates no pair tuples)
@@ -405,7 +405,6 @@ class DeviceDataset:
         return out
 
     def _collate_triples(self, hb, x, pos, bvec, rei, blob, o):
-        from ...pretrain_GeoSSL import TripleBatch
         from ...layout import prepare_batch
         B, T, dev = hb.num_graphs, hb.n_triples, self.device
         tri = torch.empty(3, T, dtype=torch.int64, device=dev)
@@ -555,7 +554,7 @@ class DatasetBatch:
         return self
 
     def fingerprint(self):
-        """pretrain_GeoSSL.structure_fingerprint of the collated batch, from the host sizes alone."""
+        """batch.structure_fingerprint of the collated batch, from the host sizes alone."""
         fp = self.__dict__.get("_fp")
         if fp is None and self._triples:   # (sampled triples: only the same molecules share index tensors)
             fp = self.__dict__["_fp"] = ("triples", id(self._dataset), self.ids.tobytes())

@@ -464,6 +464,16 @@ def module_status(module, device, message):
     return st
 
 
+def poll_status(model):
+    """The deferred index check of a backbone behind a replayed step: the embedding kernel flags an out-of-range atom type
+    in the status word, but model.forward's own arm() does nothing while a graph is captured and a replay never reaches it
+    (nor can a graph queue the host copy itself) - read here: IndexError up to eight steps late, like Embedding's, not never."""
+    st = model.__dict__.get("_geossl_status")
+    if st is not None:
+        st.poll()
+        st.arm(every=8)
+
+
 # Optional per-entry-point HIP-event timing (bench.py): {entry point name: [(start_event, end_event), ...]}.
 # Events are recorded on the stream the kernels are launched on (torch's current stream).
 TIMERS = None

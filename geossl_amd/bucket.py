@@ -4,7 +4,7 @@ size sequence.
 The reference's loader is ``DataLoaderAtomTuple(dataset, batch_size, shuffle=True)`` over ragged molecules
 (examples/pretrain_GeoSSL.py:301, Geom3D/dataloaders/dataloaders_AtomTuple.py:81-88; with BFS masking the sizes are
 re-drawn every epoch, Geom3D/datasets/datasets_3D.py:24-67): no two batches share a size sequence, so a graph keyed by
-the sequence (``pretrain_GeoSSL.structure_fingerprint``) is never replayed there.  A ``Bucket`` fixes what a captured
+the sequence (``batch.structure_fingerprint``) is never replayed there.  A ``Bucket`` fixes what a captured
 graph binds - addresses, grids, by-value counts - at a CAPACITY (atoms, pair slots, super-edges, work items of the
 aggregation; the number of molecules is the loader's batch size) and turns everything else into device DATA:
 
@@ -65,6 +65,7 @@ from .switches import env as _env, masked_painn_buckets, painn_sparse_buckets, s
 
 from . import _lib
 from ._lib import call, ptr, stream
+from .batch import Batch, TripleBatch, _tensor_uid
 
 MAX_N = 255         # largest molecule a bucket takes (the limit of the aggregation's work list and of the heads)
 SMALL_N = 33        # ... and the largest one of the register-form aggregation's size classes: buckets whose molecules
@@ -336,7 +337,7 @@ def tensors_ok(batch):
     if option_of(batch) == TRIPLES:
         return triple_tensors_ok(batch)
     sei = batch.super_edge_index
-    from .pretrain_GeoSSL import _tensor_uid   # (lifetime-unique stamps: id() of a freed tensor is handed out again)
+    # (lifetime-unique stamps: id() of a freed tensor is handed out again)
     tag = tuple((_tensor_uid(t_), t_._version) for t_ in (batch.x, batch.positions, batch.batch, sei))
     got = batch.__dict__.get("_geossl_tensors_ok")
     if got is not None and got[0] == tag:
@@ -857,7 +858,6 @@ class Bucket:
 
     def __init__(self, device, B, caps, option, x_cols=2, max_n=SMALL_N, kind="schnet", E_cap=0, n_rbf=20, views=2,
                  T_cap=0):
-        from .pretrain_GeoSSL import Batch, TripleBatch
         if views not in (1, 2):
             raise ValueError("a bucket holds one or two views")
         if option == TRIPLES and views != 1:

@@ -32,6 +32,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .batch import Batch
 from .pretrain_Supervised import model_width, readout_of
 from .step import Objective, StepTrainer, backbone_latent, engine_for
 from .switches import env as _env
@@ -103,7 +104,7 @@ _BATCH_VECTORS = OrderedDict()   # (device, both size sequences) -> the fused ba
 def _fused_batch_vector(batch, sizes):
     """cat(batch_active, batch_inactive + B).  It is a function of the two size sequences, so batches that agree in them
     get the SAME tensor object: the layout cached on it is built once, and a step graph - which identifies such a batch
-    by its index tensors (pretrain_GeoSSL.structure_fingerprint) - serves them all."""
+    by its index tensors (batch.structure_fingerprint) - serves them all."""
     key = (batch.batch_active.device, sizes.tobytes())
     vec = _BATCH_VECTORS.get(key)
     if vec is None:
@@ -128,10 +129,9 @@ def _host_sizes(batch, side):
 
 def fused_batch(batch):
     """The two conformations as ONE batch of 2B structures [active 0 .. B-1 | inactive 0 .. B-1] - a plain
-    ``pretrain_GeoSSL.Batch`` without tuples - built once per batch object and kept on it.  PaiNN: the inactive side's
+    ``batch.Batch`` without tuples - built once per batch object and kept on it.  PaiNN: the inactive side's
     edges are shifted by the TOTAL active atom count (the loader has already applied the per-side running counts).
     ``y`` is the batch's label tensor as float32, taken anew at every call."""
-    from .pretrain_GeoSSL import Batch
     if isinstance(batch, Batch) or hasattr(batch, "pairs"):
         return batch
     if _is_handle(batch):   # a PairedBatch: the 2B structures are a handle on the dataset's structures - no host cat
@@ -399,7 +399,6 @@ class LEPTrainer(StepTrainer):
         write_labels(g, fb)
 
     def _one_pass(self, batch):
-        from .pretrain_GeoSSL import Batch
         _check_handle(batch, self.model_3d)
         if not isinstance(batch, Batch) and not hasattr(batch, "pairs") and not _fused_batch_ok(batch):
             raise ValueError("LEPTrainer needs CUDA batches of B >= 2 pairs with one label per pair; use do_LEP for "

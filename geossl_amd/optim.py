@@ -7,6 +7,7 @@ from .switches import env as _env
 
 from . import _lib
 from ._lib import call, ptr, stream
+from .replay import _MT_PENDING, _restore_backward_threads
 
 
 class FlatParams:
@@ -296,9 +297,8 @@ def _adam_pre_hook(optimizer, args, kwargs):
 
 
 def _adam_post_hook(optimizer, args, kwargs):
-    # the step's backward has run by now: autograd's thread switch goes back to the caller's setting (pretrain_GeoSSL)
+    # the step's backward has run by now: autograd's thread switch goes back to the caller's setting (replay.py)
     try:
-        from .pretrain_GeoSSL import _MT_PENDING, _restore_backward_threads
         if _MT_PENDING:
             _restore_backward_threads()
     except Exception:

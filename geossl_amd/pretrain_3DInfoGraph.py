@@ -6,7 +6,7 @@ criterion, discriminator)`` has the reference's signature and returns ``(loss, a
 (csrc/infograph_head.hip) when it can and the reference's ATen code otherwise.  ``do_3DInfoGraph(args, batch, model,
 discriminator)`` is the loop body :92-108 as one call: the backbone's latent, then the fused head with the readout inside
 it (sigmoid summary, discriminator scores of every atom against its own and the next molecule, both BCE means and the
-accuracy counts), forward + backward replayed from HIP graphs by ``pretrain_GeoSSL._AutogradStep`` when gradients are
+accuracy counts), forward + backward replayed from HIP graphs by ``autograd_step._AutogradStep`` when gradients are
 wanted.  Its loss supports the reference's own ``optimizer.zero_grad(); loss.backward(); optimizer.step()`` with a stock
 ``torch.optim.Adam``.  ``InfoGraphTrainer`` is the ``train()`` body with all parameters in one flat buffer (one fused
 Adam launch, one all-reduce per step) and no host sync in ``step``.
@@ -17,8 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .pretrain_GeoSSL import Args
-from .step import Objective, StepTrainer, backbone_forward, backbone_latent, engine_for, with_counts
+from .step import Args, Objective, StepTrainer, backbone_forward, backbone_latent, engine_for, with_counts
 from .switches import env as _env
 
 

@@ -5,7 +5,7 @@ on the HIP path.
 ATen code).  ``do_ChargePrediction(args, batch, model, charge_predictor)`` is the loop body :62-81 as one call and returns
 the loss: the masked-atom draw and its write into the atom types (csrc/charge_head.hip, one launch), the backbone's
 latent on the masked types, then the fused head (masked-row Linear + cross-entropy, forward and backward), replayed from
-HIP graphs by ``pretrain_GeoSSL._AutogradStep`` when gradients are wanted.  The returned loss supports the reference's
+HIP graphs by ``autograd_step._AutogradStep`` when gradients are wanted.  The returned loss supports the reference's
 own ``optimizer.zero_grad(); loss.backward(); optimizer.step()`` with a stock ``torch.optim.Adam``.
 ``ChargePredictionTrainer`` is the ``train()`` body with all parameters in one flat buffer (one fused Adam launch, one
 all-reduce per step) and the mask drawn on the device by default.
@@ -20,6 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
+from .pretrain_GeoSSL import _next_noise_key
 from .step import Objective, StepTrainer, backbone_forward, backbone_latent, engine_for
 from .switches import env as _env
 
@@ -81,7 +82,6 @@ def numpy_mask(M, ratio):
 def device_seed(dev):
     """A fresh 64-bit seed of the device draw as an int64 [1] tensor, derived from torch's CUDA generator on the host
     (torch.cuda.manual_seed governs it)."""
-    from .pretrain_GeoSSL import _next_noise_key
     s = _next_noise_key(dev)
     return torch.tensor([s - (1 << 64) if s >= 1 << 63 else s], dtype=torch.long).to(dev, non_blocking=True)
 

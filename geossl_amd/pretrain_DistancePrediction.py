@@ -4,7 +4,7 @@
 ATen code).  ``do_DistancePrediction(args, batch, model, distance_predictor)`` is the loop body :66-79 as one call and
 returns the loss: the backbone's latent, then the fused distance head (csrc/distance_head.hip: two per-atom projections
 instead of the [S, 2F] edge features, no index_add scatters), with forward + backward replayed from HIP graphs by
-``pretrain_GeoSSL._AutogradStep`` when gradients are wanted.  The returned loss supports the reference's own
+``autograd_step._AutogradStep`` when gradients are wanted.  The returned loss supports the reference's own
 ``optimizer.zero_grad(); loss.backward(); optimizer.step()`` with a stock ``torch.optim.Adam``.
 ``DistancePredictionTrainer`` is the ``train()`` body with all parameters in one flat buffer (one fused Adam launch, one
 all-reduce per step).
@@ -14,8 +14,7 @@ import torch.nn as nn
 
 from . import ops
 from .layout import UngroupedSuperEdges
-from .pretrain_GeoSSL import Args
-from .step import Objective, StepTrainer, backbone_forward, backbone_latent, engine_for
+from .step import Args, Objective, StepTrainer, backbone_forward, backbone_latent, engine_for
 from .switches import env as _env
 
 

@@ -7,24 +7,23 @@ passed with ``NCSN_models=``.  ``DDMTrainer`` is the training-loop body (:234-26
 parameters in one flat buffer: one fused Adam launch and one RCCL all-reduce per step.
 
 Forward + backward of a step are captured into HIP graphs keyed on a FINGERPRINT of the batch's index structure
-(``structure_fingerprint``) and replayed - by ``DDMTrainer`` and, for a caller that keeps the reference's own loop
-(``loss, acc = do_DDM(...); optimizer.zero_grad(); loss.backward(); optimizer.step()``, :249-260), by ``do_DDM``
-itself: the loss it returns is the output of an autograd node whose backward hands the replayed gradients to autograd.
+(``batch.structure_fingerprint``) and replayed (``replay.StepGraphs``) - by ``DDMTrainer`` and, for a caller that keeps
+the reference's own loop (``loss, acc = do_DDM(...); optimizer.zero_grad(); loss.backward(); optimizer.step()``,
+:249-260), by ``do_DDM`` itself (``autograd_step._AutogradStep``): the loss it returns is the output of an autograd node
+whose backward hands the replayed gradients to autograd.  The batch types, the graph engine and the trainer base are
+re-exported from ``batch.py``, ``replay.py``, ``autograd_step.py`` and ``step.py``.
 """
-import ctypes as C
-import os
-import threading
-import warnings
-from collections import OrderedDict
-
 import numpy as np
 import torch
 from .switches import env as _env
 
-from . import _lib, bucket as bk, ops
+from . import _lib, ops
 from ._lib import call, ptr, stream
+from .autograd_step import _AutogradStep, _ReplayedLoss, _StepLoss, _Ticket  # noqa: F401
+from .batch import Batch, TripleBatch, _tensor_uid, canonical_option, structure_fingerprint  # noqa: F401
 from .layout import MolLayout
-from .step import Objective, StepTrainer, _OWN_CAPTURE, engine_for, latent, own_capture_open, with_counts  # noqa: F401
+from .replay import StepGraphs, _MT_PENDING, _NOISE_KEYS, _restore_backward_threads  # noqa: F401
+from .step import Args, Objective, StepTrainer, _OWN_CAPTURE, engine_for, latent, own_capture_open, with_counts  # noqa: F401
 
 NCSN_model_01 = None
 NCSN_model_02 = None
@@ -229,479 +228,6 @@ def _do_ddm_eager(args, batch, model, mu, sigma, heads, noise, fuse_views, devic
                           out_scale=0.5)
 
 
-class Batch:
-    """Device-resident collated batch with the attributes do_DDM / NCSN_version_03 read
-    (BatchAtomTuple, dataloaders_AtomTuple.py:40-78)."""
-
-    def __init__(self, x, positions, batch, super_edge_index, radius_edge_index=None, num_graphs=None, sizes=None,
-                 canonical=None):
-        self.x, self.positions, self.batch, self.super_edge_index = x, positions, batch, super_edge_index
-        self.radius_edge_index = radius_edge_index
-        self._num_graphs = num_graphs
-        # host-side knowledge of the collation (structure_fingerprint): atoms per molecule, and the AtomTupleExtractor
-        # option when super_edge_index is its full enumeration in batch order
-        self._sizes = None if sizes is None else [int(n) for n in sizes]
-        self._canonical = canonical
-
-    @property
-    def num_graphs(self):
-        if self._num_graphs is None:
-            self._num_graphs = self.batch[-1].item() + 1  # dataloaders_AtomTuple.py:75-78
-        return self._num_graphs
-
-    @classmethod
-    def from_numpy(cls, d, device, prepare=True):
-        """prepare=False: the index structures of the step are built (from the host sizes) by the first step that needs
-        them - a step that replays a capacity-bucket graph never does."""
-        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
-        rei = t(d["radius_edge_index"]) if "radius_edge_index" in d else None
-        ng = int(len(d["sizes"])) if "sizes" in d else None
-        canonical = canonical_option(d["sizes"], d["super_edge_index"]) if "sizes" in d else None
-        out = cls(t(d["x"]), t(d["positions"]), t(d["batch"]), t(d["super_edge_index"]), rei, ng, d.get("sizes"),
-                  canonical)
-        if "sizes" in d:  # collation knows the molecule sizes on the host: index structures without a device read-back
-            from .layout import prepare_batch
-            prepare_batch(out.batch, out.super_edge_index, d["sizes"], lazy=not prepare)
-        return out
-
-    def to(self, device):
-        dev = torch.device(device)
-        if all(a is None or (a.device == dev or (dev.index is None and a.device.type == dev.type))
-               for a in (self.x, self.positions, self.batch, self.super_edge_index, self.radius_edge_index)):
-            return self  # (already there: like Tensor.to, no new object - what is cached on this one stays)
-        mv = lambda a: None if a is None else a.to(device)
-        return Batch(mv(self.x), mv(self.positions), mv(self.batch), mv(self.super_edge_index),
-                     mv(self.radius_edge_index), self._num_graphs, self._sizes, self._canonical)
-
-
-class TripleBatch(Batch):
-    """Device-resident collated batch of atom TRIPLES with the attributes the loop of
-    examples/pretrain_TorsionAnglePrediction.py:64-78 reads (BatchAtomTriple, dataloaders_AtomTriple.py:34-72):
-    ``super_edge_index`` is int64 [3, T] (grouped by molecule in batch order) and ``super_edge_angle`` float32 [T] its
-    targets.  The list is sampled: never a function of the sizes (``_canonical`` stays None)."""
-
-    _triples = True
-
-    def __init__(self, x, positions, batch, super_edge_index, super_edge_angle, radius_edge_index=None, num_graphs=None,
-                 sizes=None):
-        super().__init__(x, positions, batch, super_edge_index, radius_edge_index, num_graphs, sizes, None)
-        self.super_edge_angle = super_edge_angle
-
-    @classmethod
-    def from_numpy(cls, d, device):
-        """From a dict with x, positions, batch, super_edge_index [3, T], super_edge_angle [T], sizes [, radius_edge_index]
-        (collated on the host: triples grouped by molecule in batch order)."""
-        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
-        rei = t(d["radius_edge_index"]) if "radius_edge_index" in d else None
-        sizes = d.get("sizes")
-        out = cls(t(d["x"]), t(d["positions"]), t(d["batch"]), t(np.asarray(d["super_edge_index"]).reshape(3, -1)),
-                  t(np.asarray(d["super_edge_angle"], dtype=np.float32).reshape(-1)), rei,
-                  None if sizes is None else int(len(sizes)), sizes)
-        if sizes is not None:
-            from .layout import prepare_batch
-            prepare_batch(out.batch, out.super_edge_index, sizes, lazy=True)
-        return out
-
-    def to(self, device):
-        dev = torch.device(device)
-        if all(a is None or (a.device == dev or (dev.index is None and a.device.type == dev.type))
-               for a in (self.x, self.positions, self.batch, self.super_edge_index, self.super_edge_angle,
-                         self.radius_edge_index)):
-            return self
-        mv = lambda a: None if a is None else a.to(device)
-        return TripleBatch(mv(self.x), mv(self.positions), mv(self.batch), mv(self.super_edge_index),
-                           mv(self.super_edge_angle), mv(self.radius_edge_index), self._num_graphs, self._sizes)
-
-
-_PAIR_CACHE = {}
-
-
-def canonical_option(sizes, super_edge_index):
-    """"combination" / "permutation" when the HOST array super_edge_index [2, S] is exactly AtomTupleExtractor's full
-    enumeration (dataloaders_AtomTuple.py:19-24, ratio = 1) of molecules with these sizes, collated in batch order with
-    node offsets (:64-65); None otherwise.  Such index tensors are a function of the sizes alone."""
-    from .synthetic import combination_pairs, permutation_pairs
-    sizes = np.asarray(sizes, dtype=np.int64)
-    sei = np.asarray(super_edge_index)
-    S = sei.shape[1] if sei.ndim == 2 else -1
-    off = np.concatenate([[0], np.cumsum(sizes)])
-    for option, count, pairs in (("combination", sizes * (sizes - 1) // 2, combination_pairs),
-                                 ("permutation", sizes * (sizes - 1), permutation_pairs)):
-        if int(count.sum()) != S or S == 0:
-            continue
-        parts = []
-        for m, n in enumerate(sizes.tolist()):
-            if (option, n) not in _PAIR_CACHE:
-                _PAIR_CACHE[(option, n)] = pairs(n)
-            parts.append(_PAIR_CACHE[(option, n)] + off[m])
-        if np.array_equal(np.concatenate(parts, axis=1), sei):
-            return option
-    return None
-
-
-_UID = [0]
-
-
-def _tensor_uid(t_):
-    """A number that identifies the tensor OBJECT for as long as it lives and is never handed out again (id() is: CPython
-    reuses the address of a freed tensor, and a streaming loader would then look like a batch that came back)."""
-    uid = t_.__dict__.get("_geossl_uid") if hasattr(t_, "__dict__") else None
-    if uid is None:
-        _UID[0] += 1
-        uid = _UID[0]
-        try:
-            t_._geossl_uid = uid
-        except AttributeError:
-            return ("id", id(t_))
-    return uid
-
-
-def structure_fingerprint(batch, model_3d="schnet"):
-    """Hashable identity of everything a captured step binds besides x, positions and the noise: the batch vector,
-    super_edge_index and (PaiNN) radius_edge_index with the index structures derived from them.
-
-    * A batch that carries its molecule sizes on the host AND whose super_edge_index is known to be the extractor's
-      full enumeration (``_sizes`` / ``_canonical``: set by ``Batch.from_numpy``, ``BatchAtomTuple.from_sizes`` and by
-      ``BatchAtomTuple.from_data_list`` over molecules that went through ``AtomTupleExtractor(ratio=1)``) has index
-      tensors that are a function of the sizes: the fingerprint is the sizes, so every batch of a shuffled loader with
-      the same molecule sizes in the same order shares a graph - and no other batch does.
-    * Anything else (sampled tuples, PaiNN's geometry-dependent edge list, batches built by hand) is identified by
-      the tensor OBJECTS and their versions: a graph is replayed only for the very tensors it was captured on (a
-      device-resident, pre-collated batch that comes back every epoch)."""
-    if getattr(batch, "_dataset", None) is not None and model_3d != "painn":
-        return batch.fingerprint()   # a handle on a device-resident dataset: its index tensors ARE a function of the sizes
-    tag = lambda t_: None if t_ is None else (_tensor_uid(t_), t_._version, tuple(t_.shape))
-    rei = getattr(batch, "radius_edge_index", None) if model_3d == "painn" else None
-    tags = (tag(batch.batch), tag(batch.super_edge_index), tag(rei))
-    if getattr(batch, "_triples", False):   # (a triple batch: its targets are bound by a per-structure graph too)
-        tags += (tag(batch.super_edge_angle),)
-    cached = batch.__dict__.get("_geossl_fp")
-    if cached is not None and cached[0] == tags:
-        return cached[1]
-    sizes, canon = getattr(batch, "_sizes", None), getattr(batch, "_canonical", None)
-    if sizes is not None and canon is not None and rei is None and model_3d != "painn":
-        fp = ("sizes", canon, int(batch.batch.numel()), int(batch.super_edge_index.size(1)),
-              np.asarray(sizes, dtype=np.int32).tobytes())
-    else:
-        fp = ("tensors",) + tags
-    batch.__dict__["_geossl_fp"] = (tags, fp)
-    return fp
-
-
-class Args:
-    """The three fields do_DDM reads from the reference's argparse namespace."""
-
-    def __init__(self, model_3d="schnet", normalize=False):
-        self.model_3d = model_3d
-        self.normalize = normalize
-
-
-_NOISE_KEYS = ("pos_noise", "noise_level_1", "dist_noise_1", "noise_level_2", "dist_noise_2")
-
-
-class StepGraphs:
-    """HIP graphs of forward + backward of the DDM step; all in ONE memory pool (their activations are dead between
-    steps, so N graphs cost the device memory of the largest plus the static inputs and the loss of each).
-    ``fwd_bwd(batch, noise) -> loss`` is the owner's eager step; it must leave the gradients in buffers that are the same
-    for every call (the graph binds their addresses).  Least-recently-used graphs are dropped beyond ``max_graphs``.
-
-    Which graph serves a batch (``mode="auto"``):
-
-    * a batch of EQUAL-SIZED molecules, and anything a bucket cannot take (PaiNN's geometry-dependent edge list, sampled
-      tuples, batches built by hand): one graph per ``structure_fingerprint`` - the size sequence, or the tensor objects;
-      a structure that only a fingerprint identifies is captured on its SECOND sighting (a loader that never repeats one
-      never pays for a capture);
-    * a batch with a SPARSE layout (a structure of 256 to 1024 atoms - LBA's pockets - or GEOSSL_SPARSE_PAIRS=1) in a
-      one-view SchNet step that reads no pair tuples (``pair_tuples=False``: Supervised, and LEP with its 2B structures
-      [active | inactive]): one graph per number of structures in a sparse bucket (``bucket.SPARSE``) - by default the handles of a DeviceLoader, with
-      ``GEOSSL_SPARSE_BUCKETS=1`` collated batches too (``=0``: neither; such a batch is served as the first entry says);
-      a PaiNN step of that kind whose batch brings radius edges on the device (a dataset built with ``radius=``, or a
-      collated ``radius_edge_index``) takes the same bucket with an edges part, under ``GEOSSL_PAINN_SPARSE_BUCKETS``;
-    * every other SchNet batch - ragged molecules in shuffled order, the reference's loader (pretrain_GeoSSL.py:301) - one
-      graph per (molecules in the batch, tuple option) at a CAPACITY (``geossl_amd/bucket.py``): the graph's kernels read
-      the batch's real atom / pair-slot / super-edge counts and every index structure from device memory, so ONE graph
-      replays on any size sequence; a batch that outgrows the capacity makes a larger bucket (its graph is captured
-      again: a handful of times at the start of a run).
-
-    ``mode="structure"``: per-structure graphs only, captured at the first sighting (pre-collated, device-resident
-    batches that come back every epoch)."""
-
-    def __init__(self, fwd_bwd, model_3d, max_graphs=256, split=None, mode="auto", normalize=False, modules=None,
-                 noise_keys=None, views=2, pair_tuples=True):
-        # split = (fwd(batch, noise) -> loss with its autograd graph, bwd(loss)): forward and backward captured as TWO
-        # graphs (same pool, same capture stream; replayed in this order) - the forward's loss is then on the device
-        # before the backward runs, and the backward can run on a side stream while the host goes on (_AutogradStep)
-        self.fwd_bwd, self.model_3d, self.max_graphs, self.split = fwd_bwd, model_3d, max_graphs, split
-        self.mode, self.normalize = mode, normalize
-        self.modules = modules  # (backbone, head, head): what bucket.modules_ok looks at (None: no capacity buckets)
-        # the random draws a step takes as static inputs (the contrastive objectives: the position noise only)
-        self.noise_keys = _NOISE_KEYS if noise_keys is None else tuple(noise_keys)
-        # views of the molecules the backbone sees in a bucket (1: the Distance / Charge Prediction steps)
-        self.views = views
-        # the step reads the batch's pair tuples (step.Objective.pair_tuples); False: a one-view SchNet step whose
-        # batches with a sparse layout go through a sparse bucket
-        self.pair_tuples = pair_tuples
-        self.graphs, self.pool = OrderedDict(), None
-        self.enabled = True
-        self.captures = 0
-        self._warned = False
-        self._seen = OrderedDict()
-        self.bucket_ok = True   # cleared when a bucket capture failed: per-structure graphs from then on
-        self._mod_ok = None
-        # a float32 buffer the owner wants cleared before every replay (its flat gradient buffer): done by the launch that
-        # refreshes the graph's inputs instead of a fill node inside the graph (one launch less per step)
-        self.zero_with_refresh = None
-
-    def __len__(self):
-        return len(self.graphs)
-
-    # ---- which graph
-    def bucket_key(self, batch):
-        """("bucket", molecules, option) when the batch goes through a capacity bucket (bucket.route), else None."""
-        if (self.mode != "auto" or not self.bucket_ok or _env("GEOSSL_NO_BUCKETS") or self.modules is None):
-            return None
-        option = bk.route(batch, self.model_3d, self.views, self.pair_tuples, self.normalize)
-        if option is None or not self._modules_ok():
-            return None
-        return ("bucket", len(batch._sizes), option)
-
-    def _modules_ok(self):
-        """bucket.modules_ok of this engine's modules, remembered per state of the switches it reads (the modules of a
-        StepGraphs are fixed: a replaced parameter rebuilds the engine, _AutogradStep.unchanged / DDMTrainer)."""
-        env = tuple(_env(k) for k in bk.MODULE_SWITCHES + bk.PAINN_SWITCHES)
-        if self._mod_ok is None or self._mod_ok[0] != env:
-            self._mod_ok = (env, bk.modules_ok(*self.modules))
-        return self._mod_ok[1]
-
-    def lookup(self, batch):
-        """The graph that serves this batch (None: not captured yet, or its bucket is too small)."""
-        key = self.bucket_key(batch)
-        if key is not None:
-            g = self.graphs.get(key)
-            counts = None if g is None else g["bucket"].fits_batch(batch)
-            if counts is None:
-                return None
-            g["counts"] = counts
-            self.graphs.move_to_end(key)
-            return g
-        fp = structure_fingerprint(batch, self.model_3d)
-        g = self.graphs.get(fp)
-        if g is not None:
-            self.graphs.move_to_end(fp)
-        return g
-
-    def capture_now(self, batch):
-        """Should a batch without a graph be captured at this sighting?  Buckets and equal-sized molecules: yes (their
-        graph serves every later batch of the kind); a structure known by fingerprint only: from its second sighting on
-        (mode "structure": always)."""
-        if self.mode != "auto" or self.bucket_key(batch) is not None:
-            return True
-        if bk.is_uniform(batch) and getattr(batch, "_canonical", None) is not None and self.model_3d == "schnet":
-            return True
-        return self.seen_before(batch)
-
-    def seen_before(self, batch):
-        """True from the second call on for one fingerprint (a bounded memory of hashes: a collision or a forgotten
-        entry only moves the moment of a capture)."""
-        h = hash(structure_fingerprint(batch, self.model_3d))
-        seen = h in self._seen
-        self._seen[h] = True
-        self._seen.move_to_end(h)
-        while len(self._seen) > 8192:
-            self._seen.popitem(last=False)
-        return seen
-
-    # ---- capture
-    def _evict(self):
-        while len(self.graphs) >= self.max_graphs:
-            if not self._warned:
-                warnings.warn("more than %d distinct batch structures: the least recently used step graphs are dropped "
-                              "and captured again when they come back (raise max_graphs, or run without graphs)"
-                              % self.max_graphs)
-                self._warned = True
-            self.graphs.popitem(last=False)
-
-    def capture(self, batch, noise):
-        """Capture fwd_bwd on static inputs: clones of x / positions / the five noise tensors with the batch's own index
-        tensors bound as they are (per-structure graph), or the buffers of a capacity bucket filled from the batch.  None
-        when the capture failed: the owner runs eagerly (a failed bucket: per-structure graphs) from then on."""
-        key = self.bucket_key(batch)
-        if key is not None:
-            g = self._capture_bucket(key, batch, noise)
-            if g is not None or not self.enabled:
-                return g
-            key = None  # the bucket could not be captured: this batch's own structure
-        fp = structure_fingerprint(batch, self.model_3d)
-        self._evict()
-        if getattr(batch, "_triples", False):   # (triples and targets bound as they are, like the other index tensors)
-            sb = TripleBatch(batch.x.clone(), batch.positions.clone(), batch.batch, batch.super_edge_index,
-                             batch.super_edge_angle, getattr(batch, "radius_edge_index", None), batch.num_graphs,
-                             getattr(batch, "_sizes", None))
-        else:
-            sb = Batch(batch.x.clone(), batch.positions.clone(), batch.batch, batch.super_edge_index,
-                       getattr(batch, "radius_edge_index", None), batch.num_graphs, getattr(batch, "_sizes", None),
-                       getattr(batch, "_canonical", None))
-        sn = {k: noise[k].clone() for k in self.noise_keys}
-        g = self._capture(sb, sn)
-        if g is not None:
-            self.graphs[fp] = g
-        return g
-
-    def _capture_bucket(self, key, batch, noise):
-        old = self.graphs.pop(key, None)
-        prev = None if old is None else old["bucket"].sizes()
-        del old  # (its graph and static buffers go before the larger ones are made)
-        self._evict()
-        args = bk.Bucket.sizing(batch, key[2], self.model_3d, self.views,
-                                getattr(getattr(self.modules[0], "radial_basis", None), "n_rbf", 20), prev)
-        try:
-            bkt = bk.Bucket(**args)
-            counts = bkt.fill(batch)
-        except (ValueError, RuntimeError) as e:
-            warnings.warn("capacity bucket not usable for this batch (%s); per-structure graphs from now on" % e)
-            self.bucket_ok = False
-            return None
-        sn = bkt.static_noise(self.noise_keys)
-        g0 = dict(bucket=bkt, noise=sn, counts=counts)
-        self.copy_noise(g0, noise)
-        g = self._capture(bkt.batch, sn)
-        if g is None:
-            self.enabled, self.bucket_ok = True, False  # (eager fallback is for a failed per-structure capture)
-            return None
-        g.update(bucket=bkt, counts=counts)
-        self.graphs[key] = g
-        return g
-
-    def _capture(self, sb, sn):
-        import time
-        timing = [] if _env("GEOSSL_CAPTURE_TIMING") else None
-
-        def lap(name):
-            if timing is not None:
-                torch.cuda.synchronize()
-                timing.append((name, time.perf_counter()))
-        lap("start")
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):  # warm-up off the capture: builds the cached layouts, sets kernel attributes
-            for _ in range(2 if not self.graphs else 1):
-                self.fwd_bwd(sb, sn)
-        torch.cuda.current_stream().wait_stream(side)
-        # nothing may be pending on the device when the capture starts (in a multi-rank job the collective's
-        # watchdog thread polls events of earlier all-reduces), and calls of other threads must not invalidate it
-        torch.cuda.synchronize()
-        lap("warm-up passes")
-        graph, graph_bwd = torch.cuda.CUDAGraph(), None
-        # No garbage collection while a capture is open: a collection that happens to run there finalises whatever old
-        # graphs, events and streams sit in unreachable cycles (an engine of a model that is gone), and destroying a
-        # graph or querying an event inside a capture aborts the process.  (Not collecting up front either: a full
-        # collection of a process with torch loaded costs 45 ms, as much as the rest of the capture.)
-        import gc
-        gc_was_on = gc.isenabled()
-        gc.disable()
-        _OWN_CAPTURE[0] += 1   # (the owner's passes leave the gradient buffer to `refresh` only inside THIS capture)
-        try:
-            extra = None   # an owner's forward may return (loss, extra): extra = static outputs beside the loss
-            if self.split is None:
-                with torch.cuda.graph(graph, pool=self.pool, capture_error_mode="thread_local"):
-                    loss = self.fwd_bwd(sb, sn)
-                if isinstance(loss, tuple):
-                    loss, extra = loss
-                if self.pool is None:
-                    self.pool = graph.pool()
-            else:
-                cap = torch.cuda.Stream()  # both captures on ONE stream: autograd runs a node's backward where its forward ran
-                with torch.cuda.graph(graph, pool=self.pool, stream=cap, capture_error_mode="thread_local"):
-                    live = self.split[0](sb, sn)
-                if isinstance(live, tuple):
-                    live, extra = live
-                if self.pool is None:
-                    self.pool = graph.pool()
-                graph_bwd = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph_bwd, pool=self.pool, stream=cap, capture_error_mode="thread_local"):
-                    self.split[1](live)
-                loss = live.detach()
-                del live
-        except Exception as e:  # capture is an optimisation: fall back to eager execution, loudly
-            warnings.warn("HIP-graph capture of the DDM step failed (%s: %s); running eagerly" % (type(e).__name__, e))
-            torch.cuda.synchronize()
-            self.enabled = False
-            return None
-        finally:
-            _OWN_CAPTURE[0] -= 1
-            if gc_was_on:
-                gc.enable()
-        lap("capture + instantiate")
-        if timing is not None:
-            print("capture timing (ms):", ", ".join("%s %.1f" % (n, 1e3 * (t - timing[i][1])) for i, (n, t) in enumerate(timing[1:])))
-        self.captures += 1
-        return dict(graph=graph, graph_bwd=graph_bwd, batch=sb, noise=sn, loss=loss, zero=self.zero_with_refresh,
-                    extra=extra)
-
-    # ---- per-step refresh of a graph's static inputs
-    @staticmethod
-    def noise_views(g, batch=None):
-        """The graph's five static noise tensors at the size of THIS batch (a bucket's are capacity-sized: the real rows
-        are the leading ones) - what a caller's draws are written into."""
-        bkt = g.get("bucket")
-        if bkt is None:
-            return g["noise"]
-        N, P, S, W = g["counts"]
-        # (the noise levels are per molecule: B is exact; a mask list holds k <= N entries, copy_noise writes k)
-        real = {"N": N, "S": S}
-        return {k: (v[:real[r]] if (r := bk.NOISE_SHAPES[k][0]) in real else v) for k, v in g["noise"].items()}
-
-    @staticmethod
-    def copy_noise(g, noise):
-        into = StepGraphs.noise_views(g)
-        for k in into:   # (the graph's own draws: all five of a DDM step)
-            dst = into[k]
-            # (the leading k entries: the mask kernel reads as many as the batch's k; a paired step - LEP - has one
-            # label per PAIR, the leading half of a bucket's structure count)
-            if k == "mask_idx" or (k == "target" and noise[k].numel() * 2 == dst.numel()):
-                dst = dst[:noise[k].numel()]
-            dst.copy_(noise[k].view_as(dst))
-
-    @staticmethod
-    def refresh(g, batch, noise=None):
-        """x, positions and (if given) the five noise tensors of this step into the graph's static inputs; a bucket also
-        gets the batch's index structures and real counts."""
-        bkt, zero = g.get("bucket"), g.get("zero")
-        if bkt is not None:
-            try:
-                bkt.fill(batch, g["counts"], zero=zero)
-            except ValueError as e:  # (tensors the bucket cannot copy: the caller runs this step eagerly)
-                warnings.warn("capacity bucket refused a batch (%s); the step runs eagerly" % e)
-                return False
-        elif getattr(batch, "_dataset", None) is not None:
-            # molecules of a device-resident dataset: gathered straight into the graph's static x / positions
-            from .layout import get_layout
-            sb = g["batch"]
-            batch._dataset.gather_into(batch, sb.x, sb.positions, get_layout(sb.batch).mol_ptr, zero)
-        else:
-            dx, dp, sx, sp = g["batch"].x, g["batch"].positions, batch.x, batch.positions
-            if (sx.is_cuda and sp.is_cuda and sx.dtype == dx.dtype and sp.dtype == dp.dtype and sx.shape == dx.shape
-                    and sp.shape == dp.shape and all(t_.is_contiguous() for t_ in (dx, dp, sx, sp))):
-                if zero is None:
-                    call("geossl_copy2", ptr(dx), ptr(sx), dx.numel() * dx.element_size(), ptr(dp), ptr(sp),
-                         dp.numel() * dp.element_size(), stream())  # one launch instead of two copies
-                else:
-                    cb = _lib.CopyBatch()
-                    for k, (d_, s_, nb) in enumerate(((dx, sx, dx.numel() * dx.element_size()),
-                                                      (dp, sp, dp.numel() * dp.element_size()),
-                                                      (zero, None, zero.numel() * 4))):
-                        cb.dst[k], cb.src[k], cb.bytes[k] = ptr(d_), (ptr(s_) if s_ is not None else None), nb
-                    call("geossl_copy_n", C.byref(cb), 3, stream())
-            else:
-                dx.copy_(sx)
-                dp.copy_(sp)
-                if zero is not None:
-                    zero.zero_()
-        if noise is not None:
-            StepGraphs.copy_noise(g, noise)
-        return True
-
-
 _PINNED = {"i": 0, "slots": [[None, None], [None, None]]}  # ring of two pinned staging buffers (grow-only) + copy events
 
 
@@ -796,353 +322,6 @@ def draw_step_noise_fused(batch, n1, n2, mu, sigma, into=None):
          ptr(into["pos_noise"]), ptr(into["noise_level_1"]), ptr(into["dist_noise_1"]), ptr(into["noise_level_2"]),
          ptr(into["dist_noise_2"]), stream())
     return into
-
-
-class _ReplayedLoss(torch.autograd.Function):
-    """The loss of a replayed step as a differentiable function of the parameters: forward returns the loss the forward
-    graph computed, backward waits for the backward graph (replayed on the engine's side stream right behind the forward)
-    and hands autograd its gradients, scaled by the upstream gradient - one launch; every parameter's gradient is a view
-    of the product."""
-
-    @staticmethod
-    def forward(ctx, loss, engine, ticket, *params):
-        ctx.engine, ctx.ticket = engine, ticket
-        return loss.view_as(loss)
-
-    @staticmethod
-    def backward(ctx, gout):
-        eng, ticket = ctx.engine, ctx.ticket
-        src = eng.collect(ticket)
-        pre = ticket.pop("views", None)
-        if pre is not None:
-            # the step's own output buffer and its per-parameter views were made in do_DDM, while the host was going to
-            # wait for the forward anyway; handing them out once keeps them stealable (AccumulateGrad adopts a gradient
-            # nobody else references - the list dies with this frame)
-            buf, outs = pre
-            torch.mul(src, gout, out=buf)
-            return (None, None, None) + tuple(outs)
-        g = src * gout
-        # one split for all parameters, then a reshape each (two tensor operations per parameter were a third of this
-        # backward's host time at 59 parameters - and the host is what bounds the loop at small batches)
-        outs = [v if len(shape) == 1 else v.view(shape) for v, (shape, _) in zip(g.split_with_sizes(eng.numels), eng.shapes)]
-        return (None, None, None) + tuple(outs)
-
-
-class _StepLoss(torch.Tensor):
-    """The loss do_DDM's graph path hands to a caller that owns its optimizer - an ordinary tensor attached to the autograd
-    graph (``_ReplayedLoss`` with every parameter as an input: ``torch.autograd.grad``, scaled losses, sums with other
-    terms all differentiate through it as before) whose plain ``loss.backward()`` (pretrain_GeoSSL.py:259) does not go
-    through the autograd engine: the step's gradients are already in the engine's buffer, so backward() copies them into
-    the step's own buffer (one launch) and points every parameter's ``.grad`` at its view - what the 59 AccumulateGrad
-    nodes of the engine path do one queue round trip each (0.34 ms per step on the host, which is what bounds the loop at
-    the reference's batch size).  Anything else - a gradient argument, retain_graph, create_graph, inputs=, a parameter
-    that already holds a gradient (accumulation over several backward() calls) or carries a tensor hook, an arithmetic
-    result (ops on this class return plain tensors) - takes the engine.  GEOSSL_NO_DIRECT_BACKWARD: always the engine."""
-
-    __torch_function__ = torch._C._disabled_torch_function_impl
-
-    def backward(self, gradient=None, retain_graph=None, create_graph=False, inputs=None):
-        st = self.__dict__.pop("_geossl_step", None)
-        if (st is not None and gradient is None and not retain_graph and not create_graph and inputs is None
-                and st[0].direct_backward(st[1])):
-            return None
-        return torch.Tensor.backward(self, gradient, retain_graph, create_graph, inputs)
-
-
-class _Ticket(dict):
-    """The claim of one do_DDM step on the gradients its backward replay leaves in the engine's buffer ("serial",
-    "event", "g", "used").  The replay runs on a side stream and READS the parameters: when a loss is dropped without
-    backward() (a skipped non-finite step followed by an EMA update, load_state_dict, another loss's optimizer step) the
-    caller's stream is made to wait for the replay here, so that no later parameter write can overtake it."""
-
-    def __del__(self):
-        try:
-            _restore_backward_threads(self)
-        except Exception:
-            pass
-        try:
-            if (not self.get("used") and self.get("event") is not None and not torch.cuda.is_current_stream_capturing()
-                    and not self["event"].query()):
-                torch.cuda.current_stream().wait_event(self["event"])
-        except Exception:  # interpreter shutdown, a destroyed context: nothing left to order
-            pass
-
-
-class _AutogradStep:
-    """do_DDM's graph path for a caller that owns its optimizer (the reference loop, pretrain_GeoSSL.py:249-260).
-
-    Forward and backward of the step are captured as TWO graphs per index structure (one memory pool, one capture
-    stream).  ``run`` draws the step's noise like the eager path (same generators, same order), refreshes the graph
-    inputs, replays the forward on the caller's stream and the backward on a side stream right behind it, and returns
-    the loss behind ``_ReplayedLoss``.  The reference's ``loss.detach().item()`` (:255) therefore waits for the forward
-    only; ``optimizer.zero_grad()``, ``loss.backward()`` (one wait + one multiply; AccumulateGrad adopts the views) and
-    the launches of ``optimizer.step()`` are issued by the host WHILE the backward graph runs.  The backward's gradients
-    land in a flat static buffer (the parameters' .grad point into it only while a step is captured); a step whose
-    backward() has not been called when the next step arrives keeps a snapshot of them."""
-
-    def __init__(self, model, n1, n2, objective=None):
-        self.model, self.n1, self.n2 = model, n1, n2
-        # the step.Objective of this engine (default: DDM) says everything that differs between objectives: the heads'
-        # parameters, the graphs' key and per-step static inputs, the forward, and what `run` returns.  The heads are
-        # the objective's own: two NCSN heads (DDM), none (n1 = n2 = None: the contrastive steps), or one (n1).
-        self.objective = objective = DDM if objective is None else objective
-        heads = [m for m in (n1, n2) if m is not None]
-        # the parameters the step reaches (a parameter outside it - an atomref table, PaiNN's output layers - gets no
-        # gradient at all, like in the eager path, not a zero one)
-        backbone = model._params() if hasattr(model, "_params") else _schnet_step_params(model)
-        seen, self.params = set(), []
-        for p in list(backbone) + [q for h in heads for q in objective.head_params(h)]:
-            if id(p) not in seen and p.requires_grad:
-                seen.add(id(p))
-                self.params.append(p)
-        dev = self.params[0].device
-        # the parameters move into ONE flat buffer (values unchanged; they stay ordinary leaves): the gradients this
-        # engine hands to autograd are views of one flat buffer at the same offsets, which lets a stock torch.optim.Adam
-        # over these parameters run as one launch (optim.ParamHome and its step hook)
-        from .optim import ParamHome
-        self.home = ParamHome.of(self.params)
-        self.gflat = torch.zeros(sum(p.numel() for p in self.params), dtype=torch.float32, device=dev)
-        self._one = torch.ones((), dtype=torch.float32, device=dev)
-        self.views, off = [], 0
-        for p in self.params:
-            self.views.append(self.gflat[off:off + p.numel()].view_as(p))
-            off += p.numel()
-        self.shapes = tuple((tuple(p.shape), p.numel()) for p in self.params)
-        self.numels = [n for _, n in self.shapes]
-        # where every parameter of the three modules hangs (submodule, name) with its object, address and grad flag:
-        # `unchanged()` compares them per call without walking the module trees
-        self._where = []
-        for m in [self.model] + heads:
-            seen_mod = set()
-            for sub in m.modules():
-                if id(sub) in seen_mod:
-                    continue
-                seen_mod.add(id(sub))
-                for name, p in sub._parameters.items():
-                    if p is not None:
-                        self._where.append((sub._parameters, name, p, p.data_ptr(), p.requires_grad))
-        self.graphs = {}   # objective.graph_key(args) -> StepGraphs
-        self._cfg = None
-        # static outputs of the graph `run` just replayed, for an objective whose `result` leaves them here (the caller
-        # takes them at once and clears this)
-        self.extra = None
-        self._side = torch.cuda.Stream(device=dev)   # the backward graphs replay here
-        self._bwd_done = None                        # event behind the last backward replay
-        self._ticket = None                          # the step whose gradients are in gflat: {"serial", "event", "g"}
-        self._serial = 0
-
-    def unchanged(self):
-        """No parameter of the three modules was replaced, moved or (un)frozen since the engine was built (its graphs bind
-        the parameters' addresses)."""
-        for d, name, p, addr, rg in self._where:
-            if d.get(name) is not p or p.data_ptr() != addr or p.requires_grad != rg:
-                return False
-        return True
-
-    # The engine hangs on the backbone module (model.__dict__) and holds graphs, streams and events: a copy or a pickle
-    # of the model (copy.deepcopy for an EMA twin, torch.save(model)) carries None instead and builds its own on first use.
-    def __deepcopy__(self, memo):
-        return None
-
-    def __reduce__(self):
-        return (type(None), ())
-
-    def _fwd(self, batch, noise):
-        args, mu, sigma = self._cfg
-        return self.objective.forward(self, args, mu, sigma, batch, noise)
-
-    def _bwd(self, loss):
-        held = [p.grad for p in self.params]
-        # tensor hooks of the caller (gradient clipping, logging, reducers) belong to ITS backward, which runs later on
-        # the node `run` returns; the passes in here are internal - and in direct mode the nodes hand autograd no
-        # gradients at all, so a hook would be called with None
-        hooks = []
-        for p in self.params:
-            h = getattr(p, "_backward_hooks", None)
-            if h:
-                hooks.append((h, list(h.items())))
-                h.clear()
-        if not own_capture_open():
-            self.gflat.zero_()  # (a replayed step: cleared by the launch that refreshes the graph's inputs, StepGraphs.refresh)
-        for p, v in zip(self.params, self.views):
-            p.grad = v
-        try:
-            with _lib.direct_grads():  # kernels accumulate straight into the static buffer
-                loss.backward(self._one)  # (a standing 1.0: backward() would fill a new one, a launch per step)
-            for p, v in zip(self.params, self.views):  # anything autograd replaced goes back into the buffer
-                if p.grad is not None and p.grad.data_ptr() != v.data_ptr():
-                    v.copy_(p.grad)
-        finally:
-            for p, h in zip(self.params, held):
-                p.grad = h
-            for h, items in hooks:
-                h.update(items)
-
-    def _fwd_bwd(self, batch, noise):
-        loss = self._fwd(batch, noise)
-        if isinstance(loss, tuple):
-            self._bwd(loss[0])
-            return loss[0].detach(), loss[1]
-        self._bwd(loss)
-        return loss.detach()
-
-    def collect(self, ticket):
-        """The gradients of the step `ticket` stands for (unscaled, read-only): the snapshot taken when a later step was
-        about to overwrite them, else the static buffer itself once its backward replay is complete."""
-        if ticket["g"] is not None:
-            return ticket["g"]
-        if ticket["serial"] != self._serial:
-            raise RuntimeError("the gradients of this do_DDM step are gone (a later step replaced them after this step's "
-                               "backward had already run once); call backward(retain_graph=...) before the next do_DDM")
-        torch.cuda.current_stream().wait_event(ticket["event"])
-        ticket["used"] = True
-        return self.gflat
-
-    def direct_backward(self, ticket):
-        """loss.backward() of the step `ticket` stands for without the autograd engine (_StepLoss): True when done."""
-        if _env("GEOSSL_NO_DIRECT_BACKWARD") or ticket.get("used") or "views" not in ticket:
-            return False
-        # hooks on the parameters' AccumulateGrad NODES (DistributedDataParallel's reducer) cannot be seen from here: with
-        # more than one rank initialised the engine runs, whoever reduces the gradients
-        dist = torch.distributed
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            return False
-        for p in self.params:
-            # (an existing gradient: accumulate like AccumulateGrad would; a tensor hook: call it like the engine would)
-            if p.grad is not None or p._backward_hooks or getattr(p, "_post_accumulate_grad_hooks", None):
-                return False
-        src = self.collect(ticket)   # (the caller's stream waits for the backward replay)
-        buf, outs = ticket.pop("views")
-        buf.copy_(src)               # d loss / d loss = 1: the engine path multiplies by it, same values
-        for p, v in zip(self.params, outs):
-            p.grad = v
-        return True
-
-    def run(self, args, batch, mu, sigma, noise, device_noise):
-        """-> `objective.result` of the replayed step (the loss, or the loss and more), or None: run this step eagerly."""
-        if getattr(batch, "_dataset", None) is None and (not batch.positions.is_cuda or batch.positions.requires_grad):
-            return None
-        obj = self.objective
-        key = obj.graph_key(args)   # (whatever a graph binds by value is part of it)
-        sg = self.graphs.get(key)
-        if sg is None:
-            sg = self.graphs[key] = StepGraphs(self._fwd_bwd, args.model_3d, split=(self._fwd, self._bwd),
-                                               mode=getattr(args, "step_graph_mode", "auto"),
-                                               normalize=obj.normalize and bool(getattr(args, "normalize", False)),
-                                               modules=(self.model, self.n1, self.n2),
-                                               noise_keys=obj.noise_keys(args), views=obj.views,
-                                               pair_tuples=obj.pair_tuples)
-            sg.zero_with_refresh = self.gflat
-        if not sg.enabled:
-            return None
-        self._cfg = (obj.step_args(args), mu, sigma)
-        g = sg.lookup(batch)
-        if g is None and not sg.capture_now(batch):
-            # first sighting of an index structure that only its own graph can serve (sampled tuples, PaiNN edge lists,
-            # batches built by hand): eager - a loader that never repeats such a structure never pays for a capture, one
-            # that comes back is captured on its second step.  Ragged SchNet batches of a loader share ONE capacity-bucket
-            # graph and equal-sized molecules one per-structure graph: those are captured right away.
-            return None
-        main = torch.cuda.current_stream()
-        if self._bwd_done is not None:
-            # the last backward replay reads the activations and writes the gradient buffer this step is about to reuse
-            main.wait_event(self._bwd_done)
-            t = self._ticket
-            if t is not None and t["g"] is None and not t.get("used"):
-                t["g"] = self.gflat.clone()  # a step still waiting for its backward() keeps its gradients
-        if g is None:
-            drawn = obj.capture_inputs(self, args, batch, mu, sigma, noise, device_noise)
-            g = sg.capture(batch, drawn)
-            if g is None:
-                return None
-            if not sg.refresh(g, batch, drawn):
-                return None
-        else:
-            if not sg.refresh(g, batch):
-                return None  # (the bucket refused the batch's tensors: this step as eager launches)
-            if obj.write_inputs is not None:
-                obj.write_inputs(self, args, sg, g, batch, mu, sigma, noise, device_noise)
-        g["graph"].replay()            # forward: the loss is on the device when this is done
-        loss = g["loss"].clone()
-        fwd_done = torch.cuda.Event()
-        fwd_done.record(main)
-        self._side.wait_event(fwd_done)
-        with torch.cuda.stream(self._side):  # backward: behind the forward, beside whatever the host queues next
-            g["graph_bwd"].replay()
-            self._bwd_done = torch.cuda.Event()
-            self._bwd_done.record(self._side)
-        self._serial += 1
-        prev = self._ticket
-        if prev is not None:
-            _restore_backward_threads(prev)  # (a loss that never saw its backward(): its switch goes back first)
-        self._ticket = _Ticket(serial=self._serial, event=self._bwd_done, g=None)
-        _single_thread_backward(self._ticket)
-        buf = torch.empty_like(self.gflat)   # this step's (scaled) gradients as autograd will receive them
-        # (a one-dimensional parameter's piece of the split already has its shape: no view for the biases - half the list)
-        self._ticket["views"] = (buf, [v if len(shape) == 1 else v.view(shape)
-                                       for v, (shape, _) in zip(buf.split_with_sizes(self.numels), self.shapes)])
-        # deferred index check of the backbone: the embedding kernel flagged an out-of-range atom type in the status
-        # word, but model.forward's own arm() does nothing while a graph is captured and a replay never reaches it -
-        # read the word here like DDMTrainer.step does (IndexError up to eight steps late, like Embedding's, not never)
-        st = self.model.__dict__.get("_geossl_status")
-        if st is not None:
-            st.poll()
-            st.arm(every=8)
-        out = _ReplayedLoss.apply(loss, self, self._ticket, *self.params).as_subclass(_StepLoss)
-        out._geossl_step = (self, self._ticket)
-        return obj.result(self, out, g)
-
-
-_MT_PENDING = []   # tickets of this process whose autograd thread switch is still to be put back
-
-
-def _single_thread_backward(ticket):
-    """The loss of a replayed step has ONE node behind it (_ReplayedLoss) and its 59 AccumulateGrads; autograd would hand
-    them to its per-device worker thread and wake the caller when it is done - a hand-over that costs 0.13 ms per
-    backward() (measured, tools/ref_loop_profile.py), a fifth of a whole step at the reference's batch size.  With
-    multithreading off the calling thread runs the backward itself.  The switch is autograd's own, thread-local
-    (torch.autograd.set_multithreading_enabled); it is turned off when do_DDM hands out the loss and put back to what the
-    caller had at the optimizer step that follows (a global optimizer post-step hook, optim.py) or, without one, at the
-    next do_DDM - it cannot be put back from inside the backward: the engine restores the thread state it saw at
-    backward()'s entry when the pass ends.  Other autograd work of the caller after the step - graphs that span several
-    devices - sees its own setting.  GEOSSL_KEEP_AUTOGRAD_THREADS leaves the switch alone."""
-    if _env("GEOSSL_KEEP_AUTOGRAD_THREADS"):
-        return
-    if torch.autograd.is_multithreading_enabled():
-        torch.autograd.set_multithreading_enabled(False)
-        # a small token, not the ticket: the pending list must not keep a step's gradient buffer alive, and the switch is
-        # THREAD-LOCAL - it is put back only by the thread that turned it off (ADVICE r05)
-        token = ticket["mt_token"] = _MtToken(threading.get_ident())
-        _MT_PENDING.append(token)
-
-
-class _MtToken:
-    __slots__ = ("thread", "live")
-
-    def __init__(self, thread):
-        self.thread, self.live = thread, True
-
-
-def _restore_backward_threads(ticket=None):
-    """Put autograd's multithreading switch back for `ticket` (None: for every step of THIS thread that is still
-    pending).  A call from another thread (a ticket finalised by the garbage collector there) leaves the token pending:
-    the owning thread's next step / optimizer hook restores it."""
-    me = threading.get_ident()
-    if ticket is not None:
-        token = ticket.pop("mt_token", None) if isinstance(ticket, dict) else None
-        todo = [] if token is None else [token]
-    else:
-        todo = [t for t in _MT_PENDING if t.thread == me]
-    for t in todo:
-        if t.live and t.thread == me:
-            t.live = False
-            torch.autograd.set_multithreading_enabled(True)
-    _MT_PENDING[:] = [p for p in _MT_PENDING if p.live]
-
-
-def _schnet_step_params(model):
-    from .Geom3D.models.schnet import _core_params
-    return _core_params(model)
 
 
 def _ddm_forward(engine, args, mu, sigma, batch, noise):

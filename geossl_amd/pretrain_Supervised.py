@@ -4,7 +4,7 @@
 ``do_Supervised(args, batch, model, graph_pred_linear, TRAIN_mean, TRAIN_std, task_id)`` is the loop body :79-104 as one
 call: the backbone's latent, then the fused head of csrc/property_head.hip with the readout inside it (graph_pred_linear,
 the normalised target, the L1 / MSE mean), forward + backward replayed from HIP graphs by
-``pretrain_GeoSSL._AutogradStep`` when gradients are wanted.  Its loss supports the reference's own
+``autograd_step._AutogradStep`` when gradients are wanted.  Its loss supports the reference's own
 ``optimizer.zero_grad(); loss.backward(); optimizer.step()`` with a stock ``torch.optim.Adam``.  ``predict_Supervised``
 is eval()'s forward (finetune_qm9.py:290-374): the de-normalised predictions.  ``SupervisedTrainer`` is the ``train()``
 body with backbone and head in one flat buffer (one fused Adam launch, one all-reduce per step) and no host sync in

@@ -5,7 +5,7 @@ on the HIP path.
 reference's ATen code).  ``do_TorsionAnglePrediction(args, batch, model, torsion_angle_predictor)`` is the loop body
 :64-78 as one call and returns the loss: the backbone's latent, then the fused triple head (csrc/torsion_head.hip: three
 per-atom projections instead of the [T, 3F] triple features, no index_add scatters), with forward + backward replayed
-from HIP graphs by ``pretrain_GeoSSL._AutogradStep`` when gradients are wanted.  The returned loss supports the
+from HIP graphs by ``autograd_step._AutogradStep`` when gradients are wanted.  The returned loss supports the
 reference's own ``optimizer.zero_grad(); loss.backward(); optimizer.step()`` with a stock ``torch.optim.Adam``.
 ``TorsionAnglePredictionTrainer`` is the ``train()`` body with all parameters in one flat buffer (one fused Adam launch,
 one all-reduce per step).
@@ -20,8 +20,8 @@ import torch.nn as nn
 
 from . import _lib, ops
 from .layout import UngroupedSuperEdges
-from .pretrain_GeoSSL import Args, TripleBatch  # (TripleBatch: the device batch type of collated triple batches)
-from .step import Objective, StepTrainer, backbone_forward, backbone_latent, engine_for
+from .batch import TripleBatch  # (the device batch type of collated triple batches)
+from .step import Args, Objective, StepTrainer, backbone_forward, backbone_latent, engine_for
 from .switches import env as _env
 
 

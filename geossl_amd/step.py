@@ -1,22 +1,23 @@
 """What every pretraining objective's step shares on the host: the descriptor the graph engine calls (``Objective``),
-the engine kept on the backbone module (``engine_for``), the backbone call (``backbone_latent`` / ``backbone_forward``)
-and the trainer base (``StepTrainer``).  The objective modules plug into this one; nothing here knows an objective by
-name.
+the engine kept on the backbone module (``engine_for``: an ``autograd_step._AutogradStep``), the backbone call
+(``backbone_latent`` / ``backbone_forward``) and the trainer base (``StepTrainer``, on ``replay.StepGraphs``).  The
+objective modules plug into this one; nothing here knows an objective by name.
 """
 import torch
 
 from . import _lib
+from .autograd_step import _AutogradStep
 from .optim import FlatParams, FusedAdam
 from .parallel import GradAllReduce
+from .replay import StepGraphs, _OWN_CAPTURE, own_capture_open  # noqa: F401
 
-_OWN_CAPTURE = [0]  # > 0 while StepGraphs._capture has a capture open
 
+class Args:
+    """The three fields do_DDM reads from the reference's argparse namespace."""
 
-def own_capture_open():
-    """True while a StepGraphs capture of this library is recording on the current stream: the one situation in which the
-    step's passes leave clearing the gradient buffer to StepGraphs.refresh.  A caller that captures the step in a CUDA
-    graph of ITS OWN gets the fill recorded into that graph like any other launch."""
-    return _OWN_CAPTURE[0] > 0 and torch.cuda.is_current_stream_capturing()
+    def __init__(self, model_3d="schnet", normalize=False):
+        self.model_3d = model_3d
+        self.normalize = normalize
 
 
 # ---- the objective, as the graph engine sees it --------------------------------------------------------------------------
@@ -25,7 +26,7 @@ def _no_inputs(engine, args, batch, mu, sigma, noise, device_noise):
 
 
 class Objective:
-    """Everything ``pretrain_GeoSSL._AutogradStep`` needs to know about ONE objective; an instance is defined next to
+    """Everything ``autograd_step._AutogradStep`` needs to know about ONE objective; an instance is defined next to
     the objective's ``*_step_fused`` and passed to the engine.  The defaults are those of a step with one head, one view
     of the molecules and no per-step input beside the batch (Distance Prediction).
 
@@ -69,7 +70,6 @@ def engine_for(model, slot, objective, n1=None, n2=None):
     is another object or a parameter was replaced, moved or frozen since (the graphs bind parameter addresses)."""
     eng = model.__dict__.get(slot)
     if eng is None or eng.n1 is not n1 or eng.n2 is not n2 or not eng.unchanged():
-        from .pretrain_GeoSSL import _AutogradStep
         eng = model.__dict__[slot] = _AutogradStep(model, n1, n2, objective=objective)
     return eng
 
@@ -138,7 +138,6 @@ class StepTrainer:
 
     def __init__(self, modules, model_3d, lr, weight_decay, use_graph, max_graphs, graph_mode, noise_keys=(), views=1,
                  one_dtype=torch.float32, pair_tuples=True):
-        from .pretrain_GeoSSL import StepGraphs
         self.model = modules[0]
         self.flat = FlatParams(modules)
         self.opt = FusedAdam(self.flat, lr=lr, weight_decay=weight_decay)
@@ -182,18 +181,16 @@ class StepTrainer:
 
     def _graph_fwd_bwd(self, batch, noise=None):
         sg = self.step_graphs
-        g = sg.lookup(batch)
-        if g is None:
-            if not sg.capture_now(batch):  # a structure only its own graph can serve, seen for the first time: eager
-                return self._eager(batch, noise)
+        g, capture = sg.plan(batch)
+        if g is None and not capture:  # a structure only its own graph can serve, seen for the first time: eager
+            return self._eager(batch, noise)
+        if capture:
             noise = self._capture_inputs(batch, noise)
-            g = sg.capture(batch, noise)
-            if g is None:  # capture failed: eager from now on
+        g = sg.load(g, batch, noise, self._write_inputs)
+        if g is None:  # (the bucket refused the batch's tensors: this step as eager launches)
+            if not sg.enabled:  # capture failed: eager from now on
                 self.use_graph = False
-                return self._eager(batch, noise)
-        if not sg.refresh(g, batch):
-            return self._eager(batch, noise)  # (the bucket refused the batch's tensors: this step as eager launches)
-        self._write_inputs(g, batch, noise)
+            return self._eager(batch, noise)
         g["graph"].replay()
         # (clones: the static outputs are overwritten by the next replay, and freed with their graph when that is dropped)
         if self.with_extra:
@@ -201,10 +198,7 @@ class StepTrainer:
         return g["loss"].clone()
 
     def _finish(self, out):
-        st = self.model.__dict__.get("_geossl_status")
-        if st is not None:  # deferred index check of the backbone (a replayed graph cannot queue the host copy itself)
-            st.poll()
-            st.arm(every=8)  # an out-of-range atom type surfaces up to eight steps late
+        _lib.poll_status(self.model)
         scale = self.reduce()
         self.opt.step(grad_scale=scale)
         return out

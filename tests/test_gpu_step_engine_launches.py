@@ -1,0 +1,295 @@
+"""The step-graph engine makes the same C-ABI calls, in the same order, on every route from a batch to a replay.
+
+Per case a few consecutive steps at the smallest shapes that take the route, with `call` of `_lib` and of every loaded
+`geossl_amd` module that imported it wrapped by a recorder: the entry points each step calls must be those below, and
+beside them the owner's `captures`, its number of graphs and the keys of a graph's entry.  A step of at most a dozen
+calls - a replay - is written out; a longer one - an eager step, or a capture with its warm-up passes - is held as
+(number of calls, sha1 of the names joined by blanks).  The lists were RECORDED ON THE PARENT of the commit that moved the
+engine out of pretrain_GeoSSL.py into geossl_amd/replay.py and geossl_amd/autograd_step.py - by `run_case` below, run
+from a job script on the code before the move, not on the code under test - so the test states that the move (and
+whatever touches the capture, the sightings memory, the static-input copy or the replay protocol next) changes no launch.
+What the launches compute is the subject of the bit-for-bit tests of the routes (test_gpu_round4.py, test_gpu_round5.py,
+test_gpu_round6.py, test_gpu_force_training.py, test_gpu_sparse_bucket.py)."""
+import hashlib
+import importlib
+import pkgutil
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+SCHNET = dict(hidden_channels=128, num_filters=128, num_interactions=2, num_gaussians=51, cutoff=5.0, node_class=9,
+              readout="mean")
+PAINN = dict(n_atom_basis=128, n_interactions=2, n_rbf=20, cutoff=5.0, max_z=9, n_out=1, readout="add")
+RAGGED = ((6, 5, 6, 4), (3, 4, 5, 6), (5, 3, 3, 6))   # (the largest first: the bucket of the first step takes all three)
+STEP_KEYS = ["batch", "extra", "graph", "graph_bwd", "loss", "noise", "zero"]
+CASES = ("a: DDMTrainer, ragged SchNet", "b: DDMTrainer, equal sizes", "c: DDMTrainer, PaiNN by hand",
+         "d: reference loop", "e: DistancePredictionTrainer", "f: SupervisedTrainer, sparse bucket",
+         "g: GraphedForward", "h: ForceTrainer, SchNet", "h: ForceTrainer, PaiNN")
+
+
+def _raw(sizes, seed):
+    from geossl_amd.synthetic import make_batch
+    raw = make_batch(0, seed=seed, sizes=np.asarray(sizes, dtype=np.int64))
+    raw["x"][:, 0] = np.clip(raw["x"][:, 0], 1, 8)
+    return raw
+
+
+def _batch(sizes, seed):
+    from geossl_amd import pretrain_GeoSSL as pg
+    return pg.Batch.from_numpy(_raw(sizes, seed), DEV)
+
+
+def _by_hand(sizes, seed):
+    """A batch as a caller builds it from its own tensors: no host sizes, the radius graph of its positions."""
+    from geossl_amd import ops
+    from geossl_amd import pretrain_GeoSSL as pg
+    from helpers import t
+    raw = _raw(sizes, seed)
+    bt = pg.Batch(t(raw["x"], DEV), t(raw["positions"], DEV), t(raw["batch"], DEV), t(raw["super_edge_index"], DEV),
+                  num_graphs=len(sizes))
+    bt.radius_edge_index = ops.radius_graph(bt.positions, 5.0, bt.batch)
+    return bt
+
+
+def _schnet(**kw):
+    from filler import fill_module_
+    from geossl_amd.Geom3D.models import SchNet
+    return fill_module_(SchNet(**dict(SCHNET, **kw))).to(DEV)
+
+
+def _painn():
+    from filler import fill_module_
+    from geossl_amd.Geom3D.models import PaiNN
+    return fill_module_(PaiNN(**PAINN)).to(DEV)
+
+
+def _heads():
+    from helpers import product_ncsn
+    return product_ncsn(128, 50, 2, DEV), product_ncsn(128, 50, 2, DEV, scale=0.9)
+
+
+class _Recorder:
+    """`call` of _lib and of every loaded geossl_amd module that holds it, wrapped; one list of names per step."""
+
+    def __init__(self, patch):
+        import geossl_amd
+        from geossl_amd import _lib
+        # every module of the package is loaded first: one that a step imported while `call` is wrapped would keep the
+        # wrapper for good (`from ._lib import call`) and hand a later case's calls to this one
+        for m in pkgutil.walk_packages(geossl_amd.__path__, "geossl_amd."):
+            importlib.import_module(m.name)
+        self.patch, self.real, self.steps, self.on = patch, _lib.call, [], False
+
+    def _record(self, name, *a):
+        if self.on:   # (between steps a case builds its next batch: not the engine's calls)
+            self.steps[-1].append(name[len("geossl_"):])
+        return self.real(name, *a)
+
+    def step(self, fn):
+        for name, mod in list(sys.modules.items()):
+            if name.startswith("geossl_amd") and mod is not None and mod.__dict__.get("call") is self.real:
+                self.patch(mod, "call", self._record)
+        self.steps.append([])
+        self.on = True
+        try:
+            out = fn()
+            torch.cuda.synchronize()
+        finally:
+            self.on = False
+        return out
+
+
+def _flat(*modules):
+    return torch.cat([p.detach().reshape(-1) for m in modules for p in m.parameters()]).clone()
+
+
+def run_case(case, patch, setenv):
+    """-> (the names each step called, {"captures", "graphs", "keys"}, {"loss": [per step], "params": one vector}).
+    patch / setenv: monkeypatch's setattr and setenv (or a job script's own)."""
+    from geossl_amd import pretrain_GeoSSL as pg
+    from geossl_amd import _lib
+    _lib.load()
+    torch.manual_seed(7)
+    torch.cuda.manual_seed(7)
+    rec = _Recorder(patch)
+    letter = case[0]
+    losses = []
+    if letter in "abc":
+        kind = "painn" if letter == "c" else "schnet"
+        model, (n1, n2) = (_painn() if letter == "c" else _schnet()), _heads()
+        tr = pg.DDMTrainer(model, n1, n2, lr=5e-4, model_3d=kind, use_graph=True)
+        if letter == "a":
+            batches = [_batch(s, 20 + i) for i, s in enumerate(RAGGED)]
+        elif letter == "b":
+            batches = [_batch((5, 5, 5, 5), 30 + i) for i in range(3)]
+        else:
+            batches = [_by_hand(RAGGED[0], 40)] * 3
+        for bt in batches:
+            losses.append(rec.step(lambda: tr.step(bt)).clone())
+        sg, modules = tr.step_graphs, (model, n1, n2)
+        stats = dict(captures=sg.captures, graphs=len(sg.graphs), keys=sorted(next(iter(sg.graphs.values()))))
+        route = next(iter(sg.graphs))[0]
+        assert route == {"a": "bucket", "b": "sizes", "c": "tensors"}[letter], route
+    elif letter == "d":
+        model, (n1, n2) = _schnet(), _heads()
+        opt = torch.optim.Adam([{"params": model.parameters()}, {"params": n1.parameters()}, {"params": n2.parameters()}],
+                               lr=5e-4)
+        args = pg.Args("schnet")
+
+        def ref_step(bt):
+            loss, _ = pg.do_DDM(args, bt, model, NCSN_models=(n1, n2), mu=0.0, sigma=0.3, graph=True)
+            value = loss.detach().item()
+            opt.zero_grad()
+            loss.backward()
+            opt.step()
+            return value
+        for i, s in enumerate(RAGGED):
+            bt = _batch(s, 20 + i)
+            losses.append(torch.tensor(rec.step(lambda: ref_step(bt))))
+        (sg,) = model.__dict__["_geossl_autograd_step"].graphs.values()
+        modules = (model, n1, n2)
+        stats = dict(captures=sg.captures, graphs=len(sg.graphs), keys=sorted(next(iter(sg.graphs.values()))))
+        assert next(iter(sg.graphs))[0] == "bucket" and next(iter(sg.graphs.values()))["graph_bwd"] is not None
+    elif letter == "e":
+        from filler import fill_module_
+        from geossl_amd.pretrain_DistancePrediction import DistancePredictionTrainer, DistancePredictor
+        model, head = _schnet(), fill_module_(DistancePredictor(128)).to(DEV)
+        tr = DistancePredictionTrainer(model, head, lr=5e-4, use_graph=True)
+        for i, s in enumerate(RAGGED):
+            bt = _batch(s, 20 + i)
+            losses.append(rec.step(lambda: tr.step(bt)).clone())
+        sg, modules = tr.step_graphs, (model, head)
+        stats = dict(captures=sg.captures, graphs=len(sg.graphs), keys=sorted(next(iter(sg.graphs.values()))))
+        assert next(iter(sg.graphs))[0] == "bucket"
+    elif letter == "f":
+        import lba_structures as ls
+        from filler import fill_module_
+        from geossl_amd.pretrain_Supervised import SupervisedTrainer
+        from helpers import t
+        setenv("GEOSSL_SPARSE_BUCKETS", "1")   # (collated batches take the sparse bucket with the switch on)
+        model, head = _schnet(cutoff=10.0), fill_module_(torch.nn.Linear(128, 1)).to(DEV)
+        tr = SupervisedTrainer(model, head, 0.0, 1.0, task_id=0, loss="mse", lr=5e-4, use_graph=True)
+        for i, sizes in enumerate(((260, 256), (256, 260), (260, 256))):
+            s = ls.structures(sizes, i)
+            bt = pg.Batch(t(s["x"], DEV), t(s["positions"], DEV), t(s["batch"], DEV), None, num_graphs=2, sizes=sizes)
+            bt.y = torch.tensor([0.5, -1.25], device=DEV)
+            losses.append(rec.step(lambda: tr.step(bt)).clone())
+        sg, modules = tr.step_graphs, (model, head)
+        stats = dict(captures=sg.captures, graphs=len(sg.graphs), keys=sorted(next(iter(sg.graphs.values()))))
+        assert next(iter(sg.graphs)) == ("bucket", 2, "sparse"), list(sg.graphs)
+    elif letter == "g":
+        from geossl_amd.graphed import GraphedForward
+        model = _schnet()
+        gf = GraphedForward(model)
+        uni = [_batch((5, 5, 5, 5), 30 + i) for i in range(2)]
+        rag = _batch(RAGGED[0], 20)
+        flat_x = _batch((5, 5, 5, 5), 32)
+        flat_x.x = flat_x.x[:, 0].contiguous()   # (a 1-D x against the 2-D x the graph of this size sequence was made on)
+        for bt in uni + [rag, rag, rag, flat_x]:   # capture, replay; eager, capture, replay; eager
+            losses.append(rec.step(lambda: gf(bt)).clone())
+        modules = (model,)
+        stats = dict(captures=gf.captures, graphs=len(gf.graphs), keys=sorted(next(iter(gf.graphs.values()))))
+        assert gf.enabled
+    else:
+        from filler import fill_module_
+        from geossl_amd.Geom3D.models.painn import Dense
+        from geossl_amd.graphed import ForceTrainer
+        kind = "painn" if case.endswith("PaiNN") else "schnet"
+        if kind == "painn":
+            model = _painn()
+            head = fill_module_(model.create_output_layers()).to(DEV)
+        else:
+            model, head = _schnet(readout="add"), fill_module_(Dense(128, 1)).to(DEV)
+        tr = ForceTrainer(model, head, model_3d=kind, lr=5e-4)
+        gen = torch.Generator().manual_seed(3)
+        kept = _by_hand((4, 4), 50)   # (PaiNN: the very same edge tensor every step)
+        for i in range(3):
+            bt = kept if kind == "painn" else _batch((4, 4), 50 + i)
+            y_e, y_f = torch.randn(2, generator=gen).to(DEV), torch.randn(8, 3, generator=gen).to(DEV)
+            losses.append(rec.step(lambda: tr.step(bt, y_e, y_f)).clone())
+        modules = (model, head)
+        stats = dict(captures=tr.captures, graphs=len(tr.graphs), keys=sorted(next(iter(tr.graphs.values()))))
+        assert tr.use_graph
+    values = {"loss": [v.detach().double().reshape(-1).cpu() for v in losses], "params": _flat(*modules).cpu()}
+    return rec.steps, stats, values
+
+
+def short(step, ordered=True):
+    """A step's names as EXPECTED holds them: written out up to a dozen, else (how many, their digest).  ordered=False:
+    the digest of the sorted names - what the force-training cases hold, whose eager and capture steps called the
+    second-order tape's entry points in an order that differed between two runs of the parent itself (the same calls
+    as often; their replay steps are written out like all others)."""
+    if len(step) <= 12:
+        return " ".join(step)
+    return (len(step), hashlib.sha1(" ".join(step if ordered else sorted(step)).encode()).hexdigest()[:16])
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_step_engine_launch_sequence(case, monkeypatch):
+    steps, stats, values = run_case(case, monkeypatch.setattr, monkeypatch.setenv)
+    assert all(torch.isfinite(v).all() for v in values["loss"]) and torch.isfinite(values["params"]).all()
+    want_steps, want_stats = EXPECTED[case]
+    assert stats == want_stats, stats
+    assert len(steps) == len(want_steps)
+    for k, (got, want) in enumerate(zip(steps, want_steps)):
+        assert short(got, ordered=not case.startswith("h")) == want, "step %d: %s" % (k, " ".join(got))
+
+
+# per case: (one entry per step in `short` form, the owner's counts and the keys of a graph's entry); written by the job
+# script that ran `run_case` on the parent commit (twice, in two processes and two orders of the cases: the same lists)
+_BUCKET_KEYS = ["batch", "bucket", "counts", "extra", "graph", "graph_bwd", "loss", "noise", "zero"]
+_FORCE_KEYS = ["bvec", "graph", "loss", "ones", "pos", "rei", "x", "y_e", "y_f"]
+EXPECTED = {
+    "a: DDMTrainer, ragged SchNet": ([
+        (67, "f1b1ce4918d00058"),
+        "gather_molecules ddm_noise_seeded adam_step",
+        "gather_molecules ddm_noise_seeded adam_step",
+    ], {"captures": 1, "graphs": 1, "keys": _BUCKET_KEYS}),
+    "b: DDMTrainer, equal sizes": ([
+        (66, "0f45ac0f6f596b2b"),
+        "copy_n ddm_noise_seeded adam_step",
+        "copy_n ddm_noise_seeded adam_step",
+    ], {"captures": 1, "graphs": 1, "keys": STEP_KEYS}),
+    "c: DDMTrainer, PaiNN by hand": ([
+        (50, "0a1a75f926780d60"),
+        (117, "e8ad290282ac8445"),
+        "copy_n ddm_noise_seeded adam_step",
+    ], {"captures": 1, "graphs": 1, "keys": STEP_KEYS}),
+    "d: reference loop": ([
+        (66, "c1a76ded1212d253"),
+        "gather_molecules adam_step",
+        "gather_molecules adam_step",
+    ], {"captures": 1, "graphs": 1, "keys": _BUCKET_KEYS}),
+    "e: DistancePredictionTrainer": ([
+        (60, "4d7f8152fc7d501f"),
+        "gather_molecules adam_step",
+        "gather_molecules adam_step",
+    ], {"captures": 1, "graphs": 1, "keys": _BUCKET_KEYS}),
+    "f: SupervisedTrainer, sparse bucket": ([
+        (67, "9de0e24d10b5d478"),
+        "gather_molecules adam_step",
+        "gather_molecules adam_step",
+    ], {"captures": 1, "graphs": 1, "keys": _BUCKET_KEYS}),
+    "g: GraphedForward": ([
+        (22, "c1eb25a53f402d28"),
+        "copy2",
+        (14, "4a54030f4f042e39"),
+        (22, "7f2d159afd8d2f3c"),
+        "copy2",
+        (14, "4a54030f4f042e39"),
+    ], {"captures": 2, "graphs": 2, "keys": ["batch_vec", "graph", "layout", "out", "pos", "x"]}),
+    "h: ForceTrainer, SchNet": ([
+        (1037, "297144397fcef8f0"),
+        "copy_n adam_step",
+        "copy_n adam_step",
+    ], {"captures": 1, "graphs": 1, "keys": _FORCE_KEYS}),
+    "h: ForceTrainer, PaiNN": ([
+        (779, "3740ceed3b937739"),
+        (2321, "1249d6c5da60340b"),
+        "copy_n adam_step",
+    ], {"captures": 1, "graphs": 1, "keys": _FORCE_KEYS}),
+}
