@@ -73,9 +73,21 @@ class _Staging:
         slot[1].record()
 
 
+def check_force(force, n_atoms):
+    """The per-atom targets of a DeviceDataset as a float32 [n_atoms, 3] tensor (where they are); ValueError for any
+    other shape or row count."""
+    f = force if torch.is_tensor(force) else torch.from_numpy(np.ascontiguousarray(force))
+    if f.dim() != 2 or f.size(1) != 3:
+        raise ValueError("force is [Ntot, 3]: one row per atom, got %s" % (tuple(f.shape),))
+    if f.size(0) != int(n_atoms):
+        raise ValueError("sizes sum to %d atoms, force has %d rows" % (int(n_atoms), f.size(0)))
+    return f.to(torch.float32)
+
+
 class DeviceDataset:
     def __init__(self, x, positions, sizes, device, option="combination", radius=None, max_num_neighbors=32,
-                 bond_index=None, bond_counts=None, y=None, triples=None, triple_counts=None, triple_angle=None):
+                 bond_index=None, bond_counts=None, y=None, triples=None, triple_counts=None, triple_angle=None,
+                 force=None):
         """x [Ntot, C] int64 (or [Ntot]: one column), positions [Ntot, 3] float32 (numpy or tensors; molecule after
         molecule), sizes [M] atoms per molecule.  option: the AtomTupleExtractor enumeration of the batches drawn from it.  radius: also build the
         per-molecule radius_edge_index (PaiNN) on this geometry.  bond_index [2, Etot] (local atom indices, molecule
@@ -83,7 +95,9 @@ class DeviceDataset:
         (or [M]): per-molecule targets, kept in device memory as float32 (the Supervised / fine-tuning steps).
         triples [3, Ttot] int (local atom indices, molecule after molecule) with triple_counts [M]: the atom triples of
         angle prediction (AtomTripleExtractor output per molecule); triple_angle [Ttot] float32 their targets, or None:
-        computed once on the device by ops.triple_angles (this library's definition: the angle at the middle atom)."""
+        computed once on the device by ops.triple_angles (this library's definition: the angle at the middle atom).
+        force [Ntot, 3] float32: a per-atom target (MD17's forces, datasets_MD17.py), one row per atom, kept in device
+        memory; a handle shows its molecules' rows as ``.force``."""
         if option not in _OPTIONS:
             raise ValueError("option is 'combination' or 'permutation'")
         dev = torch.device(device)
@@ -130,6 +144,9 @@ class DeviceDataset:
                 self.y = self.y.reshape(-1, 1)
             if self.y.dim() != 2 or self.y.size(0) != M:
                 raise ValueError("y holds one row of targets per molecule: [%d, T], got %s" % (M, tuple(self.y.shape)))
+        self.force = None
+        if force is not None:
+            self.force = check_force(force, Nt).to(dev).contiguous()
 
     def mol_off(self):
         """The atom offsets of the molecules [M + 1] as an int64 device tensor (uploaded once, on first use)."""
@@ -151,8 +168,12 @@ class DeviceDataset:
     def from_data_list(cls, data_list, device, **kw):
         """From the reference's per-molecule records (``Data`` objects with ``x`` and ``positions``,
         datasets_3D.py:69-80, ``edge_index`` when every record has one, and ``y`` - a row of targets per molecule, the
-        Molecule3D ``data.y`` - when every record has one): concatenated once, uploaded once."""
+        Molecule3D ``data.y`` - and ``force``, a row per atom, the MD17 records' - when every record has one):
+        concatenated once, uploaded once."""
         x = torch.cat([torch.as_tensor(d.x) for d in data_list], dim=0)
+        fs = [getattr(d, "force", None) for d in data_list]
+        if "force" not in kw and data_list and all(f_ is not None for f_ in fs):
+            kw["force"] = torch.cat([torch.as_tensor(f_, dtype=torch.float32).reshape(-1, 3) for f_ in fs], dim=0)
         ys = [getattr(d, "y", None) for d in data_list]
         if "y" not in kw and data_list and all(y_ is not None for y_ in ys):
             kw["y"] = torch.stack([torch.as_tensor(y_, dtype=torch.float32).reshape(-1) for y_ in ys], dim=0)
@@ -370,6 +391,7 @@ class DeviceDataset:
         N, S = hb.n_atoms, (0 if self.triples is not None else hb.n_super)   # (a triple dataset enumerates no pair tuples)
         with_edges = self.edges is not None
         blob, o = self.upload_plan(hb, with_edges)
+        hb.__dict__["_plan"] = (blob, o)   # (the uploaded offsets: a per-atom target is gathered from them, `.force`)
         x = torch.empty(N, self.x_cols, dtype=torch.int64, device=dev)
         pos = torch.empty(N, 3, dtype=torch.float32, device=dev)
         bvec = torch.empty(N, dtype=torch.int64, device=dev)
@@ -543,6 +565,26 @@ class DatasetBatch:
         if got is None:
             ids = torch.from_numpy(self.ids).to(ds.device, non_blocking=False)
             got = self.__dict__["_y"] = ds.y.index_select(0, ids).reshape(-1)
+        return got
+
+    @property
+    def force(self):
+        """The per-atom targets of the batch's atoms [N, 3] (finetune_md17.py:49 ``batch_data.force``): gathered on the
+        device on first access, in one launch (geossl_gather_atom_rows) from the source offsets the position gather
+        uploaded.  None for a dataset without them."""
+        ds = self._dataset
+        if getattr(ds, "force", None) is None:
+            return None
+        if self._mask is not None:
+            raise ValueError("a masked handle has no forces: the forces of a masked subgraph are not the frame's")
+        got = self.__dict__.get("_force")
+        if got is None:
+            from ...ops import gather_atom_rows
+            self.materialize()
+            blob, o = self.__dict__["_plan"]
+            base = blob.data_ptr()
+            got = self.__dict__["_force"] = gather_atom_rows(ds.force, base + 4 * o["src_off"], base + 4 * o["mol_ptr"],
+                                                             self.num_graphs, self.n_atoms)
         return got
 
     def to(self, device, **kw):
@@ -736,6 +778,9 @@ class DeviceLoader:
             if getattr(dataset, "triples", None) is not None:
                 raise ValueError("mask_ratio > 0 with a triple dataset is not supported: the sampled triples name atoms "
                                  "by index, and masking renumbers them")
+            if getattr(dataset, "force", None) is not None:
+                raise ValueError("mask_ratio > 0 with a dataset that holds per-atom forces is not supported: the forces "
+                                 "of a masked subgraph are not the frame's")
             dataset.check_masking(self.mask_ratio)
 
     def __len__(self):

@@ -300,6 +300,10 @@ PROTOTYPES = {
     "geossl_property_bwd_dyn": (i32, [i64, i32, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp, i32, vp, vp, vp, vp,
                                       vp, vp, i32, vp, vp]),
     "geossl_property_targets": (i32, [vp, i64, i32, i32, vp, vp, i64, vp, vp]),
+    # MD17 evaluation: energy head + seed, error sums, per-atom targets (csrc/force_head.hip)
+    "geossl_energy_head_fwd": (i32, [vp, i64, i32, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "geossl_force_metrics_accumulate": (i32, [vp, vp, i64, vp, vp, i64, vp, vp]),
+    "geossl_gather_atom_rows": (i32, [vp, i64, i32, vp, vp, i64, i64, vp, vp]),
     # LEP pair head (csrc/pair_head.hip)
     "geossl_pair_head_width_ok": (i32, [i32]),
     "geossl_pair_head_workspace_floats": (i64, [i64]),

@@ -1436,6 +1436,73 @@ def property_targets(y, task_id, mol_off, src_off, B, out):
     return out
 
 
+# ---- MD17 evaluation (csrc/force_head.hip) ------------------------------------------------------------------------------
+def energy_head(h, params, layout, readout):
+    """finetune_md17.py:94-97 after the backbone with the seed of :99's position gradient -> (energy [B], seed [N, F] =
+    d(sum of the energies) / dh), no autograd: h [N, F] the per-atom latent, params (w, b) of Linear(F, 1) or (W1, b1, w2,
+    b2) of PaiNN's default create_output_layers(), layout the batch's MolLayout, readout "mean" / "add" ("sum")."""
+    _check_property(h, layout, readout, params)
+    h = _f32(h.detach())
+    N, F = h.shape
+    B = int(layout.B)
+    if int(layout.N) != N:
+        raise ValueError("energy head: the layout has %d atoms, h %d rows" % (int(layout.N), N))
+    ps = [p.detach().contiguous() for p in params]
+    mlp = len(ps) == 4
+    energy = torch.empty(B, dtype=torch.float32, device=h.device)
+    seed = torch.empty(N, F, dtype=torch.float32, device=h.device)
+    call("geossl_energy_head_fwd", ptr(h), N, F, ptr(layout.mol_ptr), B, PROPERTY_READOUTS[readout], 1 if mlp else 0,
+         ptr(ps[0]), ptr(ps[1]), ptr(ps[2] if mlp else None), ptr(ps[3] if mlp else None), ptr(energy), ptr(seed),
+         stream())
+    return energy, seed
+
+
+def force_metrics_buffer(device):
+    """The zeroed accumulator of force_metrics_accumulate: int64 [4] holding (two fp64 sums, two int64 counts)."""
+    return torch.zeros(4, dtype=torch.int64, device=device)
+
+
+def force_metrics_accumulate(pred_energy, y, dE_dpos, force_target, acc):
+    """Adds one batch of finetune_md17.py:116-117's absolute errors onto `acc` (force_metrics_buffer): pred_energy, y [B];
+    dE_dpos (the predicted force is its negative), force_target [N, 3].  Elements whose dE_dpos is NaN are skipped on
+    both sides (:104-107).  No sync; read `acc` once with force_metrics_read."""
+    _lib.require_cuda(pred_energy, y, dE_dpos, force_target, acc)
+    pe, yy = _f32(pred_energy.detach()).reshape(-1), _f32(y.detach()).reshape(-1)
+    g, ft = _f32(dE_dpos.detach()), _f32(force_target.detach())
+    if yy.numel() != pe.numel():
+        raise ValueError("y has %d elements, pred_energy %d" % (yy.numel(), pe.numel()))
+    if g.dim() != 2 or g.size(1) != 3 or tuple(ft.shape) != tuple(g.shape):
+        raise ValueError("dE_dpos and force_target are [N, 3], got %s and %s" % (tuple(g.shape), tuple(ft.shape)))
+    if acc.dtype != torch.int64 or acc.numel() != 4 or not acc.is_contiguous():
+        raise ValueError("acc is the int64 [4] buffer of force_metrics_buffer")
+    call("geossl_force_metrics_accumulate", ptr(pe), ptr(yy), pe.numel(), ptr(g), ptr(ft), g.size(0), ptr(acc), stream())
+    return acc
+
+
+def force_metrics_read(acc):
+    """The one device read of an evaluation -> (sum |dE|, sum |dF|, energies counted, force elements counted)."""
+    host = acc.cpu()
+    sums = host[:2].view(torch.float64)
+    return float(sums[0]), float(sums[1]), int(host[2]), int(host[3])
+
+
+def gather_atom_rows(src, src_off, mol_ptr, B, N, out=None):
+    """Rows of the per-atom array src [Ntot, C] float32 of B molecules into batch order -> [N, C]: src_off (int32 [B],
+    a device address or tensor) the molecules' first rows in src, mol_ptr (int32 [B + 1]) their offsets in the batch.
+    out: a contiguous float32 [N, C] tensor to write (a graph's static input)."""
+    _lib.require_cuda(src, out)
+    if src.dtype != torch.float32 or src.dim() != 2 or not src.is_contiguous():
+        raise ValueError("src is a contiguous float32 [Ntot, C] tensor")
+    if out is None:
+        out = torch.empty(int(N), src.size(1), dtype=torch.float32, device=src.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (int(N), src.size(1)) or not out.is_contiguous():
+        raise ValueError("out is a contiguous float32 [%d, %d] tensor" % (int(N), src.size(1)))
+    a = lambda v: ptr(v) if torch.is_tensor(v) else v
+    call("geossl_gather_atom_rows", ptr(src), src.size(0), src.size(1), a(src_off), a(mol_ptr), int(B), int(N), ptr(out),
+         stream())
+    return out
+
+
 # ---- LEP pair head (csrc/pair_head.hip) ---------------------------------------------------------------------------------
 class _PairHead(torch.autograd.Function):
     """The LEP step after the backbone (finetune_lep.py:40-45) on csrc/pair_head.hip -> (loss fp32 scalar, z [B] fp32

@@ -81,6 +81,26 @@ def painn_sparse_buckets(handle):
     return True if v == "1" else bool(handle) and PAINN_SPARSE_BUCKETS_DEFAULT
 
 
+# What the unset GEOSSL_MD17_COMPLETE_EDGES means for a PaiNN batch the complete pair list can serve (finetune_md17.py):
+# the outcome of the measurement in profiles/md17_bench.json by the rule stated there.
+MD17_COMPLETE_EDGES_DEFAULT = True
+
+
+def md17_complete_edges(applies):
+    """``GEOSSL_MD17_COMPLETE_EDGES``: PaiNN's MD17 step and evaluation run on the interned complete pair list of
+    (batch size, atoms per molecule) in place of the frame's own radius list - the cosine cutoff's ``[d < r]`` factor makes
+    every pair beyond the cutoff an exact zero, and the interned index tensors let one captured graph replay for a whole
+    trajectory.  ``applies``: every molecule of the batch has the same size n <= 33 and the backbone is the stock PaiNN;
+    where it does not, no value of the switch substitutes anything.  ``1``: wherever it applies; ``0``: never - the
+    batch's own edges, the route before; unset: ``MD17_COMPLETE_EDGES_DEFAULT``."""
+    if not applies:
+        return False
+    v = env("GEOSSL_MD17_COMPLETE_EDGES")
+    if v == "0":
+        return False
+    return True if v == "1" else MD17_COMPLETE_EDGES_DEFAULT
+
+
 # What the unset GEOSSL_PAINN_TILE means for a layout with a structure above 255 atoms: the outcome of the measurement in
 # profiles/painn_tile_bench.json by the rule stated there (DESIGN section 5).
 PAINN_TILE_DEFAULT = True

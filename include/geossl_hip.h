@@ -1199,6 +1199,26 @@ int geossl_pair_position_grad_sparse(const float* pos, const float* pair_d, cons
                                      const int32_t* inc_pair, const uint32_t* inc_src, int64_t N, int64_t P, int L,
                                      float* dpos, hipStream_t stream);
 
+/* ---- MD17 evaluation: energy head with its seed, error sums, per-atom targets (csrc/force_head.hip) ----------------
+ * geossl_energy_head_fwd : energy[B] = head(readout(h)) and seed[N][F] = d(sum_b energy_b)/dh in one launch, for the two
+ *   heads and the widths of geossl_property_fwd (geossl_property_width_ok; head 0: W1 = w [F], b1 = b [1], W2 = b2 = NULL;
+ *   head 1: W1 [F/2][F], b1 [F/2], W2 = w2 [F/2], b2 [1]) with its arithmetic; readout 0 = add, 1 = mean.  mol_ptr [B + 1]
+ *   are atom offsets in [0, N]; the seed rows of every molecule are written.  Deterministic, no atomics.
+ * geossl_force_metrics_accumulate : acc = [sum |pred_energy - y| (f64), sum |-dE_dpos - force_target| (f64), B (i64),
+ *   counted force elements (i64)] (32 bytes, 8-byte aligned) has this call's sums ADDED onto it: the caller zeroes it
+ *   and reads it once per epoch.  pred_energy, y [B]; dE_dpos, force_target [N][3].  Differences in fp32, sums in fp64 in
+ *   a fixed order; an element whose dE_dpos is NaN is skipped on both sides and not counted; energies are never skipped.
+ *   One block; calls on one stream are ordered, and a captured graph may hold the launch (acc is its only state).
+ * geossl_gather_atom_rows : dst rows [mol_ptr[b], mol_ptr[b + 1]) = src rows [src_off[b], ...) for b < B; src [n_src][C],
+ *   dst [N][C] float32.  A molecule whose offsets leave either array is not copied.                                  */
+int geossl_energy_head_fwd(const float* h, int64_t N, int F, const int32_t* mol_ptr, int64_t B, int readout, int head,
+                           const float* W1, const float* b1, const float* W2, const float* b2, float* energy,
+                           float* seed, hipStream_t stream);
+int geossl_force_metrics_accumulate(const float* pred_energy, const float* y, int64_t B, const float* dE_dpos,
+                                    const float* force_target, int64_t N, void* acc, hipStream_t stream);
+int geossl_gather_atom_rows(const float* src, int64_t n_src, int C, const int32_t* src_off, const int32_t* mol_ptr,
+                            int64_t B, int64_t N, float* dst, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
