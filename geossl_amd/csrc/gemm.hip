@@ -420,6 +420,7 @@ extern "C" int geossl_linear_prepared(const float* X, int ldx, const uint32_t* i
                                       const float* res, const float* tprev, float* Y, int ldy, int64_t R, int K,
                                       int NO, int flags, hipStream_t stream) {
   if (R <= 0) return 0;
+  if (R > INT_MAX) return (int)hipErrorInvalidValue;  // (the kernels count rows in 32 bits)
   if (image == nullptr || geossl_linear_image_words(K, NO) == 0) return (int)hipErrorInvalidValue;
   if (ldx < K || ldy < NO || (ldx & 3) || (ldy & 3)) return (int)hipErrorInvalidValue;
   return launch_linear_split(X, ldx, reinterpret_cast<const float*>(image), reinterpret_cast<const u32x4*>(image), bias,
@@ -430,6 +431,7 @@ extern "C" int geossl_linear(const float* X, int ldx, const float* W, const floa
                              const float* tprev, float* Y, int ldy, int64_t R, int K, int NO, int transB, int flags,
                              hipStream_t stream) {
   if (R <= 0) return 0;
+  if (R > INT_MAX) return (int)hipErrorInvalidValue;  // (the kernels count rows in 32 bits)
   if (K % 8 != 0 || K > 256 || NO > 256) return (int)hipErrorInvalidValue;
   if (ldx < K || ldy < NO || (ldx & 3) || (ldy & 3) || (NO & 3)) return (int)hipErrorInvalidValue;
   if (K == 32 || K == 64 || K == 128)

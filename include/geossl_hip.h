@@ -179,7 +179,8 @@ int geossl_pair_product(const float* a, const float* b, const int32_t* pair_i, c
 /* ---- atom-row Linear — ATen Linear at schnet.py:99,101,166,189,191 and its autograd.
  * Y[r][n] = epi(sum_k X[r][k] * Bm[k][n]); transB=1: W is torch layout [NO][K] (forward);
  * transB=0: W is [K][NO] (backward w.r.t. input: dX = dY W).  K % 8 == 0, K,NO <= 256.  ldx / ldy: row strides of
- * X and of Y (res and tprev share ldy), so column slices of wider tensors can be read / written in place.   */
+ * X and of Y (res and tprev share ldy), so column slices of wider tensors can be read / written in place.
+ * R > INT_MAX is refused (hipErrorInvalidValue, nothing launched): the kernels count rows in 32 bits.        */
 int geossl_linear(const float* X, int ldx, const float* W, const float* bias, const float* res, const float* tprev,
                   float* Y, int ldy, int64_t R, int K, int NO, int transB, int flags, hipStream_t stream);
 
