@@ -304,6 +304,8 @@ PROTOTYPES = {
     "geossl_energy_head_fwd": (i32, [vp, i64, i32, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
     "geossl_force_metrics_accumulate": (i32, [vp, vp, i64, vp, vp, i64, vp, vp]),
     "geossl_gather_atom_rows": (i32, [vp, i64, i32, vp, vp, i64, i64, vp, vp]),
+    # evaluation passes: error sums and result rows of one batch (csrc/eval_collect.hip)
+    "geossl_eval_collect": (i32, [vp, vp, i64, i32, i64, vp, vp, vp, vp]),
     # LEP pair head (csrc/pair_head.hip)
     "geossl_pair_head_width_ok": (i32, [i32]),
     "geossl_pair_head_workspace_floats": (i64, [i64]),

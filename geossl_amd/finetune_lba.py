@@ -106,13 +106,25 @@ def predict_LBA(args, batch, model, graph_pred_linear):
 
 
 @torch.no_grad()
-def eval_LBA(args, loader, model, graph_pred_linear):
+def eval_LBA(args, loader, model, graph_pred_linear, use_graph=False):
     """examples/finetune_lba.py eval(), :68-101 -> (rmse, pearson, spearman, y_true, y_pred).  Batches are moved to the
-    backbone's device; Pearson is np.corrcoef, Spearman the Pearson correlation of average ranks."""
+    backbone's device; Pearson is np.corrcoef, Spearman the Pearson correlation of average ranks.  ``use_graph=True`` (GPU
+    modules; CPU modules take the loop below whole): the loop is ``evaluate.Evaluator.run`` - forward-only graphs on the
+    training step's routing, no read inside the loop - and y_true / y_pred are float32 numpy arrays read once.  The one
+    known difference: the RMSE is sqrt(sum of the fp32 squared errors in fp64 over all rows / rows) instead of the sum of
+    per-batch fp32 means times B."""
     model.eval()
     if graph_pred_linear is not None:
         graph_pred_linear.eval()
     device = next(model.parameters()).device
+    if use_graph and device.type == "cuda":
+        if args.model_3d not in ("schnet", "painn"):
+            raise Exception("3D model {} not included.".format(args.model_3d))
+        from .evaluate import evaluator_for
+        ev = evaluator_for(model, graph_pred_linear, args.model_3d, "property", 0)
+        ev.stats.set(0.0, 1.0)
+        _, sum_s, rows, y_true, y_pred = ev.run(loader, eager=lambda b: predict_LBA(args, b, model, graph_pred_linear))
+        return (np.sqrt(sum_s / rows), np.corrcoef(y_true, y_pred)[0, 1], spearman(y_true, y_pred), y_true, y_pred)
 
     loss_all, total = 0, 0
     y_true, y_pred = [], []

@@ -320,13 +320,24 @@ def average_precision(y_true, y_score):
 
 
 @torch.no_grad()
-def eval_LEP(args, loader, model, graph_pred_linear):
+def eval_LEP(args, loader, model, graph_pred_linear, use_graph=False):
     """examples/finetune_lep.py eval(), :66-101 -> (sqrt(sum_b loss_b B_b / total), roc, pr, y_true, y_pred) with the
-    script's nn.BCEWithLogitsLoss().  Batches are moved to the backbone's device."""
+    script's nn.BCEWithLogitsLoss().  Batches are moved to the backbone's device.  ``use_graph=True`` (GPU modules; CPU
+    modules take the loop below whole): the loop is ``evaluate.Evaluator.run`` - forward-only graphs of the one-pass batch
+    on the training step's routing, no read inside the loop - and y_true / y_pred are float32 numpy arrays read once.
+    The one known difference: the loss figure is sqrt(sum of the fp32 BCE terms in fp64 over all rows / rows) instead of
+    the sum of per-batch fp32 means times B."""
     model.eval()
     if graph_pred_linear is not None:
         graph_pred_linear.eval()
     device = next(model.parameters()).device
+    if use_graph and device.type == "cuda":
+        if args.model_3d not in ("schnet", "painn"):
+            raise Exception("3D model {} not included.".format(args.model_3d))
+        from .evaluate import evaluator_for
+        ev = evaluator_for(model, graph_pred_linear, args.model_3d, "pair")
+        sum_a, _, rows, y_true, y_pred = ev.run(loader, eager=lambda b: predict_LEP(args, b, model, graph_pred_linear))
+        return np.sqrt(sum_a / rows), roc_auc(y_true, y_pred), average_precision(y_true, y_pred), y_true, y_pred
     criterion = nn.BCEWithLogitsLoss()
 
     loss_all, total = 0, 0
@@ -412,5 +423,19 @@ class LEPTrainer(StepTrainer):
         return super()._graph_fwd_bwd(self._one_pass(batch), noise)
 
     def predict(self, batch):
-        """eval()'s logits of one batch with the trainer's parameters."""
-        return predict_LEP(_StepArgs(self.model_3d), batch, self.model, self.head)
+        """eval()'s logits of one batch with the trainer's parameters; with ``use_graph`` through the forward-only graphs
+        of ``evaluate.Evaluator``."""
+        eager = lambda b: predict_LEP(_StepArgs(self.model_3d), b, self.model, self.head)
+        if self.use_graph:
+            from .evaluate import evaluator_for
+            _check_handle(batch, self.model_3d)
+            return evaluator_for(self.model, self.head, self.model_3d, "pair").predict(batch, eager)
+        return eager(batch)
+
+    def evaluate(self, loader, use_graph=None):
+        """eval() over a loader with the trainer's parameters -> what ``eval_LEP`` returns.  use_graph None: replayed
+        when the trainer's ``use_graph`` is on, else the measured default ``evaluate.USE_GRAPH_DEFAULT["pair"]``."""
+        if use_graph is None:
+            from .evaluate import USE_GRAPH_DEFAULT
+            use_graph = self.use_graph or USE_GRAPH_DEFAULT["pair"]
+        return eval_LEP(_StepArgs(self.model_3d), loader, self.model, self.head, use_graph=use_graph)

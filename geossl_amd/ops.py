@@ -1503,6 +1503,46 @@ def gather_atom_rows(src, src_off, mol_ptr, B, N, out=None):
     return out
 
 
+# ---- evaluation passes (csrc/eval_collect.hip) --------------------------------------------------------------------------
+EVAL_KINDS = {"regression": 0, "bce": 1}
+
+
+def eval_buffer(device):
+    """The zeroed accumulator of eval_collect: int64 [4] holding (fp64 sum a, fp64 sum s, int64 rows, one unused word)."""
+    return torch.zeros(4, dtype=torch.int64, device=device)
+
+
+def eval_collect(pred, target, kind, offset, out_pred, out_true, acc):
+    """One batch of an evaluation pass onto `acc` (eval_buffer) and into the result arrays: pred, target float32 [B];
+    kind "regression" / 0 (a = |pred - target|, s = (pred - target)^2) or "bce" / 1 (a = the BCE-with-logits term of the
+    logit pred and the label target, s = 0); out_pred / out_true: float32 [M] arrays whose rows [offset, offset + B)
+    are written, or None (the sums alone).  No sync; read `acc` once with eval_read."""
+    kind = EVAL_KINDS.get(kind, kind)
+    if kind not in (0, 1):
+        raise ValueError("eval_collect: kind is 'regression' (0) or 'bce' (1), got %r" % (kind,))
+    _lib.require_cuda(pred, target, out_pred, out_true, acc)
+    p, t = _f32(pred.detach()).reshape(-1), _f32(target.detach()).reshape(-1)
+    B, offset = p.numel(), int(offset)
+    if t.numel() != B:
+        raise ValueError("eval_collect: target has %d elements, pred %d" % (t.numel(), B))
+    if acc.dtype != torch.int64 or acc.numel() != 4 or not acc.is_contiguous():
+        raise ValueError("eval_collect: acc is the int64 [4] buffer of eval_buffer")
+    for o in (out_pred, out_true):
+        if o is not None and (o.dtype != torch.float32 or o.dim() != 1 or not o.is_contiguous() or offset < 0
+                              or offset + B > o.numel()):
+            raise ValueError("eval_collect: a result array is a contiguous float32 [M] with offset + B <= M "
+                             "(offset %d, B %d)" % (offset, B))
+    call("geossl_eval_collect", ptr(p), ptr(t), B, kind, offset, ptr(out_pred), ptr(out_true), ptr(acc), stream())
+    return acc
+
+
+def eval_read(acc):
+    """The one small device read of an evaluation pass -> (sum a, sum s, rows)."""
+    host = acc.cpu()
+    sums = host[:2].view(torch.float64)
+    return float(sums[0]), float(sums[1]), int(host[2])
+
+
 # ---- LEP pair head (csrc/pair_head.hip) ---------------------------------------------------------------------------------
 class _PairHead(torch.autograd.Function):
     """The LEP step after the backbone (finetune_lep.py:40-45) on csrc/pair_head.hip -> (loss fp32 scalar, z [B] fp32

@@ -6,10 +6,12 @@ call: the backbone's latent, then the fused head of csrc/property_head.hip with 
 the normalised target, the L1 / MSE mean), forward + backward replayed from HIP graphs by
 ``autograd_step._AutogradStep`` when gradients are wanted.  Its loss supports the reference's own
 ``optimizer.zero_grad(); loss.backward(); optimizer.step()`` with a stock ``torch.optim.Adam``.  ``predict_Supervised``
-is eval()'s forward (finetune_qm9.py:290-374): the de-normalised predictions.  ``SupervisedTrainer`` is the ``train()``
+is eval()'s forward (finetune_qm9.py:290-374): the de-normalised predictions; ``eval_Supervised`` is eval() over a loader
+(:278-384), replayed from the forward-only graphs of geossl_amd/evaluate.py.  ``SupervisedTrainer`` is the ``train()``
 body with backbone and head in one flat buffer (one fused Adam launch, one all-reduce per step) and no host sync in
 ``step``.  Anything the kernels do not serve runs the reference's own ATen lines on our backbone.
 """
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -275,6 +277,58 @@ def predict_Supervised(args, batch, model, graph_pred_linear, TRAIN_mean, TRAIN_
     return ops.property_predict(h, ps, lay, readout_of(model), _stats_tensor(h.device, TRAIN_mean, TRAIN_std), dyn=dyn)
 
 
+@torch.no_grad()
+def eval_Supervised(args, loader, model, graph_pred_linear, TRAIN_mean, TRAIN_std, task_id=6, use_graph=None,
+                    arrays=True, stats=None):
+    """examples/finetune_qm9.py eval(), :278-384 -> (mae, y_true, y_scores): float32 numpy arrays in loader order, y_true
+    the raw target column, y_scores = pred * TRAIN_std + TRAIN_mean, mae = np.mean(np.abs(y_scores - y_true)) of the two
+    arrays on the host.  Batches are moved to the backbone's device.  ``use_graph`` (None:
+    ``evaluate.USE_GRAPH_DEFAULT["property"]``, set from the measurement in DESIGN 5): the loop is ``evaluate.Evaluator.run`` - one forward-only graph per batch size
+    of a ragged loader, the rows collected on the device by one launch per batch, one read of each array behind the loop;
+    a batch the fused head refuses gets ``predict_Supervised`` as it is, and CPU modules take the reference's loop whole.
+    ``arrays=False`` -> the MAE alone, from the fp64 sum of |y_scores - y_true| kept on the device (graph route; else
+    from the arrays).  stats: a ``_Stats`` the graphs read instead of the evaluator's own (the trainer's)."""
+    if args.model_3d not in ("schnet", "painn"):
+        raise Exception("3D model {} not included.".format(args.model_3d))
+    model.eval()
+    if graph_pred_linear is not None:
+        graph_pred_linear.eval()
+    params = list(model.parameters())
+    device = params[0].device if params else torch.device("cpu")
+    from . import evaluate
+    if use_graph is None:
+        use_graph = evaluate.USE_GRAPH_DEFAULT["property"]
+    if use_graph and device.type == "cuda":
+        ev = evaluate.evaluator_for(model, graph_pred_linear, args.model_3d, "property", task_id, stats=stats)
+        ev.stats.set(TRAIN_mean, TRAIN_std)
+        sum_a, _, rows, y_true, y_scores = ev.run(
+            loader, arrays, eager=lambda b: predict_Supervised(args, b, model, graph_pred_linear, TRAIN_mean, TRAIN_std))
+        if not arrays:
+            return sum_a / rows if rows else float("nan")
+        mae = np.mean(np.abs(y_scores - y_true))
+        return mae, y_true, y_scores
+
+    y_true = []
+    y_scores = []
+    for batch in loader:
+        if hasattr(batch, "to"):
+            batch = batch.to(device)
+        pred = predict_Supervised(args, batch, model, graph_pred_linear, TRAIN_mean, TRAIN_std)
+        B = pred.size()[0]
+        y = batch.y.view(B, -1)[:, task_id]
+
+        y_true.append(y)
+        y_scores.append(pred)
+
+    y_true = torch.cat(y_true, dim=0).cpu().numpy()
+    y_scores = torch.cat(y_scores, dim=0).cpu().numpy()
+
+    mae = np.mean(np.abs(y_scores - y_true))
+    if not arrays:
+        return float(mae)
+    return mae, y_true, y_scores
+
+
 # -------------------------------------------------------------------------------------------------------- trainer
 class SupervisedTrainer(StepTrainer):
     """The body of ``train()`` (pretrain_Supervised.py:66-119, finetune_qm9.py:163-275): backbone latent, fused property
@@ -334,6 +388,22 @@ class SupervisedTrainer(StepTrainer):
         return super().step(batch)
 
     def predict(self, batch):
-        """eval()'s predictions of one batch with the trainer's parameters and (mean, std)."""
+        """eval()'s predictions of one batch with the trainer's parameters and (mean, std); with ``use_graph`` through
+        the forward-only graphs of ``evaluate.Evaluator`` (which read the trainer's (mean, std) tensor)."""
         mean, std = self.stats.host
-        return predict_Supervised(self.args, batch, self.model, self.head, mean, std)
+        eager = lambda b: predict_Supervised(self.args, b, self.model, self.head, mean, std)
+        if self.use_graph:
+            from .evaluate import evaluator_for
+            return evaluator_for(self.model, self.head, self.model_3d, "property", self.task_id,
+                                 stats=self.stats).predict(batch, eager)
+        return eager(batch)
+
+    def evaluate(self, loader, arrays=True, use_graph=None):
+        """eval() over a loader with the trainer's parameters and (mean, std) -> what ``eval_Supervised`` returns:
+        (mae, y_true, y_scores), or the MAE alone with ``arrays=False``.  use_graph None: replayed when the trainer's
+        ``use_graph`` is on, else ``eval_Supervised``'s measured default."""
+        mean, std = self.stats.host
+        if use_graph is None:
+            use_graph = True if self.use_graph else None
+        return eval_Supervised(self.args, loader, self.model, self.head, mean, std, self.task_id, use_graph=use_graph,
+                               arrays=arrays, stats=self.stats)

@@ -1220,6 +1220,16 @@ int geossl_force_metrics_accumulate(const float* pred_energy, const float* y, in
 int geossl_gather_atom_rows(const float* src, int64_t n_src, int C, const int32_t* src_off, const int32_t* mol_ptr,
                             int64_t B, int64_t N, float* dst, hipStream_t stream);
 
+/* ---- evaluation passes: error sums and result rows of one batch (csrc/eval_collect.hip) -----------------------------
+ * geossl_eval_collect : acc = [sum a (f64), sum s (f64), rows (i64), unused (i64)] (32 bytes, 8-byte aligned) has this
+ *   batch's sums and B ADDED onto it: the caller zeroes it before a pass and reads it once behind it.  Per row, in fp32:
+ *   kind 0 (regression) d = pred - target, a = |d|, s = d d; kind 1 (BCE with logits, z = pred, y = target)
+ *   a = max(z, 0) - z y + log1p(exp(-|z|)), s = 0; the sums in fp64 in a fixed order, no atomics.  out_pred[offset + b] =
+ *   pred[b] and out_true[offset + b] = target[b] for b < B; either output may be NULL (the sums alone).  offset is a host
+ *   value (the launch is made eagerly behind a replay).  One block; B = 0 returns 0 without a launch.                  */
+int geossl_eval_collect(const float* pred, const float* target, int64_t B, int kind, int64_t offset, float* out_pred,
+                        float* out_true, void* acc, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
