@@ -24,6 +24,7 @@ from torch.utils.data import DataLoader
 
 from ... import _lib
 from ..._lib import call, ptr, stream
+from ...batch import sampled_count
 from ...layout import get_layout
 
 _INDEX_KEYS = ("edge_index", "radius_edge_index", "super_edge_index")  # offset by the node count when collated (:64-65)
@@ -98,7 +99,7 @@ class AtomTupleExtractor:
         sei = _tuples_np(n, self.option)
         if self.ratio < 1:
             M = sei.shape[1]
-            sampled_M = int(M * self.ratio)
+            sampled_M = sampled_count(M, self.ratio)
             sampled = np.random.choice(M, sampled_M, replace=False)
             sei = sei[:, sampled]
         return torch.tensor(sei, dtype=torch.long)
@@ -110,6 +111,9 @@ class AtomTupleExtractor:
         # the full enumeration is a function of the atom count: collated batches of such molecules can share step graphs
         # (batch.structure_fingerprint); a sampled subset (ratio < 1) is not
         data._sei_canonical = self.option if self.ratio >= 1 else None
+        # ... but HOW MANY it keeps is (batch.sampled_count): collated batches of such molecules can share the step graph
+        # of a sampled capacity bucket, which takes the tuples themselves as data (bucket.option_of)
+        data._sei_sampled = (self.option, float(self.ratio)) if self.ratio < 1 else None
         return data
 
     def _from_batch_vector(self, batch):
@@ -143,6 +147,7 @@ class BatchAtomTuple(Data):
         self.batch = batch
         self._sizes = None       # atoms per molecule (host integers) when the collation knows them
         self._canonical = None   # the AtomTupleExtractor option when super_edge_index is its full enumeration
+        self._sampled = None     # (option, ratio) when it is AtomTupleExtractor(ratio < 1) output of every molecule
         self._num_graphs = None
 
     @staticmethod
@@ -173,6 +178,8 @@ class BatchAtomTuple(Data):
         out._num_graphs = len(sizes)
         marks = {getattr(data, "_sei_canonical", None) for data in data_list}
         out._canonical = marks.pop() if len(marks) == 1 else None
+        marks = {getattr(data, "_sei_sampled", None) for data in data_list}
+        out._sampled = marks.pop() if len(marks) == 1 and out._canonical is None else None
         return out.contiguous()
 
     @classmethod

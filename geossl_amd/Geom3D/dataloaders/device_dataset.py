@@ -31,6 +31,13 @@ step at the reference's batch size).  Here the molecules are uploaded once:
   handle takes a count launch and a read-back of B counts before the gather; a PaiNN capacity bucket (``bucket.Bucket.
   fill``) keeps the counts on the device instead (``geossl_masked_edge_offsets``) and is sized by the handle's host-side
   bound ``n_edges_bound``.
+* ``DeviceLoader(tuple_ratio=r)`` yields SAMPLED handles: the reference's ``AtomTupleExtractor(ratio < 1)``
+  (``--distance_sample_ratio``) - every molecule keeps ``int(M * r)`` of its M tuples (``batch.sampled_count``: known on
+  the host before the draw, like a masked batch's sizes), chosen on the device by ``geossl_sampled_tuples``
+  (csrc/sampled_tuples.hip, ``tuple_rng="device"``) or by the reference's own ``np.random.choice`` calls on the host
+  (``"numpy"``).  Such a handle carries the kept counts and the mark ``_sampled = (option, ratio)`` (``_canonical`` is
+  None: nothing about it is the full enumeration); a sampled capacity bucket draws its tuples behind the gather, and
+  ``handle.super_edge_index`` is the same launch into fresh memory.
 * ``PairedDeviceDataset``: LEP's protein-ligand pairs (Geom3D/dataloaders/dataloaders_LEP.py) - ONE ``DeviceDataset``
   over the 2M structures, active m at id m and inactive m at id M + m, with the labels ``y [M]`` beside it.  The loader
   yields ``PairedBatch`` handles; the batch of 2B structures ``[active | inactive]`` that the one-pass step runs on
@@ -43,7 +50,7 @@ import torch
 
 from ... import _lib
 from ..._lib import call, ptr, stream
-from ...batch import Batch, TripleBatch
+from ...batch import Batch, TripleBatch, kept_tuples
 from . import masking
 
 _OPTIONS = {"combination": 0, "permutation": 1}
@@ -318,14 +325,16 @@ class DeviceDataset:
         return DatasetBatch(self, ids)
 
     def upload_plan(self, hb, with_edges):
-        """int32 words [src_off (B) | mol_ptr (B+1) | se_ptr (B+1) | e_src_off (B) | e_ptr (B+1)] of a handle on the
-        device (fresh memory) -> (tensor, offsets)."""
+        """int32 words [src_off (B) | mol_ptr (B+1) | se_ptr (B+1) | e_src_off (B) | e_ptr (B+1) | mol_id (B, a sampled
+        handle)] of a handle on the device (fresh memory) -> (tensor, offsets)."""
         B = hb.num_graphs
         o = {"src_off": 0, "mol_ptr": B, "se_ptr": 2 * B + 1}
         words = 3 * B + 2
         if with_edges:
             o["e_src_off"], o["e_ptr"] = words, words + B
             words += 2 * B + 1
+        if hb._sampled is not None:
+            o["mol_id"], words = words, words + B
         slot = self._staging.take(words)
         h = slot[0].numpy()
         h[0:B] = self.off[hb.ids]
@@ -333,8 +342,12 @@ class DeviceDataset:
         np.cumsum(hb._sizes, out=mp[1:])
         h[B:2 * B + 1] = mp
         sp = np.zeros(B + 1, dtype=np.int64)
-        pairs = self.pairs[hb.ids] if hb._mask is None else hb._sizes * (hb._sizes - 1) // 2
-        np.cumsum(pairs * (1 if self.option == "combination" else 2), out=sp[1:])
+        if hb._sampled is not None:   # (the kept counts; the draw's counter: the low word of the dataset ids)
+            np.cumsum(hb.tuple_counts, out=sp[1:])
+            h[o["mol_id"]:o["mol_id"] + B] = (hb.ids & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+        else:
+            pairs = self.pairs[hb.ids] if hb._mask is None else hb._sizes * (hb._sizes - 1) // 2
+            np.cumsum(pairs * (1 if self.option == "combination" else 2), out=sp[1:])
         h[2 * B + 1:3 * B + 2] = sp
         if with_edges and hb._mask is not None:   # (masked: the batch's edge offsets follow the count launch)
             h[o["e_src_off"]:o["e_src_off"] + B] = self.edge_off[hb.ids]
@@ -401,7 +414,8 @@ class DeviceDataset:
         base = blob.data_ptr()
         g.src_off, g.mol_ptr, g.se_ptr = base + 4 * o["src_off"], base + 4 * o["mol_ptr"], base + 4 * o["se_ptr"]
         g.x_dst, g.pos_dst, g.batch_dst = ptr(x), ptr(pos), ptr(bvec)
-        if S:
+        sampled = hb._sampled is not None   # (its tuples come from geossl_sampled_tuples behind the gather)
+        if S and not sampled:
             g.sei0, g.sei1 = ptr(sei[0]), ptr(sei[1])
         rei = None
         if hb._mask is not None:
@@ -422,9 +436,30 @@ class DeviceDataset:
             call("geossl_gather_molecules", C.byref(g), B, stream())
         if self.triples is not None:   # a triple dataset: the handle shows its triples and their angles
             return self._collate_triples(hb, x, pos, bvec, rei, blob, o)
-        out = Batch(x, pos, bvec, sei, rei, B, hb._sizes, self.option)
+        if sampled:
+            self._sampled_tuples(hb, blob, o, sei)
+        out = Batch(x, pos, bvec, sei, rei, B, hb._sizes, None if sampled else self.option)
+        out._sampled = hb._sampled
         prepare_batch(bvec, sei, hb._sizes, lazy=True)
         return out
+
+    def _sampled_tuples(self, hb, blob, o, sei):
+        """The tuples of a sampled handle into `sei` [2, S]: drawn by geossl_sampled_tuples from the handle's seed, or -
+        a host-drawn list - copied in and checked by it; the same launch a bucket fill makes for the handle."""
+        draw, B, base = hb._tuple_draw, hb.num_graphs, blob.data_ptr()
+        if not sei.size(1):
+            return
+        if draw.seed is None:
+            sei.copy_(torch.from_numpy(draw.tuples))
+        st = self.__dict__.get("_tuple_status")
+        if st is None:
+            st = self.__dict__["_tuple_status"] = _lib.StatusWord(self.device, "a sampled handle's tuples leave their "
+                                                                  "molecules")
+        st.poll()
+        call("geossl_sampled_tuples", base + 4 * o["mol_ptr"], base + 4 * o["se_ptr"], B, _OPTIONS[self.option],
+             base + 4 * o["mol_id"], 0 if draw.seed is None else 1, 0 if draw.seed is None else int(draw.seed),
+             hb.n_atoms, sei.size(1), ptr(sei[0]), ptr(sei[1]), None, None, ptr(st.word), stream())
+        st.arm(every=8)
 
     def _collate_triples(self, hb, x, pos, bvec, rei, blob, o):
         from ...layout import prepare_batch
@@ -500,6 +535,9 @@ class DeviceDataset:
             call("geossl_gather_molecules", C.byref(g), B, stream())
 
 
+_SAMPLED_STAMP = [0]   # the last stamp handed to a sampled handle's fingerprint (never handed out again)
+
+
 class DatasetBatch:
     """``batch_size`` molecules of a ``DeviceDataset`` by id: what the loader hands to a step.  Host side only - ids,
     sizes, counts; the collated tensors exist once somebody asks for them.  `mask` (masking.MaskDraw): a masked batch
@@ -507,7 +545,7 @@ class DatasetBatch:
     when it is collated (``n_edges`` is None until then; ``n_edges_bound`` is an upper bound known on the host, which is
     what a PaiNN capacity bucket is sized by - its fill counts the survivors on the device and reads nothing back)."""
 
-    def __init__(self, dataset, ids, mask=None):
+    def __init__(self, dataset, ids, mask=None, tuples=None):
         self._dataset = dataset
         self.ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int64))
         if self.ids.ndim != 1 or not self.ids.size:
@@ -524,6 +562,17 @@ class DatasetBatch:
         # a triple dataset: the handle's super_edge_index are its sampled triples - nothing the sizes determine
         self._triples = getattr(dataset, "triples", None) is not None
         self._canonical = None if self._triples else dataset.option
+        # `tuples` (TupleDraw): a SAMPLED batch - AtomTupleExtractor(ratio < 1) over its molecules.  The kept counts are a
+        # function of the sizes (``tuple_counts``); which tuples is the draw's.  ``_sampled`` = (option, ratio) is the mark
+        # a sampled capacity bucket reads (bucket.option_of); ``_canonical`` stays None: nothing here is the enumeration
+        self._sampled, self._tuple_draw, self.tuple_counts = None, tuples, None
+        if tuples is not None:
+            if self._triples:
+                raise ValueError("sampled pair tuples of a triple dataset are not supported: its batches show triples")
+            self._canonical, self._sampled = None, (dataset.option, float(tuples.ratio))
+            self.tuple_counts = kept_tuples(self._sizes, dataset.option, tuples.ratio)
+            if tuples.tuples is not None and tuples.tuples.shape != (2, int(self.tuple_counts.sum())):
+                raise ValueError("the tuples of a sampled batch hold int(M * ratio) columns per molecule")
         if self._triples and mask is not None:
             raise ValueError("atom masking of a triple dataset is not supported (its triples name atoms by index)")
         self.n_triples = int(dataset.triple_cnt[self.ids].sum()) if self._triples else 0
@@ -533,6 +582,8 @@ class DatasetBatch:
         self.n_atoms = int(self._sizes.sum())
         P = int(dataset.pairs[self.ids].sum()) if mask is None else int((self._sizes * (self._sizes - 1) // 2).sum())
         self.n_super = P if dataset.option == "combination" else 2 * P
+        if tuples is not None:
+            self.n_super = int(self.tuple_counts.sum())
         self.n_edges = int(dataset.edge_cnt[self.ids].sum()) if dataset.edges is not None and mask is None else None
         # what a capacity is sized by: the edge count, or - masked - a host-side upper bound on the survivors (a molecule
         # keeps at most the edges it has and at most the k (k - 1) ordered pairs of its k kept atoms); None without edges
@@ -600,10 +651,34 @@ class DatasetBatch:
         fp = self.__dict__.get("_fp")
         if fp is None and self._triples:   # (sampled triples: only the same molecules share index tensors)
             fp = self.__dict__["_fp"] = ("triples", id(self._dataset), self.ids.tobytes())
+        if fp is None and self._sampled is not None:
+            # sampled tuples: only the same draw shares index tensors - this handle alone.  A lifetime-unique stamp, not
+            # id(): a shuffled loader's handles are freed step by step and CPython hands their addresses out again
+            _SAMPLED_STAMP[0] += 1
+            fp = self.__dict__["_fp"] = ("sampled", _SAMPLED_STAMP[0])
         if fp is None:
             fp = self.__dict__["_fp"] = ("sizes", self._canonical, self.n_atoms, self.n_super,
                                          np.asarray(self._sizes, dtype=np.int32).tobytes())
         return fp
+
+
+class TupleDraw:
+    """How the tuples of one sampled batch are chosen: `seed` (device draw, geossl_sampled_tuples) or `tuples` (the
+    host's list: int64 [2, S] batch atom ids, molecule after molecule, each molecule's in the order np.random.choice
+    drew them - what the host extractor's collated batch holds)."""
+
+    def __init__(self, ratio, seed=None, tuples=None):
+        self.ratio, self.seed, self.tuples = ratio, seed, tuples
+
+
+TUPLE_RNGS = ("device", "numpy")
+
+
+def check_tuple_ratio(ratio):
+    r = float(ratio)
+    if not (0.0 < r <= 1.0):
+        raise ValueError("tuple_ratio is in (0, 1], got %r" % (ratio,))
+    return r
 
 
 class PairedDeviceDataset:
@@ -758,13 +833,22 @@ class DeviceLoader:
     a generator seeded by one draw of the default generator), so a run is reproducible against the reference's loader."""
 
     def __init__(self, dataset, batch_size=1, shuffle=True, drop_last=False, generator=None, mask_ratio=0.0,
-                 mask_rng="device"):
+                 mask_rng="device", tuple_ratio=1.0, tuple_rng="device"):
         """mask_ratio > 0: yield masked handles (the reference's ``--GeoSSL_atom_masking_ratio``, datasets_3D.py:77-78).
         mask_rng "device": the kept atoms are drawn on the GPU from Philox-4x32-10, keyed by one np.random.randint
         draw per epoch (so np.random.seed(seed) repeats a run) with counter (molecule id, draw index); the rule is in
         include/geossl_hip.h (geossl_gather_masked_molecules) and DESIGN 2.  "numpy": the reference's own BFS and
         np.random draws on the host, molecule after molecule in batch order when the handle is yielded (bit-for-bit
-        the masks of a reference run; about as slow as it)."""
+        the masks of a reference run; about as slow as it).
+
+        tuple_ratio < 1: yield SAMPLED handles - the reference's ``--distance_sample_ratio``, AtomTupleExtractor(ratio)
+        (pretrain_GeoSSL.py:295, pretrain_DistancePrediction.py:111): every molecule keeps int(M * ratio) of its M
+        tuples.  tuple_rng "device": the kept tuples are drawn on the GPU (geossl_sampled_tuples: the smallest Philox
+        keys of the enumeration's slots, counter (slot, molecule id); the rule is in include/geossl_hip.h), keyed by one
+        more np.random.randint draw per epoch, made after the mask seed and only when tuple_ratio < 1.  "numpy": the
+        reference's own np.random.choice call per molecule in batch order when the handle is yielded; with
+        mask_rng="numpy" the two interleave per molecule, mask draws first (Molecule3DDataset.__getitem__, then the
+        transform).  Not for triple datasets, paired datasets or molecules above 255 atoms (the sparse bucket)."""
         self.dataset, self.batch_size, self.shuffle, self.drop_last = dataset, int(batch_size), shuffle, drop_last
         self.generator = generator
         self.mask_ratio = masking.check_ratio(mask_ratio)
@@ -782,6 +866,20 @@ class DeviceLoader:
                 raise ValueError("mask_ratio > 0 with a dataset that holds per-atom forces is not supported: the forces "
                                  "of a masked subgraph are not the frame's")
             dataset.check_masking(self.mask_ratio)
+        self.tuple_ratio = check_tuple_ratio(tuple_ratio)
+        if tuple_rng not in TUPLE_RNGS:
+            raise ValueError("tuple_rng is 'device' or 'numpy'")
+        self.tuple_rng = tuple_rng
+        if self.tuple_ratio < 1:
+            if isinstance(dataset, PairedDeviceDataset):
+                raise ValueError("tuple_ratio < 1 with a paired dataset is not supported: the LEP step reads no tuples "
+                                 "and its loader samples none")
+            if getattr(dataset, "triples", None) is not None:
+                raise ValueError("tuple_ratio < 1 with a triple dataset is not supported: its batches show the sampled "
+                                 "triples, not pair tuples (sample those with sample_triples(ratio))")
+            if len(dataset) and int(dataset.sizes.max()) > 255:
+                raise ValueError("tuple_ratio < 1 takes molecules of at most 255 atoms: larger structures go through the "
+                                 "sparse bucket, which enumerates no tuples")
 
     def __len__(self):
         n = len(self.dataset)
@@ -803,17 +901,38 @@ class DeviceLoader:
 
     def __iter__(self):
         order, bs = self.order(), self.batch_size
-        r = self.mask_ratio
-        if r == 0:
+        r, tr = self.mask_ratio, self.tuple_ratio
+        if r == 0 and tr >= 1:
             for k in range(len(self)):
                 yield self.dataset.batch(order[k * bs:(k + 1) * bs])
             return
         ds = self.dataset
-        seed = int(np.random.randint(0, 2 ** 63 - 1, dtype=np.int64)) if self.mask_rng == "device" else None
+        seed = int(np.random.randint(0, 2 ** 63 - 1, dtype=np.int64)) if r > 0 and self.mask_rng == "device" else None
+        tseed = int(np.random.randint(0, 2 ** 63 - 1, dtype=np.int64)) if tr < 1 and self.tuple_rng == "device" else None
+        host_mask, host_tuples = r > 0 and seed is None, tr < 1 and tseed is None
+        ext = None
+        if host_tuples:
+            from .dataloaders_AtomTuple import AtomTupleExtractor
+            ext = AtomTupleExtractor(tr, ds.option)
         for k in range(len(self)):
             ids = order[k * bs:(k + 1) * bs]
-            keep = None
-            if seed is None:
-                keep = np.concatenate([masking.reference_bfs(int(ds.sizes[i]), ds.successors(int(i)), r)
-                                       for i in ids]).astype(np.int32)
-            yield DatasetBatch(ds, ids, masking.MaskDraw(r, seed=seed, keep=keep))
+            keep, tuples = None, None
+            if host_mask or host_tuples:
+                # the reference's own draws, molecule after molecule: the BFS of __getitem__, then the transform's
+                # np.random.choice over the tuples of the atoms that are left
+                keeps, tups, at = [], [], 0
+                for i in ids:
+                    n = int(ds.sizes[i])
+                    if host_mask:
+                        keeps.append(masking.reference_bfs(n, ds.successors(int(i)), r))
+                    if r > 0:
+                        n = int(masking.kept_count(n, r))
+                    if host_tuples:
+                        tups.append(ext._one(n).numpy() + at)
+                    at += n
+                if host_mask:
+                    keep = np.concatenate(keeps).astype(np.int32)
+                if host_tuples:
+                    tuples = np.ascontiguousarray(np.concatenate(tups, axis=1).astype(np.int64))
+            yield DatasetBatch(ds, ids, masking.MaskDraw(r, seed=seed, keep=keep) if r > 0 else None,
+                               TupleDraw(tr, seed=tseed, tuples=tuples) if tr < 1 else None)

@@ -336,6 +336,8 @@ PROTOTYPES = {
     "geossl_gather_live_rows": (i32, [vp, vp, vp, i64, i32, i32, vp, vp]),
     "geossl_live_pairs_build": (i32, [vp] * 8 + [i64, i64, f32] + [vp] * 9),
     "geossl_cfconv_filter_fwd_rows": (i32, [vp, vp, i64, P(FilterWeights), i32, i32, i32, vp, f32, vp, vp, vp, vp, vp]),
+    # sampled atom tuples (csrc/sampled_tuples.hip)
+    "geossl_sampled_tuples": (i32, [vp, vp, i64, i32, vp, i32, u64, i64, i64, vp, vp, vp, vp, vp, vp]),
 }
 
 _lib = None

@@ -18,6 +18,10 @@ class Batch:
         # option when super_edge_index is its full enumeration in batch order
         self._sizes = None if sizes is None else [int(n) for n in sizes]
         self._canonical = canonical
+        # (option, ratio) when super_edge_index is AtomTupleExtractor(ratio < 1) output of that option, grouped by
+        # molecule in batch order with int(M * ratio) tuples per molecule (`_canonical` is None then): which tuples
+        # is data, how many is a function of the sizes - what a sampled capacity bucket takes (bucket.option_of)
+        self._sampled = None
 
     @property
     def num_graphs(self):
@@ -46,8 +50,10 @@ class Batch:
                for a in (self.x, self.positions, self.batch, self.super_edge_index, self.radius_edge_index)):
             return self  # (already there: like Tensor.to, no new object - what is cached on this one stays)
         mv = lambda a: None if a is None else a.to(device)
-        return Batch(mv(self.x), mv(self.positions), mv(self.batch), mv(self.super_edge_index),
-                     mv(self.radius_edge_index), self._num_graphs, self._sizes, self._canonical)
+        out = Batch(mv(self.x), mv(self.positions), mv(self.batch), mv(self.super_edge_index),
+                    mv(self.radius_edge_index), self._num_graphs, self._sizes, self._canonical)
+        out._sampled = self._sampled
+        return out
 
 
 class TripleBatch(Batch):
@@ -87,6 +93,26 @@ class TripleBatch(Batch):
         mv = lambda a: None if a is None else a.to(device)
         return TripleBatch(mv(self.x), mv(self.positions), mv(self.batch), mv(self.super_edge_index),
                            mv(self.super_edge_angle), mv(self.radius_edge_index), self._num_graphs, self._sizes)
+
+
+def sampled_count(M, ratio):
+    """Tuples AtomTupleExtractor(ratio < 1) keeps of M (dataloaders_AtomTuple.py:27): Python's ``int(M * ratio)`` - the
+    ONE place this number is computed (``int(100 * 0.29)`` is 28, as in the reference; no kernel computes it)."""
+    return int(M * ratio)
+
+
+def tuple_slots(n, option):
+    """Tuples of the full enumeration of an n-atom molecule: n (n - 1) / 2 "combination", n (n - 1) "permutation"."""
+    n = int(n)
+    return 0 if n < 2 else (n * (n - 1) // 2 if option == "combination" else n * (n - 1))
+
+
+def kept_tuples(sizes, option, ratio):
+    """``sampled_count`` of every molecule's enumeration, as an int64 array (one Python evaluation per distinct size)."""
+    n = np.asarray(sizes, dtype=np.int64).reshape(-1)
+    uniq, inv = np.unique(n, return_inverse=True)
+    k = np.asarray([sampled_count(tuple_slots(v, option), ratio) for v in uniq.tolist()], dtype=np.int64)
+    return k[inv] if n.size else np.zeros(0, dtype=np.int64)
 
 
 _PAIR_CACHE = {}

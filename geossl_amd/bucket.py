@@ -25,6 +25,7 @@ part     present when                   blob sections it writes        device bu
 atoms    always                         dims, mol_ptr, src_off         x, positions, batch_vec, b2
 pairs    not sparse                     pair_ptr, stats; SchNet: work  SchNet: pair_i, pair_j, agg_targets
 tuples   "combination" / "permutation"  se_ptr, inc_ptr                sei, inc_idx
+sampled  (option, ratio), ratio < 1      se_ptr, mol_id                 sei, inc_idx; inc_ptr is the device's too
 triples  "triples" (views = 1)          dims[D_T], t_src_off, t_ptr    triples, triple_angle
 edges    PaiNN, not sparse              e_src_off, e_ptr, big0, big1   the _Edges buffers, the two status words
 sedges   PaiNN, sparse                  e_src_off, e_ptr               radius_edge_index, both incidence lists, status
@@ -61,11 +62,11 @@ import ctypes as C
 
 import numpy as np
 import torch
-from .switches import env as _env, masked_painn_buckets, painn_sparse_buckets, sparse_buckets
+from .switches import env as _env, masked_painn_buckets, painn_sparse_buckets, sampled_buckets, sparse_buckets
 
 from . import _lib
 from ._lib import call, ptr, stream
-from .batch import Batch, TripleBatch, _tensor_uid
+from .batch import Batch, TripleBatch, _tensor_uid, kept_tuples
 
 MAX_N = 255         # largest molecule a bucket takes (the limit of the aggregation's work list and of the heads)
 SMALL_N = 33        # ... and the largest one of the register-form aggregation's size classes: buckets whose molecules
@@ -162,6 +163,18 @@ SPARSE = "sparse"
 SPARSE_MAX_N_CLASSES = (256, 512, 1024)   # its bound on the molecule size (LDS of the list's build: up to 139 KB)
 
 
+def is_sampled(option):
+    """A SAMPLED tuple option ``(base, ratio)`` - ("combination", 0.3): AtomTupleExtractor(ratio < 1) output.  How many
+    tuples a molecule keeps is ``batch.sampled_count`` of its enumeration - a function of the sizes, so se_ptr, S, the
+    divisor and every capacity stay host work; WHICH tuples is per-step data of the bucket (the sampled part)."""
+    return isinstance(option, tuple)
+
+
+def base_option(option):
+    """The enumeration a tuple option draws from: "combination" / "permutation" of a sampled one, else the option."""
+    return option[0] if isinstance(option, tuple) else option
+
+
 def sparse_max_n_class(hi, prev=None):
     """The sparse bucket's bound on the molecule size for a batch whose largest molecule has `hi` atoms (the classes
     double: the head room is in the class itself); never below a previous bucket's."""
@@ -225,8 +238,13 @@ def sparse_eligible(batch, model_3d="schnet"):
 def option_of(batch):
     """What a bucket for this batch enumerates: the AtomTupleExtractor option of a canonical pair enumeration, "triples"
     for a collated AtomTripleExtractor batch (or a handle of a triple dataset) - its list is per-step DATA of the bucket,
-    not a function of the sizes - or None."""
-    return TRIPLES if getattr(batch, "_triples", False) else getattr(batch, "_canonical", None)
+    not a function of the sizes -, the sampled option ``(base, ratio)`` of a batch marked as AtomTupleExtractor(ratio < 1)
+    output (``_sampled``: a DeviceLoader(tuple_ratio=) handle, a collated batch of the host extractor's molecules), or
+    None."""
+    if getattr(batch, "_triples", False):
+        return TRIPLES
+    canon = getattr(batch, "_canonical", None)
+    return canon if canon is not None else getattr(batch, "_sampled", None)
 
 
 def n_triples(batch):
@@ -244,7 +262,10 @@ def batch_counts(sizes, option, views=2):
         return int(n.sum()), 0, 0, 0
     from .layout import aggregate_by_targets, work_items_bound
     P = int((n * (n - 1) // 2).sum())
-    S = P if option == "combination" else (0 if option == TRIPLES else 2 * P)
+    if is_sampled(option):
+        S = int(kept_tuples(n, *option).sum())
+    else:
+        S = P if option == "combination" else (0 if option == TRIPLES else 2 * P)
     W = work_items_bound(np.concatenate([n] * views), aggregate_by_targets(views * len(n)))   # (a bound: 8 padded queues)
     return int(n.sum()), P, S, W
 
@@ -256,7 +277,10 @@ def eligible(batch, model_3d, normalize=False):
     device per step, geossl_painn_edge_layout)."""
     sizes, canon = getattr(batch, "_sizes", None), option_of(batch)
     if (model_3d not in ("schnet", "painn") or normalize or sizes is None
-            or canon not in ("combination", "permutation", TRIPLES) or not len(sizes)):
+            or (canon not in ("combination", "permutation", TRIPLES) and not is_sampled(canon)) or not len(sizes)):
+        return False
+    # sampled tuples (GEOSSL_SAMPLED_BUCKETS): a loader's handles by default - no other replayed route exists for them
+    if is_sampled(canon) and not sampled_buckets(getattr(batch, "_dataset", None) is not None):
         return False
     lo, hi = size_range(batch)
     if lo < 1 or hi > MAX_N or hi < 2:
@@ -296,9 +320,11 @@ def route(batch, model_3d, views, pair_tuples, normalize):
             and _env("GEOSSL_PAINN_TILE") != "0" and not _env("GEOSSL_PAINN_VECTOR")
             and sparse_eligible(batch, "painn")):
         return SPARSE
-    if not eligible(batch, model_3d, normalize) or (model_3d != "painn" and is_uniform(batch)):
+    option = option_of(batch)
+    # (equal-sized molecules share their tuples only when those are the full enumeration)
+    if not eligible(batch, model_3d, normalize) or (model_3d != "painn" and is_uniform(batch) and not is_sampled(option)):
         return None
-    return option_of(batch)
+    return option
 
 
 def handle_edges(batch):
@@ -343,8 +369,12 @@ def tensors_ok(batch):
     if got is not None and got[0] == tag:
         return got[1]
     n = sizes_array(batch)
-    P = int((n * (n - 1) // 2).sum())
-    S = P if batch._canonical == "combination" else 2 * P
+    option = option_of(batch)
+    if is_sampled(option):
+        S = int(kept_tuples(n, *option).sum())
+    else:
+        P = int((n * (n - 1) // 2).sum())
+        S = P if option == "combination" else 2 * P
     ok = (_atom_tensors_ok(batch, int(n.sum()))
           and sei.is_cuda and sei.dtype == torch.long and sei.dim() == 2 and sei.size(0) == 2 and sei.size(1) == S
           and sei.stride(1) == 1)
@@ -479,7 +509,9 @@ def host_plan(sizes, option, views=2):
     (largest first, stable; 27 .. 33-atom molecules as 2 or 4 items, larger ones one item per atom: molecule | part << 24;
     over the B molecules of view 0 only when views = 1); the divisor of NCSN.py:210-212
     (last molecule with a super-edge, + 1); inc_ptr [N + 1] (an atom of an n-atom molecule lies on n - 1 tuples of the
-    "combination" enumeration, 2 (n - 1) of "permutation").  option "sparse": counts (N, 0, 0, 0) and ``mol_ptr``
+    "combination" enumeration, 2 (n - 1) of "permutation").  A sampled option ``(base, ratio)``: S = sum k_m, se_ptr from
+    the k_m = int(M_m * ratio), the divisor "last molecule with k_m > 0, + 1", ``kept`` = the k_m and NO inc_ptr (it depends
+    on the draw: geossl_sampled_tuples writes it).  option "sparse": counts (N, 0, 0, 0) and ``mol_ptr``
     [B + 1] of the one view - no pair, tuple or work entry exists."""
     n = sizes if isinstance(sizes, np.ndarray) else np.asarray(sizes, dtype=np.int64)
     B = n.shape[0]
@@ -488,7 +520,7 @@ def host_plan(sizes, option, views=2):
         np.cumsum(n, out=mp[1:])
         return dict(counts=(int(mp[-1]), 0, 0, 0), mol_ptr=mp)
     N, P, S, W = batch_counts(n, option, views)
-    mult = 1 if option == "combination" else (0 if option == TRIPLES else 2)
+    mult = 1 if option == "combination" else (0 if option == TRIPLES or is_sampled(option) else 2)
     mp = np.zeros(B + 1, dtype=np.int64)
     np.cumsum(n, out=mp[1:])
     npair = n * (n - 1) // 2
@@ -498,11 +530,22 @@ def host_plan(sizes, option, views=2):
     work = aggregate_work_list(np.concatenate([n] * views), aggregate_by_targets(views * B))
     if work.size > W:
         raise ValueError("aggregation work list longer than its bound")   # (work_items_bound: cannot happen)
+    out = dict(counts=(N, P, S, W), mol_ptr2=np.concatenate([mp, mp[1:] + N]), pair_ptr2=np.concatenate([pp, pp[1:] + P]),
+               work=work)
+    if is_sampled(option):
+        # a sampled option: k_m = int(M_m * ratio) tuples per molecule (batch.kept_tuples); the divisor is the last
+        # molecule that KEEPS a tuple, + 1; the incidence pointers depend on the draw and are the device's to write
+        k = kept_tuples(n, *option)
+        sp = np.zeros(B + 1, dtype=np.int64)
+        np.cumsum(k, out=sp[1:])
+        has = np.nonzero(k > 0)[0]
+        out.update(se_ptr=sp, divisor=int(has[-1]) + 1 if has.size else 0, kept=k)
+        return out
     has = np.nonzero(npair > 0)[0]
     ip = np.zeros(N + 1, dtype=np.int64)
     np.cumsum(np.repeat((n - 1) * mult, n), out=ip[1:])
-    return dict(counts=(N, P, S, W), mol_ptr2=np.concatenate([mp, mp[1:] + N]), pair_ptr2=np.concatenate([pp, pp[1:] + P]),
-                se_ptr=pp * mult, work=work, divisor=int(has[-1]) + 1 if has.size else 0, inc_ptr=ip)
+    out.update(se_ptr=pp * mult, divisor=int(has[-1]) + 1 if has.size else 0, inc_ptr=ip)
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ the parts of a bucket
@@ -540,7 +583,7 @@ class _Atoms(_Part):
         b.x, b.batch_vec = torch.zeros(b.N_cap, x_cols, **i64), torch.zeros(b.N_cap, **i64)
         b.positions = torch.zeros(b.N_cap, 3, dtype=torch.float32, device=b.device)
         b.b2 = torch.zeros(b.views * b.N_cap, **i64)   # placeholder for the backbone's `batch` argument
-        g.option, g.x_cols = (0 if self.option in ("combination", SPARSE) else 1), x_cols
+        g.option, g.x_cols = (0 if base_option(self.option) in ("combination", SPARSE) else 1), x_cols
         g.mol_ptr, self.src_ptr = b._base + 4 * self.mol.start, b._base + 4 * self.src.start
         g.x_dst, g.pos_dst, g.batch_dst = ptr(b.x), ptr(b.positions), ptr(b.batch_vec)
 
@@ -596,6 +639,49 @@ class _Tuples(_Part):
         g = b._g
         g.sei0, g.sei1 = ptr(b.sei[0]), ptr(b.sei[1])
         g.inc_ptr, g.inc_idx = ptr(b.sel.inc_ptr), ptr(b.sel.inc_idx)
+
+
+class _SampledTuples(_Part):
+    """A sampled option ``(base, ratio)``: se_ptr from the host (the kept counts are a function of the sizes), the tuples
+    and both incidence arrays by ONE launch behind the gather (geossl_sampled_tuples; the gather's sei / inc pointers
+    stay NULL) - drawn there from the handle's seed, or checked there after a collated batch's tensor / a handle's
+    host-drawn list was copied in.  A tuple that leaves its molecule sets the status word, polled a few fills late."""
+
+    def __init__(self, lay):
+        o, B = lay.off, lay.B
+        self.B, self.base = B, _TUPLE_OPTIONS[lay.option[0]]
+        self.se, self.ids = slice(o["se_ptr"], o["se_ptr"] + B + 1), slice(o["mol_id"], o["mol_id"] + B)
+
+    def write_host(self, h, hp, n, N, P, S, E, T, masked_edges, src):
+        h[self.se] = hp["se_ptr"]
+        if src is not None:   # (the low word of the molecules' dataset ids: the draw's counter)
+            h[self.ids] = (np.asarray(src[5], dtype=np.int64) & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+
+    def attach(self, b):
+        self.b = b
+        b.tuple_status = _lib.StatusWord(b.device, "super_edge_index must be grouped by molecule in batch order with both "
+                                         "ends of a tuple in the same molecule and different (collated "
+                                         "AtomTupleExtractor output is)")
+        # (geossl_sampled_tuples: mol_ptr, se_ptr, B, option, mol_id | capacities, outputs, status)
+        self.head = (b._g.mol_ptr, b._base + 4 * self.se.start, self.B, self.base, b._base + 4 * self.ids.start)
+        self.tail = (b.N_cap, b.S_cap, ptr(b.sei[0]), ptr(b.sei[1]), ptr(b.sel.inc_ptr), ptr(b.sel.inc_idx),
+                     ptr(b.tuple_status.word))
+
+    def after(self, batch, ds, N, E, T, masked_edges):
+        b = self.b
+        draw = getattr(batch, "_tuple_draw", None) if ds is not None else None
+        seed = None if draw is None else draw.seed
+        if seed is None:   # the batch's own tuples: a collated tensor, or a handle's host-drawn list (batch atom ids)
+            sei = batch.super_edge_index if ds is None else torch.from_numpy(draw.tuples)
+            if sei.size(1):
+                b.sei[:, :sei.size(1)].copy_(sei)
+        _poll(b.tuple_status)
+        call("geossl_sampled_tuples", *self.head, 0 if seed is None else 1, 0 if seed is None else int(seed), *self.tail,
+             stream())
+        b.tuple_status.arm(every=8)
+
+
+_TUPLE_OPTIONS = {"combination": 0, "permutation": 1}
 
 
 class _Triples(_Part):
@@ -804,6 +890,8 @@ class BlobLayout:
                     ("big0", 2 * Nc if nb > 0 else 0), ("big1", 2 * Nc if nb > 1 else 0), ("src_off", B),
                     ("e_src_off", B if painn else 0), ("e_ptr", B + 1 if painn else 0),
                     ("t_src_off", B if triples else 0), ("t_ptr", B + 1 if triples else 0))
+        if is_sampled(option):   # (the molecules' dataset ids, the counter of a device draw: a sampled bucket's alone)
+            sections += (("mol_id", B),)
         self.off, at = {}, 0
         for name, words in sections:
             at = _round_up(at, 2) if name == "stats" else at
@@ -812,6 +900,7 @@ class BlobLayout:
         self.words = at
         kinds = ((_Atoms,) + (() if sparse else (_Pairs,))
                  + ((_Tuples,) if option in ("combination", "permutation") else ())
+                 + ((_SampledTuples,) if is_sampled(option) else ())
                  + ((_Triples,) if triples else ())
                  + (((_SparseEdgesPart if sparse else _EdgesPart),) if painn else ()))
         self.parts = tuple(kind_(self) for kind_ in kinds)
@@ -821,10 +910,11 @@ class BlobLayout:
 def host_image(h, lay, n, counts=None, src=None, E=0, T=None, masked_edges=False):
     """The host half of a fill: everything of the blob that is a function of the molecule sizes `n` - and, for a handle
     on a dataset, of where the chosen molecules (their edges, their triples) start there: src = (src_off, edge_off,
-    edge_cnt, triple_off, triple_cnt) of the chosen ids, None for a collated batch - into `h`, an int32 numpy view of
-    `lay.words` words (the bucket's pinned staging slot; in a test a plain array).  E: the batch's edges (PaiNN), T: its
-    triples; masked_edges: the edge count and e_ptr are the device's to write.  Words the batch does not define are left
-    as they are (a reused slot keeps what an earlier fill wrote past this batch's counts)."""
+    edge_cnt, triple_off, triple_cnt[, ids - read by a sampled bucket]) of the chosen ids, None for a collated batch -
+    into `h`, an int32 numpy view of `lay.words` words (the bucket's pinned staging slot; in a test a plain array).
+    E: the batch's edges (PaiNN), T: its triples; masked_edges: the edge count and e_ptr are the device's to write.
+    Words the batch does not define are left as they are (a reused slot keeps what an earlier fill wrote past this
+    batch's counts)."""
     hp = host_plan(n, lay.option, lay.views)
     N, P, S, W = counts if counts is not None else hp["counts"]
     for write in lay.writers:
@@ -912,7 +1002,8 @@ class Bucket:
         if option == TRIPLES:
             self.batch = TripleBatch(self.x, self.positions, self.batch_vec, self.triples, self.triple_angle, None, B, None)
         else:
-            self.batch = Batch(self.x, self.positions, self.batch_vec, self.sei, None, B, None, option)
+            self.batch = Batch(self.x, self.positions, self.batch_vec, self.sei, None, B, None,
+                               None if is_sampled(option) else option)
         self.batch._bucket = self
         self.real = None  # (N, P, S, W) of the batch last filled in
 
@@ -980,7 +1071,8 @@ class Bucket:
         elif option_of(batch) != opt:
             raise ValueError("batch and bucket disagree on the tuple option")
         if ds is not None:   # (a triples or sparse bucket does not read the dataset's tuple option)
-            if ((opt in ("combination", "permutation") and ds.option != opt) or ds.x_cols != x_cols
+            if ((base_option(opt) in ("combination", "permutation") and ds.option != base_option(opt))
+                    or ds.x_cols != x_cols
                     or ds.device != self.x.device):
                 raise ValueError("dataset and bucket disagree (tuple option, x columns or device)")
             if painn and ds.edges is None:
@@ -1009,7 +1101,8 @@ class Bucket:
         from there.  One pinned upload (`host_image`: everything that is a function of the molecule sizes) + one launch
         (geossl_gather_molecules: atom rows, batch vector and the cleared buffer; per part super-edges and incidence
         lists, pair-slot atoms, radius edges) + what the parts launch behind it (triples of a handle:
-        geossl_gather_triples, of a collated batch two copies; PaiNN: geossl_painn_edge_layout).  A masked handle adds
+        geossl_gather_triples, of a collated batch two copies; sampled tuples: geossl_sampled_tuples, behind one copy
+        of the batch's own list where it has one; PaiNN: geossl_painn_edge_layout).  A masked handle adds
         the small upload of its mask and launches geossl_gather_masked_molecules instead: the BFS and the gather are that
         one launch.  A masked PaiNN handle is four launches - count (BFS + survivors per molecule),
         geossl_masked_edge_offsets (e_ptr and dims[D_E2] on the device), gather, geossl_painn_edge_layout_dyn - and
@@ -1030,7 +1123,7 @@ class Bucket:
         if ds is not None:   # a handle: where its molecules (their edges, their triples) start in the dataset
             ids, painn, triples = batch.ids, self.kind == "painn", self.option == TRIPLES
             src = (ds.off[ids], ds.edge_off[ids] if painn else None, ds.edge_cnt[ids] if painn else None,
-                   ds.triple_off[ids] if triples else None, ds.triple_cnt[ids] if triples else None)
+                   ds.triple_off[ids] if triples else None, ds.triple_cnt[ids] if triples else None, ids)
         host_image(slot[0].numpy(), self.layout, n, counts, src, E, T, masked_edges)
         self.blob.copy_(slot[0], non_blocking=True)
         slot[1] = torch.cuda.Event()

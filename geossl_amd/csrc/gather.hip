@@ -17,23 +17,14 @@
 // the host's size table (cumulative sums over B integers, uploaded with the step's other pointer arrays): no read-back.
 // HBM-bound integer work: a few hundred KB per step, one wave-coalesced store stream per array.
 #include "common.h"
+#include "enumerate.h"
 #include "geossl_hip.h"
+
+using namespace geossl;
 
 namespace {
 
 constexpr int GATHER_THREADS = 256;
-
-// slot p of the lexicographic i<j enumeration of n atoms -> (a, b);  row(a) = a n - a (a + 1) / 2 - a - 1, slot = row(a) + b
-__device__ __forceinline__ void pair_of_slot(int p, int n, int& a, int& b) {
-  const float t = (float)(2 * n - 1);
-  int g = (int)((t - sqrtf(fmaxf(t * t - 8.0f * (float)p, 0.0f))) * 0.5f);
-  g = g < 0 ? 0 : (g > n - 2 ? n - 2 : g);
-  // first slot of row a: a n - a (a + 1) / 2 (the float estimate is off by at most one)
-  while (g > 0 && g * n - g * (g + 1) / 2 > p) --g;
-  while (g < n - 2 && (g + 1) * n - (g + 1) * (g + 2) / 2 <= p) ++g;
-  a = g;
-  b = p - (g * n - g * (g + 1) / 2) + g + 1;
-}
 
 // the blocks behind the molecules clear the float buffer
 __device__ __forceinline__ void clear_zero_block(const GeosslGather& g, int B) {
@@ -147,33 +138,6 @@ __global__ __launch_bounds__(GATHER_THREADS) void k_gather_molecules(GeosslGathe
 
 // ---- masked gather (BFS atom masking of datasets_3D.py:24-67 / datasets_3D_Radius.py:43-87)
 constexpr int MASK_MAX_N = 2048;   // 64 lanes x one 32-bit word of the visited / frontier bitsets
-
-// Philox-4x32-10 (Salmon et al., SC'11), word 0 of the block for counter (c0, c1, 0, 0)
-__device__ __forceinline__ uint32_t philox_w0(uint32_t c0, uint32_t c1, uint64_t seed) {
-  uint32_t c2 = 0, c3 = 0, k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-    c1 = (uint32_t)p1;
-    c3 = (uint32_t)p0;
-    c0 = n0;
-    c2 = n2;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return c0;
-}
-
-__device__ __forceinline__ int wave_incl_scan(int v) {
-  const int lane = __lane_id();
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int t = __shfl_up(v, d);
-    if (lane >= d) v += t;
-  }
-  return v;
-}
 
 // position of the r-th set bit (0-based) of w
 __device__ __forceinline__ int select_bit(uint32_t w, int r) {

@@ -135,7 +135,8 @@ class StepGraphs:
     Which graph serves a batch (``mode="auto"``):
 
     * a batch of EQUAL-SIZED molecules, and anything a bucket cannot take (PaiNN's geometry-dependent edge list, sampled
-      tuples, batches built by hand): one graph per ``structure_fingerprint`` - the size sequence, or the tensor objects;
+      tuples without the ``_sampled`` mark, batches built by hand): one graph per ``structure_fingerprint`` - the size
+      sequence, or the tensor objects;
       a structure that only a fingerprint identifies is captured on its SECOND sighting (a loader that never repeats one
       never pays for a capture);
     * a batch with a SPARSE layout (a structure of 256 to 1024 atoms - LBA's pockets - or GEOSSL_SPARSE_PAIRS=1) in a
@@ -148,7 +149,11 @@ class StepGraphs:
       graph per (molecules in the batch, tuple option) at a CAPACITY (``geossl_amd/bucket.py``): the graph's kernels read
       the batch's real atom / pair-slot / super-edge counts and every index structure from device memory, so ONE graph
       replays on any size sequence; a batch that outgrows the capacity makes a larger bucket (its graph is captured
-      again: a handful of times at the start of a run).
+      again: a handful of times at the start of a run).  SAMPLED tuples (``AtomTupleExtractor(ratio < 1)``: the handles
+      of a ``DeviceLoader(tuple_ratio=)``, collated batches of the host extractor's molecules) take a bucket whose option
+      is ``(option, ratio)``: the kept counts are a function of the sizes, the tuples are drawn or checked on the device
+      behind the gather - handles by default, collated batches under ``GEOSSL_SAMPLED_BUCKETS=1`` (``=0``: neither;
+      such a batch is then served as the first entry says).
 
     ``mode="structure"``: per-structure graphs only, captured at the first sighting (pre-collated, device-resident
     batches that come back every epoch).
@@ -233,10 +238,10 @@ class StepGraphs:
     # ---- from a batch to a replay
     def plan(self, batch):
         """-> (the graph that serves this batch or None, whether one is to be captured for it now).  (None, False): this
-        step runs eagerly - the first sighting of an index structure that only its own graph can serve (sampled tuples,
-        PaiNN edge lists, batches built by hand): a loader that never repeats such a structure never pays for a capture,
-        one that comes back is captured on its second step.  Ragged SchNet batches of a loader share ONE capacity-bucket
-        graph and equal-sized molecules one per-structure graph: those are captured right away."""
+        step runs eagerly - the first sighting of an index structure that only its own graph can serve (unmarked sampled
+        tuples, PaiNN edge lists, batches built by hand): a loader that never repeats such a structure never pays for a
+        capture, one that comes back is captured on its second step.  Ragged SchNet batches of a loader share ONE
+        capacity-bucket graph and equal-sized molecules one per-structure graph: those are captured right away."""
         g = self.lookup(batch)
         return g, g is None and self.capture_now(batch)
 

@@ -61,6 +61,27 @@ def sparse_buckets(handle):
     return True if v == "1" else bool(handle)
 
 
+# What the unset GEOSSL_SAMPLED_BUCKETS means for COLLATED sampled batches: the outcome of the measurement in
+# profiles/sampled_tuples_bench.json by the rule "on only if no slower than the route before at bs = 128 and 1024"
+# (the DDM step of collated sampled batches through the bucket is 14 - 33 % shorter at bs = 128; at
+# bs = 1024 the host's per-molecule enumeration is the step either way, three of the four cells are 2 - 10 % shorter and
+# one is 0.8 % longer, all inside the run-to-run spread - not shown to be no slower there, so: opt-in).
+SAMPLED_BUCKETS_COLLATED_DEFAULT = False
+
+
+def sampled_buckets(handle):
+    """``GEOSSL_SAMPLED_BUCKETS``: batches of sampled atom tuples (``AtomTupleExtractor(ratio < 1)``: the handles of a
+    ``DeviceLoader(tuple_ratio=)``, collated batches of the host extractor's molecules) replay one capacity-bucket graph
+    per (batch size, option, ratio) - the tuples are per-step data of the bucket (``bucket.is_sampled``).  ``1``: handles and
+    collated batches; ``0``: neither - eager launches, a per-structure graph for a batch object that comes back (the
+    routing before that bucket existed).  Unset: handles do (no other replayed route exists for them); collated batches
+    by ``SAMPLED_BUCKETS_COLLATED_DEFAULT`` (they do not: opt-in with ``1``)."""
+    v = env("GEOSSL_SAMPLED_BUCKETS")
+    if v == "0":
+        return False
+    return True if v == "1" else (bool(handle) or SAMPLED_BUCKETS_COLLATED_DEFAULT)
+
+
 # What the unset GEOSSL_PAINN_SPARSE_BUCKETS means for the handles of a DeviceLoader: the outcome of the measurement in
 # profiles/painn_bucket_bench.json by the rule stated there (DESIGN section 5).
 PAINN_SPARSE_BUCKETS_DEFAULT = True

@@ -1230,6 +1230,29 @@ int geossl_gather_atom_rows(const float* src, int64_t n_src, int C, const int32_
 int geossl_eval_collect(const float* pred, const float* target, int64_t B, int kind, int64_t offset, float* out_pred,
                         float* out_true, void* acc, hipStream_t stream);
 
+/* ---- sampled atom tuples of a batch: AtomTupleExtractor(ratio < 1) on the device (csrc/sampled_tuples.hip) ------------
+ * One block per molecule m < B (n = mol_ptr[m + 1] - mol_ptr[m] <= 255 atoms from batch row a0 = mol_ptr[m] on), launched
+ * behind the gather of a capacity bucket.  The molecule owns the k = se_ptr[m + 1] - se_ptr[m] columns of sei0 / sei1 from
+ * se_ptr[m] on.  k is NEVER computed here: it is the host's int(M * ratio) (Python float arithmetic, batch.kept_tuples),
+ * M = n (n - 1) / 2 slots of itertools.combinations order (option 0) or n (n - 1) of itertools.permutations (option 1).
+ * draw != 0: slot s gets the 64-bit key (w0 << 32) | w1, (w0, w1, ., .) = Philox-4x32-10 of the counter
+ *   (s, mol_id[m], 0, 0) under the key words (seed & 0xffffffff, seed >> 32).  The k slots with the smallest (key, s) are
+ *   kept (k > M: refused), unranked and written in ASCENDING SLOT ORDER with a0 added.  mol_id [B] int32: what
+ *   identifies the molecule in its dataset (the low word of its id), so a molecule's draw does not depend on its batch.
+ * draw == 0: sei0 / sei1 already hold the batch's tuples (a collated batch's tensor, a host-drawn list); mol_id and seed
+ *   are not read.
+ * Both: a tuple whose ends do not both lie in [a0, a0 + n) or are the same atom sets status[0] = 1 (nullable; nothing
+ *   resets it) and is left out of the lists below.  inc_ptr (nullable; int64 [N + 1]): inc_ptr[a0 + i] = 2 se_ptr[m] + the
+ *   exclusive scan of the molecule's atom degrees (both ends count); the last molecule also writes inc_ptr[a0 + n] =
+ *   2 se_ptr[B].  inc_idx (nullable; int32 [2 S]): for every atom the ids of the tuples it lies on, ascending - exactly
+ *   what geossl_incidence_count + an exclusive scan + geossl_incidence_fill (sides = 3) give for the same list.
+ * Integer work only: LDS counters, no floating atomics; the same inputs give the same bits.  N_cap / S_cap: rows of the
+ * atom arrays / columns of sei (2 S_cap < 2^31); a molecule whose offsets leave them (or n > 255) sets the status word
+ * and writes nothing. */
+int geossl_sampled_tuples(const int32_t* mol_ptr, const int32_t* se_ptr, int64_t B, int option, const int32_t* mol_id,
+                          int draw, uint64_t seed, int64_t N_cap, int64_t S_cap, int64_t* sei0, int64_t* sei1,
+                          int64_t* inc_ptr, int32_t* inc_idx, int32_t* status, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
