@@ -1,9 +1,17 @@
 #!/usr/bin/env python3
-"""GeoSSL-DDM pretraining with geossl_amd.pretrain_GeoSSL.DDMTrainer on a device-resident dataset: every step gathers
-its molecules on the device, draws its noise there and replays one capacity-bucket graph per batch size.
+"""GeoSSL-DDM / GeoSSL-RR pretraining with geossl_amd.pretrain_GeoSSL.DDMTrainer / RRTrainer on a device-resident
+dataset: every step gathers its molecules on the device, draws its noise there and replays one capacity-bucket graph per
+batch size.
 
-    python examples/pretrain_GeoSSL.py [--model_3d schnet|painn] [--data FILE.npz] [--epochs 100]
-                                       [--GeoSSL_atom_masking_ratio 0] [--distance_sample_ratio 1] ...
+    python examples/pretrain_GeoSSL.py [--GeoSSL_option DDM|RR] [--model_3d schnet|painn] [--data FILE.npz]
+                                       [--epochs 100] [--GeoSSL_atom_masking_ratio 0] [--distance_sample_ratio 1] ...
+
+``--GeoSSL_option RR`` (representation reconstruction): two AutoEncoder heads - this project's own definition, the
+reference tree has none - with ``--AE_loss l1|l2|cosine``, ``--detach_target`` / ``--no_detach_target``, ``--beta``
+(unused), ``--normalize`` and ``--ae_lr`` (the reference's loop gives the AE groups lr = gnn_2d_lr_scale).  The
+reference's defaults (l2, detached target, no --normalize) leave the scale of the representations free: on a freshly
+initialised SchNet the l2 loss then GROWS from step to step - with torch's own ATen heads exactly as with the fused ones;
+``--normalize`` (or ``--AE_loss cosine``, or ``--no_detach_target``) bounds it.
 
 ``--GeoSSL_atom_masking_ratio m`` > 0: BFS atom masking over the records' bond graph (``bond_index [2, Etot]`` /
 ``bond_counts [M]`` in the data file; synthetic molecules get one), drawn on the device (``DeviceLoader(mask_ratio=m)``).
@@ -24,9 +32,9 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from geossl_amd.Geom3D.dataloaders.device_dataset import DeviceDataset, DeviceLoader  # noqa: E402
-from geossl_amd.Geom3D.models import PaiNN, SchNet  # noqa: E402
+from geossl_amd.Geom3D.models import AutoEncoder, PaiNN, SchNet  # noqa: E402
 from geossl_amd.NCSN import NCSN_version_03  # noqa: E402
-from geossl_amd.pretrain_GeoSSL import DDMTrainer  # noqa: E402
+from geossl_amd.pretrain_GeoSSL import DDMTrainer, RRTrainer  # noqa: E402
 
 
 def parse():
@@ -47,6 +55,17 @@ def parse():
     p.add_argument("--GeoSSL_sigma_end", type=float, default=0.01)
     p.add_argument("--GeoSSL_num_noise_level", type=int, default=50)
     p.add_argument("--GeoSSL_anneal_power", type=float, default=2.0)
+    p.add_argument("--GeoSSL_option", type=str, default="DDM", choices=["DDM", "RR"])
+    # RR (config.py:177-183): the loss of the two AutoEncoder heads, whether the target view is detached, and beta (accepted,
+    # unused: it belongs to a variational variant the reference never constructs)
+    p.add_argument("--AE_loss", type=str, default="l2", choices=["l1", "l2", "cosine"])
+    p.add_argument("--detach_target", dest="detach_target", action="store_true")
+    p.add_argument("--no_detach_target", dest="detach_target", action="store_false")
+    p.set_defaults(detach_target=True)
+    p.add_argument("--beta", type=float, default=1)
+    p.add_argument("--normalize", action="store_true")
+    p.add_argument("--ae_lr", type=float, default=None,
+                   help="learning rate of the two AE heads (the reference's loop: args.gnn_2d_lr_scale); default: --lr")
     p.add_argument("--tuple_rng", type=str, default="device", choices=["device", "numpy"])
     p.add_argument("--no_graph", action="store_true", help="eager launches for the step")
     p.add_argument("--emb_dim", type=int, default=128)
@@ -86,10 +105,18 @@ def main():
     else:
         model = SchNet(hidden_channels=args.emb_dim, num_filters=args.emb_dim, num_interactions=args.num_interactions,
                        num_gaussians=args.num_gaussians, cutoff=args.cutoff, readout=args.readout, node_class=9)
-    heads = [NCSN_version_03(args.emb_dim, args.GeoSSL_sigma_begin, args.GeoSSL_sigma_end, args.GeoSSL_num_noise_level,
-                             "symmetry", args.GeoSSL_anneal_power).to(device) for _ in range(2)]
-    trainer = DDMTrainer(model.to(device), heads[0], heads[1], lr=args.lr, weight_decay=args.decay, mu=args.GeoSSL_mu,
-                         sigma=args.GeoSSL_sigma, model_3d=args.model_3d, use_graph=not args.no_graph)
+    if args.GeoSSL_option == "RR":
+        heads = [AutoEncoder(emb_dim=args.emb_dim, loss=args.AE_loss, detach_target=args.detach_target,
+                             beta=args.beta).to(device) for _ in range(2)]
+        trainer = RRTrainer(model.to(device), heads[0], heads[1], lr=args.lr, weight_decay=args.decay, mu=args.GeoSSL_mu,
+                            sigma=args.GeoSSL_sigma, normalize=args.normalize, model_3d=args.model_3d,
+                            use_graph=not args.no_graph, ae_lr=args.ae_lr)
+    else:
+        heads = [NCSN_version_03(args.emb_dim, args.GeoSSL_sigma_begin, args.GeoSSL_sigma_end,
+                                 args.GeoSSL_num_noise_level, "symmetry", args.GeoSSL_anneal_power).to(device)
+                 for _ in range(2)]
+        trainer = DDMTrainer(model.to(device), heads[0], heads[1], lr=args.lr, weight_decay=args.decay, mu=args.GeoSSL_mu,
+                             sigma=args.GeoSSL_sigma, model_3d=args.model_3d, use_graph=not args.no_graph)
     for epoch in range(1, args.epochs + 1):
         t0 = time.time()
         losses = [trainer.step(batch) for batch in loader]

@@ -338,6 +338,11 @@ PROTOTYPES = {
     "geossl_cfconv_filter_fwd_rows": (i32, [vp, vp, i64, P(FilterWeights), i32, i32, i32, vp, f32, vp, vp, vp, vp, vp]),
     # sampled atom tuples (csrc/sampled_tuples.hip)
     "geossl_sampled_tuples": (i32, [vp, vp, i64, i32, vp, i32, u64, i64, i64, vp, vp, vp, vp, vp, vp]),
+    # GeoSSL-RR AutoEncoder heads (csrc/rr_head.hip)
+    "geossl_rr_head_width_ok": (i32, [i32]),
+    "geossl_rr_head_workspace_floats": (i64, [i64]),
+    "geossl_rr_head_fwd": (i32, [vp, vp, i64, i32, i32, vp, vp, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp]),
+    "geossl_rr_head_bwd": (i32, [vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]),
 }
 
 _lib = None

@@ -433,6 +433,11 @@ def modules_ok(model, n1=None, n2=None):
             from .finetune_lep import head_params as pair_head_params
             return pair_head_params(n1) is not None and property_readout_of(model) is not None
         return head_width(n1) == 128 and property_readout_of(model) is not None
+    from .Geom3D.models.autoencoder import AutoEncoder
+    if isinstance(n1, AutoEncoder) or isinstance(n2, AutoEncoder):
+        # the RR step: two distinct AutoEncoders of width 128 the fused heads serve (their rows are the 2B readouts: exact)
+        from .pretrain_GeoSSL import fused_heads_ok as rr_heads_ok
+        return rr_heads_ok(n1, n2) and n1.emb_dim == 128
     if not (isinstance(n1, NCSN_version_03) and isinstance(n2, NCSN_version_03)) or n1 is n2 \
             or n1.emb_dim != 128 or n2.emb_dim != 128:
         return False

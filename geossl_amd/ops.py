@@ -1634,3 +1634,95 @@ def pair_predict(h, w, b, layout, readout, dyn=None):
     call("geossl_pair_head_predict_dyn", ptr(h), N, F, ptr(layout.mol_ptr), B, PROPERTY_READOUTS[readout],
          ptr(w.detach().contiguous()), ptr(b.detach().contiguous()), ptr(z), _dyn(dyn, "n_atoms"), stream())
     return z
+
+
+# ---- GeoSSL-RR: the two AutoEncoder heads of a step (csrc/rr_head.hip) ---------------------------------------------------
+RR_LOSSES = {"l1": 0, "l2": 1, "cosine": 2}
+RR_STATS = {"fwd": 0, "bwd": 0}   # calls of the fused head (tests: a step took the kernels)
+
+
+def rr_head_width_ok(F):
+    """The width the fused AutoEncoder heads serve: F = 128."""
+    return bool(_lib.load().geossl_rr_head_width_ok(int(F)))
+
+
+def _ptr_array(tensors):
+    """A host array of device pointers (kept alive by the caller for the duration of the call)."""
+    return np.array([0 if t is None else t.data_ptr() for t in tensors], dtype=np.uint64)
+
+
+def rr_head_forward(X, Y, params, buffers, bn, kind):
+    """geossl_rr_head_fwd -> (loss, saved): X, Y [B, 128] contiguous fp32; params: the 12 detached parameters (per head
+    W1, b1, gamma, beta, W2, b2); buffers: per head running_mean, running_var, num_batches_tracked - updated IN PLACE;
+    bn: ((eps, momentum), (eps, momentum)).  saved = (zhat [2, B, F], istd [2, F], act [2, B, F], p [2, B, F])."""
+    B, F = X.shape
+    f32 = dict(dtype=torch.float32, device=X.device)
+    zhat, act, p = torch.empty(2, B, F, **f32), torch.empty(2, B, F, **f32), torch.empty(2, B, F, **f32)
+    istd = torch.empty(2, F, **f32)
+    ws = torch.empty(int(_lib.load().geossl_rr_head_workspace_floats(B)), **f32)
+    loss = torch.empty((), **f32)
+    pa, ba = _ptr_array(params), _ptr_array(buffers)
+    call("geossl_rr_head_fwd", ptr(X), ptr(Y), B, F, RR_LOSSES[kind], pa.ctypes.data, ba.ctypes.data, float(bn[0][0]),
+         float(bn[0][1]), float(bn[1][0]), float(bn[1][1]), ptr(zhat), ptr(istd), ptr(act), ptr(p), ptr(ws), ptr(loss),
+         stream())
+    RR_STATS["fwd"] += 1
+    return loss, (zhat, istd, act, p)
+
+
+def rr_head_backward(X, Y, params, saved, kind, detach_target, gout, grads, accumulate):
+    """geossl_rr_head_bwd -> dxy [2B, 128]: rows [0, B) the gradient of X, rows [B, 2B) that of Y; grads: 12 buffers,
+    written or (accumulate) added to."""
+    B, F = X.shape
+    f32 = dict(dtype=torch.float32, device=X.device)
+    zhat, istd, act, p = saved
+    dp, dz = torch.empty(2, B, F, **f32), torch.empty(2, B, F, **f32)
+    dt = None if detach_target else torch.empty(2, B, F, **f32)
+    dxy = torch.empty(2 * B, F, **f32)
+    tn = torch.empty(int(_lib.load().geossl_tn_workspace_floats(B, F, F, 4)), **f32)
+    pa, ga = _ptr_array(params), _ptr_array(grads)
+    call("geossl_rr_head_bwd", ptr(X), ptr(Y), B, F, RR_LOSSES[kind], 1 if detach_target else 0, pa.ctypes.data,
+         ptr(zhat), ptr(istd), ptr(act), ptr(p), ptr(gout), ptr(dp), ptr(dz), ptr(dt), ga.ctypes.data,
+         1 if accumulate else 0, ptr(dxy), ptr(tn), stream())
+    RR_STATS["bwd"] += 1
+    return dxy
+
+
+class _RRHeads(torch.autograd.Function):
+    """(AE_1(X, Y) + AE_2(Y, X)) / 2 (examples/pretrain_GeoSSL.py:96-98) on csrc/rr_head.hip -> loss fp32 scalar.  The
+    backward returns dX, dY (two halves of one buffer: split_views' backward joins them without a copy) and the heads'
+    gradients through autograd, or, inside _lib.direct_grads() with dense fp32 .grad tensors, adds them into those."""
+
+    @staticmethod
+    def forward(ctx, X, Y, kind, detach_target, bn, buffers, *params):
+        X, Y = _f32(X.detach()), _f32(Y.detach())
+        ps = [p.detach().contiguous() for p in params]
+        loss, saved = rr_head_forward(X, Y, ps, buffers, bn, kind)
+        ctx.save_for_backward(X, Y, *saved, *ps)
+        ctx.kind, ctx.detach_target, ctx.params = kind, detach_target, params
+        ctx.set_materialize_grads(False)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        params = ctx.params
+        if gout is None:
+            return (None,) * (6 + len(params))
+        X, Y, zhat, istd, act, p = ctx.saved_tensors[:6]
+        ps = ctx.saved_tensors[6:]
+        direct, grads = _param_grads(params)
+        g = gout.to(torch.float32).contiguous()
+        dxy = rr_head_backward(X, Y, ps, (zhat, istd, act, p), ctx.kind, ctx.detach_target, g, grads, direct)
+        B = X.size(0)
+        return (dxy[:B], dxy[B:], None, None, None, None) + ((None,) * len(params) if direct else tuple(grads))
+
+
+def rr_heads(X, Y, kind, detach_target, bn, buffers, params):
+    """The fused loss of both AutoEncoder heads -> fp32 scalar: X, Y [B, 128] (B >= 2) the two views' readouts, kind
+    "l1" / "l2" / "cosine", bn ((eps, momentum) per head), buffers (running_mean, running_var, num_batches_tracked per
+    head; updated in place), params (W1, b1, gamma, beta, W2, b2 per head)."""
+    _lib.require_cuda(X, Y, *buffers, *params)
+    if (X.dim() != 2 or X.shape != Y.shape or not rr_head_width_ok(X.size(1)) or X.size(0) < 2 or len(params) != 12
+            or len(buffers) != 6 or kind not in RR_LOSSES):
+        raise ValueError("rr_heads: X, Y [B, 128] with B >= 2, 12 parameters, 6 buffers and a loss of %s; got %s, %s, %r"
+                         % (tuple(RR_LOSSES), tuple(X.shape), tuple(Y.shape), kind))
+    return _RRHeads.apply(X, Y, kind, bool(detach_target), bn, buffers, *params)

@@ -12,6 +12,10 @@ the reference's own loop (``loss, acc = do_DDM(...); optimizer.zero_grad(); loss
 :249-260), by ``do_DDM`` itself (``autograd_step._AutogradStep``): the loss it returns is the output of an autograd node
 whose backward hands the replayed gradients to autograd.  The batch types, the graph engine and the trainer base are
 re-exported from ``batch.py``, ``replay.py``, ``autograd_step.py`` and ``step.py``.
+
+The other options of the script live here too: ``do_InfoNCE`` / ``do_EBM_NCE`` with ``ContrastiveTrainer`` (:103-176) and
+``do_RR`` with ``RRTrainer`` (:77-100; its ``AutoEncoder`` heads are this project's own definition,
+``Geom3D/models/autoencoder.py``, on the fused kernels of csrc/rr_head.hip).
 """
 import numpy as np
 import torch
@@ -668,6 +672,215 @@ class ContrastiveTrainer(StepTrainer):
 
     def step(self, batch, noise=None):
         """One training step -> (loss, counts) on the device."""
+        if self.use_graph and (noise is not None or self.device_noise):
+            return self._finish(self._graph_fwd_bwd(batch, noise))
+        return self._finish(self._fwd_bwd(batch, noise))
+
+
+# ---- representation reconstruction: --GeoSSL_option=RR (pretrain_GeoSSL.py:77-100) --------------------------------------
+# The reference's do_RR reads the module globals AE_model_01/02 (:95-96, built at :320-321); here they are module
+# attributes with the same names, or can be passed with ``AE_models=``.  The AutoEncoder class itself is THIS PROJECT'S
+# definition (Geom3D/models/autoencoder.py): the reference tree does not contain one.
+AE_model_01 = None
+AE_model_02 = None
+
+
+class RRArgs:
+    """The fields do_RR reads from the reference's argparse namespace (model_3d, normalize) and what a graph of the step
+    binds beside them: the heads' loss kind and ``detach_target`` (config.py:177-183) and the addresses of their
+    BatchNorm buffers (the kernels update them in place)."""
+
+    def __init__(self, model_3d="schnet", normalize=False, heads=None):
+        self.model_3d, self.normalize = model_3d, bool(normalize)
+        self.heads_key = None if heads is None else _rr_heads_key(heads)
+
+
+def _rr_bn(head):
+    return head.fc_layers[1]
+
+
+def _rr_buffers(head):
+    bn = _rr_bn(head)
+    return [bn.running_mean, bn.running_var, bn.num_batches_tracked]
+
+
+def _rr_heads_key(heads):
+    return tuple((h.loss, bool(h.detach_target), float(_rr_bn(h).eps), float(_rr_bn(h).momentum))
+                 + tuple(b.data_ptr() for b in _rr_buffers(h)) for h in heads)
+
+
+def fused_head_ok(head):
+    """This project's AutoEncoder (not a subclass) as the fused kernels compute it: training mode, width 128,
+    fc_layers = Linear, stock BatchNorm1d with affine parameters, running statistics and a momentum, ReLU, Linear; one of
+    the three losses; contiguous fp32 CUDA parameters that all require a gradient."""
+    from .Geom3D.models.autoencoder import AE_LOSSES, AutoEncoder
+    nn = torch.nn
+    if type(head) is not AutoEncoder or not head.training or head.loss not in AE_LOSSES:
+        return False
+    fc = getattr(head, "fc_layers", None)
+    if type(fc) is not nn.Sequential or [type(m) for m in fc] != [nn.Linear, nn.BatchNorm1d, nn.ReLU, nn.Linear]:
+        return False
+    bn = fc[1]
+    if not (bn.affine and bn.track_running_stats and bn.momentum is not None and bn.training and fc[0].training
+            and bn.running_mean is not None and bn.num_batches_tracked is not None and bn.running_mean.is_cuda
+            and bn.running_mean.dtype == torch.float32 and bn.num_batches_tracked.dtype == torch.long):
+        return False
+    F_ = head.emb_dim
+    shapes = [(F_, F_), (F_,), (F_,), (F_,), (F_, F_), (F_,)]
+    ps = list(head.parameters())
+    if [tuple(p.shape) for p in ps] != shapes or fc[0].bias is None or fc[3].bias is None:
+        return False
+    if not all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.requires_grad for p in ps):
+        return False
+    return ops.rr_head_width_ok(F_)
+
+
+def fused_heads_ok(a, b):
+    """Two DISTINCT fused-ok AutoEncoders with the same loss and ``detach_target`` and no parameter or buffer in common:
+    what one set of launches serves."""
+    if a is None or b is None or a is b or not (fused_head_ok(a) and fused_head_ok(b)):
+        return False
+    if a.loss != b.loss or bool(a.detach_target) != bool(b.detach_target) or a.emb_dim != b.emb_dim:
+        return False
+    mine = {t.data_ptr() for t in list(a.parameters()) + _rr_buffers(a)}
+    return not (mine & {t.data_ptr() for t in list(b.parameters()) + _rr_buffers(b)})
+
+
+def rr_heads_aten(a, b, X, Y):
+    """:95-97 as the reference writes them, on the heads' own ATen forward."""
+    AE_loss_1 = a(X, Y)
+    AE_loss_2 = b(Y, X)
+    return (AE_loss_1 + AE_loss_2) / 2
+
+
+def rr_heads_loss(a, b, X, Y):
+    """(AE_1(X, Y) + AE_2(Y, X)) / 2 -> fp32 scalar: both heads in the fused launches (csrc/rr_head.hip) where
+    ``fused_heads_ok`` holds and X, Y are fp32 CUDA rows of the heads' width with B >= 2; the ATen lines otherwise (eval
+    mode, other widths, subclasses, CPU tensors; B = 1 in training mode raises torch's own ValueError there)."""
+    if (fused_heads_ok(a, b) and X.is_cuda and Y.is_cuda and X.dtype == Y.dtype == torch.float32 and X.dim() == 2
+            and X.shape == Y.shape and X.size(1) == a.emb_dim and X.size(0) >= 2):
+        buffers = _rr_buffers(a) + _rr_buffers(b)
+        from .replay import warming_up
+        if warming_up():   # a pass that is no step of the caller's: the running statistics stay where they are
+            buffers = [t.clone() for t in buffers]
+        bn = tuple((float(_rr_bn(h).eps), float(_rr_bn(h).momentum)) for h in (a, b))
+        return ops.rr_heads(X, Y, a.loss, bool(a.detach_target), bn, buffers, list(a.parameters()) + list(b.parameters()))
+    return rr_heads_aten(a, b, X, Y)
+
+
+def _rr_eager(args, batch, model, mu, sigma, heads, noise, device_noise):
+    """The step as eager launches: both views through the backbone as one fused batch, readout, --normalize, the split
+    (``_contrastive_views``), then the two heads."""
+    X, Y = _contrastive_views(args, batch, model, mu, sigma, noise, device_noise)
+    return rr_heads_loss(heads[0], heads[1], X, Y)
+
+
+def rr_step_aten(args, batch, model, AE_models, mu=0.0, sigma=0.3, noise=None, device_noise=False):
+    """The step with the heads in ATen whatever they are (the restatement the kernels are tested against, and the route
+    of everything they refuse)."""
+    X, Y = _contrastive_views(args, batch, model, mu, sigma, noise, device_noise)
+    return rr_heads_aten(AE_models[0], AE_models[1], X, Y)
+
+
+RR = Objective(
+    "RR", lambda eng, args, mu, sigma, batch, noise: _rr_eager(args, batch, eng.model, mu, sigma, (eng.n1, eng.n2), noise, True),
+    views=2, head_params=lambda h: list(h.parameters()),
+    graph_key=lambda args: ("RR", args.model_3d, bool(getattr(args, "normalize", False)), getattr(args, "heads_key", None)),
+    noise_keys=lambda args: ("pos_noise",),
+    step_args=lambda args: RRArgs(args.model_3d, getattr(args, "normalize", False)),
+    capture_inputs=lambda eng, args, batch, mu, sigma, noise, device_noise:
+        draw_views_noise(batch, mu, sigma, device_noise, noise),
+    write_inputs=lambda eng, args, sg, g, batch, mu, sigma, noise, device_noise:
+        draw_views_noise(batch, mu, sigma, device_noise, noise, into=sg.noise_views(g)))
+
+
+def do_RR(args, batch, model, mu=0.0, sigma=0.3, AE_models=None, noise=None, device_noise=False, graph=None, **kwargs):
+    """pretrain_GeoSSL.py:77-100 -> (AE_loss fp32 scalar tensor, 0).  The heads are ``AE_models=(a, b)`` or the module
+    globals ``AE_model_01/02``; further keywords (the loop passes ``criterion=``, :246-248) are ignored like in the
+    reference.  noise: optional {"pos_noise": [N, 3]}; device_noise / graph as in do_DDM: with two fused-ok heads forward +
+    backward replay from HIP graphs (capacity buckets included; the heads' BatchNorm buffers move once per step, eager or
+    replayed), and the loss supports the reference's own ``loss.backward()`` with a stock ``torch.optim.Adam``."""
+    a, b = AE_models if AE_models is not None else (AE_model_01, AE_model_02)
+    if a is None or b is None:
+        raise RuntimeError("set geossl_amd.pretrain_GeoSSL.AE_model_01/02 or pass AE_models=(a, b)")
+    if graph is None:
+        graph = getattr(args, "step_graph", _env("GEOSSL_NO_STEP_GRAPH") is None)
+    if (graph and torch.is_grad_enabled() and not torch.cuda.is_current_stream_capturing() and fused_heads_ok(a, b)
+            and batch.num_graphs >= 2):
+        rargs = RRArgs(args.model_3d, getattr(args, "normalize", False), (a, b))
+        rargs.step_graph_mode = getattr(args, "step_graph_mode", "auto")
+        loss = engine_for(model, "_geossl_rr_step", RR, a, b).run(rargs, batch, mu, sigma, noise, device_noise)
+        if loss is not None:
+            return loss, 0
+    return _rr_eager(args, batch, model, mu, sigma, (a, b), noise, device_noise), 0
+
+
+class RRTrainer(StepTrainer):
+    """The body of ``train()`` (pretrain_GeoSSL.py:234-260) for --GeoSSL_option RR: both views through the backbone as
+    one fused batch, readout, the two AutoEncoder heads in fused launches, backward, gradient all-reduce, Adam -
+    ``[model, ae1, ae2]`` in one flat buffer, no host sync inside ``step(batch, noise=None) -> loss``.
+
+    ``use_graph=True``: forward + backward are captured into HIP graphs and replayed (StepGraphs: ragged batches and
+    DeviceLoader handles share one two-view capacity-bucket graph per batch size; the position noise is drawn into the
+    graph's static input; the heads' BatchNorm buffers are updated in place by the replayed kernels).
+
+    ``ae_lr=None``: the heads run at the backbone's ``lr`` (one Adam launch).  The reference's loop gives the two AE
+    groups ``lr = args.gnn_2d_lr_scale`` (:335-337: the scale itself, 1.0 by default); pass it as ``ae_lr`` for that
+    schedule - a second ``geossl_adam_step`` launch over the heads' range of the flat buffer.
+
+    Under data parallelism the gradients are all-reduced like the other trainers'; the BatchNorm batch statistics stay
+    PER RANK, as with DistributedDataParallel without SyncBatchNorm (each rank's running statistics follow its own
+    batches)."""
+
+    def __init__(self, model, ae_01, ae_02, lr=5e-4, weight_decay=0.0, mu=0.0, sigma=0.3, normalize=False,
+                 model_3d="schnet", device_noise=True, use_graph=False, max_graphs=256, graph_mode="auto", ae_lr=None):
+        if not fused_heads_ok(ae_01, ae_02):
+            raise ValueError("RRTrainer needs two distinct AutoEncoders of width 128 in training mode on the GPU with the "
+                             "same loss and detach_target; use do_RR for anything else")
+        self.n1, self.n2 = ae_01, ae_02
+        self.args = RRArgs(model_3d, normalize)
+        self.mu, self.sigma = mu, sigma
+        self.device_noise = device_noise
+        super().__init__([model, ae_01, ae_02], model_3d, lr, weight_decay, use_graph, max_graphs, graph_mode,
+                         noise_keys=("pos_noise",), views=2)
+        self.ae_lr = ae_lr
+        self._n_backbone = sum(p.numel() for p in model.parameters() if p.requires_grad)
+
+    def _forward(self, batch, noise):
+        if noise is None:
+            noise = draw_views_noise(batch, self.mu, self.sigma, self.device_noise)
+        return _rr_eager(self.args, batch, self.model, self.mu, self.sigma, (self.n1, self.n2), noise, self.device_noise)
+
+    def _capture_inputs(self, batch, noise):
+        return draw_views_noise(batch, self.mu, self.sigma, self.device_noise, noise)
+
+    def _write_inputs(self, g, batch, noise):
+        if noise is None:   # the step's own draw straight into the graph's static input
+            draw_views_noise(g["batch"], self.mu, self.sigma, self.device_noise, into=g["noise"])
+        else:
+            StepGraphs.copy_noise(g, noise)
+
+    def set_lr(self, lr, ae_lr=None):
+        """The learning rate of the next steps (a scheduler's value); ae_lr: the heads' (None: unchanged)."""
+        self.opt.lr = lr
+        if ae_lr is not None:
+            self.ae_lr = ae_lr
+
+    def _finish(self, out):
+        if self.ae_lr is None or float(self.ae_lr) == float(self.opt.lr):
+            return super()._finish(out)
+        _lib.poll_status(self.model)
+        scale = self.reduce()
+        opt, fp, nb = self.opt, self.flat, self._n_backbone
+        opt.step_count += 1
+        for lo, hi, lr in ((0, nb, opt.lr), (nb, fp.numel, self.ae_lr)):   # the backbone's range, then the heads'
+            call("geossl_adam_step", ptr(fp.flat[lo:hi]), ptr(fp.grad[lo:hi]), ptr(opt.exp_avg[lo:hi]),
+                 ptr(opt.exp_avg_sq[lo:hi]), hi - lo, float(lr), float(opt.betas[0]), float(opt.betas[1]), float(opt.eps),
+                 float(opt.weight_decay), opt.step_count, float(scale), stream())
+        return out
+
+    def step(self, batch, noise=None):
+        """One training step -> loss on the device."""
         if self.use_graph and (noise is not None or self.device_noise):
             return self._finish(self._graph_fwd_bwd(batch, noise))
         return self._finish(self._fwd_bwd(batch, noise))

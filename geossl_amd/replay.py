@@ -28,14 +28,27 @@ def own_capture_open():
 
 
 # ---- the capture ---------------------------------------------------------------------------------------------------------
+_WARMING = [0]  # > 0 while the passes of a warm_up run
+
+
+def warming_up():
+    """True inside the passes of `warm_up`: extra runs of the step that are not steps of the caller.  A step with state
+    beside its gradients (the BatchNorm buffers of the RR heads) keeps that state out of them."""
+    return _WARMING[0] > 0
+
+
 def warm_up(passes):
     """`passes()` on a side stream, off the capture that follows: builds the cached layouts, sets kernel attributes.
     Nothing may be pending on the device when that capture starts (in a multi-rank job the collective's watchdog thread
     polls events of earlier all-reduces), and calls of other threads must not invalidate it: the device is drained."""
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        passes()
+    _WARMING[0] += 1
+    try:
+        with torch.cuda.stream(side):
+            passes()
+    finally:
+        _WARMING[0] -= 1
     torch.cuda.current_stream().wait_stream(side)
     torch.cuda.synchronize()
 

@@ -1253,6 +1253,35 @@ int geossl_sampled_tuples(const int32_t* mol_ptr, const int32_t* se_ptr, int64_t
                           int draw, uint64_t seed, int64_t N_cap, int64_t S_cap, int64_t* sei0, int64_t* sei1,
                           int64_t* inc_ptr, int32_t* inc_idx, int32_t* status, hipStream_t stream);
 
+/* ---- GeoSSL-RR: the two AutoEncoder heads of examples/pretrain_GeoSSL.py:77-100 (csrc/rr_head.hip) ---------------------
+ * The AutoEncoder is THIS PROJECT'S definition (geossl_amd/Geom3D/models/autoencoder.py): p = Linear2(relu(BatchNorm1d(
+ * Linear1(x)))) and a loss of p against y: kind 0 "l1" mean |p - y|, 1 "l2" mean (p - y)^2, 2 "cosine" - mean over the rows
+ * of <p, y> / (max(|p|, 1e-8) max(|y|, 1e-8)).  Both heads run in the same launches: head 0 on (X, Y), head 1 on (Y, X);
+ * X, Y [B][F] fp32, F = 128 (geossl_rr_head_width_ok), 2 <= B <= 2^20 (an exact count on every route).
+ * params / grads: HOST arrays of 12 device pointers, per head W1 [F][F], b1 [F], gamma [F], beta [F], W2 [F][F], b2 [F];
+ * buffers: host array of 6 device pointers, per head running_mean [F], running_var [F], num_batches_tracked (int64 [1]).
+ * Forward: Z = a W1^T + b1; per column the batch mean and the biased variance over the B rows; zhat [2][B][F] (out) =
+ *   (Z - mean) istd with istd [2][F] (out) = 1 / sqrt(var + eps_h); act [2][B][F] (out) = relu(gamma zhat + beta);
+ *   p [2][B][F] (out) = act W2^T + b2; loss [1] = (loss_0 + loss_1) / 2 (fp64 sums in a fixed order, stored as fp32).  The
+ *   same pass updates the buffers IN PLACE: running = (1 - momentum_h) running + momentum_h (mean | var B / (B - 1)),
+ *   num_batches_tracked + 1.  workspace: geossl_rr_head_workspace_floats(B) floats, 8-byte aligned.  5 launches.
+ * Backward from the upstream gradient gout[0]: dp [2][B][F] (scratch), dz [2][B][F] (scratch; ends as the gradient of Z),
+ *   dt [2][B][F] (scratch: the gradients of the heads' targets; non-NULL exactly when detach_target == 0); the 12
+ *   parameter gradients written, or added to with accumulate = 1 (the four weight and bias pairs through
+ *   geossl_linear_wgrad, tn_workspace: geossl_tn_workspace_floats(B, F, F, 4) floats); dxy [2B][F] (out): rows [0, B) the
+ *   gradient of X = head 0's input gradient (+ head 1's target gradient), rows [B, 2B) that of Y.  l1: sign(0) = 0.
+ *   6 launches.  The two dense products of each pass run on the matrix pipe with three-way split operands; no atomics:
+ *   the same bits every launch. */
+int geossl_rr_head_width_ok(int F);
+int64_t geossl_rr_head_workspace_floats(int64_t B);
+int geossl_rr_head_fwd(const float* X, const float* Y, int64_t B, int F, int loss_kind, const float* const* params,
+                       float* const* buffers, float eps0, float momentum0, float eps1, float momentum1, float* zhat,
+                       float* istd, float* act, float* p, float* workspace, float* loss, hipStream_t stream);
+int geossl_rr_head_bwd(const float* X, const float* Y, int64_t B, int F, int loss_kind, int detach_target,
+                       const float* const* params, const float* zhat, const float* istd, const float* act,
+                       const float* p, const float* gout, float* dp, float* dz, float* dt, float* const* grads,
+                       int accumulate, float* dxy, float* tn_workspace, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
