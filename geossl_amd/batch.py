@@ -158,6 +158,11 @@ def _tensor_uid(t_):
     return uid
 
 
+def tensor_tag(t_):
+    """What identifies a tensor that a graph binds as it is: the object, its version and its shape; None for None."""
+    return None if t_ is None else (_tensor_uid(t_), t_._version, tuple(t_.shape))
+
+
 def structure_fingerprint(batch, model_3d="schnet"):
     """Hashable identity of everything a captured step binds besides x, positions and the noise: the batch vector,
     super_edge_index and (PaiNN) radius_edge_index with the index structures derived from them.
@@ -172,11 +177,10 @@ def structure_fingerprint(batch, model_3d="schnet"):
       device-resident, pre-collated batch that comes back every epoch)."""
     if getattr(batch, "_dataset", None) is not None and model_3d != "painn":
         return batch.fingerprint()   # a handle on a device-resident dataset: its index tensors ARE a function of the sizes
-    tag = lambda t_: None if t_ is None else (_tensor_uid(t_), t_._version, tuple(t_.shape))
     rei = getattr(batch, "radius_edge_index", None) if model_3d == "painn" else None
-    tags = (tag(batch.batch), tag(batch.super_edge_index), tag(rei))
+    tags = (tensor_tag(batch.batch), tensor_tag(batch.super_edge_index), tensor_tag(rei))
     if getattr(batch, "_triples", False):   # (a triple batch: its targets are bound by a per-structure graph too)
-        tags += (tag(batch.super_edge_angle),)
+        tags += (tensor_tag(batch.super_edge_angle),)
     cached = batch.__dict__.get("_geossl_fp")
     if cached is not None and cached[0] == tags:
         return cached[1]

@@ -23,7 +23,7 @@ import torch
 from . import _lib, ops
 from . import finetune_lep as lep
 from . import pretrain_Supervised as sup
-from .replay import StepGraphs
+from .replay import StepGraphs, parameter_addresses
 from .step import backbone_latent
 
 __all__ = ["Evaluator", "evaluator_for"]
@@ -57,7 +57,7 @@ class Evaluator:
         self.graphs = StepGraphs(self._forward, model_3d, max_graphs, mode=graph_mode, modules=(model, head, None),
                                  noise_keys=("target",), views=1, pair_tuples=False)
         self.enabled = True
-        self.bound = self._addresses()
+        self.bound = parameter_addresses(model, head)
 
     def __deepcopy__(self, memo):
         return None
@@ -69,11 +69,8 @@ class Evaluator:
     def captures(self):
         return self.graphs.captures
 
-    def _addresses(self):
-        return tuple(p.data_ptr() for m in (self.model, self.head) if m is not None for p in m.parameters())
-
     def unchanged(self):
-        return self.bound == self._addresses()
+        return self.bound == parameter_addresses(self.model, self.head)
 
     # ---- the forward a graph holds
     @torch.no_grad()

@@ -23,19 +23,18 @@ GEMMs and pairs within rounding of the cutoff (where the envelope is ~0 anyway).
 ``GEOSSL_MD17_COMPLETE_EDGES`` = 0 / 1 forces the choice (switches.md17_complete_edges).
 """
 import types
-from collections import OrderedDict
 
 import numpy as np
 import torch
 import torch.nn as nn
 from torch.autograd import grad
 
-from . import _lib, ops, switches
+from . import _lib, bucket as bk, ops, switches
 from .batch import Batch
 from .graphed import ForceTrainer
 from .layout import get_layout
 from .pretrain_Supervised import model_width, readout_of
-from .replay import capture, copy_static, make_room, seen_before, warm_up
+from .replay import StructureGraphs, capture, copy_static, owned_batch_vector, parameter_addresses, sizes_key, warm_up
 from .step import latent
 
 __all__ = ["do_MD17", "predict_MD17", "eval_MD17", "MD17Trainer", "complete_edges", "COMPLETE_MAX_N"]
@@ -87,11 +86,7 @@ def complete_edges(B, n, device="cpu"):
 
 def _uniform_size(batch):
     """n when the host knows that every molecule of the batch has n atoms, else None."""
-    sizes = getattr(batch, "_sizes", None)
-    if sizes is None or not len(sizes):
-        return None
-    n = int(sizes[0])
-    return n if all(int(s) == n for s in sizes) else None
+    return bk.size_range(batch)[0] if bk.is_uniform(batch) else None
 
 
 def complete_applies(batch, model):
@@ -281,22 +276,17 @@ def _fused_predict_ok(model, graph_pred_linear, batch):
     return ps
 
 
-class _Predictor:
-    """The captured forward-with-forces graphs of (backbone, head): one per batch structure, keyed by the host sizes like
-    GraphedForward - equal-sized molecules at the first sighting, ragged SchNet batches at the second; PaiNN only on the
-    interned complete pair list (a frame's own edge list is an input whose length a graph would bind)."""
+class _Predictor(StructureGraphs):
+    """The captured forward-with-forces graphs of (backbone, head), one per batch structure (StructureGraphs' docstring);
+    PaiNN only on the interned complete pair list: a frame's own edge list is an input whose length a graph would bind."""
 
     def __init__(self, model, head, model_3d, max_graphs=16):
-        self.model, self.head, self.model_3d, self.max_graphs = model, head, model_3d, max_graphs
-        self.graphs, self.pool, self.captures, self.enabled = OrderedDict(), None, 0, True
-        self._seen = OrderedDict()
-        self.bound = self._addresses()
-
-    def _addresses(self):
-        return tuple(p.data_ptr() for m in (self.model, self.head) for p in m.parameters())
+        super().__init__(max_graphs)
+        self.model, self.head, self.model_3d = model, head, model_3d
+        self.bound = parameter_addresses(model, head)
 
     def unchanged(self):
-        return self.bound == self._addresses()
+        return self.bound == parameter_addresses(self.model, self.head)
 
     def _eager(self, ps, x, pos, bvec, rei):
         x = x if self.model_3d == "painn" or x.dim() == 1 else x[:, 0]
@@ -307,36 +297,21 @@ class _Predictor:
         next call."""
         rei = getattr(batch, "radius_edge_index", None) if self.model_3d == "painn" else None
         sizes = getattr(batch, "_sizes", None)
-        interned = self.model_3d != "painn" or getattr(batch, "_complete", False)
-        if (not (use_graph and self.enabled) or sizes is None or not interned
-                or torch.cuda.is_current_stream_capturing()):
+        hit = (use_graph and sizes is not None and (self.model_3d != "painn" or getattr(batch, "_complete", False))
+               and self.lookup(sizes_key(batch.batch.numel(), sizes) + (tuple(batch.x.shape),),
+                               lambda: bk.is_uniform(batch), lambda: self._capture(ps, batch, rei)))
+        if not hit:
             return self._eager(ps, batch.x, batch.positions, batch.batch, rei)
-        key = (int(batch.batch.numel()), np.asarray(sizes, dtype=np.int32).tobytes(), tuple(batch.x.shape))
-        g = self.graphs.get(key)
-        if g is None:
-            if _uniform_size(batch) is None and not seen_before(self._seen, key, 4096):   # ragged: second sighting
-                return self._eager(ps, batch.x, batch.positions, batch.batch, rei)
-            g = self._capture(ps, batch, rei)
-            if g is None:
-                return self._eager(ps, batch.x, batch.positions, batch.batch, rei)
-            make_room(self.graphs, self.max_graphs)
-            self.graphs[key] = g
-        else:
-            self.graphs.move_to_end(key)
+        g, made = hit
+        if not made:   # (a new graph's static inputs are clones of this batch)
             copy_static([(g["x"], batch.x), (g["pos"], batch.positions)])
         g["graph"].replay()
         _lib.poll_status(self.model)
         return g["out"]
 
     def _capture(self, ps, batch, rei):
-        # the graph binds the addresses of the index structures cached on the batch vector: the entry owns them - a
-        # private clone with the host sizes re-attached (SchNet), or the interned vector and edges (PaiNN)
-        x, pos = batch.x.clone(), batch.positions.detach().clone()
-        if self.model_3d == "painn":
-            bvec = batch.batch
-        else:
-            bvec = batch.batch.clone()
-            bvec._geossl_sizes = ([int(n) for n in batch._sizes], bvec._version)
+        x, pos = batch.x.clone(), batch.positions.detach().clone()   # (PaiNN: the interned vector and edges)
+        bvec = batch.batch if self.model_3d == "painn" else owned_batch_vector(batch.batch, batch._sizes)
         if self._eager(ps, x, pos, bvec, rei) is None:
             return None
 
@@ -349,7 +324,6 @@ class _Predictor:
             graph, out = cap.record(lambda: self._eager(ps, x, pos, bvec, rei))
         if not cap.ok:
             return None
-        self.captures += 1
         return dict(graph=graph, x=x, pos=pos, out=out, bvec=bvec, rei=rei, layout=get_layout(bvec))
 
 
@@ -475,17 +449,14 @@ class MD17Trainer(ForceTrainer):
                 or getattr(ds, "force", None) is None or torch.cuda.is_current_stream_capturing()):
             return None
         B, N = handle.num_graphs, handle.n_atoms
-        if self.model_3d == "painn":
+        ei = bvec = None
+        if self.model_3d == "painn":   # (the interned tensors the collated route would put into its batch)
             if not switches.md17_complete_edges(complete_applies(handle, self.model)):
                 return None
             ei, bvec = complete_edges(B, _uniform_size(handle), ds.device)
-            key = self._key(types.SimpleNamespace(batch=bvec, radius_edge_index=ei))
-        else:
-            key = ("sizes", N, np.asarray(handle._sizes, dtype=np.int32).tobytes())
-        g = self.graphs.get(key)
-        if g is None or tuple(g["x"].shape) != (N, ds.x_cols):
+        g = self.get(self._key(bvec, ei, handle._sizes, N))
+        if g is None or tuple(g["x"].shape) != (N, ds.x_cols):   # (another x: the collated route uses this key next)
             return None
-        self.graphs.move_to_end(key)
         mol_ptr = get_layout(g["bvec"]).mol_ptr
         ds.gather_into(handle, g["x"], g["pos"], mol_ptr)
         src_off = ds.__dict__["_src_off_dev"]   # (the offsets gather_into uploaded: stream order keeps them for these two)

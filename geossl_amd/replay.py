@@ -1,6 +1,6 @@
 """Capturing a step into HIP graphs and replaying it: the one capture every owner of graphs goes through (``warm_up``,
-``capture``), its bounded memories (``seen_before``, ``make_room``), the copy into a graph's static inputs
-(``copy_static``), the graphs of a training step (``StepGraphs``) and the autograd thread switch of a replayed loss.
+``capture``), its bounded memories (``seen_before``, ``make_room``), the copy into a graph's static inputs (``copy_static``),
+the graphs per batch structure (``StructureGraphs``) and per training step (``StepGraphs``), a replayed loss's thread switch.
 """
 import ctypes as C
 import gc
@@ -9,11 +9,12 @@ import time
 import warnings
 from collections import OrderedDict
 
+import numpy as np
 import torch
 
 from . import _lib, bucket as bk
 from ._lib import call, ptr, stream
-from .batch import Batch, TripleBatch, structure_fingerprint
+from .batch import Batch, TripleBatch, structure_fingerprint, tensor_tag
 from .layout import get_layout
 from .switches import env as _env
 
@@ -133,6 +134,79 @@ def copy_static(pairs, zero=None):
             d.copy_(s)
         if zero is not None:
             zero.zero_()
+
+
+# ---- one graph per batch structure ---------------------------------------------------------------------------------------
+def sizes_key(n_atoms, sizes):
+    """Key of a structure whose index tensors are a function of the host sizes: equal size sequences share a graph."""
+    return ("sizes", int(n_atoms), np.asarray(sizes, dtype=np.int32).tobytes())
+
+
+def tensors_key(*tensors):
+    """Key of a structure only its tensor OBJECTS identify (batch.tensor_tag: object, version, shape; None stays None)."""
+    return ("tensors",) + tuple(tensor_tag(t_) for t_ in tensors)
+
+
+def owned_batch_vector(batch_vec, sizes=None):
+    """A graph binds the ADDRESSES of the index structures (mol_ptr, pair_ptr, pair atoms, aggregation work list, the loop
+    plan), which are cached on the batch vector (`_geossl_layout`).  Its entry therefore owns this private clone - with the
+    host sizes (`sizes`, else the vector's own while its version matches) re-attached, so the clone builds the same layout
+    - and keeps it alive as long as the graph: the caller's batch may be freed without those addresses being reused."""
+    bvec = batch_vec.clone()
+    hs = getattr(batch_vec, "_geossl_sizes", None)   # (host sizes, tensor version), layout.prepare_batch
+    if sizes is None and hs is not None and hs[1] == batch_vec._version:
+        sizes = hs[0]
+    if sizes is not None:
+        bvec._geossl_sizes = ([int(n) for n in sizes], bvec._version)
+    return bvec
+
+
+def parameter_addresses(*modules):   # (None: skipped; an owner of graphs is rebuilt when its modules' parameters moved)
+    return tuple(p.data_ptr() for m in modules if m is not None for p in m.parameters())
+
+
+class StructureGraphs:
+    """One captured graph per batch structure: the counterpart of StepGraphs' buckets and the one place that knows the
+    protocol.  ``graphs``: the entries an owner's capture builds, by key, least recently used first, at most ``max_graphs``, in
+    ONE memory ``pool``; ``captures`` counts them; a failed capture clears ``enabled`` (FT's ``use_graph``).  A key is captured
+    at first sight where its owner says so, else at the second within ``seen_bound`` sightings (a loader that never repeats a
+    structure never pays).  Nothing is looked up or captured while the current stream is capturing: that call runs eagerly,
+    into the caller's graph.  Derived: GF graphed.GraphedForward, FT graphed.ForceTrainer, P finetune_md17._Predictor.
+    served (else eager): GF fingerprint kind "sizes" on CUDA; FT all while use_graph; P host sizes, PaiNN on complete edges
+    key: GF its fingerprint; FT PaiNN tensors_key(bvec, edges), else sizes_key or tensors_key(bvec); P sizes_key + x.shape
+    ... captured at first sight: GF, P for equal-sized molecules; FT for a sizes_key
+    1-D against 2-D x on a hit: GF, FT that call runs eagerly and the graph stays; P the shape is in the key
+    the call that captures: GF, P replay without a copy (the statics are clones of the batch); FT copies in, then replays
+    warm-up: GF eager pass, loop_plan(); FT the body twice; P eager probe (None: no capture), eager pass, SchNet loop_plan()
+    poll_status after a replay: GF, P yes; FT no, deliberately for now (host work in a step whose launches are pinned)"""
+
+    def __init__(self, max_graphs, enabled=True, seen_bound=4096):
+        self.graphs, self._seen, self.pool, self.captures = OrderedDict(), OrderedDict(), None, 0
+        self.max_graphs, self.enabled, self.seen_bound = max_graphs, enabled, seen_bound
+
+    def get(self, key):   # (for a caller that only replays: the entry, now the most recently used one, or None)
+        g = self.graphs.get(key)
+        if g is not None:
+            self.graphs.move_to_end(key)
+        return g
+
+    def lookup(self, key, first_sight, make):
+        """-> (entry, whether it was just made), or None: this call runs eagerly - cache off, stream capturing, a first
+        sighting, or a failed ``make() -> entry or None``.  ``first_sight() -> bool`` is asked only on a miss."""
+        if not self.enabled or (torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing()):
+            return None   # (is_initialized: a host without a device has no stream to ask)
+        g = self.get(key)
+        if g is not None:
+            return g, False
+        if not first_sight() and not seen_before(self._seen, key, self.seen_bound):
+            return None
+        g = make()
+        if g is None:
+            return None
+        self.captures += 1
+        make_room(self.graphs, self.max_graphs)
+        self.graphs[key] = g
+        return g, True
 
 
 # ---- the graphs of a training step -------------------------------------------------------------------------------------

@@ -28,7 +28,9 @@ RAGGED = ((6, 5, 6, 4), (3, 4, 5, 6), (5, 3, 3, 6))   # (the largest first: the 
 STEP_KEYS = ["batch", "extra", "graph", "graph_bwd", "loss", "noise", "zero"]
 CASES = ("a: DDMTrainer, ragged SchNet", "b: DDMTrainer, equal sizes", "c: DDMTrainer, PaiNN by hand",
          "d: reference loop", "e: DistancePredictionTrainer", "f: SupervisedTrainer, sparse bucket",
-         "g: GraphedForward", "h: ForceTrainer, SchNet", "h: ForceTrainer, PaiNN")
+         "g: GraphedForward", "h: ForceTrainer, SchNet", "h: ForceTrainer, PaiNN",
+         "i: predict_MD17, SchNet", "i: predict_MD17, PaiNN",
+         "j: MD17Trainer, handles, SchNet", "j: MD17Trainer, handles, PaiNN")
 
 
 def _raw(sizes, seed):
@@ -70,6 +72,23 @@ def _painn():
 def _heads():
     from helpers import product_ncsn
     return product_ncsn(128, 50, 2, DEV), product_ncsn(128, 50, 2, DEV, scale=0.9)
+
+
+def _force_modules(kind):
+    """Backbone and energy head of the force-training and MD17 cases."""
+    from filler import fill_module_
+    from geossl_amd.Geom3D.models.painn import Dense
+    if kind == "painn":
+        model = _painn()
+        return model, fill_module_(model.create_output_layers()).to(DEV)
+    return _schnet(readout="add"), fill_module_(Dense(128, 1)).to(DEV)
+
+
+def _fresh_complete_edges(patch):
+    """No interned complete pair list from an earlier case: the list and the layouts cached on its tensors are built once
+    per process, so their launches would otherwise fall to whichever case runs first."""
+    from geossl_amd import finetune_md17
+    patch(finetune_md17, "_COMPLETE", {})
 
 
 class _Recorder:
@@ -194,16 +213,59 @@ def run_case(case, patch, setenv):
         modules = (model,)
         stats = dict(captures=gf.captures, graphs=len(gf.graphs), keys=sorted(next(iter(gf.graphs.values()))))
         assert gf.enabled
+    elif letter == "i":
+        import types
+        from geossl_amd.finetune_md17 import _predictor, predict_MD17
+        kind = "painn" if case.endswith("PaiNN") else "schnet"
+        model, head = _force_modules(kind)
+        args = types.SimpleNamespace(model_3d=kind)
+
+        def frame(sizes, seed, flat=True):   # (MD17 batches: 1-D x, host sizes, PaiNN with the frame's own radius list)
+            from geossl_amd import ops
+            bt = _batch(sizes, seed)
+            if flat:
+                bt.x = bt.x[:, 0].contiguous()
+            if kind == "painn":
+                bt.radius_edge_index = ops.radius_graph(bt.positions, 5.0, bt.batch)
+            return bt
+        if kind == "schnet":   # capture, replay; eager, capture, replay; a 2-D x behind the 1-D ones: another key
+            batches = ([frame((4, 4), 60 + i) for i in range(2)] + [frame((4, 3), 62 + i) for i in range(3)]
+                       + [frame((4, 4), 65, flat=False)])
+        else:                  # capture, replay on the complete pair list; the frame's own edges: eager
+            batches = [frame((4, 4), 60 + i) for i in range(3)]
+            _fresh_complete_edges(patch)
+        for i, bt in enumerate(batches):
+            if kind == "painn" and i == 2:
+                setenv("GEOSSL_MD17_COMPLETE_EDGES", "0")
+            e, f = rec.step(lambda: predict_MD17(args, bt, model, head))
+            losses.append(torch.cat([e.reshape(-1), f.reshape(-1)]))
+        modules, pr = (model, head), _predictor(model, head, kind)
+        stats = dict(captures=pr.captures, graphs=len(pr.graphs), keys=sorted(next(iter(pr.graphs.values()))))
+        assert pr.enabled
+    elif letter == "j":
+        from geossl_amd.Geom3D.dataloaders.device_dataset import DeviceDataset, DeviceLoader
+        from geossl_amd.finetune_md17 import MD17Trainer
+        kind = "painn" if case.endswith("PaiNN") else "schnet"
+        model, head = _force_modules(kind)
+        raws = [_raw((4, 4), 70 + i) for i in range(4)]
+        gen = torch.Generator().manual_seed(3)
+        ds = DeviceDataset(np.concatenate([r["x"][:, 0] for r in raws]), np.concatenate([r["positions"] for r in raws]),
+                           [4] * 8, DEV, y=torch.randn(8, generator=gen), force=torch.randn(32, 3, generator=gen),
+                           radius=5.0 if kind == "painn" else None)
+        tr = MD17Trainer(model, head, model_3d=kind, lr=5e-4)
+        if kind == "painn":
+            _fresh_complete_edges(patch)
+        # SchNet (a sizes key): collated and captured, then replays from the handle; PaiNN (the interned tensors' key): the
+        # collated step eagerly, then captured, then replays from the handle
+        for hb in DeviceLoader(ds, batch_size=2, shuffle=False):
+            losses.append(rec.step(lambda: tr.step(hb)).clone())
+        modules = (model, head)
+        stats = dict(captures=tr.captures, graphs=len(tr.graphs), keys=sorted(next(iter(tr.graphs.values()))))
+        assert tr.use_graph and len(losses) == 4
     else:
-        from filler import fill_module_
-        from geossl_amd.Geom3D.models.painn import Dense
         from geossl_amd.graphed import ForceTrainer
         kind = "painn" if case.endswith("PaiNN") else "schnet"
-        if kind == "painn":
-            model = _painn()
-            head = fill_module_(model.create_output_layers()).to(DEV)
-        else:
-            model, head = _schnet(readout="add"), fill_module_(Dense(128, 1)).to(DEV)
+        model, head = _force_modules(kind)
         tr = ForceTrainer(model, head, model_3d=kind, lr=5e-4)
         gen = torch.Generator().manual_seed(3)
         kept = _by_hand((4, 4), 50)   # (PaiNN: the very same edge tensor every step)
@@ -220,7 +282,7 @@ def run_case(case, patch, setenv):
 
 def short(step, ordered=True):
     """A step's names as EXPECTED holds them: written out up to a dozen, else (how many, their digest).  ordered=False:
-    the digest of the sorted names - what the force-training cases hold, whose eager and capture steps called the
+    the digest of the sorted names - what the force-training cases (h, j) hold, whose eager and capture steps called the
     second-order tape's entry points in an order that differed between two runs of the parent itself (the same calls
     as often; their replay steps are written out like all others)."""
     if len(step) <= 12:
@@ -236,12 +298,13 @@ def test_step_engine_launch_sequence(case, monkeypatch):
     assert stats == want_stats, stats
     assert len(steps) == len(want_steps)
     for k, (got, want) in enumerate(zip(steps, want_steps)):
-        assert short(got, ordered=not case.startswith("h")) == want, "step %d: %s" % (k, " ".join(got))
+        assert short(got, ordered=case[0] not in "hj") == want, "step %d: %s" % (k, " ".join(got))
 
 
 # per case: (one entry per step in `short` form, the owner's counts and the keys of a graph's entry); written by the job
 # script that ran `run_case` on the parent commit (twice, in two processes and two orders of the cases: the same lists)
 _BUCKET_KEYS = ["batch", "bucket", "counts", "extra", "graph", "graph_bwd", "loss", "noise", "zero"]
+_PREDICT_KEYS = ["bvec", "graph", "layout", "out", "pos", "rei", "x"]
 _FORCE_KEYS = ["bvec", "graph", "loss", "ones", "pos", "rei", "x", "y_e", "y_f"]
 EXPECTED = {
     "a: DDMTrainer, ragged SchNet": ([
@@ -291,5 +354,30 @@ EXPECTED = {
         (779, "3740ceed3b937739"),
         (2321, "1249d6c5da60340b"),
         "copy_n adam_step",
+    ], {"captures": 1, "graphs": 1, "keys": _FORCE_KEYS}),
+    "i: predict_MD17, SchNet": ([
+        (53, "594796d420592639"),
+        "copy2",
+        (22, "b77776ec2932984b"),
+        (53, "3eddd29ae86e0e26"),
+        "copy2",
+        (53, "594796d420592639"),
+    ], {"captures": 3, "graphs": 3, "keys": _PREDICT_KEYS}),
+    "i: predict_MD17, PaiNN": ([
+        (108, "96819637f0d12e94"),
+        "copy2",
+        (38, "d952c1b4e6859739"),
+    ], {"captures": 1, "graphs": 1, "keys": _PREDICT_KEYS}),
+    "j: MD17Trainer, handles, SchNet": ([
+        (1039, "7cba23c2145edcab"),
+        "gather_molecules property_targets gather_atom_rows adam_step",
+        "gather_molecules property_targets gather_atom_rows adam_step",
+        "gather_molecules property_targets gather_atom_rows adam_step",
+    ], {"captures": 1, "graphs": 1, "keys": _FORCE_KEYS}),
+    "j: MD17Trainer, handles, PaiNN": ([
+        (785, "d488987973e625c9"),
+        (2323, "7a5627b0c4bec9a4"),
+        "gather_molecules property_targets gather_atom_rows adam_step",
+        "gather_molecules property_targets gather_atom_rows adam_step",
     ], {"captures": 1, "graphs": 1, "keys": _FORCE_KEYS}),
 }
