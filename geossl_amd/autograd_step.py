@@ -97,6 +97,8 @@ class _AutogradStep:
     land in a flat static buffer (the parameters' .grad point into it only while a step is captured); a step whose
     backward() has not been called when the next step arrives keeps a snapshot of them."""
 
+    capacity_draws = False   # draws land at the caller's real row counts: torch's RNG stream, as eager (step.draw_target)
+
     def __init__(self, model, n1, n2, objective):
         self.model, self.n1, self.n2 = model, n1, n2
         # the step.Objective of this engine says everything that differs between objectives: the heads'
@@ -164,8 +166,7 @@ class _AutogradStep:
         return (type(None), ())
 
     def _fwd(self, batch, noise):
-        args, mu, sigma = self._cfg
-        return self.objective.forward(self, args, mu, sigma, batch, noise)
+        return self.objective.forward(self, self._cfg, batch, noise)
 
     def _bwd(self, loss):
         held = [p.grad for p in self.params]
@@ -234,8 +235,9 @@ class _AutogradStep:
             p.grad = v
         return True
 
-    def run(self, args, batch, mu, sigma, noise, device_noise):
-        """-> `objective.result` of the replayed step (the loss, or the loss and more), or None: run this step eagerly."""
+    def run(self, args, batch, noise=None):
+        """-> `objective.result` of the replayed step (the loss, or the loss and more), or None: run this step eagerly.
+        args: the objective's step-args object; noise: the caller's per-step inputs, if any."""
         if getattr(batch, "_dataset", None) is None and (not batch.positions.is_cuda or batch.positions.requires_grad):
             return None
         obj = self.objective
@@ -251,7 +253,7 @@ class _AutogradStep:
             sg.zero_with_refresh = self.gflat
         if not sg.enabled:
             return None
-        self._cfg = (obj.step_args(args), mu, sigma)
+        self._cfg = args
         g, capture = sg.plan(batch)
         if g is None and not capture:
             return None
@@ -263,12 +265,12 @@ class _AutogradStep:
             if t is not None and t["g"] is None and not t.get("used"):
                 t["g"] = self.gflat.clone()  # a step still waiting for its backward() keeps its gradients
         if capture:   # (a failed capture has cleared sg.enabled: eager from now on)
-            drawn = obj.capture_inputs(self, args, batch, mu, sigma, noise, device_noise)
+            drawn = obj.capture_inputs(self, args, batch, noise)
             g = sg.load(None, batch, drawn, lambda g, _, drawn: sg.copy_noise(g, drawn))
         elif obj.write_inputs is None:
             g = sg.load(g, batch)
         else:
-            g = sg.load(g, batch, write=lambda g, *_: obj.write_inputs(self, args, sg, g, batch, mu, sigma, noise, device_noise))
+            g = sg.load(g, batch, write=lambda g, *_: obj.write_inputs(self, args, g, batch, noise))
         if g is None:
             return None  # (no graph, or the bucket refused the batch's tensors: this step as eager launches)
         g["graph"].replay()            # forward: the loss is on the device when this is done

@@ -34,17 +34,10 @@ import torch.nn as nn
 from . import ops
 from .batch import Batch
 from .pretrain_Supervised import model_width, readout_of
-from .step import Objective, StepTrainer, backbone_latent, engine_for
-from .switches import env as _env
+from .step import Objective, StepTrainer, backbone_latent, run_graphed, stock_bce
 
 
 # ---------------------------------------------------------------------------------------------------- what is served
-def _stock_bce(criterion):
-    """nn.BCEWithLogitsLoss() as the script builds it (:226): mean, no weight, no pos_weight, not a subclass."""
-    return (type(criterion) is nn.BCEWithLogitsLoss and criterion.weight is None and criterion.pos_weight is None
-            and criterion.reduction == "mean")
-
-
 def head_params(head):
     """(weight, bias) of a head the kernels serve - nn.Linear(2F, 1) with a bias, fp32 CUDA parameters, F a served
     width - or None."""
@@ -227,10 +220,11 @@ class _StepArgs:
 # are read, so a batch with a sparse layout - a structure above 255 atoms - may go through a sparse bucket of 2B structures)
 LEP = Objective(
     "LEP",
-    lambda eng, args, mu, sigma, batch, noise: lep_step_fused(args.model_3d, batch, eng.model, eng.n1, noise["target"])[0],
+    lambda owner, args, fb, noise:   # (noise None: an eager step, the batch's own labels)
+        lep_step_fused(args.model_3d, fb, owner.model, owner.n1, noise["target"] if noise is not None else fb.y)[0],
     noise_keys=lambda args: ("target",),
-    capture_inputs=lambda eng, args, batch, mu, sigma, noise, device_noise: {"target": batch.y},
-    write_inputs=lambda eng, args, sg, g, batch, mu, sigma, noise, device_noise: write_labels(g, batch),
+    capture_inputs=lambda owner, args, fb, noise: {"target": fb.y},
+    write_inputs=lambda owner, args, g, fb, noise: write_labels(g, fb),
     pair_tuples=False)
 
 
@@ -249,16 +243,12 @@ def do_LEP(args, batch, model, graph_pred_linear, criterion=None, graph=None):
     if args.model_3d not in ("schnet", "painn"):
         raise Exception("3D model {} not included.".format(args.model_3d))
     _check_handle(batch, args.model_3d)
-    if not (_stock_bce(criterion) and modules_ok(model, graph_pred_linear) and _fused_batch_ok(batch)):
+    if not (stock_bce(criterion) and modules_ok(model, graph_pred_linear) and _fused_batch_ok(batch)):
         return lep_step_aten(args, batch, model, graph_pred_linear, criterion)
     fb = fused_batch(batch)
-    if graph is None:
-        graph = getattr(args, "step_graph", _env("GEOSSL_NO_STEP_GRAPH") is None)
-    if graph and torch.is_grad_enabled() and not torch.cuda.is_current_stream_capturing():
-        eng = engine_for(model, "_geossl_lep_step", LEP, graph_pred_linear)
-        loss = eng.run(_StepArgs(args.model_3d, getattr(args, "step_graph_mode", "auto")), fb, 0.0, 0.0, None, False)
-        if loss is not None:
-            return loss
+    loss = run_graphed(args, graph, model, "_geossl_lep_step", LEP, _StepArgs(args.model_3d), fb, n1=graph_pred_linear)
+    if loss is not None:
+        return loss
     return lep_step_fused(args.model_3d, fb, model, graph_pred_linear, fb.y)[0]
 
 
@@ -389,26 +379,10 @@ class LEPTrainer(StepTrainer):
         if model_3d not in ("schnet", "painn"):
             raise Exception("3D model {} not included.".format(model_3d))
         self.head, self.model_3d = graph_pred_linear, model_3d
-        super().__init__([model, graph_pred_linear], model_3d, lr, weight_decay, use_graph, max_graphs, graph_mode,
-                         noise_keys=("target",), views=1, pair_tuples=False)
+        super().__init__([model, graph_pred_linear], LEP, _StepArgs(model_3d), lr, weight_decay, use_graph, max_graphs,
+                         graph_mode)
 
-    @property
-    def lr(self):
-        return self.opt.lr
-
-    def set_lr(self, lr):
-        """The learning rate of the following steps (an epoch-level scheduler: optim.cosine_annealing_lr)."""
-        self.opt.lr = float(lr)
-
-    def _forward(self, fb, noise):
-        return lep_step_fused(self.model_3d, fb, self.model, self.head, noise["target"] if noise is not None else fb.y)[0]
-
-    def _capture_inputs(self, fb, noise):
-        return {"target": fb.y}
-
-    def _write_inputs(self, g, fb, noise):
-        write_labels(g, fb)
-
+    # the trainer's own: a collated pair batch or a pair handle becomes the one-pass batch before either route
     def _one_pass(self, batch):
         _check_handle(batch, self.model_3d)
         if not isinstance(batch, Batch) and not hasattr(batch, "pairs") and not _fused_batch_ok(batch):

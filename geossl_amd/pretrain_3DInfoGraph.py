@@ -17,8 +17,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .step import Args, Objective, StepTrainer, backbone_forward, backbone_latent, engine_for, with_counts
-from .switches import env as _env
+from .step import Args, Objective, StepTrainer, backbone_forward, backbone_latent, run_graphed, with_counts
+from .step import stock_bce as criterion_ok  # (a stock mean nn.BCEWithLogitsLoss: what the fused loss computes)
 
 
 def uniform(size, value):
@@ -50,12 +50,6 @@ def cycle_index(num, shift):
     arr = torch.arange(num) + shift
     arr[-shift:] = torch.arange(shift)
     return arr
-
-
-def criterion_ok(criterion):
-    """A stock mean nn.BCEWithLogitsLoss (no weight, no pos_weight, not a subclass): what the fused loss computes."""
-    return (type(criterion) is nn.BCEWithLogitsLoss and criterion.reduction == "mean" and criterion.weight is None
-            and criterion.pos_weight is None)
 
 
 def fused_head_ok(discriminator):
@@ -134,7 +128,7 @@ def infograph_step_fused(args, batch, model, discriminator):
 
 # (no random draws; forward -> (loss, counts): the counts are a static output of the forward graph)
 INFOGRAPH = Objective("InfoGraph",
-                      lambda eng, args, mu, sigma, batch, noise: infograph_step_fused(args, batch, eng.model, eng.n1),
+                      lambda owner, args, batch, noise: infograph_step_fused(args, batch, owner.model, owner.n1),
                       result=with_counts)
 
 
@@ -169,16 +163,11 @@ def do_3DInfoGraph(args, batch, model, discriminator, criterion=None, graph=None
     if not (criterion_ok(criterion) and fused_head_ok(discriminator) and readout_of(model) is not None
             and _fused_batch_ok(batch)):
         return infograph_step_aten(args, batch, model, discriminator, criterion)
-    if graph is None:
-        graph = getattr(args, "step_graph", _env("GEOSSL_NO_STEP_GRAPH") is None)
     N = _n_atoms(batch)
-    if graph and torch.is_grad_enabled() and not torch.cuda.is_current_stream_capturing():
-        a = Args(args.model_3d)
-        a.step_graph_mode = getattr(args, "step_graph_mode", "auto")
-        got = engine_for(model, "_geossl_infograph_step", INFOGRAPH, discriminator).run(a, batch, 0.0, 0.0, None, False)
-        if got is not None:
-            loss, counts = got
-            return loss, infograph_acc(counts, N)
+    got = run_graphed(args, graph, model, "_geossl_infograph_step", INFOGRAPH, Args(args.model_3d), batch, n1=discriminator)
+    if got is not None:
+        loss, counts = got
+        return loss, infograph_acc(counts, N)
     loss, counts = infograph_step_fused(args, batch, model, discriminator)
     return loss, infograph_acc(counts.tolist(), N)
 
@@ -199,10 +188,7 @@ class InfoGraphTrainer(StepTrainer):
                              "256) on the GPU and a backbone with an unscaled mean / add readout; use do_3DInfoGraph for "
                              "anything else")
         self.discriminator = discriminator
-        self.args = Args(model_3d)
-        super().__init__([model, discriminator], model_3d, lr, weight_decay, use_graph, max_graphs, graph_mode)
+        super().__init__([model, discriminator], INFOGRAPH, Args(model_3d), lr, weight_decay, use_graph, max_graphs,
+                         graph_mode)
 
     with_extra = True   # step(batch) -> (loss, counts)
-
-    def _forward(self, batch, noise):
-        return infograph_step_fused(self.args, batch, self.model, self.discriminator)

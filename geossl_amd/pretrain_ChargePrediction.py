@@ -21,8 +21,8 @@ import torch.nn as nn
 
 from . import _lib, ops
 from .pretrain_GeoSSL import _next_noise_key
-from .step import Objective, StepTrainer, backbone_forward, backbone_latent, engine_for
-from .switches import env as _env
+from .replay import StepGraphs
+from .step import Objective, StepTrainer, backbone_forward, backbone_latent, run_graphed
 
 node_class = 9   # examples/pretrain_ChargePrediction.py:106 (the mask token is node_class - 1)
 MASK_RNGS = ("numpy", "device")
@@ -160,9 +160,9 @@ class ChargeArgs:
         self.normalize = False
 
 
-def _write_mask(eng, args, sg, g, batch, mu, sigma, noise, device_noise):
+def _write_mask(owner, args, g, batch, mask):
     if args.mask_rng == "numpy":   # (this step's host draw into the graph's static list; a device graph advances its seed)
-        sg.copy_noise(g, noise)
+        StepGraphs.copy_noise(g, mask if mask is not None else draw_mask("numpy", batch, args.charge_masking_ratio))
 
 
 def _keep_extra(eng, out, g):
@@ -174,10 +174,10 @@ def _keep_extra(eng, out, g):
 # by-value argument of its mask launch; forward -> (loss, (masked atoms, k)): static outputs of the forward graph
 CHARGE = Objective(
     "ChargePrediction",
-    lambda eng, args, mu, sigma, batch, noise: charge_step_fused(args, batch, eng.model, eng.n1, noise),
+    lambda owner, args, batch, mask: charge_step_fused(args, batch, owner.model, owner.n1, mask),
     graph_key=lambda args: ("ChargePrediction", args.model_3d, float(args.charge_masking_ratio), args.mask_rng),
     noise_keys=lambda args: ("mask_idx" if args.mask_rng == "numpy" else "mask_seed",),
-    capture_inputs=lambda eng, args, batch, mu, sigma, noise, device_noise: noise,
+    capture_inputs=lambda owner, args, batch, mask: mask,
     write_inputs=_write_mask, result=_keep_extra)
 
 
@@ -202,18 +202,15 @@ def do_ChargePrediction(args, batch, model, charge_predictor, graph=None):
     if not (fused_head_ok(charge_predictor) and _fused_batch_ok(batch)):
         return charge_step_aten(args, batch, model, charge_predictor)
     mask = draw_mask(rng, batch, ratio)
-    if graph is None:
-        graph = getattr(args, "step_graph", _env("GEOSSL_NO_STEP_GRAPH") is None)
     handle = getattr(batch, "_dataset", None) is not None
-    if (graph and torch.is_grad_enabled() and not torch.cuda.is_current_stream_capturing()
-            and (handle or hasattr(batch, "super_edge_index"))):
-        a = ChargeArgs(args.model_3d, ratio, rng)
-        a.step_graph_mode = getattr(args, "step_graph_mode", "auto")
-        eng = engine_for(model, "_geossl_charge_step", CHARGE, charge_predictor)
-        loss = eng.run(a, batch, 0.0, 0.0, mask, False)
+    if handle or hasattr(batch, "super_edge_index"):
+        slot = "_geossl_charge_step"
+        loss = run_graphed(args, graph, model, slot, CHARGE, ChargeArgs(args.model_3d, ratio, rng), batch, mask,
+                           charge_predictor)
         if loss is not None:
             # (the graph's static outputs live in its memory pool: no reference to them may outlive this call, or a
             # later recapture that frees the graph would leave them behind)
+            eng = model.__dict__[slot]
             idx, eng.extra = eng.extra[0], None
             if not handle:
                 # the reference's write into the caller's types (:66): the graph masked its own copy of x
@@ -242,14 +239,13 @@ class ChargePredictionTrainer(StepTrainer):
         if mask_rng not in MASK_RNGS:
             raise ValueError("mask_rng is 'numpy' or 'device'")
         self.predictor = charge_predictor
-        self.args = ChargeArgs(model_3d, charge_masking_ratio, mask_rng)
         self._seeds = None
         if mask_rng == "device" and seed is not None:
             # successive seeds of this trainer: splitmix64 of (seed, n) - one for the eager buffer, one per capture
             self._seeds = [int(seed), 0]
         self.key = "mask_seed" if mask_rng == "device" else "mask_idx"
-        super().__init__([model, charge_predictor], model_3d, lr, weight_decay, use_graph, max_graphs, graph_mode,
-                         noise_keys=(self.key,))
+        super().__init__([model, charge_predictor], CHARGE, ChargeArgs(model_3d, charge_masking_ratio, mask_rng), lr,
+                         weight_decay, use_graph, max_graphs, graph_mode)
         # the eager steps' seed, advanced per draw
         self.seed = self._new_seed(self.flat.grad.device) if mask_rng == "device" else None
 
@@ -264,9 +260,8 @@ class ChargePredictionTrainer(StepTrainer):
         x ^= x >> 31
         return torch.tensor([x - (1 << 64) if x >= 1 << 63 else x], dtype=torch.long).to(dev)
 
-    def _forward(self, batch, mask):
-        return charge_step_fused(self.args, batch, self.model, self.predictor, mask)
-
+    # the trainer's own: its seed sequence - one seed for the eager steps, a fresh one per capture (the engine's mask
+    # comes from do_ChargePrediction, drawn per call)
     def _mask(self, batch, fresh=False):
         if self.key == "mask_idx":
             return draw_mask("numpy", batch, self.args.charge_masking_ratio)
@@ -279,9 +274,9 @@ class ChargePredictionTrainer(StepTrainer):
         return self._mask(batch, fresh=True)
 
     def _write_inputs(self, g, batch, mask):
-        # a capture's own mask; then device masks: nothing to upload (the graph's seed advances on the device); numpy:
-        # this step's draw
-        if mask is None and self.key == "mask_idx":
-            mask = self._mask(batch)
-        if mask is not None:
-            self.step_graphs.copy_noise(g, mask)
+        # the trainer's own: a capture's fresh seed goes into its graph once; from then on device masks upload nothing
+        # (the graph's seed advances on the device) and numpy masks are the objective's write, this step's draw
+        if mask is not None and self.key == "mask_seed":
+            StepGraphs.copy_noise(g, mask)
+        else:
+            super()._write_inputs(g, batch, mask)

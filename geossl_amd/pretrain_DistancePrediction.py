@@ -14,8 +14,7 @@ import torch.nn as nn
 
 from . import ops
 from .layout import UngroupedSuperEdges
-from .step import Args, Objective, StepTrainer, backbone_forward, backbone_latent, engine_for
-from .switches import env as _env
+from .step import Args, Objective, StepTrainer, backbone_forward, backbone_latent, run_graphed
 
 
 class DistancePredictor(nn.Module):
@@ -62,7 +61,7 @@ def distance_step_fused(args, batch, model, distance_predictor):
 
 # (no random draws: the positions as they are; the tuple option is part of each StepGraphs key - bucket key / fingerprint)
 DISTANCE = Objective("DistancePrediction",
-                     lambda eng, args, mu, sigma, batch, noise: distance_step_fused(args, batch, eng.model, eng.n1))
+                     lambda owner, args, batch, noise: distance_step_fused(args, batch, owner.model, owner.n1))
 
 
 def distance_step_aten(args, batch, model, distance_predictor):
@@ -97,16 +96,11 @@ def do_DistancePrediction(args, batch, model, distance_predictor, graph=None):
         raise Exception("3D model {} not included.".format(args.model_3d))
     if not (fused_head_ok(distance_predictor) and _fused_batch_ok(batch)):
         return distance_step_aten(args, batch, model, distance_predictor)
-    if graph is None:
-        graph = getattr(args, "step_graph", _env("GEOSSL_NO_STEP_GRAPH") is None)
     try:
-        if graph and torch.is_grad_enabled() and not torch.cuda.is_current_stream_capturing():
-            a = Args(args.model_3d)
-            a.step_graph_mode = getattr(args, "step_graph_mode", "auto")
-            eng = engine_for(model, "_geossl_distance_step", DISTANCE, distance_predictor)
-            loss = eng.run(a, batch, 0.0, 0.0, None, False)
-            if loss is not None:
-                return loss
+        loss = run_graphed(args, graph, model, "_geossl_distance_step", DISTANCE, Args(args.model_3d), batch,
+                           n1=distance_predictor)
+        if loss is not None:
+            return loss
         return distance_step_fused(args, batch, model, distance_predictor)
     except UngroupedSuperEdges:
         # (super-edges that are not grouped by molecule in batch order: no incidence lists for the fused backward)
@@ -127,8 +121,5 @@ class DistancePredictionTrainer(StepTrainer):
             raise ValueError("DistancePredictionTrainer needs the reference predictor at a width of the fused head "
                              "(64, 128, 256 or 512) on the GPU; use do_DistancePrediction for anything else")
         self.predictor = distance_predictor
-        self.args = Args(model_3d)
-        super().__init__([model, distance_predictor], model_3d, lr, weight_decay, use_graph, max_graphs, graph_mode)
-
-    def _forward(self, batch, noise):
-        return distance_step_fused(self.args, batch, self.model, self.predictor)
+        super().__init__([model, distance_predictor], DISTANCE, Args(model_3d), lr, weight_decay, use_graph, max_graphs,
+                         graph_mode)

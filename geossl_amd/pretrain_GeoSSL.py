@@ -27,7 +27,8 @@ from .autograd_step import _AutogradStep, _ReplayedLoss, _StepLoss, _Ticket  # n
 from .batch import Batch, TripleBatch, _tensor_uid, canonical_option, structure_fingerprint  # noqa: F401
 from .layout import MolLayout
 from .replay import StepGraphs, _MT_PENDING, _NOISE_KEYS, _restore_backward_threads  # noqa: F401
-from .step import Args, Objective, StepTrainer, _OWN_CAPTURE, engine_for, latent, own_capture_open, with_counts  # noqa: F401
+from .step import (Args, Objective, StepTrainer, _OWN_CAPTURE, draw_target, engine_for, latent, own_capture_open,  # noqa: F401
+                   run_graphed, stock_bce, with_counts)
 
 NCSN_model_01 = None
 NCSN_model_02 = None
@@ -148,11 +149,9 @@ def do_DDM(args, batch, model, criterion=None, mu=0.0, sigma=0.3, num_neg=1, NCS
     n1, n2 = NCSN_models if NCSN_models is not None else (NCSN_model_01, NCSN_model_02)
     if n1 is None or n2 is None:
         raise RuntimeError("set geossl_amd.pretrain_GeoSSL.NCSN_model_01/02 or pass NCSN_models=(m1, m2)")
-    if graph is None:
-        graph = getattr(args, "step_graph", _env("GEOSSL_NO_STEP_GRAPH") is None)
-    if graph and torch.is_grad_enabled() and not torch.cuda.is_current_stream_capturing() and fuse_views:
-        eng = engine_for(model, "_geossl_autograd_step", DDM, n1, n2)
-        loss = eng.run(args, batch, mu, sigma, noise, device_noise)
+    if fuse_views:
+        dargs = Args(args.model_3d, bool(getattr(args, "normalize", False)), mu, sigma, device_noise)
+        loss = run_graphed(args, graph, model, "_geossl_autograd_step", DDM, dargs, batch, noise, n1, n2)
         if loss is not None:
             return loss, 0
     return _do_ddm_eager(args, batch, model, mu, sigma, (n1, n2), noise, fuse_views, device_noise), 0
@@ -328,8 +327,9 @@ def draw_step_noise_fused(batch, n1, n2, mu, sigma, into=None):
     return into
 
 
-def _ddm_forward(engine, args, mu, sigma, batch, noise):
-    return _do_ddm_eager(args, batch, engine.model, mu, sigma, (engine.n1, engine.n2), noise, True, True)
+def _ddm_forward(owner, args, batch, noise):
+    return _do_ddm_eager(args, batch, owner.model, args.mu, args.sigma, (owner.n1, owner.n2), noise, True,
+                         args.device_noise)
 
 
 def _ddm_head_params(head):
@@ -337,16 +337,20 @@ def _ddm_head_params(head):
     return _head_params(head)
 
 
+def _ddm_write(owner, args, g, batch, noise):
+    on, into = draw_target(owner, g, batch, noise)
+    draw_step_noise(on, owner.n1, owner.n2, args.mu, args.sigma, args.device_noise, noise, into=into)
+
+
 # the five draws of a step are the static inputs of its graphs: made for a capture, drawn into them before a replay
+# (whatever the caller gave is copied instead of drawn)
 DDM = Objective(
     "DDM", _ddm_forward, views=2, normalize=True, head_params=_ddm_head_params,
     graph_key=lambda args: (args.model_3d, bool(getattr(args, "normalize", False))),
     noise_keys=lambda args: _NOISE_KEYS,
-    step_args=lambda args: Args(args.model_3d, bool(getattr(args, "normalize", False))),
-    capture_inputs=lambda eng, args, batch, mu, sigma, noise, device_noise:
-        draw_step_noise(batch, eng.n1, eng.n2, mu, sigma, device_noise, noise),
-    write_inputs=lambda eng, args, sg, g, batch, mu, sigma, noise, device_noise:
-        draw_step_noise(batch, eng.n1, eng.n2, mu, sigma, device_noise, noise, into=sg.noise_views(g)))
+    capture_inputs=lambda owner, args, batch, noise:
+        draw_step_noise(batch, owner.n1, owner.n2, args.mu, args.sigma, args.device_noise, noise),
+    write_inputs=_ddm_write)
 
 
 class DDMTrainer(StepTrainer):
@@ -365,30 +369,28 @@ class DDMTrainer(StepTrainer):
 
     def __init__(self, model, ncsn_01, ncsn_02, lr=5e-4, weight_decay=0.0, mu=0.0, sigma=0.3, model_3d="schnet",
                  device_noise=True, use_graph=False, overlap_heads=True, max_graphs=256, graph_mode="auto"):
-        self.n1, self.n2 = ncsn_01, ncsn_02
-        self.args = Args(model_3d)
-        self.mu, self.sigma = mu, sigma
-        self.device_noise = device_noise
         # two-pass NCSN backward only (GEOSSL_NCSN_SPLIT_BWD): its weight-gradient kernels on a side stream, concurrent
         # with the backbone's backward; the default one-pass backward has nothing to overlap
         self.overlap_heads = overlap_heads
         self._zero_outside = True
         self._side = None
-        super().__init__([model, ncsn_01, ncsn_02], model_3d, lr, weight_decay, use_graph, max_graphs, graph_mode,
-                         noise_keys=None, views=2)
+        super().__init__([model, ncsn_01, ncsn_02], DDM, Args(model_3d, False, mu, sigma, device_noise), lr, weight_decay,
+                         use_graph, max_graphs, graph_mode)
 
     @property
     def _graphs(self):
         return self.step_graphs.graphs
 
+    # DDMTrainer's own: the gradient buffer is cleared by the step itself unless `_zero_outside` leaves it to its own
+    # capture's refresh, and the step's device draws are the trainer's (`_draw_noise`), eager or replayed alike
     def _fwd_bwd(self, batch, noise):
         if not (self._zero_outside and own_capture_open()):
             self.flat.zero_grad()  # (a replayed step: cleared with the refresh of the graph's inputs, StepGraphs.refresh)
-        if noise is None and self.device_noise:
+        if noise is None and self.args.device_noise:
             noise = self._draw_noise(batch)  # the trainer's own stream, eager launches or replayed graph alike
-        return self._backward(_do_ddm_eager(self.args, batch, self.model, self.mu, self.sigma, (self.n1, self.n2), noise,
-                                            True, self.device_noise))
+        return self._backward(self._forward(batch, noise))
 
+    # DDMTrainer's own: the heads' weight gradients on the NCSN side stream
     def _backward(self, loss):
         from . import NCSN as _ncsn
         if self._side is None and self.overlap_heads:
@@ -405,29 +407,31 @@ class DDMTrainer(StepTrainer):
 
     _NOISE_KEYS = _NOISE_KEYS
 
+    # DDMTrainer's own: its device draws are ONE seeded launch (`_draw_noise`), where DDM's hooks - the engine's - make
+    # torch's five; a caller's noise takes the hooks
     def _capture_inputs(self, batch, noise):
-        return self._draw_noise(batch) if noise is None else noise  # (the capture needs tensors to clone)
+        return self._draw_noise(batch) if noise is None else super()._capture_inputs(batch, noise)
 
     def _write_inputs(self, g, batch, noise):
-        if noise is None:  # the step's own draws go straight into the graph's static inputs (no staging copies)
-            self._draw_noise(g["batch"], into=g["noise"])  # (g["batch"]: a bucket's draws cover its capacity)
+        if noise is None:  # straight into the graph's static inputs (g["batch"]: a bucket's draws cover its capacity)
+            self._draw_noise(g["batch"], into=g["noise"])
         else:
-            StepGraphs.copy_noise(g, noise)
+            super()._write_inputs(g, batch, noise)
 
     def _draw_noise(self, batch, into=None):
         """The five random draws of a step on the device (perturb: pretrain_GeoSSL.py:72; the heads: NCSN.py:190,194),
         as tensors - new ones, or in place into `into`."""
+        a = self.args
         if _env("GEOSSL_TORCH_DRAWS"):  # the five torch calls (the form before geossl_ddm_noise)
-            return draw_step_noise(batch, self.n1, self.n2, self.mu, self.sigma, True, None, into)
-        return draw_step_noise_fused(batch, self.n1, self.n2, self.mu, self.sigma, into)
+            return draw_step_noise(batch, self.n1, self.n2, a.mu, a.sigma, True, None, into)
+        return draw_step_noise_fused(batch, self.n1, self.n2, a.mu, a.sigma, into)
 
     def step(self, batch, noise=None, structure_key=None):
         """One training step.  ``structure_key`` is accepted for compatibility and ignored: graphs are found by the
-        batch's own fingerprint."""
-        if self.use_graph and ((noise is None and self.device_noise)
-                               or (noise is not None and all(k in noise for k in _NOISE_KEYS))):
-            return self._finish(self._graph_fwd_bwd(batch, noise))
-        return self._finish(self._fwd_bwd(batch, noise))
+        batch's own fingerprint.  A ``noise`` that lacks one of the five draws runs eagerly (the rest is drawn there)."""
+        if noise is not None and not all(k in noise for k in _NOISE_KEYS):
+            return self._finish(self._eager(batch, noise))
+        return super().step(batch, noise)
 
 
 # ---- the contrastive objectives: --GeoSSL_option=InfoNCE / EBM_NCE (pretrain_GeoSSL.py:103-176) -----------------------
@@ -443,8 +447,9 @@ class ContrastiveArgs:
     """The fields do_InfoNCE / do_EBM_NCE read from the reference's argparse namespace (examples/config.py:171-172: T
     0.1, normalize off) plus num_neg, which the reference passes as an argument."""
 
-    def __init__(self, model_3d="schnet", normalize=False, T=0.1, num_neg=1):
+    def __init__(self, model_3d="schnet", normalize=False, T=0.1, num_neg=1, mu=0.0, sigma=0.3, device_noise=True):
         self.model_3d, self.normalize, self.T, self.num_neg = model_3d, bool(normalize), float(T), int(num_neg)
+        self.mu, self.sigma, self.device_noise = mu, sigma, device_noise   # perturb's draw (step.Args)
 
 
 def _stock_ce(c):
@@ -455,8 +460,7 @@ def _stock_ce(c):
 
 def _stock_bce(c):
     """nn.BCEWithLogitsLoss() as the reference builds it (:344), or None: what the EBM-NCE kernels compute."""
-    return c is None or (type(c) is torch.nn.BCEWithLogitsLoss and c.weight is None and c.pos_weight is None
-                         and c.reduction == "mean")
+    return stock_bce(c, or_none=True)
 
 
 def draw_views_noise(batch, mu, sigma, device_noise, given=None, into=None):
@@ -572,23 +576,25 @@ def _contrastive_objective(option):
     """The step.Objective of one contrastive option: no heads (the readout is part of the step), two views, capacity
     buckets whatever `normalize` says (the row normalisation is over the 2B readout rows, an exact count), one static
     draw; a graph binds T and num_neg (by-value arguments of its loss launches); -> (loss, counts)."""
-    def cargs(args):
-        return ContrastiveArgs(args.model_3d, getattr(args, "normalize", False), getattr(args, "T", 0.1),
-                               getattr(args, "num_neg", 1))
-
     def key(args):
         return (option, args.model_3d, bool(getattr(args, "normalize", False)), float(getattr(args, "T", 0.1)),
                 int(getattr(args, "num_neg", 1)))
 
     return Objective(
-        option, lambda eng, args, mu, sigma, batch, noise:
-            _contrastive_eager(option, args, batch, eng.model, mu, sigma, noise, True),
-        views=2, graph_key=key, noise_keys=lambda args: ("pos_noise",), step_args=cargs,
-        capture_inputs=lambda eng, args, batch, mu, sigma, noise, device_noise:
-            draw_views_noise(batch, mu, sigma, device_noise, noise),
-        write_inputs=lambda eng, args, sg, g, batch, mu, sigma, noise, device_noise:
-            draw_views_noise(batch, mu, sigma, device_noise, noise, into=sg.noise_views(g)),
-        result=with_counts)
+        option, lambda owner, args, batch, noise:
+            _contrastive_eager(option, args, batch, owner.model, args.mu, args.sigma, noise, args.device_noise),
+        views=2, graph_key=key, noise_keys=lambda args: ("pos_noise",), capture_inputs=_capture_views_noise,
+        write_inputs=_write_views_noise, result=with_counts)
+
+
+# the one draw of a two-view step (the contrastive options, RR), perturb's, is the static input of its graphs
+def _capture_views_noise(owner, args, batch, noise):
+    return draw_views_noise(batch, args.mu, args.sigma, args.device_noise, noise)
+
+
+def _write_views_noise(owner, args, g, batch, noise):
+    on, into = draw_target(owner, g, batch, noise)
+    draw_views_noise(on, args.mu, args.sigma, args.device_noise, noise, into=into)
 
 
 INFONCE, EBM_NCE = (_contrastive_objective(o) for o in CONTRASTIVE_OPTIONS)
@@ -600,16 +606,12 @@ def _do_contrastive(obj, args, batch, model, criterion, mu, sigma, num_neg, nois
     if not stock:
         crit = CE_criterion if objective == "InfoNCE" else criterion
         return _contrastive_with_criterion(objective, args, batch, model, crit, mu, sigma, num_neg, noise, device_noise)
-    cargs = ContrastiveArgs(args.model_3d, getattr(args, "normalize", False), getattr(args, "T", 0.1), num_neg)
-    if graph is None:
-        graph = getattr(args, "step_graph", _env("GEOSSL_NO_STEP_GRAPH") is None)
-    if graph and torch.is_grad_enabled() and not torch.cuda.is_current_stream_capturing():
-        cargs.step_graph_mode = getattr(args, "step_graph_mode", "auto")
-        eng = engine_for(model, "_geossl_contrastive_step_" + objective, obj)
-        out = eng.run(cargs, batch, mu, sigma, noise, device_noise)
-        if out is not None:
-            loss, counts = out
-            return loss, contrastive_acc(objective, counts, batch.num_graphs, num_neg)
+    cargs = ContrastiveArgs(args.model_3d, getattr(args, "normalize", False), getattr(args, "T", 0.1), num_neg, mu, sigma,
+                            device_noise)
+    out = run_graphed(args, graph, model, "_geossl_contrastive_step_" + objective, obj, cargs, batch, noise)
+    if out is not None:
+        loss, counts = out
+        return loss, contrastive_acc(objective, counts, batch.num_graphs, num_neg)
     loss, counts = _contrastive_eager(objective, cargs, batch, model, mu, sigma, noise, device_noise)
     return loss, contrastive_acc(objective, counts.tolist(), batch.num_graphs, num_neg)
 
@@ -645,36 +647,14 @@ class ContrastiveTrainer(StepTrainer):
         if option not in CONTRASTIVE_OPTIONS:
             raise ValueError("option is one of %s" % (CONTRASTIVE_OPTIONS,))
         self.option = option
-        self.args = ContrastiveArgs(model_3d, normalize, T, num_neg)
-        self.mu, self.sigma = mu, sigma
-        self.device_noise = device_noise
         # (capacity buckets with no heads; `normalize` is over the 2B readout rows and does not keep a batch off them;
         # EBM-NCE's loss is a float64 scalar: so is the standing 1.0 of its backward)
-        super().__init__([model], model_3d, lr, weight_decay, use_graph, max_graphs, graph_mode, noise_keys=("pos_noise",),
-                         views=2, one_dtype=torch.float64 if option == "EBM_NCE" else torch.float32)
+        super().__init__([model], INFONCE if option == "InfoNCE" else EBM_NCE,
+                         ContrastiveArgs(model_3d, normalize, T, num_neg, mu, sigma, device_noise), lr, weight_decay,
+                         use_graph, max_graphs, graph_mode,
+                         one_dtype=torch.float64 if option == "EBM_NCE" else torch.float32)
 
-    with_extra = True
-
-    def _forward(self, batch, noise):
-        if noise is None:
-            noise = draw_views_noise(batch, self.mu, self.sigma, self.device_noise)
-        return _contrastive_eager(self.option, self.args, batch, self.model, self.mu, self.sigma, noise,
-                                  self.device_noise)
-
-    def _capture_inputs(self, batch, noise):
-        return draw_views_noise(batch, self.mu, self.sigma, self.device_noise, noise)
-
-    def _write_inputs(self, g, batch, noise):
-        if noise is None:   # the step's own draw straight into the graph's static input
-            draw_views_noise(g["batch"], self.mu, self.sigma, self.device_noise, into=g["noise"])
-        else:
-            StepGraphs.copy_noise(g, noise)
-
-    def step(self, batch, noise=None):
-        """One training step -> (loss, counts) on the device."""
-        if self.use_graph and (noise is not None or self.device_noise):
-            return self._finish(self._graph_fwd_bwd(batch, noise))
-        return self._finish(self._fwd_bwd(batch, noise))
+    with_extra = True   # step(batch, noise=None) -> (loss, counts)
 
 
 # ---- representation reconstruction: --GeoSSL_option=RR (pretrain_GeoSSL.py:77-100) --------------------------------------
@@ -690,9 +670,10 @@ class RRArgs:
     binds beside them: the heads' loss kind and ``detach_target`` (config.py:177-183) and the addresses of their
     BatchNorm buffers (the kernels update them in place)."""
 
-    def __init__(self, model_3d="schnet", normalize=False, heads=None):
+    def __init__(self, model_3d="schnet", normalize=False, heads=None, mu=0.0, sigma=0.3, device_noise=True):
         self.model_3d, self.normalize = model_3d, bool(normalize)
         self.heads_key = None if heads is None else _rr_heads_key(heads)
+        self.mu, self.sigma, self.device_noise = mu, sigma, device_noise   # perturb's draw (step.Args)
 
 
 def _rr_bn(head):
@@ -783,15 +764,11 @@ def rr_step_aten(args, batch, model, AE_models, mu=0.0, sigma=0.3, noise=None, d
 
 
 RR = Objective(
-    "RR", lambda eng, args, mu, sigma, batch, noise: _rr_eager(args, batch, eng.model, mu, sigma, (eng.n1, eng.n2), noise, True),
-    views=2, head_params=lambda h: list(h.parameters()),
+    "RR", lambda owner, args, batch, noise:
+        _rr_eager(args, batch, owner.model, args.mu, args.sigma, (owner.n1, owner.n2), noise, args.device_noise),
+    views=2,
     graph_key=lambda args: ("RR", args.model_3d, bool(getattr(args, "normalize", False)), getattr(args, "heads_key", None)),
-    noise_keys=lambda args: ("pos_noise",),
-    step_args=lambda args: RRArgs(args.model_3d, getattr(args, "normalize", False)),
-    capture_inputs=lambda eng, args, batch, mu, sigma, noise, device_noise:
-        draw_views_noise(batch, mu, sigma, device_noise, noise),
-    write_inputs=lambda eng, args, sg, g, batch, mu, sigma, noise, device_noise:
-        draw_views_noise(batch, mu, sigma, device_noise, noise, into=sg.noise_views(g)))
+    noise_keys=lambda args: ("pos_noise",), capture_inputs=_capture_views_noise, write_inputs=_write_views_noise)
 
 
 def do_RR(args, batch, model, mu=0.0, sigma=0.3, AE_models=None, noise=None, device_noise=False, graph=None, **kwargs):
@@ -803,13 +780,9 @@ def do_RR(args, batch, model, mu=0.0, sigma=0.3, AE_models=None, noise=None, dev
     a, b = AE_models if AE_models is not None else (AE_model_01, AE_model_02)
     if a is None or b is None:
         raise RuntimeError("set geossl_amd.pretrain_GeoSSL.AE_model_01/02 or pass AE_models=(a, b)")
-    if graph is None:
-        graph = getattr(args, "step_graph", _env("GEOSSL_NO_STEP_GRAPH") is None)
-    if (graph and torch.is_grad_enabled() and not torch.cuda.is_current_stream_capturing() and fused_heads_ok(a, b)
-            and batch.num_graphs >= 2):
-        rargs = RRArgs(args.model_3d, getattr(args, "normalize", False), (a, b))
-        rargs.step_graph_mode = getattr(args, "step_graph_mode", "auto")
-        loss = engine_for(model, "_geossl_rr_step", RR, a, b).run(rargs, batch, mu, sigma, noise, device_noise)
+    if fused_heads_ok(a, b) and batch.num_graphs >= 2:
+        rargs = RRArgs(args.model_3d, getattr(args, "normalize", False), (a, b), mu, sigma, device_noise)
+        loss = run_graphed(args, graph, model, "_geossl_rr_step", RR, rargs, batch, noise, a, b)
         if loss is not None:
             return loss, 0
     return _rr_eager(args, batch, model, mu, sigma, (a, b), noise, device_noise), 0
@@ -837,29 +810,12 @@ class RRTrainer(StepTrainer):
         if not fused_heads_ok(ae_01, ae_02):
             raise ValueError("RRTrainer needs two distinct AutoEncoders of width 128 in training mode on the GPU with the "
                              "same loss and detach_target; use do_RR for anything else")
-        self.n1, self.n2 = ae_01, ae_02
-        self.args = RRArgs(model_3d, normalize)
-        self.mu, self.sigma = mu, sigma
-        self.device_noise = device_noise
-        super().__init__([model, ae_01, ae_02], model_3d, lr, weight_decay, use_graph, max_graphs, graph_mode,
-                         noise_keys=("pos_noise",), views=2)
+        super().__init__([model, ae_01, ae_02], RR, RRArgs(model_3d, normalize, None, mu, sigma, device_noise), lr,
+                         weight_decay, use_graph, max_graphs, graph_mode)
         self.ae_lr = ae_lr
         self._n_backbone = sum(p.numel() for p in model.parameters() if p.requires_grad)
 
-    def _forward(self, batch, noise):
-        if noise is None:
-            noise = draw_views_noise(batch, self.mu, self.sigma, self.device_noise)
-        return _rr_eager(self.args, batch, self.model, self.mu, self.sigma, (self.n1, self.n2), noise, self.device_noise)
-
-    def _capture_inputs(self, batch, noise):
-        return draw_views_noise(batch, self.mu, self.sigma, self.device_noise, noise)
-
-    def _write_inputs(self, g, batch, noise):
-        if noise is None:   # the step's own draw straight into the graph's static input
-            draw_views_noise(g["batch"], self.mu, self.sigma, self.device_noise, into=g["noise"])
-        else:
-            StepGraphs.copy_noise(g, noise)
-
+    # RRTrainer's own: two learning rates, the backbone's and the heads'
     def set_lr(self, lr, ae_lr=None):
         """The learning rate of the next steps (a scheduler's value); ae_lr: the heads' (None: unchanged)."""
         self.opt.lr = lr
@@ -878,9 +834,3 @@ class RRTrainer(StepTrainer):
                  ptr(opt.exp_avg_sq[lo:hi]), hi - lo, float(lr), float(opt.betas[0]), float(opt.betas[1]), float(opt.eps),
                  float(opt.weight_decay), opt.step_count, float(scale), stream())
         return out
-
-    def step(self, batch, noise=None):
-        """One training step -> loss on the device."""
-        if self.use_graph and (noise is not None or self.device_noise):
-            return self._finish(self._graph_fwd_bwd(batch, noise))
-        return self._finish(self._fwd_bwd(batch, noise))

@@ -17,8 +17,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .step import Objective, StepTrainer, backbone_forward, backbone_latent, engine_for
-from .switches import env as _env
+from .step import Objective, StepTrainer, backbone_forward, backbone_latent, run_graphed
 
 
 # ---------------------------------------------------------------------------------------------------- what is served
@@ -201,16 +200,17 @@ class _StepArgs:
 
 # (no draws: the batch's target column, the graph's static input "target", is the one per-step input beside the
 # molecules; a graph binds the loss kind, the task column is chosen when the targets are written)
+def _supervised_forward(owner, args, batch, noise):
+    target = noise["target"] if noise is not None else target_column(batch, args.task_id)   # (None: an eager step)
+    return supervised_step_fused(args, batch, owner.model, owner.n1, target, args.stats, args.loss)[0]
+
+
 SUPERVISED = Objective(
-    "Supervised",
-    lambda eng, args, mu, sigma, batch, noise:
-        supervised_step_fused(args, batch, eng.model, eng.n1, noise["target"], args.stats, args.loss)[0],
+    "Supervised", _supervised_forward,
     graph_key=lambda args: ("Supervised", args.model_3d, args.loss, args.task_id),
     noise_keys=lambda args: ("target",),
-    capture_inputs=lambda eng, args, batch, mu, sigma, noise, device_noise:
-        {"target": target_column(batch, args.task_id)},
-    write_inputs=lambda eng, args, sg, g, batch, mu, sigma, noise, device_noise:
-        write_targets(g, batch, args.task_id),
+    capture_inputs=lambda owner, args, batch, noise: {"target": target_column(batch, args.task_id)},
+    write_inputs=lambda owner, args, g, batch, noise: write_targets(g, batch, args.task_id),
     pair_tuples=False)
 
 
@@ -237,17 +237,16 @@ def do_Supervised(args, batch, model, graph_pred_linear, TRAIN_mean, TRAIN_std, 
         return supervised_step_aten(args, batch, model, graph_pred_linear, TRAIN_mean, TRAIN_std, task_id, criterion)
     _raise_like_squeeze(_n_mols(batch))
     kind = loss_kind(criterion)
-    if graph is None:
-        graph = getattr(args, "step_graph", _env("GEOSSL_NO_STEP_GRAPH") is None)
-    if graph and torch.is_grad_enabled() and not torch.cuda.is_current_stream_capturing():
-        eng = engine_for(model, "_geossl_supervised_step", SUPERVISED, graph_pred_linear)
+    a = _StepArgs(args.model_3d, kind, task_id, None)
+
+    def stats_on(eng):   # the (mean, std) tensor the engine's graphs read lives on the engine
         if "stats" not in eng.__dict__:
             eng.stats = _Stats(eng.gflat.device)
-        a = _StepArgs(args.model_3d, kind, task_id, eng.stats.set(TRAIN_mean, TRAIN_std),
-                      getattr(args, "step_graph_mode", "auto"))
-        loss = eng.run(a, batch, 0.0, 0.0, None, False)
-        if loss is not None:
-            return loss
+        a.stats = eng.stats.set(TRAIN_mean, TRAIN_std)
+    loss = run_graphed(args, graph, model, "_geossl_supervised_step", SUPERVISED, a, batch, n1=graph_pred_linear,
+                       prepare=stats_on)
+    if loss is not None:
+        return loss
     dev = head_params(graph_pred_linear)[0].device
     loss, _ = supervised_step_fused(args, batch, model, graph_pred_linear, target_column(batch, task_id),
                                     _stats_tensor(dev, TRAIN_mean, TRAIN_std), kind)
@@ -354,36 +353,17 @@ class SupervisedTrainer(StepTrainer):
                              "unscaled mean / add readout; use do_Supervised for anything else")
         self.head = graph_pred_linear
         self.model_3d, self.loss_kind, self.task_id = model_3d, loss, int(task_id)
-        super().__init__([model, graph_pred_linear], model_3d, lr, weight_decay, use_graph, max_graphs, graph_mode,
-                         noise_keys=("target",), pair_tuples=False)
-        self.stats = _Stats(self.flat.grad.device)
+        self.stats = _Stats(ps[0].device)
         self.stats.set(TRAIN_mean, TRAIN_std)
-        self.args = _StepArgs(model_3d, loss, task_id, self.stats.t)
-
-    @property
-    def lr(self):
-        return self.opt.lr
-
-    def set_lr(self, lr):
-        """The learning rate of the following steps (an epoch-level scheduler: optim.cosine_annealing_lr)."""
-        self.opt.lr = float(lr)
+        super().__init__([model, graph_pred_linear], SUPERVISED, _StepArgs(model_3d, loss, task_id, self.stats.t), lr,
+                         weight_decay, use_graph, max_graphs, graph_mode)
 
     def set_stats(self, mean, std):
         """TRAIN_mean / TRAIN_std of the following steps (read on the device: no recapture)."""
         self.stats.set(mean, std)
 
-    def _forward(self, batch, noise):
-        target = noise["target"] if noise is not None else target_column(batch, self.task_id)
-        return supervised_step_fused(self.args, batch, self.model, self.head, target, self.stats.t, self.loss_kind)[0]
-
-    def _capture_inputs(self, batch, noise):
-        return {"target": target_column(batch, self.task_id)}
-
-    def _write_inputs(self, g, batch, noise):
-        write_targets(g, batch, self.task_id)
-
     def step(self, batch):
-        """One training step -> the loss on the device."""
+        """One training step -> the loss on the device.  (The trainer's own: the reference's IndexError at B = 1.)"""
         _raise_like_squeeze(_n_mols(batch))
         return super().step(batch)
 

@@ -21,8 +21,7 @@ import torch.nn as nn
 from . import _lib, ops
 from .layout import UngroupedSuperEdges
 from .batch import TripleBatch  # (the device batch type of collated triple batches)
-from .step import Args, Objective, StepTrainer, backbone_forward, backbone_latent, engine_for
-from .switches import env as _env
+from .step import Args, Objective, StepTrainer, backbone_forward, backbone_latent, run_graphed
 
 
 class TorsionAnglePredictor(nn.Module):
@@ -89,7 +88,7 @@ def torsion_step_fused(args, batch, model, torsion_angle_predictor):
 
 # (no random draws; triples and targets are the batch's own: static inputs of a "triples" bucket that its fill refreshes)
 TORSION = Objective("TorsionAnglePrediction",
-                    lambda eng, args, mu, sigma, batch, noise: torsion_step_fused(args, batch, eng.model, eng.n1))
+                    lambda owner, args, batch, noise: torsion_step_fused(args, batch, owner.model, owner.n1))
 
 
 def torsion_step_aten(args, batch, model, torsion_angle_predictor):
@@ -140,19 +139,14 @@ def do_TorsionAnglePrediction(args, batch, model, torsion_angle_predictor, graph
         raise Exception("3D model {} not included.".format(args.model_3d))
     if not (fused_head_ok(torsion_angle_predictor) and _fused_batch_ok(batch)):
         return torsion_step_aten(args, batch, model, torsion_angle_predictor)
-    if graph is None:
-        graph = getattr(args, "step_graph", _env("GEOSSL_NO_STEP_GRAPH") is None)
     try:
         tb = _as_triple_batch(batch)
-        if graph and torch.is_grad_enabled() and not torch.cuda.is_current_stream_capturing():
-            if getattr(tb, "_dataset", None) is None:
-                _check_grouped(tb.batch, tb.super_edge_index)   # (before a graph binds or a bucket copies the list)
-            a = Args(args.model_3d)
-            a.step_graph_mode = getattr(args, "step_graph_mode", "auto")
-            eng = engine_for(model, "_geossl_torsion_step", TORSION, torsion_angle_predictor)
-            loss = eng.run(a, tb, 0.0, 0.0, None, False)
-            if loss is not None:
-                return loss
+        if getattr(tb, "_dataset", None) is None:
+            _check_grouped(tb.batch, tb.super_edge_index)   # (before a graph binds or a bucket copies the list)
+        loss = run_graphed(args, graph, model, "_geossl_torsion_step", TORSION, Args(args.model_3d), tb,
+                           n1=torsion_angle_predictor)
+        if loss is not None:
+            return loss
         return torsion_step_fused(args, tb, model, torsion_angle_predictor)
     except UngroupedSuperEdges:
         # (triples that are not grouped by molecule in batch order: no per-molecule runs for the fused backward)
@@ -174,11 +168,8 @@ class TorsionAnglePredictionTrainer(StepTrainer):
             raise ValueError("TorsionAnglePredictionTrainer needs the reference predictor at a width of the fused head "
                              "(64, 128, 256 or 512) on the GPU; use do_TorsionAnglePrediction for anything else")
         self.predictor = torsion_angle_predictor
-        self.args = Args(model_3d)
-        super().__init__([model, torsion_angle_predictor], model_3d, lr, weight_decay, use_graph, max_graphs, graph_mode)
-
-    def _forward(self, batch, noise):
-        return torsion_step_fused(self.args, batch, self.model, self.predictor)
+        super().__init__([model, torsion_angle_predictor], TORSION, Args(model_3d), lr, weight_decay, use_graph,
+                         max_graphs, graph_mode)
 
     def step(self, batch):
         """One training step -> the loss on the device.  batch: a TripleBatch, a collated BatchAtomTriple on the device, or

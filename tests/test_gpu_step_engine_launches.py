@@ -8,6 +8,9 @@ calls - a replay - is written out; a longer one - an eager step, or a capture wi
 engine out of pretrain_GeoSSL.py into geossl_amd/replay.py and geossl_amd/autograd_step.py - by `run_case` below, run
 from a job script on the code before the move, not on the code under test - so the test states that the move (and
 whatever touches the capture, the sightings memory, the static-input copy or the replay protocol next) changes no launch.
+Cases k to q - the trainers and reference-style loops of the other objectives - were recorded likewise on the parent of
+the commit that gave both owners of the step graphs one `step.Objective` per objective and the do_* functions one routing
+helper.
 What the launches compute is the subject of the bit-for-bit tests of the routes (test_gpu_round4.py, test_gpu_round5.py,
 test_gpu_round6.py, test_gpu_force_training.py, test_gpu_sparse_bucket.py)."""
 import hashlib
@@ -30,7 +33,13 @@ CASES = ("a: DDMTrainer, ragged SchNet", "b: DDMTrainer, equal sizes", "c: DDMTr
          "d: reference loop", "e: DistancePredictionTrainer", "f: SupervisedTrainer, sparse bucket",
          "g: GraphedForward", "h: ForceTrainer, SchNet", "h: ForceTrainer, PaiNN",
          "i: predict_MD17, SchNet", "i: predict_MD17, PaiNN",
-         "j: MD17Trainer, handles, SchNet", "j: MD17Trainer, handles, PaiNN")
+         "j: MD17Trainer, handles, SchNet", "j: MD17Trainer, handles, PaiNN",
+         "k: ContrastiveTrainer, InfoNCE", "k: ContrastiveTrainer, EBM_NCE", "l: RRTrainer", "l: RRTrainer, ae_lr",
+         "m: ChargePredictionTrainer, device masks", "m: ChargePredictionTrainer, numpy masks",
+         "n: TorsionAnglePredictionTrainer", "o: InfoGraphTrainer", "p: LEPTrainer, sparse bucket",
+         "p: LEPTrainer, per structure", "q: reference loop, do_InfoNCE", "q: reference loop, do_RR",
+         "q: reference loop, do_DistancePrediction", "q: reference loop, do_ChargePrediction",
+         "q: reference loop, do_Supervised")
 
 
 def _raw(sizes, seed):
@@ -72,6 +81,38 @@ def _painn():
 def _heads():
     from helpers import product_ncsn
     return product_ncsn(128, 50, 2, DEV), product_ncsn(128, 50, 2, DEV, scale=0.9)
+
+
+def _ae_heads():
+    """Two AutoEncoder heads of RR in training mode, as built (torch's CPU generator where `run_case` seeded it)."""
+    from geossl_amd.Geom3D.models import AutoEncoder
+    return [AutoEncoder(128, "l2", True).to(DEV) for _ in range(2)]
+
+
+def _triple_batch(sizes, seed):
+    """A collated batch of atom triples: every triple of every molecule, with the fp64 twin's angles."""
+    import torsion_twin as tw
+    from geossl_amd import pretrain_GeoSSL as pg
+    from geossl_amd.Geom3D.dataloaders import AtomTripleExtractor
+    raw, ext = _raw(sizes, seed), AtomTripleExtractor(1)
+    off = np.concatenate([[0], np.cumsum(sizes)])
+    tri = np.ascontiguousarray(np.concatenate([ext.triples(int(n)) + off[m] for m, n in enumerate(sizes)], axis=1))
+    ang = tw.triple_angles(torch.from_numpy(raw["positions"]), torch.from_numpy(tri)).float()
+    return pg.TripleBatch.from_numpy(dict(x=raw["x"], positions=raw["positions"], batch=raw["batch"], sizes=raw["sizes"],
+                                          super_edge_index=tri, super_edge_angle=ang.numpy()), DEV)
+
+
+def _lep_items(pair_sizes, seed):
+    """The LEP records of these pairs: 1-D atom types, float32 positions, an integer label each."""
+    import lba_structures as ls
+    from geossl_amd.Geom3D.dataloaders import Data
+    active, inactive = pair_sizes
+    sa, si = ls.structures(active, seed), ls.structures(inactive, seed + 17)
+    oa, oi = np.concatenate([[0], np.cumsum(active)]), np.concatenate([[0], np.cumsum(inactive)])
+    f = torch.from_numpy
+    return [Data(x_active=f(sa["x"][oa[b]:oa[b + 1]].copy()), positions_active=f(sa["positions"][oa[b]:oa[b + 1]].copy()),
+                 x_inactive=f(si["x"][oi[b]:oi[b + 1]].copy()), positions_inactive=f(si["positions"][oi[b]:oi[b + 1]].copy()),
+                 y=torch.tensor([(b + seed) % 2], dtype=torch.long)) for b in range(len(active))]
 
 
 def _force_modules(kind):
@@ -262,6 +303,107 @@ def run_case(case, patch, setenv):
         modules = (model, head)
         stats = dict(captures=tr.captures, graphs=len(tr.graphs), keys=sorted(next(iter(tr.graphs.values()))))
         assert tr.use_graph and len(losses) == 4
+    elif letter in "klmno":
+        from filler import fill_module_
+        np.random.seed(7)   # (the numpy masks of case m)
+        model = _schnet()
+        if letter == "k":     # device noise: the step's own draw, straight into the graph's static input
+            tr = pg.ContrastiveTrainer(model, option=case.split(", ")[1], lr=5e-4, use_graph=True)
+            modules = (model,)
+        elif letter == "l":   # ae_lr: a second Adam launch over the heads' range of the flat buffer
+            heads = _ae_heads()
+            tr = pg.RRTrainer(model, heads[0], heads[1], lr=5e-4, use_graph=True,
+                              ae_lr=1e-3 if case.endswith("ae_lr") else None)
+            modules = (model,) + tuple(heads)
+        elif letter == "m":
+            from geossl_amd.pretrain_ChargePrediction import ChargePredictionTrainer, ChargePredictor
+            head = fill_module_(ChargePredictor(128)).to(DEV)
+            tr = ChargePredictionTrainer(model, head, lr=5e-4, use_graph=True, seed=11,
+                                         mask_rng="device" if "device" in case else "numpy")
+            modules = (model, head)
+        elif letter == "n":
+            from geossl_amd.pretrain_TorsionAnglePrediction import (TorsionAnglePredictionTrainer,
+                                                                    TorsionAnglePredictor)
+            head = fill_module_(TorsionAnglePredictor(128)).to(DEV)
+            tr = TorsionAnglePredictionTrainer(model, head, lr=5e-4, use_graph=True)
+            modules = (model, head)
+        else:
+            from geossl_amd.pretrain_3DInfoGraph import Discriminator, InfoGraphTrainer
+            head = fill_module_(Discriminator(128)).to(DEV)
+            tr = InfoGraphTrainer(model, head, lr=5e-4, use_graph=True)
+            modules = (model, head)
+        for i, s in enumerate(RAGGED):
+            bt = _triple_batch(s, 20 + i) if letter == "n" else _batch(s, 20 + i)
+            out = rec.step(lambda: tr.step(bt))
+            losses.append(torch.cat([o.double().reshape(-1) for o in out]) if isinstance(out, tuple) else out.clone())
+        sg = tr.step_graphs
+        stats = dict(captures=sg.captures, graphs=len(sg.graphs), keys=sorted(next(iter(sg.graphs.values()))))
+        assert next(iter(sg.graphs))[0] == "bucket"
+    elif letter == "p":
+        from filler import fill_module_
+        from geossl_amd.Geom3D.dataloaders import BatchLEP
+        from geossl_amd.finetune_lep import LEPTrainer
+        sparse = case.endswith("sparse bucket")
+        if sparse:
+            setenv("GEOSSL_SPARSE_BUCKETS", "1")   # (collated pairs take the sparse bucket with the switch on)
+        model, head = _schnet(cutoff=10.0), fill_module_(torch.nn.Linear(256, 1)).to(DEV)
+        with torch.no_grad():
+            head.weight.mul_(0.05)   # (logits of order one with the filler's weights: no sigmoid saturates)
+        tr = LEPTrainer(model, head, lr=5e-4, use_graph=True)
+        # sparse bucket: capture, replay, replay; small pairs with the same two size sequences: eager, capture, replay
+        pairs = ((((260, 256), (256, 258)), ((256, 260), (258, 256)), ((260, 256), (256, 258))) if sparse
+                 else (((5, 4), (3, 6)),) * 3)
+        for i, ps in enumerate(pairs):
+            bt = BatchLEP.from_data_list(_lep_items(ps, i)).to(DEV)
+            losses.append(rec.step(lambda: tr.step(bt)).clone())
+        sg, modules = tr.step_graphs, (model, head)
+        stats = dict(captures=sg.captures, graphs=len(sg.graphs), keys=sorted(next(iter(sg.graphs.values()))))
+        key = next(iter(sg.graphs))
+        assert (key[0], key[-1]) == ("bucket", "sparse") if sparse else key[0] == "tensors", list(sg.graphs)
+    elif letter == "q":
+        import types
+        from filler import fill_module_
+        np.random.seed(7)   # (do_ChargePrediction's numpy masks)
+        name = case.split(", ")[1]
+        model = _schnet()
+        args = types.SimpleNamespace(model_3d="schnet", normalize=False, T=0.1, charge_masking_ratio=0.3,
+                                     mask_rng="numpy", loss="mae")
+        first = lambda out: out[0] if isinstance(out, tuple) else out
+        if name == "do_InfoNCE":
+            heads, slot = (), "_geossl_contrastive_step_InfoNCE"
+            do = lambda bt: pg.do_InfoNCE(args, bt, model, graph=True)
+        elif name == "do_RR":
+            heads, slot = tuple(_ae_heads()), "_geossl_rr_step"
+            do = lambda bt: pg.do_RR(args, bt, model, AE_models=heads, graph=True)
+        elif name == "do_DistancePrediction":
+            from geossl_amd.pretrain_DistancePrediction import DistancePredictor, do_DistancePrediction
+            heads, slot = (fill_module_(DistancePredictor(128)).to(DEV),), "_geossl_distance_step"
+            do = lambda bt: do_DistancePrediction(args, bt, model, heads[0], graph=True)
+        elif name == "do_ChargePrediction":
+            from geossl_amd.pretrain_ChargePrediction import ChargePredictor, do_ChargePrediction
+            heads, slot = (fill_module_(ChargePredictor(128)).to(DEV),), "_geossl_charge_step"
+            do = lambda bt: do_ChargePrediction(args, bt, model, heads[0], graph=True)
+        else:
+            from geossl_amd.pretrain_Supervised import do_Supervised
+            heads, slot = (fill_module_(torch.nn.Linear(128, 1)).to(DEV),), "_geossl_supervised_step"
+            do = lambda bt: do_Supervised(args, bt, model, heads[0], 0.25, 1.5, task_id=0, graph=True)
+        modules = (model,) + heads
+        opt = torch.optim.Adam([{"params": m.parameters()} for m in modules], lr=5e-4)
+
+        def ref_step(bt):
+            loss = first(do(bt))
+            value = loss.detach().item()
+            opt.zero_grad()
+            loss.backward()
+            opt.step()
+            return value
+        for i, s in enumerate(RAGGED):
+            bt = _batch(s, 20 + i)
+            bt.y = torch.linspace(-1.0, 1.0, len(s), device=DEV)
+            losses.append(torch.tensor(rec.step(lambda: ref_step(bt))))
+        (sg,) = model.__dict__[slot].graphs.values()
+        stats = dict(captures=sg.captures, graphs=len(sg.graphs), keys=sorted(next(iter(sg.graphs.values()))))
+        assert next(iter(sg.graphs))[0] == "bucket" and next(iter(sg.graphs.values()))["graph_bwd"] is not None
     else:
         from geossl_amd.graphed import ForceTrainer
         kind = "painn" if case.endswith("PaiNN") else "schnet"
@@ -306,6 +448,8 @@ def test_step_engine_launch_sequence(case, monkeypatch):
 _BUCKET_KEYS = ["batch", "bucket", "counts", "extra", "graph", "graph_bwd", "loss", "noise", "zero"]
 _PREDICT_KEYS = ["bvec", "graph", "layout", "out", "pos", "rei", "x"]
 _FORCE_KEYS = ["bvec", "graph", "loss", "ones", "pos", "rei", "x", "y_e", "y_f"]
+_GATHER_ADAM = "gather_molecules adam_step"
+_BUCKET_STATS = {"captures": 1, "graphs": 1, "keys": _BUCKET_KEYS}
 EXPECTED = {
     "a: DDMTrainer, ragged SchNet": ([
         (67, "f1b1ce4918d00058"),
@@ -380,4 +524,26 @@ EXPECTED = {
         "gather_molecules property_targets gather_atom_rows adam_step",
         "gather_molecules property_targets gather_atom_rows adam_step",
     ], {"captures": 1, "graphs": 1, "keys": _FORCE_KEYS}),
+    # cases k to q: recorded the same way on the parent of the commit that put the trainers on step.Objective and the
+    # do_* functions on step.run_graphed (two processes, two orders: the same lists in order, every step)
+    "k: ContrastiveTrainer, InfoNCE": ([(69, "d7fe70cc969a59fa")] + [_GATHER_ADAM] * 2, _BUCKET_STATS),
+    "k: ContrastiveTrainer, EBM_NCE": ([(69, "185e0aec4346a516")] + [_GATHER_ADAM] * 2, _BUCKET_STATS),
+    "l: RRTrainer": ([(69, "08f9adab9f60e898")] + [_GATHER_ADAM] * 2, _BUCKET_STATS),
+    "l: RRTrainer, ae_lr": ([(70, "92564d94a0c4c008")] + ["gather_molecules adam_step adam_step"] * 2, _BUCKET_STATS),
+    "m: ChargePredictionTrainer, device masks": ([(63, "502e5351997d595e")] + [_GATHER_ADAM] * 2, _BUCKET_STATS),
+    "m: ChargePredictionTrainer, numpy masks": ([(63, "502e5351997d595e")] + [_GATHER_ADAM] * 2, _BUCKET_STATS),
+    "n: TorsionAnglePredictionTrainer": ([(60, "e9de7ee6eea163e6")] + [_GATHER_ADAM] * 2, _BUCKET_STATS),
+    "o: InfoGraphTrainer": ([(63, "6d96f818e60bc278")] + [_GATHER_ADAM] * 2, _BUCKET_STATS),
+    "p: LEPTrainer, sparse bucket": ([(67, "e02826ead4e0180f")] + [_GATHER_ADAM] * 2, _BUCKET_STATS),
+    "p: LEPTrainer, per structure": ([
+        (25, "5a26a038b3b1bf51"),
+        (59, "7f5707a8199974dc"),
+        "copy_n adam_step",
+    ], {"captures": 1, "graphs": 1, "keys": STEP_KEYS}),
+    "q: reference loop, do_InfoNCE": ([(69, "d7fe70cc969a59fa")] + [_GATHER_ADAM] * 2, _BUCKET_STATS),
+    "q: reference loop, do_RR": ([(69, "08f9adab9f60e898")] + [_GATHER_ADAM] * 2, _BUCKET_STATS),
+    "q: reference loop, do_DistancePrediction": ([(60, "4d7f8152fc7d501f")] + [_GATHER_ADAM] * 2, _BUCKET_STATS),
+    "q: reference loop, do_ChargePrediction": ([(64, "a60ccbea4928091d")]
+                                               + ["gather_molecules charge_mask_dyn adam_step"] * 2, _BUCKET_STATS),
+    "q: reference loop, do_Supervised": ([(60, "6a243c08e880c2f7")] + [_GATHER_ADAM] * 2, _BUCKET_STATS),
 }
