@@ -389,7 +389,8 @@ __global__ void k_embedding_bwd_partial(const int64_t* __restrict__ z, int64_t z
       for (int u = 0; u < U; ++u) {
         const int64_t a = min(a0 + (int64_t)u * NG, hi - 1);
         v[u] = dh[a * F + f];
-        cls[u] = (int)z[a * zs];
+        const int64_t c64 = z[a * zs];  // range check on the 64-bit value, like the forward: 2^32 + 1 is not class 1
+        cls[u] = (c64 >= 0 && c64 < C) ? (int)c64 : -1;
       }
 #pragma unroll
       for (int u = 0; u < U; ++u)
@@ -687,15 +688,17 @@ extern "C" int geossl_embedding_bwd_dyn(const int64_t* z, int64_t z_stride, cons
                                         hipStream_t stream) {
   if (num_classes <= 0) return 0;
   if (N > 0x7FFFFFFF) return (int)hipErrorInvalidValue;
-  if (F > 256 || (size_t)num_classes * F * sizeof(float) > 160 * 1024) return (int)hipErrorInvalidValue;
-  int2* band = reinterpret_cast<int2*>(workspace + (size_t)GEOSSL_EMB_CHUNKS * num_classes * F);
+  if (F > 256) return (int)hipErrorInvalidValue;
   // Four row groups per chunk while their tables fit 48 KB of LDS (SchNet's 9 classes: 18 KB), else one.  Chunks of at
   // least 32 rows per group (a small batch: fewer chunks, a shorter list for the second stage), a multiple of 4.
   const int TF = (F + 63) / 64 * 64;
   const int ng = ((size_t)4 * num_classes * F * sizeof(float) <= 48 * 1024 && 4 * TF <= 1024) ? 4 : 1;
+  // admitted by what the launch asks for - the group tables AND their bands: 160 classes at F = 256 are 8 bytes over
+  const size_t lds = (size_t)ng * num_classes * F * sizeof(float) + ng * sizeof(int2);
+  if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
+  int2* band = reinterpret_cast<int2*>(workspace + (size_t)GEOSSL_EMB_CHUNKS * num_classes * F);
   int nchunks = (int)((N + 32 * ng - 1) / (32 * ng));
   nchunks = nchunks < 16 ? 16 : (nchunks > GEOSSL_EMB_CHUNKS ? GEOSSL_EMB_CHUNKS : (nchunks + 3) / 4 * 4);
-  const size_t lds = (size_t)ng * num_classes * F * sizeof(float) + ng * sizeof(int2);
   if (ng == 4) {
     hipLaunchKernelGGL(k_embedding_bwd_partial<4>, dim3(nchunks), dim3(4 * TF), lds, stream, z, z_stride, dh, N, F,
                        num_classes, workspace, band, dyn_N);

@@ -22,7 +22,8 @@ def assert_within(got, ref, S, c, u, what, extra=None):
     if n:
         idx = bad.nonzero()[:8]
         rows = [(tuple(int(v) for v in i), float(got[tuple(i)]), float(ref[tuple(i)]), float(S[tuple(i)])) for i in idx]
-        pytest.fail("%s: %d of %d elements outside %g u S (index, got, ref, S): %s" % (what, n, bad.numel(), c, rows))
+        cs = "c" if torch.is_tensor(c) and c.numel() > 1 else "%g" % float(c)          # (c may differ by row)
+        pytest.fail("%s: %d of %d elements outside %s u S (index, got, ref, S): %s" % (what, n, bad.numel(), cs, rows))
 
 
 def assert_sees_a_dropped_term(got, ref, S, c, u, index, term, what, extra=None):
