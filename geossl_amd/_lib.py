@@ -343,6 +343,10 @@ PROTOTYPES = {
     "geossl_rr_head_workspace_floats": (i64, [i64]),
     "geossl_rr_head_fwd": (i32, [vp, vp, i64, i32, i32, vp, vp, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp]),
     "geossl_rr_head_bwd": (i32, [vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]),
+    # molecular dynamics: the integrator around the force pass (csrc/md_integrate.hip)
+    "geossl_md_advance": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "geossl_md_finish": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, i32, i64, vp, vp, vp, vp, vp]),
+    "geossl_md_normals": (i32, [u64, u64, i64, vp, vp]),
 }
 
 _lib = None

@@ -5,6 +5,7 @@
 // the adjacency is kept as an n x ceil(n/64) bit matrix in LDS.  All outputs are written in the canonical
 // order (target-major, sources ascending) without atomics, so edge lists are bit-reproducible.
 #include "common.h"
+#include "philox.h"
 #include "radius_adj.h"
 #include "geossl_hip.h"
 
@@ -319,27 +320,7 @@ __global__ void k_copy2(uint32_t* __restrict__ d0, const uint32_t* __restrict__ 
 // stream (DDMTrainer with device noise): counter-based Philox4x32-10 keyed by a 64-bit seed read from the device (the
 // caller draws it from torch's generator, so torch.cuda.manual_seed governs the stream), counter = (group of four
 // outputs, segment); normals by Box-Muller.  Not the values torch's own calls would give - the reference's loop keeps
-// those (do_DDM).
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-    c = make_uint4(hi1 ^ c.y ^ k.x, lo1, hi0 ^ c.w ^ k.y, lo0);
-    k.x += 0x9E3779B9u;
-    k.y += 0xBB67AE85u;
-  }
-  return c;
-}
-__device__ __forceinline__ void normal4(uint4 r, float (&z)[4]) {
-  const float u0 = ((float)(r.x >> 8) + 1.0f) * (1.0f / 16777216.0f), u1 = (float)(r.y >> 8) * (1.0f / 16777216.0f);
-  const float u2 = ((float)(r.z >> 8) + 1.0f) * (1.0f / 16777216.0f), u3 = (float)(r.w >> 8) * (1.0f / 16777216.0f);
-  const float ra = sqrtf(-2.0f * logf(u0)), rb = sqrtf(-2.0f * logf(u2));
-  float sa, ca, sb, cb;
-  sincosf(6.283185307179586f * u1, &sa, &ca);
-  sincosf(6.283185307179586f * u3, &sb, &cb);
-  z[0] = ra * ca; z[1] = ra * sa; z[2] = rb * cb; z[3] = rb * sb;
-}
+// those (do_DDM).  philox4x32_10 and normal4: philox.h.
 __global__ void k_ddm_noise(const int64_t* __restrict__ seed, uint64_t seed_value, float mu, float sigma, int64_t n_pos,
                             int64_t S, int64_t B, int K1, int K2, float* __restrict__ pos_noise,
                             int64_t* __restrict__ nl1, float* __restrict__ dn1, int64_t* __restrict__ nl2,

@@ -1726,3 +1726,70 @@ def rr_heads(X, Y, kind, detach_target, bn, buffers, params):
         raise ValueError("rr_heads: X, Y [B, 128] with B >= 2, 12 parameters, 6 buffers and a loss of %s; got %s, %s, %r"
                          % (tuple(RR_LOSSES), tuple(X.shape), tuple(Y.shape), kind))
     return _RRHeads.apply(X, Y, kind, bool(detach_target), bn, buffers, *params)
+
+
+# ---- molecular dynamics: the integrator around the force pass (csrc/md_integrate.hip) --------------------------------
+MD_STATE_WORDS = 8      # int64: steps completed, step in flight + 1, seed, record_every, first step, thermostat, 2 unused
+MD_PARAM_WORDS = 4      # fp32: dt, c1, sigma_T, unused
+MD_STEP_DONE, MD_STEP_NEXT, MD_SEED, MD_RECORD_EVERY, MD_FIRST, MD_THERMOSTAT = range(6)
+
+
+def _md_dense(t, dtype, shape, what):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape):
+        raise ValueError("md: %s is a contiguous CUDA %s tensor of shape %s" % (what, str(dtype)[6:], shape))
+    return t
+
+
+def md_normals(seed, step, N, device=None, out=None):
+    """The thermostat's draws of step `step` under `seed` -> fp32 [N, 3]: what md_advance uses for its Langevin update."""
+    N = int(N)
+    if out is None:
+        out = torch.empty(N, 3, dtype=torch.float32, device=device if device is not None else "cuda")
+    _md_dense(out, torch.float32, (N, 3), "out")
+    call("geossl_md_normals", int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), N, ptr(out), stream())
+    return out
+
+
+def md_advance(pos, vel, grad, cinv_mass, rsqrt_mass, params, state):
+    """First half of an MD step, in place on pos and vel (include/geossl_hip.h): half kick with grad, drift (Langevin:
+    half drift, thermostat, half drift).  params fp32 [4], state int64 [8]: device data, read by the launch."""
+    N = pos.size(0) if torch.is_tensor(pos) and pos.dim() == 2 else -1
+    for t, what in ((pos, "pos"), (vel, "vel"), (grad, "grad")):
+        _md_dense(t, torch.float32, (N, 3), what)
+    _md_dense(cinv_mass, torch.float32, (N,), "cinv_mass")
+    _md_dense(rsqrt_mass, torch.float32, (N,), "rsqrt_mass")
+    _md_dense(params, torch.float32, (MD_PARAM_WORDS,), "params")
+    _md_dense(state, torch.int64, (MD_STATE_WORDS,), "state")
+    call("geossl_md_advance", ptr(pos), ptr(vel), ptr(grad), ptr(cinv_mass), ptr(rsqrt_mass), ptr(params), ptr(state), N,
+         stream())
+
+
+def md_finish(pos, vel, grad_new, energy_new, grad, energy, cinv_mass, ke_coef, mol_ptr, params, state, frames=None,
+              record_only=False):
+    """Second half of an MD step: the kick with grad_new (kept in grad, energy_new in energy), the molecules' kinetic
+    energies in fp64 and, when the step is one to record, its frame into `frames` = (traj_pos [R, N, 3], traj_vel
+    [R, N, 3], traj_pot [R, B] fp32, traj_kin [R, B] fp64).  record_only: no kick, slot 0 written."""
+    N = pos.size(0) if torch.is_tensor(pos) and pos.dim() == 2 else -1
+    B = energy.numel() if torch.is_tensor(energy) else -1
+    for t, what in ((pos, "pos"), (vel, "vel"), (grad_new, "grad_new"), (grad, "grad")):
+        _md_dense(t, torch.float32, (N, 3), what)
+    _md_dense(energy_new, torch.float32, (B,), "energy_new")
+    _md_dense(energy, torch.float32, (B,), "energy")
+    _md_dense(cinv_mass, torch.float32, (N,), "cinv_mass")
+    _md_dense(ke_coef, torch.float64, (N,), "ke_coef")
+    _md_dense(mol_ptr, torch.int32, (B + 1,), "mol_ptr")
+    _md_dense(params, torch.float32, (MD_PARAM_WORDS,), "params")
+    _md_dense(state, torch.int64, (MD_STATE_WORDS,), "state")
+    R, tp = 0, (None, None, None, None)
+    if frames is not None:
+        tp = frames
+        R = tp[0].size(0) if torch.is_tensor(tp[0]) and tp[0].dim() == 3 else -1
+        _md_dense(tp[0], torch.float32, (R, N, 3), "traj_pos")
+        _md_dense(tp[1], torch.float32, (R, N, 3), "traj_vel")
+        _md_dense(tp[2], torch.float32, (R, B), "traj_pot")
+        _md_dense(tp[3], torch.float64, (R, B), "traj_kin")
+    if record_only and R < 1:
+        raise ValueError("md: record_only writes slot 0 of `frames`")
+    call("geossl_md_finish", ptr(pos), ptr(vel), ptr(grad_new), ptr(energy_new), ptr(grad), ptr(energy), ptr(cinv_mass),
+         ptr(ke_coef), ptr(mol_ptr), B, N, ptr(params), ptr(state), 1 if record_only else 0, R, ptr(tp[0]), ptr(tp[1]),
+         ptr(tp[2]), ptr(tp[3]), stream())

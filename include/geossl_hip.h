@@ -1282,6 +1282,32 @@ int geossl_rr_head_bwd(const float* X, const float* Y, int64_t B, int F, int los
                        const float* p, const float* gout, float* dp, float* dz, float* dt, float* const* grads,
                        int accumulate, float* dxy, float* tn_workspace, hipStream_t stream);
 
+/* ---- molecular dynamics on a force field: the integrator around the force pass (csrc/md_integrate.hip) ----------------
+ * An MD step of B independent replicas is geossl_md_advance, the force pass on pos, geossl_md_finish.  Device state:
+ * pos, vel, grad [N][3] and energy [B] fp32; cinv_mass [N] = ACCEL / m and rsqrt_mass [N] = m^-1/2 fp32; ke_coef [N] =
+ * m / (2 ACCEL) fp64; params [4] fp32 = (dt, c1 = exp(-gamma dt), sigma_T = sqrt(1 - c1^2) sqrt(KB T ACCEL), unused);
+ * state [8] int64 = (steps completed, step in flight + 1, Philox seed, record_every, step of trajectory slot 0,
+ * thermostat 0 NVE / 1 Langevin, unused, unused).  Parameters and state are read from the device by every launch: a
+ * captured graph of these launches follows their changes.
+ * geossl_md_advance : a = (-grad) cinv_mass, vh = fma(dt/2, a, v); NVE x = fma(dt, vh, x), vel = vh; Langevin
+ *   x = fma(dt/2, vh, x), vo = fma(c1, vh, (sigma_T rsqrt_mass) xi), x = fma(dt/2, vo, x), vel = vo.  xi: the normals of
+ *   geossl_md_normals at (seed, step = state[0]).  Writes state[1] = state[0] + 1.
+ * geossl_md_finish : v = fma(dt/2, (-grad_new) cinv_mass, vel); grad = grad_new and energy = energy_new (either may BE
+ *   the other buffer); per molecule KE = sum ke_coef |v|^2 in fp64 in a fixed order, no atomics.  With s = state[1] and
+ *   d = s - state[4]: when d >= 0, d % record_every == 0 and d / record_every < frames, slot d / record_every of traj_pos
+ *   / traj_vel [frames][N][3] fp32, traj_pot [frames][B] fp32 (energy_new) and traj_kin [frames][B] fp64 is written.
+ *   Writes state[0] = s.  record_only != 0: no kick, no step word written, slot 0 written (frames >= 1).  mol_ptr
+ *   [B + 1] are atom offsets in [0, N]; frames = 0: nothing is recorded and the traj pointers may be NULL.
+ * geossl_md_normals : out [N][3] = the first three normals of Philox-4x32-10 at the counter (atom, step & 0xffffffff,
+ *   step >> 32, 0) under the key (seed & 0xffffffff, seed >> 32), Box-Muller - what geossl_md_advance draws.           */
+int geossl_md_advance(float* pos, float* vel, const float* grad, const float* cinv_mass, const float* rsqrt_mass,
+                      const float* params, int64_t* state, int64_t N, hipStream_t stream);
+int geossl_md_finish(const float* pos, float* vel, const float* grad_new, const float* energy_new, float* grad,
+                     float* energy, const float* cinv_mass, const double* ke_coef, const int32_t* mol_ptr, int64_t B,
+                     int64_t N, const float* params, int64_t* state, int record_only, int64_t frames, float* traj_pos,
+                     float* traj_vel, float* traj_pot, double* traj_kin, hipStream_t stream);
+int geossl_md_normals(uint64_t seed, uint64_t step, int64_t N, float* out, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
