@@ -347,6 +347,9 @@ PROTOTYPES = {
     "geossl_md_advance": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, vp]),
     "geossl_md_finish": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, i32, i64, vp, vp, vp, vp, vp]),
     "geossl_md_normals": (i32, [u64, u64, i64, vp, vp]),
+    # structure relaxation: FIRE around the force pass (csrc/relax.hip)
+    "geossl_fire_step": (i32, [vp] * 8 + [i64, i64] + [vp] * 5 + [i32, i64] + [vp] * 8 + [vp]),
+    "geossl_fire_active": (i32, [vp, i64, vp, vp]),
 }
 
 _lib = None

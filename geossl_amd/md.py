@@ -28,32 +28,25 @@ seeded with `seed`: a DIFFERENT stream from the device's, so a fallback trajecto
 Not built (refused with a sentence): structures above 255 atoms, and PaiNN off the interned complete pair list (one size
 n <= 33) - its radius edges would have to be rebuilt every step."""
 import math
-import types
 from collections import namedtuple
 
 import torch
 
 from . import _lib, ops
-from .finetune_md17 import (COMPLETE_MAX_N, _collated, _energy_and_gradient, _fused_predict_ok, complete_applies,
-                            complete_edges, md17_energy_force_aten, with_complete_edges)
-from .layout import get_layout
-from .replay import StructureGraphs, capture, owned_batch_vector, parameter_addresses, warm_up
+from .replicas import ACCEL, GRAPH_DEFAULT_MAX_ATOMS, MAX_ATOMS, Replicas, default_masses
 
 __all__ = ["Simulator", "Trajectory", "ACCEL", "KB", "default_masses", "STEPS_PER_REPLAY_DEFAULT", "USE_GRAPH_DEFAULT",
            "GRAPH_DEFAULT_MAX_ATOMS"]
 
-ACCEL = 4.184e-4                      # A fs^-2 per (kcal mol^-1 A^-1 amu^-1): 4184 J/kcal / (1e-3 kg/mol) * 1e-10 m/A * 1e-30
 KB = 8.31446261815324 / 4184          # kcal mol^-1 K^-1
-MAX_ATOMS = 255                       # per structure: the dense pair layout of the force pass
 # Measured defaults (tools/bench_md.py, profiles/md_bench.json, DESIGN 5).  steps_per_replay: the smallest value whose
 # median lies within the spread of the best is 4 on seven of the twelve shapes and 16 on five; nothing separates them by
-# more than 1.3 %.  use_graph None: replay up to GRAPH_DEFAULT_MAX_ATOMS, eager launches above.  The threshold is ONE data
-# point: 64 replicas of 21 atoms is the largest measured batch on which the slowest replayed run beat the fastest run of
-# the loop on predict_MD17 (with one exception below it, by 0.3 %); the next measured size, 1024 replicas, has replay,
-# eager and that loop within 2 % of one another; nothing in between was measured.
+# more than 1.3 %.  use_graph None: replay up to GRAPH_DEFAULT_MAX_ATOMS (replicas.py), eager launches above.  The
+# threshold is ONE data point: 64 replicas of 21 atoms is the largest measured batch on which the slowest replayed run beat
+# the fastest run of the loop on predict_MD17 (with one exception below it, by 0.3 %); the next measured size, 1024
+# replicas, has replay, eager and that loop within 2 % of one another; nothing in between was measured.
 STEPS_PER_REPLAY_DEFAULT = 4
 USE_GRAPH_DEFAULT = None
-GRAPH_DEFAULT_MAX_ATOMS = 64 * 21
 
 Trajectory = namedtuple("Trajectory", "positions velocities potential kinetic temperature steps")
 Trajectory.__doc__ = """Recorded frames of ``Simulator.run``: positions, velocities [R, N, 3]; potential [R, B] (fp32: the
@@ -61,26 +54,7 @@ model's energies at the recorded positions); kinetic [R, B] fp64; temperature [R
 counter of each frame).  Tensors on the simulator's device."""
 
 
-def default_masses(x):
-    """MD17's encoding (datasets_MD17.py:56-59): x is the index into possible_atomic_num_list = [1..118], so the atom's
-    mass is atomic_mass[x + 1] -> fp64 [N] on the CPU."""
-    from .Geom3D.models._atomic_mass import atomic_masses
-    table = torch.as_tensor(atomic_masses(), dtype=torch.float64).cpu()
-    z = torch.as_tensor(x).detach().cpu().long()
-    z = z if z.dim() == 1 else z[:, 0]
-    if z.numel() and (int(z.min()) < 0 or int(z.max()) + 1 >= table.numel()):
-        raise ValueError("default masses: atom types in [0, %d), got up to %d" % (table.numel() - 1, int(z.max())))
-    return table[z + 1]
-
-
-def _host_sizes(batch):
-    sizes = getattr(batch, "_sizes", None)
-    if sizes is None:
-        sizes = torch.bincount(batch.batch.detach().cpu().long()).tolist()
-    return [int(n) for n in sizes]
-
-
-class Simulator:
+class Simulator(Replicas):
     """See the module docstring.  masses: [N] in amu (None: ``default_masses(batch.x)``); dt in fs; thermostat None (NVE)
     or ("langevin", T in K, gamma in fs^-1); seed: of the thermostat's stream (None: drawn from torch's generator);
     use_graph: replay the captured step (None: for batches of at most GRAPH_DEFAULT_MAX_ATOMS atoms, where it was measured
@@ -90,49 +64,16 @@ class Simulator:
     def __init__(self, model, graph_pred_linear, batch, model_3d="schnet", masses=None, dt=0.5, thermostat=None,
                  seed=None, use_graph=USE_GRAPH_DEFAULT, steps_per_replay=STEPS_PER_REPLAY_DEFAULT, max_frames=1024,
                  energy_and_gradient=None):
-        if model_3d not in ("schnet", "painn"):
-            raise Exception("3D model {} not included.".format(model_3d))
-        if int(steps_per_replay) < 1 or int(max_frames) < 1:
-            raise ValueError("Simulator: steps_per_replay and max_frames are at least 1")
-        b = _collated(batch)
-        self.model, self.head, self.model_3d = model, graph_pred_linear, model_3d
-        self.hook = energy_and_gradient
-        self.sizes = _host_sizes(b)
-        self.B, self.N = len(self.sizes), int(b.positions.size(0))
-        if sum(self.sizes) != self.N:
-            raise ValueError("Simulator: the batch's sizes add up to %d atoms, positions has %d rows"
-                             % (sum(self.sizes), self.N))
-        if self.hook is None:
-            if max(self.sizes) > MAX_ATOMS:
-                raise ValueError("Simulator: structures of at most %d atoms (the dense pair layout of the force pass), "
-                                 "got %d" % (MAX_ATOMS, max(self.sizes)))
-            if model_3d == "painn" and (len(set(self.sizes)) != 1 or self.sizes[0] > COMPLETE_MAX_N):
-                raise ValueError("Simulator: PaiNN runs on the interned complete pair list only (molecules of one size n "
-                                 "<= %d); the radius edges of this batch would have to be rebuilt every step, which is "
-                                 "not built" % COMPLETE_MAX_N)
-        m = default_masses(b.x) if masses is None else torch.as_tensor(masses).detach().cpu().double().reshape(-1)
-        if m.numel() != self.N:
-            raise ValueError("Simulator: masses has %d entries, the batch %d atoms" % (m.numel(), self.N))
-        if not bool((m > 0).all()):
-            raise ValueError("Simulator: masses are positive")
-        self.masses = m
+        b = self._setup(model, graph_pred_linear, batch, model_3d, masses, use_graph, steps_per_replay, max_frames,
+                        energy_and_gradient)
         self.dof = torch.tensor([3 * n - 3 if n > 1 else 3 * n for n in self.sizes], dtype=torch.float64)
-        if use_graph is None:
-            use_graph = self.N <= GRAPH_DEFAULT_MAX_ATOMS
-        self.max_frames, self.steps_per_replay, self.use_graph = int(max_frames), int(steps_per_replay), bool(use_graph)
         self.seed = int(torch.randint(0, 2 ** 62, (1,))) if seed is None else int(seed)
         if not 0 <= self.seed < 2 ** 63:
             raise ValueError("Simulator: seed is an integer in [0, 2^63) (a word of the int64 state buffer), got %d"
                              % self.seed)
         self._steps = 0
         self._dt, self._thermostat = float(dt), None
-        self.graphs = None
-        ps = None if self.hook is not None else _fused_predict_ok(model, graph_pred_linear, b)
-        if ps is not None and model_3d == "painn" and not complete_applies(types.SimpleNamespace(_sizes=self.sizes), model):
-            ps = None   # (a subclass of PaiNN: the reference's lines on the complete pair list)
-        self.fused = ps is not None and self._init_fused(ps, b)
-        if not self.fused:
-            self._init_fallback(b)
+        self._route(b)
         self.set_dt(dt)
         if thermostat is None:
             self.set_thermostat()
@@ -142,30 +83,11 @@ class Simulator:
                 raise ValueError("Simulator: thermostat is None or (\"langevin\", T, gamma), got %r" % (kind,))
             self.set_thermostat(T=T, gamma=gamma)
 
-    # ---- the two routes' state
-    def _init_fused(self, ps, b):
-        dev = b.positions.device
-        if self.model_3d == "painn":
-            b = with_complete_edges(b, self.model)
-            if not getattr(b, "_complete", False):   # (the switch is off: the reference's lines instead)
-                return False
-            bvec, rei = b.batch, b.radius_edge_index
-        else:
-            bvec, rei = owned_batch_vector(b.batch, self.sizes), None
-        x = b.x.clone()
-        self._x = x if self.model_3d == "painn" or x.dim() == 1 else x[:, 0].contiguous()
-        self._ps, self._bvec, self._rei = ps, bvec, rei
-        self._pos = b.positions.detach().clone().contiguous()
-        if self._force() is None:   # (the backbone did not run as its fused node)
-            return False
+    # ---- the two routes' own state (the common part: Replicas._init_fused / _init_fallback)
+    def _alloc_fused(self, dev):
         f32 = dict(dtype=torch.float32, device=dev)
-        self._vel = torch.zeros(self.N, 3, **f32)
-        self._grad = torch.zeros(self.N, 3, **f32)
-        self._energy = torch.zeros(self.B, **f32)
-        self._cinv = (ACCEL / self.masses).to(**f32)
         self._rsqrt = self.masses.rsqrt().to(**f32)
         self._ke_coef = (self.masses / (2.0 * ACCEL)).to(dev)
-        self._mol_ptr = get_layout(bvec).mol_ptr
         self._params = torch.zeros(ops.MD_PARAM_WORDS, **f32)
         state = torch.zeros(ops.MD_STATE_WORDS, dtype=torch.int64)
         state[ops.MD_SEED], state[ops.MD_RECORD_EVERY] = self.seed, 1
@@ -173,45 +95,17 @@ class Simulator:
         R = self.max_frames
         self._frames = (torch.zeros(R, self.N, 3, **f32), torch.zeros(R, self.N, 3, **f32), torch.zeros(R, self.B, **f32),
                         torch.zeros(R, self.B, dtype=torch.float64, device=dev))
-        self.graphs = StructureGraphs(4, enabled=self.use_graph)
-        self._bound = parameter_addresses(self.model, self.head)
-        return True
 
-    def _init_fallback(self, b):
-        pos = b.positions.detach().clone()
-        dev, dt = pos.device, pos.dtype
-        self._pos, self._vel = pos, torch.zeros_like(pos)
-        self._x, self._bvec = b.x, b.batch
-        self._rei = getattr(b, "radius_edge_index", None)
-        if self.hook is None and self.model_3d == "painn":
-            self._rei = complete_edges(self.B, self.sizes[0], dev)[0]
-        self._cinv = (ACCEL / self.masses).to(device=dev, dtype=dt)[:, None]
+    def _alloc_fallback(self):
+        dev, dt = self._pos.device, self._pos.dtype
         self._rsqrt = self.masses.rsqrt().to(device=dev, dtype=dt)[:, None]
         self._ke_coef = (self.masses / (2.0 * ACCEL)).to(dev)
-        self._mol = torch.repeat_interleave(torch.arange(self.B), torch.tensor(self.sizes)).to(dev)
         self._gen = torch.Generator().manual_seed(self.seed % (2 ** 63))
-        self._grad = self._energy = None
 
     # ---- state
     @property
-    def captures(self):
-        return 0 if self.graphs is None else self.graphs.captures
-
-    @property
-    def positions(self):
-        """The live positions [N, 3] (the force pass's static input on the fused route): clone to keep a copy."""
-        return self._pos
-
-    @property
-    def velocities(self):
-        return self._vel
-
-    @property
     def step_count(self):
         return self._steps
-
-    def set_positions(self, positions):
-        self._pos.copy_(torch.as_tensor(positions).to(self._pos))
 
     def set_velocities(self, v):
         v = torch.as_tensor(v)
@@ -261,9 +155,6 @@ class Simulator:
         self._state[ops.MD_THERMOSTAT:ops.MD_THERMOSTAT + 1].fill_(0 if self._thermostat is None else 1)
 
     # ---- the fused route
-    def _force(self):
-        return _energy_and_gradient(self.model_3d, self.model, self._ps, self._x, self._pos, self._bvec, self._rei)
-
     def _step(self):
         ops.md_advance(self._pos, self._vel, self._grad, self._cinv, self._rsqrt, self._params, self._state)
         energy, grad = self._force()
@@ -276,35 +167,21 @@ class Simulator:
         ops.md_finish(self._pos, self._vel, grad, energy, self._grad, self._energy, self._cinv, self._ke_coef,
                       self._mol_ptr, self._params, self._state, self._frames, record_only=True)
 
-    def _capture(self, U):
-        """_Predictor._capture's protocol: the eager probe ran in __init__; warm-up passes that leave the state as it is
-        (the force pass, SchNet's block plan, the two integrator kernels on copies); then U steps into one graph."""
-        def passes():
-            self._force()
-            if self.model_3d == "schnet":
-                get_layout(self._bvec).loop_plan()
+    def _capture_steps(self, U):
+        def dry_run():   # (the two integrator kernels on copies)
             pos, vel, state = self._pos.clone(), self._vel.clone(), self._state.clone()
             ops.md_advance(pos, vel, self._grad, self._cinv, self._rsqrt, self._params, state)
             ops.md_finish(pos, vel, self._grad, self._energy, self._grad, self._energy, self._cinv, self._ke_coef,
                           self._mol_ptr, self._params, state)
-        warm_up(passes)
 
         def steps():
             for _ in range(U):
                 self._step()
-        with capture(self.graphs, "the MD step", "enabled") as cap:
-            graph, _ = cap.record(steps)
-        return dict(graph=graph) if cap.ok else None
+        return self._capture("the MD step", dry_run, steps)
 
-    def _graph(self):
-        if not self.use_graph:
-            return None
-        if self._bound != parameter_addresses(self.model, self.head):   # (parameters moved: the owner is rebuilt)
-            self.graphs = StructureGraphs(4, enabled=self.graphs.enabled)
-            self._bound = parameter_addresses(self.model, self.head)
+    def _step_graph(self):
         U = self.steps_per_replay
-        hit = self.graphs.lookup(("md", U), lambda: True, lambda: self._capture(U))
-        return None if not hit else hit[0]["graph"]
+        return self._graph(("md", U), lambda: self._capture_steps(U))
 
     def _advance_fused(self, n, graph):
         U = self.steps_per_replay
@@ -321,7 +198,7 @@ class Simulator:
                torch.empty(R, self.N, 3, dtype=torch.float32, device=dev),
                torch.empty(R, self.B, dtype=torch.float32, device=dev),
                torch.empty(R, self.B, dtype=torch.float64, device=dev))
-        graph = self._graph() if steps >= self.steps_per_replay else None
+        graph = self._step_graph() if steps >= self.steps_per_replay else None
         word = lambda k, v: self._state[k:k + 1].fill_(int(v))
         word(ops.MD_RECORD_EVERY, every)
         word(ops.MD_FIRST, first)
@@ -342,16 +219,6 @@ class Simulator:
         return out
 
     # ---- the fallback route
-    def _force_fallback(self):
-        if self.hook is not None:
-            energy, grad = self.hook(self._pos.detach())
-            return energy.detach(), grad.detach()
-        bd = types.SimpleNamespace(x=self._x, positions=self._pos.detach(), batch=self._bvec, radius_edge_index=self._rei)
-        args = types.SimpleNamespace(model_3d=self.model_3d)
-        with torch.enable_grad():
-            energy, force = md17_energy_force_aten(args, bd, self.model, self.head, create_graph=False)
-        return energy.detach(), force.detach().neg()
-
     def _kinetic(self):
         v2 = self._vel.double().pow(2).sum(1)
         return torch.zeros(self.B, dtype=torch.float64, device=v2.device).index_add_(0, self._mol, self._ke_coef * v2)

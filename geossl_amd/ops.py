@@ -1793,3 +1793,64 @@ def md_finish(pos, vel, grad_new, energy_new, grad, energy, cinv_mass, ke_coef, 
     call("geossl_md_finish", ptr(pos), ptr(vel), ptr(grad_new), ptr(energy_new), ptr(grad), ptr(energy), ptr(cinv_mass),
          ptr(ke_coef), ptr(mol_ptr), B, N, ptr(params), ptr(state), 1 if record_only else 0, R, ptr(tp[0]), ptr(tp[1]),
          ptr(tp[2]), ptr(tp[3]), stream())
+
+
+# ---- structure relaxation: FIRE around the force pass (csrc/relax.hip) -----------------------------------------------
+FIRE_PARAM_WORDS = 8    # fp32: ftol, dt_max, dt_min, max_step, f_inc, f_dec, alpha_start, f_alpha
+FIRE_IPARAM_WORDS = 4   # int64: n_min, record_every, call counter of trajectory slot 0, unused
+FIRE_MOL_WORDS = 4      # int32 per molecule: npos, done, nsteps, calls
+FIRE_FTOL, FIRE_DT_MAX, FIRE_DT_MIN, FIRE_MAX_STEP, FIRE_F_INC, FIRE_F_DEC, FIRE_ALPHA_START, FIRE_F_ALPHA = range(8)
+FIRE_N_MIN, FIRE_RECORD_EVERY, FIRE_FIRST = range(3)
+FIRE_NPOS, FIRE_DONE, FIRE_NSTEPS, FIRE_CALLS = range(4)
+
+
+def fire_frames(R, N, B, device, fill=None):
+    """The eight trajectory buffers of fire_step for R frames: positions, velocities [R, N, 3], energy, fmax, dt, alpha
+    [R, B] fp32, npos, done [R, B] int32."""
+    make = (lambda *s, **k: torch.zeros(*s, **k)) if fill is None else (lambda *s, **k: torch.full(s, fill, **k))
+    f32, i32 = dict(dtype=torch.float32, device=device), dict(dtype=torch.int32, device=device)
+    return (make(R, N, 3, **f32), make(R, N, 3, **f32), make(R, B, **f32), make(R, B, **f32), make(R, B, **f32),
+            make(R, B, **f32), make(R, B, **i32), make(R, B, **i32))
+
+
+def fire_step(pos, vel, grad_new, energy_new, grad, energy, cinv_mass, mol_ptr, params, iparams, mol_dt, mol_alpha,
+              mol_state, frames=None, evaluate_only=False):
+    """One FIRE step of every molecule, in place (include/geossl_hip.h): the convergence test at pos with grad_new, the
+    frame when the molecule's call counter hits a slot of `frames` (the eight buffers of `fire_frames`), the update of
+    vel, pos and the molecule's words.  evaluate_only: the test and slot 0 of `frames`, nothing else written."""
+    N = pos.size(0) if torch.is_tensor(pos) and pos.dim() == 2 else -1
+    B = energy.numel() if torch.is_tensor(energy) else -1
+    for t, what in ((pos, "pos"), (vel, "vel"), (grad_new, "grad_new"), (grad, "grad")):
+        _md_dense(t, torch.float32, (N, 3), what)
+    _md_dense(energy_new, torch.float32, (B,), "energy_new")
+    _md_dense(energy, torch.float32, (B,), "energy")
+    _md_dense(cinv_mass, torch.float32, (N,), "cinv_mass")
+    _md_dense(mol_ptr, torch.int32, (B + 1,), "mol_ptr")
+    _md_dense(params, torch.float32, (FIRE_PARAM_WORDS,), "params")
+    _md_dense(iparams, torch.int64, (FIRE_IPARAM_WORDS,), "iparams")
+    _md_dense(mol_dt, torch.float32, (B,), "mol_dt")
+    _md_dense(mol_alpha, torch.float32, (B,), "mol_alpha")
+    _md_dense(mol_state, torch.int32, (B, FIRE_MOL_WORDS), "mol_state")
+    R, tp = 0, (None,) * 8
+    if frames is not None:
+        tp = tuple(frames)
+        R = tp[0].size(0) if len(tp) == 8 and torch.is_tensor(tp[0]) and tp[0].dim() == 3 else -1
+        _md_dense(tp[0], torch.float32, (R, N, 3), "traj_pos")
+        _md_dense(tp[1], torch.float32, (R, N, 3), "traj_vel")
+        for t, what in zip(tp[2:6], ("traj_energy", "traj_fmax", "traj_dt", "traj_alpha")):
+            _md_dense(t, torch.float32, (R, B), what)
+        for t, what in zip(tp[6:], ("traj_npos", "traj_done")):
+            _md_dense(t, torch.int32, (R, B), what)
+    if evaluate_only and R < 1:
+        raise ValueError("md: evaluate_only writes slot 0 of `frames`")
+    call("geossl_fire_step", ptr(pos), ptr(vel), ptr(grad_new), ptr(energy_new), ptr(grad), ptr(energy), ptr(cinv_mass),
+         ptr(mol_ptr), B, N, ptr(params), ptr(iparams), ptr(mol_dt), ptr(mol_alpha), ptr(mol_state),
+         1 if evaluate_only else 0, R, *[ptr(t) for t in tp], stream())
+
+
+def fire_active(mol_state, active):
+    """active[0] (int32) = the number of molecules whose `done` word is 0: the one word a relaxation's host loop reads."""
+    B = mol_state.size(0) if torch.is_tensor(mol_state) and mol_state.dim() == 2 else -1
+    _md_dense(mol_state, torch.int32, (B, FIRE_MOL_WORDS), "mol_state")
+    _md_dense(active, torch.int32, (1,), "active")
+    call("geossl_fire_active", ptr(mol_state), B, ptr(active), stream())

@@ -1308,6 +1308,31 @@ int geossl_md_finish(const float* pos, float* vel, const float* grad_new, const 
                      float* traj_vel, float* traj_pot, double* traj_kin, hipStream_t stream);
 int geossl_md_normals(uint64_t seed, uint64_t step, int64_t N, float* out, hipStream_t stream);
 
+/* ---- structure relaxation on a force field: FIRE around the force pass (csrc/relax.hip) -----------------------------
+ * A step of B independent replicas is the force pass on pos, then geossl_fire_step.  Device state: pos, vel, grad [N][3]
+ * and energy [B] fp32; cinv_mass [N] = ACCEL / m fp32; params [8] fp32 = (ftol, dt_max, dt_min, max_step, f_inc, f_dec,
+ * alpha_start, f_alpha); iparams [4] int64 = (n_min, record_every, call counter of trajectory slot 0, unused); per
+ * molecule mol_dt, mol_alpha [B] fp32 and mol_state [B][4] int32 = (npos, done, nsteps, calls).  All of it is read from
+ * the device by every launch: a captured graph of these launches follows its changes.
+ * geossl_fire_step : per molecule, with F = -grad_new and fp64 reductions in a fixed order (no atomics): converged =
+ *   done or max_i |F_i| < ftol.  A converged molecule is latched (done = 1) and only its call counter moves.  Otherwise
+ *   P = sum F.v > 0 or v = 0: v = (1 - alpha) v + alpha sqrt(vv / ff) F, and after more than n_min such steps in a row
+ *   dt = min(dt f_inc, dt_max), alpha = alpha f_alpha; else v = 0, alpha = alpha_start, dt = max(dt f_dec, dt_min).
+ *   Then v += dt F cinv_mass, dr = dt v, pos += min(1, max_step / max_i |dr_i|) dr.  The fp32 rounding sequence is stated
+ *   in csrc/relax.hip.  grad = grad_new and energy = energy_new are kept (either may BE the other buffer).  With d =
+ *   calls - iparams[2]: when d >= 0, d % record_every == 0 and d / record_every < frames, slot d / record_every of traj_pos
+ *   / traj_vel [frames][N][3] and traj_energy / traj_fmax / traj_dt / traj_alpha fp32, traj_npos / traj_done int32
+ *   [frames][B] receives the state AS THE STEP FOUND IT (done: after the test at these positions).  evaluate_only != 0:
+ *   the test and the frame into slot 0 (frames >= 1), nothing else is written.  mol_ptr [B + 1] are atom offsets in
+ *   [0, N]; frames = 0: nothing is recorded and the traj pointers may be NULL.
+ * geossl_fire_active : active[0] = the number of molecules with done == 0 (one block, fixed order).                   */
+int geossl_fire_step(float* pos, float* vel, const float* grad_new, const float* energy_new, float* grad, float* energy,
+                     const float* cinv_mass, const int32_t* mol_ptr, int64_t B, int64_t N, const float* params,
+                     const int64_t* iparams, float* mol_dt, float* mol_alpha, int32_t* mol_state, int evaluate_only,
+                     int64_t frames, float* traj_pos, float* traj_vel, float* traj_energy, float* traj_fmax,
+                     float* traj_dt, float* traj_alpha, int32_t* traj_npos, int32_t* traj_done, hipStream_t stream);
+int geossl_fire_active(const int32_t* mol_state, int64_t B, int32_t* active, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
