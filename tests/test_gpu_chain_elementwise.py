@@ -22,6 +22,7 @@ import torch
 
 import chain_twin as tw
 from elementwise import assert_repeatable, assert_sees_a_dropped_term, assert_within
+from objective_harness import lib_loaded  # noqa: F401 (the autouse fixture)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -33,12 +34,6 @@ ROWS_STREAM = (1, 33, 128, 157, 192, 320, 40960, 40983, 73824)
 EVERY_ROW_COUNT = tw.LONGEST + (tw.SCHNET3,)
 CASES = [(F, name, transB, kind) for F in (128, 64, 32) for name in tw.FORMS[F] for transB in (True, False)
          for kind in tw.KINDS]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _lib_loaded():
-    from geossl_amd import _lib
-    _lib.load()
 
 
 WORST = {}

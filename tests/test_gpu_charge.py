@@ -15,6 +15,8 @@ import torch
 import charge_twin as tw
 from conftest import load_golden, rel_err
 from helpers import fill_module_, grad_summary, t, unique_named_grads
+from objective_harness import (Case, assert_one_bucket, backbone, kind_args, loader_handles, ragged_batches,
+                               reference_loop_vs_trainer, replay_vs_eager, with_radius_edges)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -324,117 +326,72 @@ def test_fallbacks_match_aten():
 
 
 # ---------------------------------------------------------------------------------------------- graph paths
-def _ragged_batches(n, B, seed, option="permutation"):
-    from geossl_amd import pretrain_GeoSSL as pg
-    from geossl_amd.synthetic import collate_subset, make_batch
-    pool = make_batch(4 * B, seed=seed, mode="B", option=option)
-    rng = np.random.default_rng(seed)
-    return [pg.Batch.from_numpy(collate_subset(pool, rng.permutation(4 * B)[:B], option=option), DEV) for _ in range(n)]
+def _heads(kind, model):
+    from geossl_amd.pretrain_ChargePrediction import ChargePredictor
+    return [fill_module_(ChargePredictor(128)).to(DEV)]
 
 
-def _model(kind):
-    from geossl_amd.Geom3D.models import PaiNN, SchNet
-    return (fill_module_(SchNet(hidden_channels=128, num_filters=128, num_interactions=6, num_gaussians=51,
-                                cutoff=10.0, node_class=9)) if kind == "schnet" else
-            fill_module_(PaiNN(n_atom_basis=128, n_interactions=3, n_rbf=20, cutoff=5.0, max_z=9, n_out=1,
-                               readout="add"))).to(DEV)
-
-
-def _grads(model, cp):
-    return [p.grad.clone() for p in list(model.parameters()) + list(cp.parameters()) if p.grad is not None]
-
-
-def _replay_vs_eager(model, cp, kind, batches, ratio=0.3):
-    """numpy masks: the eager step and the replayed one see the same draw (the numpy stream is re-seeded)."""
+def _step(args, b, model, heads, graph):
     from geossl_amd.pretrain_ChargePrediction import do_ChargePrediction
-    args = types.SimpleNamespace(model_3d=kind, charge_masking_ratio=ratio)
-    for k, b in enumerate(batches):
-        out = []
-        x0 = b.x.clone() if getattr(b, "_dataset", None) is None else None
-        for graph in (False, True):
-            if x0 is not None:
-                b.x.copy_(x0)
-            else:   # (a handle's collated tensors, which the eager step masked in place, are gathered again)
-                b._batch = None
-            model.zero_grad(set_to_none=True)
-            cp.zero_grad(set_to_none=True)
-            np.random.seed(1000 + k)
-            loss = do_ChargePrediction(args, b, model, cp, graph=graph)
-            loss.backward()
-            out.append((loss.detach().clone(), _grads(model, cp), None if x0 is None else b.x.clone()))
-        assert rel_err(out[1][0].cpu(), out[0][0].cpu()) < 1e-6, (kind, k)
-        assert len(out[1][1]) == len(out[0][1])
-        for a, c in zip(out[1][1], out[0][1]):
-            assert rel_err(a, c) < 1e-5, (kind, k)
+    return do_ChargePrediction(args, b, model, heads[0], graph=graph), ()
+
+
+def _masked_types(b):
+    """The caller's types (a collated batch's: not a handle's), masked alike on both paths."""
+    return () if getattr(b, "_dataset", None) is not None else (b.x.clone(),)
+
+
+def _same_draw(b, k):
+    """numpy masks: the eager step and the replayed one see the same draw (the numpy stream is re-seeded) on the same
+    unmasked types."""
+    x0 = b.x.clone() if getattr(b, "_dataset", None) is None else None
+
+    def reset():
         if x0 is not None:
-            assert torch.equal(out[1][2], out[0][2])   # the caller's types masked alike on both paths
-    eng = model.__dict__["_geossl_charge_step"]
-    (sg,) = eng.graphs.values()
-    return sg
+            b.x.copy_(x0)
+        else:   # (a handle's collated tensors, which the eager step masked in place, are gathered again)
+            b._batch = None
+        np.random.seed(1000 + k)
+    return reset
+
+
+def _trainer(model, heads, **kw):
+    from geossl_amd.pretrain_ChargePrediction import ChargePredictionTrainer
+    return ChargePredictionTrainer(model, heads[0], charge_masking_ratio=0.3, mask_rng="numpy", **kw)
+
+
+CASE = Case("charge", "_geossl_charge_step", _heads, kind_args(charge_masking_ratio=0.3), _step, _trainer,
+            aten_step=lambda args, b, model, heads: _step(args, b, model, heads, False),
+            head_weight=lambda heads: heads[0].predictor.weight, prepare=_same_draw, observe=_masked_types,
+            begin_loop=lambda: np.random.seed(5))
 
 
 @pytest.mark.parametrize("kind", ["schnet", "painn"])
 def test_bucket_replay_matches_eager_on_ragged_batches(kind):
-    from geossl_amd.pretrain_ChargePrediction import ChargePredictor
-    model, cp = _model(kind), fill_module_(ChargePredictor(128)).to(DEV)
-    batches = _ragged_batches(4, 24, 17)
+    model = backbone(kind)
+    heads = CASE.heads(kind, model)
+    batches = ragged_batches(4, 24, 17)
     if kind == "painn":
-        from geossl_amd import ops
-        for b in batches:
-            b.radius_edge_index = ops.radius_graph(b.positions, 5.0, b.batch)
-    sg = _replay_vs_eager(model, cp, kind, batches)
-    assert len(sg) == 1 and next(iter(sg.graphs))[0] == "bucket"
+        with_radius_edges(batches)
+    assert_one_bucket(replay_vs_eager(CASE, kind, model, heads, batches))
 
 
 @pytest.mark.parametrize("kind,mask_ratio", [("schnet", 0.0), ("painn", 0.0), ("schnet", 0.2)])
 def test_bucket_replay_matches_eager_on_device_loader(kind, mask_ratio):
     """DeviceLoader handles (with BFS atom masking: mask_ratio > 0) replay one one-view bucket graph per batch size."""
-    from geossl_amd.Geom3D.dataloaders import DeviceDataset, DeviceLoader
-    from geossl_amd.pretrain_ChargePrediction import ChargePredictor
     from geossl_amd.synthetic import add_bonds, make_molecules
     mols = make_molecules(200, seed=3, mode="C")
     if mask_ratio:
         mols = add_bonds(mols, seed=3, cut=0.3)
-    ds = DeviceDataset.from_numpy(mols, DEV, option="permutation", **({"radius": 5.0} if kind == "painn" else {}))
-    loader = DeviceLoader(ds, batch_size=32, shuffle=True, drop_last=True, generator=torch.Generator().manual_seed(2),
-                          mask_ratio=mask_ratio, mask_rng="device")
-    model, cp = _model(kind), fill_module_(ChargePredictor(128)).to(DEV)
-    sg = _replay_vs_eager(model, cp, kind, [hb for _, hb in zip(range(4), loader)])
-    assert len(sg) == 1 and next(iter(sg.graphs))[0] == "bucket"
+    model = backbone(kind)
+    handles = loader_handles(kind, dataset_kw={"mols": mols}, loader_kw={"mask_ratio": mask_ratio, "mask_rng": "device"})
+    assert_one_bucket(replay_vs_eager(CASE, kind, model, CASE.heads(kind, model), handles))
 
 
 def test_reference_loop_and_trainer_match_stock_adam():
     """Six steps of the reference loop (do_ChargePrediction, numpy masks, a stock torch.optim.Adam, graph replay) and of
     ChargePredictionTrainer (numpy masks, one bucket graph) against the same loop on eager launches."""
-    from geossl_amd.pretrain_ChargePrediction import (ChargePredictionTrainer, ChargePredictor,
-                                                      do_ChargePrediction)
-    args = types.SimpleNamespace(model_3d="schnet", charge_masking_ratio=0.3)
-
-    def ref_loop(graph):
-        m, c = _model("schnet"), fill_module_(ChargePredictor(128)).to(DEV)
-        opt = torch.optim.Adam([{"params": m.parameters(), "lr": 1e-4}, {"params": c.parameters(), "lr": 1e-4}],
-                               lr=1e-4)
-        np.random.seed(5)
-        losses = []
-        for b in _ragged_batches(6, 16, 5):
-            loss = do_ChargePrediction(args, b, m, c, graph=graph)
-            losses.append(float(loss.detach()))
-            opt.zero_grad()
-            loss.backward()
-            opt.step()
-        return losses, m, c
-
-    ref, m1, c1 = ref_loop(False)
-    rep, _, _ = ref_loop(True)
-    np.testing.assert_allclose(rep, ref, rtol=1e-4)
-    m2, c2 = _model("schnet"), fill_module_(ChargePredictor(128)).to(DEV)
-    tr = ChargePredictionTrainer(m2, c2, lr=1e-4, use_graph=True, charge_masking_ratio=0.3, mask_rng="numpy")
-    np.random.seed(5)
-    got = [float(tr.step(b)) for b in _ragged_batches(6, 16, 5)]
-    np.testing.assert_allclose(got, ref, rtol=1e-4)
-    assert rel_err(c2.predictor.weight.detach().cpu(), c1.predictor.weight.detach().cpu()) < 1e-4
-    assert rel_err(m2.lin2.weight.detach().cpu(), m1.lin2.weight.detach().cpu()) < 1e-4
-    assert len(tr.step_graphs) == 1 and next(iter(tr.step_graphs.graphs))[0] == "bucket"
+    reference_loop_vs_trainer(CASE, 6, 16, 5, per_step=False)
 
 
 @pytest.mark.parametrize("kind", ["schnet", "painn"])
@@ -448,7 +405,7 @@ def test_trainer_device_masks_over_a_loader_epoch(kind):
                                   **({"radius": 5.0} if kind == "painn" else {}))
     runs = []
     for _ in range(2):
-        tr = ChargePredictionTrainer(_model(kind), fill_module_(ChargePredictor(128)).to(DEV), lr=1e-4,
+        tr = ChargePredictionTrainer(backbone(kind), fill_module_(ChargePredictor(128)).to(DEV), lr=1e-4,
                                      model_3d=kind, use_graph=True, seed=99)
         loader = DeviceLoader(ds, batch_size=32, shuffle=True, drop_last=True,
                               generator=torch.Generator().manual_seed(4))
@@ -472,7 +429,7 @@ def test_allocator_poison_independence():
 
     def step(value):
         gc.collect()
-        model, cp = _model("schnet"), fill_module_(ChargePredictor(128)).to(DEV)
+        model, cp = backbone("schnet"), fill_module_(ChargePredictor(128)).to(DEV)
         if value is not None:
             poison(value)
         np.random.seed(meta["seed"])

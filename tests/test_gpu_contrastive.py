@@ -13,15 +13,13 @@ import torch
 
 import contrastive_twin as tw
 from conftest import load_golden, rel_err
-from helpers import fill_module_, product_schnet, t
+from helpers import fill_module_, t
+from objective_harness import backbone
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G17 = sorted(f[:-4] for f in os.listdir(os.path.join(REPO, "tests", "golden")) if f.startswith("g17_contrastive_"))
-SCHNET = dict(hidden_channels=128, num_filters=128, num_interactions=6, num_gaussians=51, cutoff=10.0, node_class=9,
-              readout="mean")
-PAINN = dict(n_atom_basis=128, n_interactions=3, n_rbf=20, cutoff=5.0, max_z=9, n_out=1, readout="add")
 
 
 def _reps(B, F, seed, normalize):
@@ -193,11 +191,6 @@ def test_g17_end_to_end(case):
 
 
 # ---------------------------------------------------------------------------------------------- graph paths
-def _model(kind):
-    from geossl_amd.Geom3D.models import PaiNN
-    return product_schnet(SCHNET, DEV) if kind == "schnet" else fill_module_(PaiNN(**PAINN)).to(DEV)
-
-
 def _batch(kind, B, seed):
     from geossl_amd import ops
     from geossl_amd import pretrain_GeoSSL as pg
@@ -217,7 +210,7 @@ def test_per_structure_graph_replay_equals_the_eager_step(kind, option):
     fn = pg.do_InfoNCE if option == "InfoNCE" else pg.do_EBM_NCE
     out = {}
     for graph in (False, True):
-        model = _model(kind)
+        model = backbone(kind)
         eng_runs = []
         for step in range(3):   # (graph: captured at the first step, replayed at the next two)
             noise = {"pos_noise": torch.randn(bt.positions.shape, generator=torch.Generator().manual_seed(50 + step)).mul_(0.3).to(DEV)}
@@ -266,7 +259,7 @@ def test_trainer_bucket_replay_on_a_shuffled_device_loader_equals_eager(option, 
     res = {}
     for use_graph in (False, True):
         torch.manual_seed(3)
-        model = _model(kind)
+        model = backbone(kind)
         tr = pg.ContrastiveTrainer(model, option=option, lr=5e-4, model_3d=kind, use_graph=use_graph, num_neg=2,
                                    normalize=option == "EBM_NCE", device_noise=True)
         hbs = _handles(ds, ratio)
@@ -295,7 +288,7 @@ def test_reference_entry_points_replay_a_bucket_on_device_loader_handles(option)
     args = types.SimpleNamespace(model_3d="schnet", normalize=True, T=0.1)
     out = {}
     for graph in (False, True):
-        model = _model("schnet")
+        model = backbone("schnet")
         params = [p for p in model.parameters() if p.requires_grad]
         hbs = _handles(ds, 0.3)
         runs = []
@@ -329,7 +322,7 @@ def test_reference_loop_graph_equals_eager(option):
     final = {}
     for graph in (False, True):
         torch.manual_seed(11)
-        model = _model("schnet")
+        model = backbone("schnet")
         opt = torch.optim.Adam(model.parameters(), lr=5e-4)
         sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, 2)
         args = types.SimpleNamespace(model_3d="schnet", normalize=False, T=0.1, step_graph=graph)
@@ -365,7 +358,7 @@ def test_step_reads_no_memory_it_has_not_written(option):
 
     def step(value):
         gc.collect()
-        model = _model("schnet")
+        model = backbone("schnet")
         if value is not None:
             poison(value)
         loss, acc = fn(args, bt, model, None, 0.0, 0.3, num_neg=2, noise=noise, graph=False)
@@ -400,7 +393,7 @@ def test_replayed_bucket_step_reads_no_memory_it_has_not_written(option):
 
     def steps(value):
         gc.collect()
-        model = _model("schnet")
+        model = backbone("schnet")
         params = [p for p in model.parameters() if p.requires_grad]
         res = []
         for _ in range(2):   # capture (+ replay), then a replay
@@ -429,7 +422,7 @@ def test_scaled_loss_scales_the_gradients(option, graph):
     noise = {"pos_noise": torch.randn(bt.positions.shape, generator=torch.Generator().manual_seed(6)).mul_(0.3).to(DEV)}
     args = types.SimpleNamespace(model_3d="schnet", normalize=False, T=0.1, step_graph_mode="structure")
     fn = pg.do_InfoNCE if option == "InfoNCE" else pg.do_EBM_NCE
-    model = _model("schnet")
+    model = backbone("schnet")
     params = [p for p in model.parameters() if p.requires_grad]
     loss, _ = fn(args, bt, model, None, 0.0, 0.3, noise=noise, graph=graph)
     g1 = torch.autograd.grad(loss, params, retain_graph=True, allow_unused=True)

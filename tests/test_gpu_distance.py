@@ -13,6 +13,8 @@ import torch
 import distance_twin as tw
 from conftest import load_golden, rel_err
 from helpers import fill_module_, grad_summary, t, unique_named_grads
+from objective_harness import (Case, assert_one_bucket, backbone, kind_args, loader_handles, ragged_batches,
+                               reference_loop_vs_trainer, replay_vs_eager, with_radius_edges)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -272,102 +274,47 @@ def test_fallbacks_match_the_twin():
 
 
 # ---------------------------------------------------------------------------------------------- graph paths
-def _ragged_batches(n, B, seed, option="permutation"):
-    from geossl_amd import pretrain_GeoSSL as pg
-    from geossl_amd.synthetic import collate_subset, make_batch
-    pool = make_batch(4 * B, seed=seed, mode="B", option=option)
-    rng = np.random.default_rng(seed)
-    return [pg.Batch.from_numpy(collate_subset(pool, rng.permutation(4 * B)[:B], option=option), DEV) for _ in range(n)]
+def _heads(kind, model):
+    from geossl_amd.pretrain_DistancePrediction import DistancePredictor
+    return [fill_module_(DistancePredictor(128)).to(DEV)]
+
+
+def _step(args, batch, model, heads, graph):
+    from geossl_amd.pretrain_DistancePrediction import do_DistancePrediction
+    return do_DistancePrediction(args, batch, model, heads[0], graph=graph), ()
+
+
+def _trainer(model, heads, **kw):
+    from geossl_amd.pretrain_DistancePrediction import DistancePredictionTrainer
+    return DistancePredictionTrainer(model, heads[0], **kw)
+
+
+CASE = Case("distance", "_geossl_distance_step", _heads, kind_args(), _step, _trainer,
+            head_weight=lambda heads: heads[0].predictor.weight)
 
 
 def test_trainer_bucket_replay_matches_reference_loop():
     """10 steps of DistancePredictionTrainer on shuffled ragged batches (no size sequence repeats) replay ONE one-view
     capacity-bucket graph, and match the reference loop on eager launches with a stock torch.optim.Adam step by step."""
-    from geossl_amd.Geom3D.models import SchNet
-    from geossl_amd.pretrain_DistancePrediction import (DistancePredictionTrainer, DistancePredictor,
-                                                        do_DistancePrediction)
-    cfg = dict(hidden_channels=128, num_filters=128, num_interactions=6, num_gaussians=51, cutoff=10.0, node_class=9)
-    batches = _ragged_batches(10, 16, 5)
-    assert len({tuple(b._sizes) for b in batches}) == 10
-    m1, d1 = fill_module_(SchNet(**cfg)).to(DEV), fill_module_(DistancePredictor(128)).to(DEV)
-    m2, d2 = fill_module_(SchNet(**cfg)).to(DEV), fill_module_(DistancePredictor(128)).to(DEV)
-    opt = torch.optim.Adam([{"params": m1.parameters(), "lr": 1e-4}, {"params": d1.parameters(), "lr": 1e-4}],
-                           lr=1e-4)
-    tr = DistancePredictionTrainer(m2, d2, lr=1e-4, use_graph=True)
-    args = types.SimpleNamespace(model_3d="schnet")
-    for k, b in enumerate(batches):
-        loss = do_DistancePrediction(args, b, m1, d1, graph=False)
-        opt.zero_grad()
-        loss.backward()
-        opt.step()
-        l2 = tr.step(b)
-        assert rel_err(l2.cpu(), loss.detach().cpu()) < 1e-4, k
-    assert rel_err(d2.predictor.weight.detach().cpu(), d1.predictor.weight.detach().cpu()) < 1e-4
-    assert rel_err(m2.lin2.weight.detach().cpu(), m1.lin2.weight.detach().cpu()) < 1e-4
-    # one graph for the batch size (a batch that outgrows the first bucket's capacity replaces it by a larger one)
-    assert len(tr.step_graphs) == 1 and 1 <= tr.step_graphs.captures <= 2
-    (key, g), = tr.step_graphs.graphs.items()
-    assert key[0] == "bucket" and g["bucket"].views == 1
-
-
-def _grads(model, dp):
-    return [p.grad.clone() for p in list(model.parameters()) + list(dp.parameters()) if p.grad is not None]
-
-
-def _replay_vs_eager(model, dp, kind, batches):
-    from geossl_amd.pretrain_DistancePrediction import do_DistancePrediction
-    args = types.SimpleNamespace(model_3d=kind)
-    for k, b in enumerate(batches):
-        out = []
-        for graph in (False, True):
-            model.zero_grad(set_to_none=True)
-            dp.zero_grad(set_to_none=True)
-            loss = do_DistancePrediction(args, b, model, dp, graph=graph)
-            loss.backward()
-            out.append((loss.detach().clone(), _grads(model, dp)))
-        assert rel_err(out[1][0].cpu(), out[0][0].cpu()) < 1e-6, (kind, k)
-        assert len(out[1][1]) == len(out[0][1])
-        for a, c in zip(out[1][1], out[0][1]):
-            assert rel_err(a, c) < 1e-5, (kind, k)
-    eng = model.__dict__["_geossl_distance_step"]
-    (sg,) = eng.graphs.values()
-    return sg
+    reference_loop_vs_trainer(CASE, 10, 16, 5, per_step=True)
 
 
 @pytest.mark.parametrize("kind", ["schnet", "painn"])
 def test_bucket_replay_matches_eager_on_ragged_batches(kind):
     """The reference loop's path (do_DistancePrediction -> _AutogradStep): shuffled ragged batches replay one one-view
     bucket graph, loss and every gradient as the eager launches give them."""
-    from geossl_amd.Geom3D.models import PaiNN, SchNet
-    from geossl_amd.pretrain_DistancePrediction import DistancePredictor
-    model = (fill_module_(SchNet(hidden_channels=128, num_filters=128, num_interactions=6, num_gaussians=51,
-                                 cutoff=10.0, node_class=9)) if kind == "schnet" else
-             fill_module_(PaiNN(n_atom_basis=128, n_interactions=3, n_rbf=20, cutoff=5.0, max_z=9, n_out=1,
-                               readout="add"))).to(DEV)
-    dp = fill_module_(DistancePredictor(128)).to(DEV)
-    batches = _ragged_batches(4, 24, 17)
+    model = backbone(kind)
+    heads = CASE.heads(kind, model)
+    batches = ragged_batches(4, 24, 17)
     if kind == "painn":
-        from geossl_amd import ops
-        for b in batches:
-            b.radius_edge_index = ops.radius_graph(b.positions, 5.0, b.batch)
-    sg = _replay_vs_eager(model, dp, kind, batches)
-    assert len(sg) == 1 and next(iter(sg.graphs))[0] == "bucket"
+        with_radius_edges(batches)
+    assert_one_bucket(replay_vs_eager(CASE, kind, model, heads, batches))
 
 
 @pytest.mark.parametrize("kind", ["schnet", "painn"])
 def test_bucket_replay_matches_eager_on_device_loader(kind):
     """DeviceLoader handles (gathered into the bucket on the device) replay one one-view bucket graph per batch size."""
-    from geossl_amd.Geom3D.dataloaders import DeviceDataset, DeviceLoader
-    from geossl_amd.Geom3D.models import PaiNN, SchNet
-    from geossl_amd.pretrain_DistancePrediction import DistancePredictor
-    from geossl_amd.synthetic import make_molecules
-    ds = DeviceDataset.from_numpy(make_molecules(200, seed=3, mode="C"), DEV, option="permutation",
-                                  **({"radius": 5.0} if kind == "painn" else {}))
-    loader = DeviceLoader(ds, batch_size=32, shuffle=True, drop_last=True, generator=torch.Generator().manual_seed(2))
-    model = (fill_module_(SchNet(hidden_channels=128, num_filters=128, num_interactions=6, num_gaussians=51,
-                                 cutoff=10.0, node_class=9)) if kind == "schnet" else
-             fill_module_(PaiNN(n_atom_basis=128, n_interactions=3, n_rbf=20, cutoff=5.0, max_z=9, n_out=1,
-                               readout="add"))).to(DEV)
-    dp = fill_module_(DistancePredictor(128)).to(DEV)
-    sg = _replay_vs_eager(model, dp, kind, [hb for _, hb in zip(range(4), loader)])
-    assert len(sg) == 1 and next(iter(sg.graphs))[0] == "bucket"
+    model = backbone(kind)
+    assert_one_bucket(replay_vs_eager(CASE, kind, model, CASE.heads(kind, model), loader_handles(kind)))
+
+

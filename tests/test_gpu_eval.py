@@ -12,6 +12,7 @@ import torch
 import eval_twin as et
 import lba_structures as ls
 from conftest import rel_err
+from objective_harness import backbone
 from test_gpu_lep import TOL_OUT
 from test_gpu_sparse_bucket import A, B_, TOL_LOSS
 
@@ -120,7 +121,7 @@ _MODULES = {}
 def _modules(kind):
     import test_gpu_supervised as sup
     if kind not in _MODULES:
-        model = sup._model(kind)
+        model = backbone(kind)
         _MODULES[kind] = (model, sup._head(kind, model))
     return _MODULES[kind]
 
@@ -193,7 +194,7 @@ def test_stale_rows_and_live_parameters():
     place - no new capture, the eager route's values under the new ones."""
     from geossl_amd.pretrain_Supervised import SupervisedTrainer
     import test_gpu_supervised as sup
-    model = sup._model("schnet")
+    model = backbone("schnet")
     head = sup._head("schnet", model)
     sizes = (33, 31, 32, 30, 33, 29, 32, 31) + (2, 3, 2, 4, 3, 2, 5, 2)
     loader, y = _dense_loader("schnet", sizes=sizes, T=1)
@@ -240,7 +241,7 @@ def _as_records(hb):
 def test_sparse_bucket_pockets(kind):
     import test_gpu_supervised as sup
     from geossl_amd.finetune_lba import eval_LBA, predict_LBA
-    model = sup._model(kind)        # (its own modules: the `dense` fixture keeps an evaluator on the shared ones)
+    model = backbone(kind)        # (its own modules: the `dense` fixture keeps an evaluator on the shared ones)
     head = sup._head(kind, model)
     loader, y = _pocket_loader(kind)
     args = _args(kind)
@@ -346,7 +347,7 @@ def test_fallbacks_inside_one_loader():
     cfg = dict(hidden_channels=64, num_filters=64, num_interactions=2, num_gaussians=8, cutoff=5.0, node_class=9)
     model = fill_module_(SchNet(**cfg)).to(DEV)
     head = fill_module_(torch.nn.Linear(64, 1)).to(DEV)
-    batches = sup._ragged_batches(9, 8, 31)
+    batches = sup._target_batches(9, 8, 31)
     b = batches[4]
     by_hand = pg.Batch(b.x, b.positions, b.batch, b.super_edge_index, num_graphs=8)
     by_hand.y = b.y

@@ -21,6 +21,7 @@ import torch
 
 import filter_twin as ft
 from test_gpu_packed_kernels import assert_sees_a_dropped_term, assert_within, pick_term
+from objective_harness import lib_loaded  # noqa: F401 (the autouse fixture)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -45,12 +46,6 @@ C_DPOS = 1.0
 CASES = [("main", F, G) for F in GRID_F for G in GRID_G] + [("edge", F, G) for F in GRID_F for G in GRID_G] + \
         [("deep", F, G) for F in GRID_F for G in DEEP_G] + \
         [(kind, F, G) for F in GRID_F for G in TINY_G for kind in ("tiny1", "tiny31")]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _lib_loaded():
-    from geossl_amd import _lib
-    _lib.load()
 
 
 WORST = {}

@@ -4,7 +4,6 @@
 eager, stock-Adam and trainer trajectories against the reference's ATen loop, and the ATen-free head."""
 import json
 import os
-import re
 import types
 
 import numpy as np
@@ -14,6 +13,8 @@ import torch
 import infograph_twin as tw
 from conftest import load_golden, rel_err
 from helpers import fill_module_, grad_summary, t, unique_named_grads
+from objective_harness import (Case, assert_one_bucket, assert_only_library_kernels, backbone, kind_args, loader_handles,
+                               ragged_batches, reference_loop_vs_trainer, replay_vs_eager, with_radius_edges)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -263,119 +264,61 @@ def test_fallbacks_match_aten():
 
 
 # ---------------------------------------------------------------------------------------------- graph paths
-def _ragged_batches(n, B, seed, option="permutation"):
-    from geossl_amd import pretrain_GeoSSL as pg
-    from geossl_amd.synthetic import collate_subset, make_batch
-    pool = make_batch(4 * B, seed=seed, mode="B", option=option)
-    rng = np.random.default_rng(seed)
-    return [pg.Batch.from_numpy(collate_subset(pool, rng.permutation(4 * B)[:B], option=option), DEV) for _ in range(n)]
-
-
-def _model(kind):
-    from geossl_amd.Geom3D.models import PaiNN, SchNet
-    return (fill_module_(SchNet(hidden_channels=128, num_filters=128, num_interactions=6, num_gaussians=51,
-                                cutoff=10.0, node_class=9)) if kind == "schnet" else
-            fill_module_(PaiNN(n_atom_basis=128, n_interactions=3, n_rbf=20, cutoff=5.0, max_z=9, n_out=1,
-                               readout="add"))).to(DEV)
-
-
-def _disc(F=128):
+def _heads(kind, model):
     from geossl_amd.pretrain_3DInfoGraph import Discriminator
-    return fill_module_(Discriminator(F)).to(DEV)
+    return [fill_module_(Discriminator(128)).to(DEV)]
 
 
-def _grads(model, disc):
-    return [p.grad.clone() for p in list(model.parameters()) + list(disc.parameters()) if p.grad is not None]
-
-
-def _replay_vs_eager(model, disc, kind, batches):
+def _step(args, batch, model, heads, graph):
     from geossl_amd.pretrain_3DInfoGraph import do_3DInfoGraph
-    args = types.SimpleNamespace(model_3d=kind)
-    for k, b in enumerate(batches):
-        out = []
-        for graph in (False, True):
-            model.zero_grad(set_to_none=True)
-            disc.zero_grad(set_to_none=True)
-            loss, acc = do_3DInfoGraph(args, b, model, disc, graph=graph)
-            loss.backward()
-            out.append((loss.detach().clone(), acc, _grads(model, disc)))
-        assert rel_err(out[1][0].cpu(), out[0][0].cpu()) < 1e-6, (kind, k)
-        assert out[1][1] == out[0][1], (kind, k)
-        assert len(out[1][2]) == len(out[0][2])
-        for a, c in zip(out[1][2], out[0][2]):
-            assert rel_err(a, c) < 1e-5, (kind, k)
-    eng = model.__dict__["_geossl_infograph_step"]
-    (sg,) = eng.graphs.values()
-    return sg
+    loss, acc = do_3DInfoGraph(args, batch, model, heads[0], graph=graph)
+    return loss, (acc,)
+
+
+def _aten_step(args, b, model, heads):
+    from geossl_amd.pretrain_3DInfoGraph import _infograph_aten
+    mr, nr = model(b.x[:, 0], b.positions, b.batch, return_latent=True)
+    loss, acc = _infograph_aten(nr, mr, b, torch.nn.BCEWithLogitsLoss(), heads[0])
+    return loss, (acc,)
+
+
+def _trainer(model, heads, **kw):
+    from geossl_amd.pretrain_3DInfoGraph import InfoGraphTrainer
+    return InfoGraphTrainer(model, heads[0], **kw)
+
+
+CASE = Case("infograph", "_geossl_infograph_step", _heads, kind_args(), _step, _trainer, aten_step=_aten_step,
+            head_weight=lambda heads: heads[0].weight, loss_of=lambda out: out[0])
 
 
 @pytest.mark.parametrize("kind", ["schnet", "painn"])
 def test_bucket_replay_matches_eager_on_ragged_batches(kind):
-    model, disc = _model(kind), _disc()
-    batches = _ragged_batches(4, 24, 17)
+    model = backbone(kind)
+    heads = CASE.heads(kind, model)
+    batches = ragged_batches(4, 24, 17)
     if kind == "painn":
-        from geossl_amd import ops
-        for b in batches:
-            b.radius_edge_index = ops.radius_graph(b.positions, 5.0, b.batch)
-    sg = _replay_vs_eager(model, disc, kind, batches)
-    assert len(sg) == 1 and next(iter(sg.graphs))[0] == "bucket" and sg.views == 1
+        with_radius_edges(batches)
+    assert_one_bucket(replay_vs_eager(CASE, kind, model, heads, batches), views=CASE.views)
 
 
 @pytest.mark.parametrize("kind", ["schnet", "painn"])
 def test_bucket_replay_matches_eager_on_device_loader(kind):
-    from geossl_amd.Geom3D.dataloaders import DeviceDataset, DeviceLoader
-    from geossl_amd.synthetic import make_molecules
-    ds = DeviceDataset.from_numpy(make_molecules(200, seed=3, mode="C"), DEV, option="permutation",
-                                  **({"radius": 5.0} if kind == "painn" else {}))
-    loader = DeviceLoader(ds, batch_size=32, shuffle=True, drop_last=True, generator=torch.Generator().manual_seed(2))
-    sg = _replay_vs_eager(_model(kind), _disc(), kind, [hb for _, hb in zip(range(4), loader)])
-    assert len(sg) == 1 and next(iter(sg.graphs))[0] == "bucket"
+    model = backbone(kind)
+    assert_one_bucket(replay_vs_eager(CASE, kind, model, CASE.heads(kind, model), loader_handles(kind)))
 
 
 def test_reference_loop_and_trainer_match_stock_adam():
     """Six steps of the reference loop with do_3DInfoGraph (graph replay, stock torch.optim.Adam over the reference's two
     groups) and of InfoGraphTrainer (one bucket graph) against the reference's ATen loop body on our backbone."""
-    from geossl_amd.pretrain_3DInfoGraph import InfoGraphTrainer, _infograph_aten, do_3DInfoGraph
-    args = types.SimpleNamespace(model_3d="schnet")
-    crit = torch.nn.BCEWithLogitsLoss()
-
-    def ref_loop(fused):
-        m, d = _model("schnet"), _disc()
-        opt = torch.optim.Adam([{"params": m.parameters(), "lr": 1e-4}, {"params": d.parameters(), "lr": 1e-4}],
-                               lr=1e-4)
-        losses, accs = [], []
-        for b in _ragged_batches(6, 16, 5):
-            if fused:
-                loss, acc = do_3DInfoGraph(args, b, m, d, graph=True)
-            else:
-                mr, nr = m(b.x[:, 0], b.positions, b.batch, return_latent=True)
-                loss, acc = _infograph_aten(nr, mr, b, crit, d)
-            losses.append(float(loss.detach()))
-            accs.append(acc)
-            opt.zero_grad()
-            loss.backward()
-            opt.step()
-        return losses, accs, m, d
-
-    ref, ref_acc, m1, d1 = ref_loop(False)
-    rep, rep_acc, _, _ = ref_loop(True)
-    np.testing.assert_allclose(rep, ref, rtol=1e-4)
-    np.testing.assert_allclose(rep_acc, ref_acc, atol=0.02)
-    m2, d2 = _model("schnet"), _disc()
-    tr = InfoGraphTrainer(m2, d2, lr=1e-4, use_graph=True)
-    got = [tr.step(b) for b in _ragged_batches(6, 16, 5)]
-    np.testing.assert_allclose([float(l) for l, _ in got], ref, rtol=1e-4)
-    assert all(c.dtype == torch.int32 and c.numel() == 2 for _, c in got)
-    assert rel_err(d2.weight.detach().cpu(), d1.weight.detach().cpu()) < 1e-4
-    assert rel_err(m2.lin2.weight.detach().cpu(), m1.lin2.weight.detach().cpu()) < 1e-4
-    assert len(tr.step_graphs) == 1 and next(iter(tr.step_graphs.graphs))[0] == "bucket"
+    r = reference_loop_vs_trainer(CASE, 6, 16, 5, per_step=False)
+    np.testing.assert_allclose([acc for acc, in r.rep_extras], [acc for acc, in r.ref_extras], atol=0.02)
+    assert all(c.dtype == torch.int32 and c.numel() == 2 for _, c in r.trainer_out)
 
 
 def test_head_launches_no_aten_arithmetic():
     """The head's forward and backward (as a replayed step captures them) call no floating-point ATen operator and
     launch only the library's kernels."""
-    from torch.profiler import ProfilerActivity, profile
-    from geossl_amd import _lib, ops
+    from geossl_amd import ops
     from geossl_amd.layout import get_layout
     x, W, _, batch, _ = _inputs([5, 18, 2, 9, 1, 12], 128, 31)
     lay = get_layout(batch.to(DEV))
@@ -383,20 +326,5 @@ def test_head_launches_no_aten_arithmetic():
     Wd = W.to(DEV).requires_grad_()
     Wd.grad = torch.zeros_like(Wd)
     one = torch.ones((), device=DEV)
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        with _lib.direct_grads():
-            loss, _ = ops.infograph_head(xd, Wd, lay, "mean")
-            loss.backward(one)
-        torch.cuda.synchronize()
-    allowed = {"aten::empty", "aten::empty_like", "aten::empty_strided", "aten::to", "aten::_to_copy", "aten::detach",
-               "detach", "aten::contiguous", "aten::slice", "aten::as_strided", "aten::view", "aten::lift_fresh",
-               "aten::alias", "aten::resize_", "aten::copy_"}
-    names = {e.name for e in prof.events() if e.name.startswith("aten::")}
-    assert names <= allowed, names - allowed
-    kernels = {e.name for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA
-               and "memcpy" not in e.name.lower() and "memset" not in e.name.lower()}
-    ours = lambda n: re.match(r"(void )?(geossl::)?k_\w+", n.replace("(anonymous namespace)::", "")) is not None
-    others = sorted(n for n in kernels if not ours(n) or "at::" in n)
-    assert kernels and not others, others
+    assert_only_library_kernels(lambda: ops.infograph_head(xd, Wd, lay, "mean")[0].backward(one))
     assert torch.isfinite(xd.grad).all() and torch.isfinite(Wd.grad).all()

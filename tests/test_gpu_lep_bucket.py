@@ -15,6 +15,7 @@ import torch
 import lba_structures as ls
 import lep_twin as lt
 from conftest import rel_err
+from objective_harness import backbone
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -64,9 +65,8 @@ def _batch(pair_sizes, seed=0):
 
 
 def _modules():
-    import test_gpu_supervised as sup
     from helpers import fill_module_
-    model = sup._model("schnet")
+    model = backbone("schnet")
     head = fill_module_(torch.nn.Linear(256, 1)).to(DEV)
     with torch.no_grad():
         head.weight.mul_(0.05)   # (logits of order one with the filler's weights: no sigmoid saturates)

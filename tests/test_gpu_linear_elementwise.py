@@ -25,6 +25,7 @@ import torch
 
 import linear_twin as tw
 from elementwise import assert_repeatable, assert_sees_a_dropped_term, assert_within
+from objective_harness import lib_loaded  # noqa: F401 (the autouse fixture)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -35,12 +36,6 @@ K_SPLIT, K_F32 = (32, 64, 128), (8, 24, 56, 200, 256)
 ROWS_SMALL = {"split": (1, 31, 32, 33, 129), "fp32": (1, 33, 97, 128, 129)}
 ROWS_SPLIT_LARGE = (32768, 32769, 32833, 65536, 65569)
 WIDTH_AT_LARGE = {32: 100, 64: 256, 128: 160}        # one width per K at the large row counts
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _lib_loaded():
-    from geossl_amd import _lib
-    _lib.load()
 
 
 WORST = {}

@@ -13,6 +13,7 @@ import torch
 
 import filter_twin as ft
 from test_gpu_packed_kernels import assert_within
+from objective_harness import lib_loaded  # noqa: F401 (the autouse fixture)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -22,12 +23,6 @@ U22, U24 = 2.0 ** -22, 2.0 ** -24
 C_BWD = 8.0                         # |got - ref| <= c u S of the filter backward (tests/test_gpu_filter_classes.py)
 SIZES = [1, 2, 18, 3, 33, 18, 2]    # 839 pair slots; molecule 1 is stretched (no live pair), molecule 3 squeezed (all live)
 SIZES_CAPPED = [1, 2, 40, 3, 33, 18, 2]   # a 40-atom molecule: the general geometry kernel (neighbour cap, bit matrix)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _lib_loaded():
-    from geossl_amd import _lib
-    _lib.load()
 
 
 # ------------------------------------------------------------------------------------------------------------ geometry

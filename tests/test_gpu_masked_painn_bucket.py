@@ -9,15 +9,10 @@ import torch
 
 from conftest import load_golden, rel_err
 from helpers import fill_module_, product_ncsn
+from objective_harness import lib_loaded  # noqa: F401 (the autouse fixture)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _lib_loaded():
-    from geossl_amd import _lib
-    _lib.load()
 
 
 def _painn():
@@ -367,17 +362,17 @@ def test_charge_prediction_on_masked_painn_handles_replays_one_bucket_graph():
     """test_gpu_charge's bucket-replay-against-eager pattern (numpy charge masks, 1e-6 / 1e-5) for the case its
     parametrisation stops short of: ("painn", 0.2) - masked PaiNN handles on a one-view bucket."""
     from geossl_amd.Geom3D.dataloaders import DeviceDataset, DeviceLoader
-    from geossl_amd.pretrain_ChargePrediction import ChargePredictor
     from geossl_amd.synthetic import add_bonds, make_molecules
-    from test_gpu_charge import _model, _replay_vs_eager
+    from objective_harness import assert_one_bucket, backbone, replay_vs_eager
+    from test_gpu_charge import CASE
     mols = add_bonds(make_molecules(200, seed=3, mode="C"), seed=3, cut=0.3)
     ds = DeviceDataset.from_numpy(mols, DEV, option="permutation", radius=5.0)
     np.random.seed(8)
     loader = DeviceLoader(ds, batch_size=32, shuffle=True, drop_last=True, generator=torch.Generator().manual_seed(2),
                           mask_ratio=0.2, mask_rng="device")
-    model, cp = _model("painn"), fill_module_(ChargePredictor(128)).to(DEV)
-    sg = _replay_vs_eager(model, cp, "painn", [hb for _, hb in zip(range(4), loader)])
-    assert len(sg) == 1 and next(iter(sg.graphs))[0] == "bucket"
+    model = backbone("painn")
+    sg = replay_vs_eager(CASE, "painn", model, CASE.heads("painn", model), [hb for _, hb in zip(range(4), loader)])
+    assert_one_bucket(sg)
     (g,) = sg.graphs.values()
     assert g["bucket"].views == 1 and g["bucket"].real_E is None and int(g["bucket"].ecap_status.word) == 0
 

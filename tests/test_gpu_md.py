@@ -11,6 +11,7 @@ import force_twin as tw
 import md_twin as mt
 from md_cases import (CASES, DT, LANGEVIN, N_ATOMS, NORMALS_SEED, STEPS, T0, THERMOSTAT_SEED, _cfg, _raw, _twin_cfg,
                       device_batch, device_modules, module_snapshot as _snapshot)
+from objective_harness import lib_loaded  # noqa: F401 (the autouse fixture)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -22,12 +23,6 @@ def _modules(kind, cfg):
 
 def _batch(kind, cfg, raw):
     return device_batch(kind, cfg, raw, DEV)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _lib_loaded():
-    from geossl_amd import _lib
-    _lib.load()
 
 
 # ------------------------------------------------------------------------------------------------ kernels alone

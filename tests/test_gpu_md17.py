@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import force_twin as tw
+from objective_harness import lib_loaded  # noqa: F401 (the autouse fixture)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -17,12 +18,6 @@ SCHNET_MD17 = dict(hidden_channels=128, num_filters=128, num_interactions=6, num
 PAINN_MD17 = dict(n_atom_basis=128, n_interactions=3, n_rbf=20, cutoff=5.0, max_z=9, n_out=1, readout="add")
 N_ATOMS = 21
 HEAD_TOL = 2e-5   # test_gpu_supervised.py::test_head_kernels_vs_fp64: the same arithmetic against fp64
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _lib_loaded():
-    from geossl_amd import _lib
-    _lib.load()
 
 
 # ------------------------------------------------------------------------------------------------------------ plumbing

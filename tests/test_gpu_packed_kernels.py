@@ -28,16 +28,11 @@ from elementwise import (REPEATS, assert_repeatable, assert_sees_a_dropped_term,
                          pick_term)
 from filter_twin import _filter_ref_and_bound  # noqa: E402
 from ncsn_twin import KEYS as _NCSN_KEYS, _ncsn_ref_and_bound  # noqa: E402
+from objective_harness import lib_loaded  # noqa: F401 (the autouse fixture)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 U22, U24 = 2.0 ** -22, 2.0 ** -24
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _lib_loaded():
-    from geossl_amd import _lib
-    _lib.load()
 
 
 # ------------------------------------------------------------------------------------------------------------- helpers

@@ -21,18 +21,13 @@ import painn_mma_case as hc
 import painn_tile_twin as tw
 from elementwise import assert_repeatable, assert_sees_a_dropped_term, assert_within, pick_term
 from helpers import t
+from objective_harness import lib_loaded  # noqa: F401 (the autouse fixture)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 NAN = float("nan")
 F = 128
 INVALID = 1   # hipErrorInvalidValue
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _lib_loaded():
-    from geossl_amd import _lib
-    _lib.load()
 
 
 def _ptr(x):

@@ -17,6 +17,7 @@ import torch
 
 import lba_structures as ls
 import painn_inc_twin as itw
+from objective_harness import backbone
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -194,7 +195,7 @@ def switch_on(monkeypatch):
 
 def _painn():
     import test_gpu_supervised as sup
-    model = sup._model("painn")
+    model = backbone("painn")
     return model, sup._head("painn", model)
 
 
@@ -328,9 +329,8 @@ LEP_B = ((260, 40, 17, 3), (1, 5, 64, 3))
 
 
 def _lep_modules():
-    import test_gpu_supervised as sup
     from helpers import fill_module_
-    model = sup._model("painn")
+    model = backbone("painn")
     head = fill_module_(torch.nn.Linear(256, 1)).to(DEV)
     with torch.no_grad():
         head.weight.mul_(0.05)   # (logits of order one with the filler's weights: no sigmoid saturates)
@@ -404,7 +404,7 @@ def test_switch_table_and_what_keeps_its_route(monkeypatch):
     assert sg.bucket_key(bare.batch([0, 5, 6, 7])) is None
     # SchNet's sparse bucket is not this switch's
     import test_gpu_supervised as sup
-    schnet = sup._model("schnet")
+    schnet = backbone("schnet")
     from geossl_amd.pretrain_Supervised import SupervisedTrainer
     ssg = SupervisedTrainer(schnet, sup._head("schnet", schnet), 0.0, 1.0, task_id=0, loss="mse", use_graph=True).step_graphs
     assert ssg.bucket_key(b) is None and ssg.bucket_key(hb) == key

@@ -10,15 +10,10 @@ import force_twin as tw
 import relax_cases as rc
 import relax_twin as rt
 from md_cases import N_ATOMS, _cfg, _raw, device_batch, device_modules, module_snapshot as _snapshot
+from objective_harness import lib_loaded  # noqa: F401 (the autouse fixture)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _lib_loaded():
-    from geossl_amd import _lib
-    _lib.load()
 
 
 def _np(t):

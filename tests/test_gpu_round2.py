@@ -14,6 +14,7 @@ import torch
 from conftest import assert_close, load_golden, max_abs_rel, rel_err
 from helpers import (cfg_of, grad_summary, ncsn_oracle_params, product_ncsn, product_schnet, schnet_oracle_params, t,
                      unique_named_grads)
+from objective_harness import lib_loaded  # noqa: F401 (the autouse fixture)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -22,12 +23,6 @@ FULL = dict(hidden_channels=128, num_filters=128, num_interactions=6, num_gaussi
             readout="mean")
 PAINN = dict(n_atom_basis=128, n_interactions=3, n_rbf=20, cutoff=5.0, max_z=9, n_out=1, readout="add")
 NOISE_KEYS = ("pos_noise", "noise_level_1", "dist_noise_1", "noise_level_2", "dist_noise_2")
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _lib_loaded():
-    from geossl_amd import _lib
-    _lib.load()
 
 
 # ------------------------------------------------------------------------------------------------ RCCL, one rank

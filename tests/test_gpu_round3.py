@@ -13,6 +13,7 @@ import torch
 
 from conftest import rel_err
 from helpers import product_ncsn, product_schnet, t, unique_named_grads
+from objective_harness import lib_loaded  # noqa: F401 (the autouse fixture)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -21,12 +22,6 @@ FULL = dict(hidden_channels=128, num_filters=128, num_interactions=6, num_gaussi
             readout="mean")
 SMALL = dict(hidden_channels=128, num_filters=128, num_interactions=2, num_gaussians=51, cutoff=5.0, node_class=9,
              readout="mean")
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _lib_loaded():
-    from geossl_amd import _lib
-    _lib.load()
 
 
 def _reference_loop(graph, steps, batches, cfg=SMALL, seed=11):

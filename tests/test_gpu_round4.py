@@ -11,6 +11,7 @@ import torch
 
 from conftest import rel_err
 from helpers import ncsn_oracle_params, product_ncsn, product_schnet, schnet_oracle_params, t, unique_named_grads
+from objective_harness import lib_loaded  # noqa: F401 (the autouse fixture)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -20,12 +21,6 @@ FULL = dict(hidden_channels=128, num_filters=128, num_interactions=6, num_gaussi
 SMALL = dict(hidden_channels=128, num_filters=128, num_interactions=2, num_gaussians=51, cutoff=5.0, node_class=9,
              readout="mean")
 TOL_OUT, TOL_GRAD = 1e-5, 1e-4
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _lib_loaded():
-    from geossl_amd import _lib
-    _lib.load()
 
 
 def _ragged_sizes(B, seed, lo=2, hi=33):

@@ -10,6 +10,7 @@ import torch
 
 from conftest import rel_err
 from helpers import product_ncsn, product_schnet, t
+from objective_harness import lib_loaded  # noqa: F401 (the autouse fixture)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -18,12 +19,6 @@ FULL = dict(hidden_channels=128, num_filters=128, num_interactions=6, num_gaussi
             readout="mean")
 SMALL = dict(hidden_channels=128, num_filters=128, num_interactions=2, num_gaussians=51, cutoff=5.0, node_class=9,
              readout="mean")
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _lib_loaded():
-    from geossl_amd import _lib
-    _lib.load()
 
 
 def _ragged_sizes(B, seed, lo=2, hi=33, mean=18.0, sd=4.0):

@@ -29,18 +29,13 @@ import torch
 
 import row_twin as tw
 from elementwise import assert_repeatable, assert_sees_a_dropped_term, assert_within, flagged
+from objective_harness import lib_loaded  # noqa: F401 (the autouse fixture)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 NAN_BITS = 0x7FC00000
 GUARD = 8
 SENTINEL = -0x12345678            # as a float about -8e27: no sum of the tests' terms
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _lib_loaded():
-    from geossl_amd import _lib
-    _lib.load()
 
 
 WORST = {}

@@ -11,6 +11,7 @@ import torch
 import lba_structures as ls
 from conftest import rel_err
 from helpers import t
+from objective_harness import backbone, replay_vs_eager
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -48,7 +49,7 @@ def _batch(sizes, seed=0, T=1):
 
 def _modules():
     import test_gpu_supervised as sup
-    model = sup._model("schnet")
+    model = backbone("schnet")
     return model, sup._head("schnet", model)
 
 
@@ -270,7 +271,7 @@ def test_do_supervised_takes_the_same_route(collated):
     import test_gpu_supervised as sup
     model, head = _modules()
     batches = [_batch(C_, T=3), _batch(A, T=3)]
-    sg = sup._replay_vs_eager(model, head, "schnet", batches, task=2, loss="mse")
+    sg = replay_vs_eager(sup._case(0.25, 1.5, task=2, loss="mse"), "schnet", model, [head], batches)
     assert len(sg) == 1 and next(iter(sg.graphs))[:1] + next(iter(sg.graphs))[2:] == ("bucket", "sparse")
 
 
@@ -329,7 +330,7 @@ def test_other_steps_keep_their_routing(collated):
     ddm = pg.DDMTrainer(model, product_ncsn(128, 50, 2, DEV), product_ncsn(128, 50, 2, DEV, scale=0.9), use_graph=True)
     for tr in (dist, ddm):
         assert tr.step_graphs.pair_tuples and tr.step_graphs.bucket_key(b) is None
-    painn = sup._model("painn")
+    painn = backbone("painn")
     from geossl_amd.pretrain_Supervised import SupervisedTrainer
     ptr_ = SupervisedTrainer(painn, sup._head("painn", painn), 0.0, 1.0, task_id=0, loss="mse", model_3d="painn",
                              use_graph=True)

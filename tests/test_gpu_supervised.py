@@ -6,7 +6,6 @@ eager on collated batches and DeviceLoader handles with targets, stock-Adam and 
 reference's ATen loop, and the ATen-free head."""
 import json
 import os
-import re
 import types
 
 import numpy as np
@@ -16,6 +15,9 @@ import torch
 import supervised_twin as tw
 from conftest import load_golden, rel_err
 from helpers import fill_module_, grad_summary, t, unique_named_grads
+from objective_harness import (Case, assert_one_bucket, assert_only_library_kernels, backbone, device_batch, kind_args,
+                               loader_handles, ragged_batches, reference_loop_vs_trainer, replay_vs_eager,
+                               with_radius_edges)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -269,25 +271,14 @@ def test_g14_finetune_qm9_through_the_trainer():
 
 
 # ---------------------------------------------------------------------------------------------- graph paths
-def _ragged_batches(n, B, seed, T=4, option="permutation"):
-    from geossl_amd import pretrain_GeoSSL as pg
-    from geossl_amd.synthetic import collate_subset, make_batch
-    pool = make_batch(4 * B, seed=seed, mode="B", option=option)
-    rng = np.random.default_rng(seed)
-    out = []
-    for _ in range(n):
-        b = pg.Batch.from_numpy(collate_subset(pool, rng.permutation(4 * B)[:B], option=option), DEV)
-        b.y = torch.from_numpy(rng.standard_normal(B * T).astype(np.float32)).to(DEV)
-        out.append(b)
-    return out
+def _with_targets(collated, rng, T=4):
+    b = device_batch(collated)
+    b.y = torch.from_numpy(rng.standard_normal(len(collated["sizes"]) * T).astype(np.float32)).to(DEV)
+    return b
 
 
-def _model(kind):
-    from geossl_amd.Geom3D.models import PaiNN, SchNet
-    return (fill_module_(SchNet(hidden_channels=128, num_filters=128, num_interactions=6, num_gaussians=51,
-                                cutoff=10.0, node_class=9)) if kind == "schnet" else
-            fill_module_(PaiNN(n_atom_basis=128, n_interactions=3, n_rbf=20, cutoff=5.0, max_z=9, n_out=1,
-                               readout="add"))).to(DEV)
+def _target_batches(n, B, seed):
+    return ragged_batches(n, B, seed, decorate=_with_targets)
 
 
 def _head(kind, model):
@@ -295,59 +286,46 @@ def _head(kind, model):
             fill_module_(model.create_output_layers())).to(DEV)
 
 
-def _grads(model, head):
-    return [p.grad.clone() for p in list(model.parameters()) + list(head.parameters()) if p.grad is not None]
+def _case(mean, std, task, loss="mae"):
+    from geossl_amd.pretrain_Supervised import SupervisedTrainer, do_Supervised, supervised_step_aten
 
+    def step(args, b, model, heads, graph):
+        return do_Supervised(args, b, model, heads[0], mean, std, task_id=task, graph=graph), ()
 
-def _replay_vs_eager(model, head, kind, batches, task=2, loss="mae"):
-    from geossl_amd.pretrain_Supervised import do_Supervised
-    args = types.SimpleNamespace(model_3d=kind, loss=loss)
-    for k, b in enumerate(batches):
-        out = []
-        for graph in (False, True):
-            model.zero_grad(set_to_none=True)
-            head.zero_grad(set_to_none=True)
-            lo = do_Supervised(args, b, model, head, 0.25, 1.5, task_id=task, graph=graph)
-            lo.backward()
-            out.append((lo.detach().clone(), _grads(model, head)))
-        assert rel_err(out[1][0].cpu(), out[0][0].cpu()) < 1e-6, (kind, k)
-        assert len(out[1][1]) == len(out[0][1])
-        for a, c in zip(out[1][1], out[0][1]):
-            assert rel_err(a, c) < 1e-5, (kind, k)
-    eng = model.__dict__["_geossl_supervised_step"]
-    (sg,) = eng.graphs.values()
-    return sg
+    def aten_step(args, b, model, heads):
+        crit = {"mae": torch.nn.L1Loss, "mse": torch.nn.MSELoss}[loss]()
+        return supervised_step_aten(args, b, model, heads[0], mean, std, task, crit), ()
+
+    def trainer(model, heads, **kw):
+        return SupervisedTrainer(model, heads[0], mean, std, task_id=task, loss=loss, **kw)
+
+    return Case("supervised", "_geossl_supervised_step", lambda kind, model: [_head(kind, model)], kind_args(loss=loss),
+                step, trainer, aten_step=aten_step, head_weight=lambda heads: heads[0].weight, batches=_target_batches)
 
 
 @pytest.mark.parametrize("kind", ["schnet", "painn"])
 def test_bucket_replay_matches_eager_on_ragged_batches(kind):
-    model = _model(kind)
-    head = _head(kind, model)
-    batches = _ragged_batches(4, 24, 17)
+    case = _case(0.25, 1.5, task=2, loss="mse" if kind == "painn" else "mae")
+    model = backbone(kind)
+    heads = case.heads(kind, model)
+    batches = _target_batches(4, 24, 17)
     if kind == "painn":
-        from geossl_amd import ops
-        for b in batches:
-            b.radius_edge_index = ops.radius_graph(b.positions, 5.0, b.batch)
-    sg = _replay_vs_eager(model, head, kind, batches, loss="mse" if kind == "painn" else "mae")
-    assert len(sg) == 1 and next(iter(sg.graphs))[0] == "bucket" and sg.views == 1
+        with_radius_edges(batches)
+    assert_one_bucket(replay_vs_eager(case, kind, model, heads, batches), views=case.views)
 
 
 @pytest.mark.parametrize("kind", ["schnet", "painn"])
 def test_bucket_replay_matches_eager_on_device_loader(kind):
     """DeviceLoader handles of a dataset that carries y: the target column is gathered per batch on the device, over a
     shuffled epoch; DatasetBatch.y is the reference's collation."""
-    from geossl_amd.Geom3D.dataloaders import DeviceDataset, DeviceLoader
-    from geossl_amd.synthetic import make_molecules
-    mols = make_molecules(200, seed=3, mode="C")
     y = np.random.default_rng(4).standard_normal((200, 5)).astype(np.float32)
-    ds = DeviceDataset.from_numpy(mols, DEV, option="permutation", y=y, **({"radius": 5.0} if kind == "painn" else {}))
-    loader = DeviceLoader(ds, batch_size=32, shuffle=True, drop_last=True, generator=torch.Generator().manual_seed(2))
-    hbs = [hb for _, hb in zip(range(4), loader)]
+    hbs = loader_handles(kind, dataset_kw={"y": y})
     for hb in hbs:
         assert torch.equal(hb.y.cpu(), torch.from_numpy(y[hb.ids]).reshape(-1))
-    model = _model(kind)
-    sg = _replay_vs_eager(model, _head(kind, model), kind, hbs, task=3)
-    assert len(sg) == 1 and next(iter(sg.graphs))[0] == "bucket"
+    case = _case(0.25, 1.5, task=3)
+    model = backbone(kind)
+    sg = replay_vs_eager(case, kind, model, case.heads(kind, model), hbs)
+    assert_one_bucket(sg)
     # the static target column of the graph holds the last batch's column
     (gg,) = sg.graphs.values()
     assert torch.equal(gg["noise"]["target"].cpu(), torch.from_numpy(y[hbs[-1].ids, 3]))
@@ -363,45 +341,15 @@ def test_dataset_without_targets_has_no_y():
 def test_reference_loop_and_trainer_match_stock_adam():
     """Six steps of the reference loop with do_Supervised (graph replay, stock torch.optim.Adam over the reference's two
     groups) and of SupervisedTrainer (one bucket graph) against the reference's ATen lines on our backbone."""
-    from geossl_amd.pretrain_Supervised import SupervisedTrainer, do_Supervised, supervised_step_aten
-    args = types.SimpleNamespace(model_3d="schnet", loss="mae")
-
-    def ref_loop(fused):
-        m = _model("schnet")
-        hd = _head("schnet", m)
-        opt = torch.optim.Adam([{"params": m.parameters(), "lr": 1e-4}, {"params": hd.parameters(), "lr": 1e-4}],
-                               lr=1e-4)
-        losses = []
-        for b in _ragged_batches(6, 16, 5):
-            if fused:
-                loss = do_Supervised(args, b, m, hd, 0.1, 1.2, task_id=1, graph=True)
-            else:
-                loss = supervised_step_aten(args, b, m, hd, 0.1, 1.2, 1, torch.nn.L1Loss())
-            losses.append(float(loss.detach()))
-            opt.zero_grad()
-            loss.backward()
-            opt.step()
-        return losses, m, hd
-
-    ref, m1, h1 = ref_loop(False)
-    rep, _, _ = ref_loop(True)
-    np.testing.assert_allclose(rep, ref, rtol=1e-4)
-    m2 = _model("schnet")
-    h2 = _head("schnet", m2)
-    tr = SupervisedTrainer(m2, h2, 0.1, 1.2, task_id=1, loss="mae", lr=1e-4, use_graph=True)
-    got = [tr.step(b) for b in _ragged_batches(6, 16, 5)]
-    np.testing.assert_allclose([float(l) for l in got], ref, rtol=1e-4)
-    assert rel_err(h2.weight.detach().cpu(), h1.weight.detach().cpu()) < 1e-4
-    assert rel_err(m2.lin2.weight.detach().cpu(), m1.lin2.weight.detach().cpu()) < 1e-4
-    assert len(tr.step_graphs) == 1 and next(iter(tr.step_graphs.graphs))[0] == "bucket"
+    reference_loop_vs_trainer(_case(0.1, 1.2, task=1), 6, 16, 5, per_step=False)
 
 
 def test_stats_change_without_recapture():
     """(mean, std) are read from device memory: new values change the replayed loss, with one capture."""
     from geossl_amd.pretrain_Supervised import do_Supervised
-    model = _model("schnet")
+    model = backbone("schnet")
     head = _head("schnet", model)
-    b = _ragged_batches(1, 16, 8)[0]
+    b = _target_batches(1, 16, 8)[0]
     args = types.SimpleNamespace(model_3d="schnet", loss="mse")
     out = []
     for mean, std in ((0.0, 1.0), (0.5, 2.0)):
@@ -418,8 +366,7 @@ def test_stats_change_without_recapture():
 def test_head_launches_no_aten_arithmetic():
     """The head's forward and backward (as a replayed step captures them) call no floating-point ATen operator and
     launch only the library's kernels."""
-    from torch.profiler import ProfilerActivity, profile
-    from geossl_amd import _lib, ops
+    from geossl_amd import ops
     from geossl_amd.layout import get_layout
     for mlp in (False, True):
         h, ps, y, sizes, task = _inputs([5, 18, 2, 9, 1, 12], 128, mlp, 31)
@@ -432,22 +379,7 @@ def test_head_launches_no_aten_arithmetic():
         yd = y.to(DEV)[:, task]
         stats = torch.tensor([0.2, 1.1], device=DEV)
         one = torch.ones((), device=DEV)
-        torch.cuda.synchronize()
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            with _lib.direct_grads():
-                loss, _ = ops.property_head(hd, pd, lay, "mean", yd, stats, "mae")
-                loss.backward(one)
-            torch.cuda.synchronize()
-        allowed = {"aten::empty", "aten::empty_like", "aten::empty_strided", "aten::to", "aten::_to_copy",
-                   "aten::detach", "detach", "aten::contiguous", "aten::slice", "aten::as_strided", "aten::view",
-                   "aten::lift_fresh", "aten::alias", "aten::resize_", "aten::copy_"}
-        names = {e.name for e in prof.events() if e.name.startswith("aten::")}
-        assert names <= allowed, names - allowed
-        kernels = {e.name for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA
-                   and "memcpy" not in e.name.lower() and "memset" not in e.name.lower()}
-        ours = lambda n: re.match(r"(void )?(geossl::)?k_\w+", n.replace("(anonymous namespace)::", "")) is not None
-        others = sorted(n for n in kernels if not ours(n) or "at::" in n)
-        assert kernels and not others, others
+        assert_only_library_kernels(lambda: ops.property_head(hd, pd, lay, "mean", yd, stats, "mae")[0].backward(one))
         assert torch.isfinite(hd.grad).all() and all(torch.isfinite(p.grad).all() for p in pd)
 
 
@@ -460,7 +392,7 @@ def test_fallbacks_match_aten_and_checkpoints_load():
     from geossl_amd.pretrain_Supervised import (SupervisedTrainer, do_Supervised, predict_Supervised,
                                                 supervised_step_aten)
     args = types.SimpleNamespace(model_3d="schnet", loss="mae")
-    b = _ragged_batches(1, 12, 23)[0]
+    b = _target_batches(1, 12, 23)[0]
     for F, crit in ((48, torch.nn.L1Loss()), (64, torch.nn.HuberLoss())):
         cfg = dict(hidden_channels=F, num_filters=F, num_interactions=2, num_gaussians=8, cutoff=5.0, node_class=9)
         model = fill_module_(SchNet(**cfg)).to(DEV)
@@ -468,16 +400,16 @@ def test_fallbacks_match_aten_and_checkpoints_load():
         got = do_Supervised(args, b, model, head, 0.3, 1.4, task_id=2, criterion=crit)
         ref = supervised_step_aten(args, b, model, head, 0.3, 1.4, 2, crit)
         assert torch.equal(got.detach(), ref.detach()), F
-    model = _model("schnet")
+    model = backbone("schnet")
     head = _head("schnet", model)
     tr = SupervisedTrainer(model, head, 0.3, 1.4, task_id=2, lr=1e-4)
-    for bb in _ragged_batches(3, 12, 24):
+    for bb in _target_batches(3, 12, 24):
         tr.step(bb)
     buf = io.BytesIO()
     torch.save({"model": model.state_dict(), "graph_pred_linear": head.state_dict()}, buf)
     buf.seek(0)
     ck = torch.load(buf)
-    m2 = _model("schnet")
+    m2 = backbone("schnet")
     h2 = _head("schnet", m2)
     m2.load_state_dict(ck["model"])
     h2.load_state_dict(ck["graph_pred_linear"])

@@ -13,16 +13,11 @@ import torch
 
 from conftest import load_golden, rel_err
 from helpers import cfg_of, fill_module_, product_schnet, t
+from objective_harness import lib_loaded  # noqa: F401 (the autouse fixture)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 TOL_GRAD = 1e-4   # the suite's bound for second-order gradients (fixtures G10 / G13); the routes agree to 1e-5 .. 3e-5
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _lib_loaded():
-    from geossl_amd import _lib
-    _lib.load()
 
 
 def _rand(*shape, seed=0, scale=1.0):

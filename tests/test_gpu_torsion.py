@@ -3,6 +3,7 @@ NaN-poisoned outputs (static and `_dyn` forms, full and sampled lists, a 255-ato
 the angle kernel against the fp64 twin, the reference's edge cases against ATen, determinism, fixture G23 through
 do_TorsionAnglePrediction, the fallbacks, and the replayed step against the eager one and against the reference loop
 with a stock torch.optim.Adam."""
+import itertools
 import json
 import os
 import types
@@ -14,6 +15,8 @@ import torch
 import torsion_twin as tw
 from conftest import load_golden, rel_err
 from helpers import fill_module_, grad_summary, t, unique_named_grads
+from objective_harness import (Case, assert_one_bucket, backbone, kind_args, loader_handles, ragged_batches,
+                               reference_loop_vs_trainer, replay_vs_eager, with_radius_edges)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -348,92 +351,59 @@ def _triple_batch(d, ratio, seed):
     return pg.TripleBatch.from_numpy(dd, DEV)
 
 
-def _ragged_batches(n, B, seed, ratio=0.01, ratios=None):
-    from geossl_amd.synthetic import collate_subset, make_batch
-    pool = make_batch(4 * B, seed=seed, mode="B")
-    rng = np.random.default_rng(seed)
-    return [_triple_batch(collate_subset(pool, rng.permutation(4 * B)[:B]), ratios[k] if ratios else ratio, seed + k)
-            for k in range(n)]
+def _triple_batches(n, B, seed, ratio=0.01, ratios=None):
+    """Batch k draws its triples under np.random.seed(seed + k), at ratios[k] where given."""
+    k = itertools.count()
+
+    def with_triples(collated, rng):
+        i = next(k)
+        return _triple_batch(collated, ratios[i] if ratios else ratio, seed + i)
+    return ragged_batches(n, B, seed, option="combination", decorate=with_triples)
+
+
+def _heads(kind, model):
+    from geossl_amd.pretrain_TorsionAnglePrediction import TorsionAnglePredictor
+    return [fill_module_(TorsionAnglePredictor(128)).to(DEV)]
+
+
+def _step(args, batch, model, heads, graph):
+    from geossl_amd.pretrain_TorsionAnglePrediction import do_TorsionAnglePrediction
+    return do_TorsionAnglePrediction(args, batch, model, heads[0], graph=graph), ()
+
+
+def _trainer(model, heads, **kw):
+    from geossl_amd.pretrain_TorsionAnglePrediction import TorsionAnglePredictionTrainer
+    return TorsionAnglePredictionTrainer(model, heads[0], **kw)
+
+
+CASE = Case("torsion", "_geossl_torsion_step", _heads, kind_args(), _step, _trainer,
+            head_weight=lambda heads: heads[0].predictor.weight, batches=_triple_batches)
+
+
+def _modules(kind):
+    model = backbone(kind)
+    return model, CASE.heads(kind, model)
 
 
 def test_trainer_bucket_replay_matches_reference_loop():
     """10 steps of TorsionAnglePredictionTrainer on shuffled ragged batches (no size sequence repeats, T differs) replay
     ONE one-view capacity-bucket graph, and match the reference loop on eager launches with a stock torch.optim.Adam
     step by step."""
-    from geossl_amd.Geom3D.models import SchNet
-    from geossl_amd.pretrain_TorsionAnglePrediction import (TorsionAnglePredictionTrainer, TorsionAnglePredictor,
-                                                            do_TorsionAnglePrediction)
-    cfg = dict(hidden_channels=128, num_filters=128, num_interactions=6, num_gaussians=51, cutoff=10.0, node_class=9)
-    batches = _ragged_batches(10, 16, 5)
-    assert len({tuple(b._sizes) for b in batches}) == 10
-    assert len({int(b.super_edge_index.size(1)) for b in batches}) > 5
-    m1, d1 = fill_module_(SchNet(**cfg)).to(DEV), fill_module_(TorsionAnglePredictor(128)).to(DEV)
-    m2, d2 = fill_module_(SchNet(**cfg)).to(DEV), fill_module_(TorsionAnglePredictor(128)).to(DEV)
-    opt = torch.optim.Adam([{"params": m1.parameters(), "lr": 1e-4}, {"params": d1.parameters(), "lr": 1e-4}],
-                           lr=1e-4)
-    tr = TorsionAnglePredictionTrainer(m2, d2, lr=1e-4, use_graph=True)
-    args = types.SimpleNamespace(model_3d="schnet")
-    for k, b in enumerate(batches):
-        loss = do_TorsionAnglePrediction(args, b, m1, d1, graph=False)
-        opt.zero_grad()
-        loss.backward()
-        opt.step()
-        l2 = tr.step(b)
-        assert rel_err(l2.cpu(), loss.detach().cpu()) < 1e-4, k
-    assert rel_err(d2.predictor.weight.detach().cpu(), d1.predictor.weight.detach().cpu()) < 1e-4
-    assert rel_err(m2.lin2.weight.detach().cpu(), m1.lin2.weight.detach().cpu()) < 1e-4
-    # one graph for the batch size (a batch that outgrows the first bucket's capacity replaces it by a larger one)
-    assert len(tr.step_graphs) == 1 and 1 <= tr.step_graphs.captures <= 2
-    (key, g), = tr.step_graphs.graphs.items()
-    assert key[0] == "bucket" and g["bucket"].views == 1
-
-
-def _grads(model, tp):
-    return [p.grad.clone() for p in list(model.parameters()) + list(tp.parameters()) if p.grad is not None]
-
-
-def _replay_vs_eager(model, tp, kind, batches):
-    from geossl_amd.pretrain_TorsionAnglePrediction import do_TorsionAnglePrediction
-    args = types.SimpleNamespace(model_3d=kind)
-    for k, b in enumerate(batches):
-        out = []
-        for graph in (False, True):
-            model.zero_grad(set_to_none=True)
-            tp.zero_grad(set_to_none=True)
-            loss = do_TorsionAnglePrediction(args, b, model, tp, graph=graph)
-            loss.backward()
-            out.append((loss.detach().clone(), _grads(model, tp)))
-        assert rel_err(out[1][0].cpu(), out[0][0].cpu()) < 1e-6, (kind, k)
-        assert len(out[1][1]) == len(out[0][1])
-        for a, c in zip(out[1][1], out[0][1]):
-            assert rel_err(a, c) < 1e-5, (kind, k)
-    eng = model.__dict__["_geossl_torsion_step"]
-    (sg,) = eng.graphs.values()
-    return sg
-
-
-def _models(kind):
-    from geossl_amd.Geom3D.models import PaiNN, SchNet
-    from geossl_amd.pretrain_TorsionAnglePrediction import TorsionAnglePredictor
-    model = (fill_module_(SchNet(hidden_channels=128, num_filters=128, num_interactions=6, num_gaussians=51,
-                                 cutoff=10.0, node_class=9)) if kind == "schnet" else
-             fill_module_(PaiNN(n_atom_basis=128, n_interactions=3, n_rbf=20, cutoff=5.0, max_z=9, n_out=1,
-                               readout="add"))).to(DEV)
-    return model, fill_module_(TorsionAnglePredictor(128)).to(DEV)
+    r = reference_loop_vs_trainer(CASE, 10, 16, 5, per_step=True)
+    assert len({int(b.super_edge_index.size(1)) for b in r.batches}) > 5
 
 
 @pytest.mark.parametrize("kind", ["schnet", "painn"])
 def test_bucket_replay_matches_eager_on_ragged_batches(kind):
     """The reference loop's path (do_TorsionAnglePrediction -> _AutogradStep): shuffled ragged batches replay one one-view
     bucket graph, loss and every gradient as the eager launches give them."""
-    model, tp = _models(kind)
-    batches = _ragged_batches(4, 24, 17)
+    model, heads = _modules(kind)
+    batches = _triple_batches(4, 24, 17)
     if kind == "painn":
-        from geossl_amd import ops
-        for b in batches:
-            b.radius_edge_index = ops.radius_graph(b.positions, 5.0, b.batch)
-    sg = _replay_vs_eager(model, tp, kind, batches)
-    assert len(sg) == 1 and next(iter(sg.graphs))[0] == "bucket" and sg.captures == 1
+        with_radius_edges(batches)
+    sg = replay_vs_eager(CASE, kind, model, heads, batches)
+    assert_one_bucket(sg)
+    assert sg.captures == 1
 
 
 def test_reference_loader_flow_replays_one_bucket_graph():
@@ -453,20 +423,21 @@ def test_reference_loader_flow_replays_one_bucket_graph():
         recs.append(d)
     batches = [b.to(DEV) for b in DataLoaderAtomTriple(recs, batch_size=16, shuffle=False)]
     assert len(batches) == 4 and all(isinstance(b, BatchAtomTriple) and b.super_edge_index.is_cuda for b in batches)
-    model, tp = _models("schnet")
-    sg = _replay_vs_eager(model, tp, "schnet", batches)
-    assert len(sg) == 1 and next(iter(sg.graphs))[0] == "bucket" and sg.captures == 1
+    model, heads = _modules("schnet")
+    sg = replay_vs_eager(CASE, "schnet", model, heads, batches)
+    assert_one_bucket(sg)
+    assert sg.captures == 1
 
 
 def test_bucket_recaptures_when_the_triples_outgrow_it():
     """A batch whose T exceeds the first bucket's triple capacity is served by a larger bucket and still matches eager."""
-    model, tp = _models("schnet")
-    batches = _ragged_batches(4, 24, 19, ratios=[0.002, 0.002, 0.2, 0.002])
+    model, heads = _modules("schnet")
+    batches = _triple_batches(4, 24, 19, ratios=[0.002, 0.002, 0.2, 0.002])
     T = [int(b.super_edge_index.size(1)) for b in batches]
-    sg = _replay_vs_eager(model, tp, "schnet", batches[:2])
+    sg = replay_vs_eager(CASE, "schnet", model, heads, batches[:2])
     (g,) = sg.graphs.values()
     assert T[2] > g["bucket"].T_cap >= max(T[:2]) and sg.captures == 1
-    sg = _replay_vs_eager(model, tp, "schnet", batches[2:])
+    sg = replay_vs_eager(CASE, "schnet", model, heads, batches[2:])
     (g,) = sg.graphs.values()
     assert len(sg) == 1 and sg.captures == 2 and g["bucket"].T_cap >= T[2]
 
@@ -487,8 +458,7 @@ def test_bucket_replay_matches_eager_on_device_loader(kind):
     glob = ds.triples[:, :int(ds.triple_cnt.sum())].long() + torch.from_numpy(
         np.repeat(off[:-1], ds.triple_cnt)).to(DEV)[None]
     assert torch.equal(ds.triple_angle[:glob.size(1)], ops.triple_angles(ds.positions, glob))
-    loader = DeviceLoader(ds, batch_size=32, shuffle=True, drop_last=True, generator=torch.Generator().manual_seed(2))
-    handles = [hb for _, hb in zip(range(4), loader)]
+    handles = loader_handles(kind, dataset=ds)
     for hb in handles[:2]:   # host collation of the same molecules
         recs = []
         for i in hb.ids:
@@ -505,9 +475,9 @@ def test_bucket_replay_matches_eager_on_device_loader(kind):
         assert torch.equal(hb.x.cpu(), want.x) and torch.equal(hb.batch.cpu(), want.batch)
     with pytest.raises(ValueError):
         DeviceLoader(ds, batch_size=32, mask_ratio=0.15)
-    model, tp = _models(kind)
-    sg = _replay_vs_eager(model, tp, kind, handles)
-    assert len(sg) == 1 and next(iter(sg.graphs))[0] == "bucket"
+    model, heads = _modules(kind)
+    sg = replay_vs_eager(CASE, kind, model, heads, handles)
+    assert_one_bucket(sg)
     (g,) = sg.graphs.values()
     # the bucket's static triples are the handle's own (refreshed by geossl_gather_triples)
     hb, bkt = handles[-1], g["bucket"]

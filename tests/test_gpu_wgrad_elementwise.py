@@ -23,6 +23,7 @@ import torch
 
 import wgrad_twin as tw
 from elementwise import assert_repeatable, assert_sees_a_dropped_term, assert_within
+from objective_harness import lib_loaded  # noqa: F401 (the autouse fixture)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -41,12 +42,6 @@ WIDTHS_ABI = [(36, 100), (100, 36), (4, 124), (60, 128)]
 def rows_256(nprob):
     """The smallest row count of a launch of `nprob` >= 2 problems with chunk = 256, plus a partial tile of one row."""
     return 256 * (-(-256 // nprob) - 1) + 33
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _lib_loaded():
-    from geossl_amd import _lib
-    _lib.load()
 
 
 WORST = {}
