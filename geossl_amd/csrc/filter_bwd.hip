@@ -6,9 +6,10 @@
 // and, with t the saved hidden activation and rbf the Gaussian smearing of d_p,
 //     dt = dO W2 ;  dU = dt * ssp'(.) ;  dW1 += dU^T rbf ;  db1 += sum dU ;  dW2 += dO^T t ;  db2 += sum dO.
 //
-// A block works on 32-row tiles of pair slots.  A tile touches the atoms of at most a few molecules, so rows
-// a_lo.. of x_l and dagg_l are staged in LDS with coalesced 16-byte loads (double buffered: the staging arrays of tile
-// t+1 are published during the MFMA phase of tile t, two barriers per tile); from them the block builds, pre-split
+// A block works on tiles of pair slots: 32 rows in the three-piece kernel, 64 rows (two 32-row M blocks behind one
+// build phase and one barrier pair) in the two-piece kernel.  A tile touches the atoms of at most a few molecules, so rows
+// a_lo.. of x_l and dagg_l are staged in LDS with coalesced 16-byte loads (the staging arrays of tile t+1 are published
+// during the MFMA phase of tile t, two barriers per tile); from them the block builds, pre-split
 // into bf16 pieces and laid out as ready-made MFMA fragments (lane i at byte 16 i: conflict-free ds_read_b128),
 //     dOr : dO as A operand with the pair row on M and the channel c on K      (for dt = dO W2; one lane per thread)
 //     rbf : Gaussian smearing as B operand with the pair row on K              (for dW1 = dU^T rbf; role-B threads)
@@ -29,6 +30,12 @@
 #include "rbf_frag.h"
 #include "split.h"
 #include "tn.h"
+
+// atoms a staged window of a 64-row tile holds (tools/filter_bwd_window_share.py: fewer fresh windows per row than 40 atoms
+// under a 32-row tile, no unstaged tile on the bench pools; 64 atoms = 64 staging registers per role-B lane: spilled)
+#ifndef FB_CAP64
+#define FB_CAP64 48
+#endif
 
 using namespace geossl;
 
@@ -511,35 +518,47 @@ __global__ __launch_bounds__(128 * NW) void k_filter_bwd(const float* __restrict
 #else
 #define FBH_MARK(slot) do {} while (0)
 #endif
-template <int F>
+// TR: pair rows per tile, 32 or 64.  A 64-row tile is two 32-row M blocks (SUB = 2) with ONE build phase, ONE barrier pair
+// and ONE set of per-tile bookkeeping (descriptors, window decision, operand exponents); every fragment array holds the
+// 32-row layout once per M block.
+template <int F, int TR>
 struct BwdLdsH {
   static constexpr int AS = F + 4;  // staged atom row stride (16-byte aligned rows)
-  static constexpr int KC = F / 16, CB = F / 32;
-  u32x4* dOr;    // [KC][2][64]
-  u32x4* tf;     // [CB][2][2][64]  t fragments: hidden-unit block x k-step x piece
-  u32x4* rbf;    // [2][2][2][64]
+  static constexpr int KC = F / 16, CB = F / 32, SUB = TR / 32;
+  static constexpr int CAP = TR == 64 ? FB_CAP64 : ATOM_CAP;  // atoms staged per window
+  static constexpr int DOR_WORDS = KC * 2 * 64, TF_WORDS = CB * 2 * 2 * 64, RBF_WORDS = RBF_TILE_WORDS;  // per M block
+  u32x4* dOr;    // [SUB][KC][2][64]
+  u32x4* tf;     // [SUB][CB][2][2][64]  t fragments: hidden-unit block x k-step x piece
+  u32x4* rbf;    // [SUB][2][2][2][64]
   int* et;       // [CB] running exponent of each role-A wave's t fragments; [CB] = scratch word of the unstaged path
   float* offs;   // [64] Gaussian centres, zero padded (the role-A waves rebuild the hidden row from them when T is not saved)
-  // staging arrays, double buffered (buffer t & 1 serves tile t): written during the MFMA phase of tile t-1, read
-  // only by the build of tile t
-  static constexpr int STAGE_FLOATS = 2 * ATOM_CAP * AS + TR + 4 * TR + 4 + 8;  // xs, ds, tdd, desc (int4), flags, window maxima
-  float* stage0;
-  __device__ float* xs(int b) const { return stage0 + b * STAGE_FLOATS; }                       // [ATOM_CAP][AS]
-  __device__ float* ds(int b) const { return xs(b) + ATOM_CAP * AS; }                            // [ATOM_CAP][AS]
-  __device__ float* tdd(int b) const { return ds(b) + ATOM_CAP * AS; }                           // [TR] distances
+  // The atom window, ONE buffer: written (when a tile gets a fresh window) during the MFMA phase of tile t-1, i.e. after
+  // the barrier that ends the build of tile t-1 - the last reader of the window it replaces - and read only by the build
+  // of tile t, after the barrier that opens it.
+  float* xs;     // [CAP][AS]
+  float* ds;     // [CAP][AS]
+  float* wmax;   // [CB][2] max |x|, max |dagg| of the window
+  // the small per-tile arrays, double buffered (buffer t & 1 serves tile t)
+  static constexpr int TILE_FLOATS = TR + 4 * TR + 4;  // tdd, desc (int4), flags
+  float* tile0;
+  __device__ float* tdd(int b) const { return tile0 + b * TILE_FLOATS; }                          // [TR] distances
   // [TR] {offset of atom i, of atom j (LDS floats if staged, else atom index), C*flag0, C*flag1}
   __device__ int4* desc(int b) const { return reinterpret_cast<int4*>(tdd(b) + TR); }
   __device__ int* flag(int b) const { return reinterpret_cast<int*>(desc(b) + TR); }             // [0] = window fits
-  __device__ float* wmax(int b) const { return reinterpret_cast<float*>(flag(b) + 4); }          // [CB][2] max |x|, max |dagg| of the window
   __device__ explicit BwdLdsH(uint8_t* smem) {
     dOr = reinterpret_cast<u32x4*>(smem);
-    tf = dOr + KC * 2 * 64;
-    rbf = tf + CB * 2 * 2 * 64;
-    et = reinterpret_cast<int*>(rbf + 2 * 2 * 2 * 64);
+    tf = dOr + SUB * DOR_WORDS;
+    rbf = tf + SUB * TF_WORDS;
+    et = reinterpret_cast<int*>(rbf + SUB * RBF_WORDS);
     offs = reinterpret_cast<float*>(et + 8);
-    stage0 = offs + 64;
+    xs = offs + 64;
+    ds = xs + CAP * AS;
+    wmax = ds + CAP * AS;
+    tile0 = wmax + 8;
   }
-  static size_t bytes() { return (size_t)(KC * 2 + CB * 4 + 8) * 1024 + 32 + 256 + (size_t)2 * STAGE_FLOATS * 4; }
+  static constexpr size_t bytes() {
+    return (size_t)SUB * (DOR_WORDS + TF_WORDS + RBF_WORDS) * 16 + 32 + 256 + (size_t)(2 * CAP * AS + 8 + 2 * TILE_FLOATS) * 4;
+  }
 };
 
 // RECOMP: T == nullptr - the hidden row t = ssp(W1 rbf(d) + b1) is not read back from HBM (the forward did not store it:
@@ -552,7 +571,7 @@ struct BwdLdsH {
 // fragments are not built here - the same words for every layer of the launch - but copied from the per-step image
 // (rbf_frag.h, k_rbf_fragments): a role-B lane requests the two 16-byte words of its item of the NEXT tile at the start
 // of a tile's MFMA phase and stores them to L.rbf where the build stores them otherwise.
-template <int NW, bool ROLE_A, bool RECOMP>
+template <int NW, bool ROLE_A, bool RECOMP, int TR>
 __device__ __forceinline__ void filter_bwd_body_h(const float* __restrict__ pair_d, const float* __restrict__ pair_c,
                                                 const uint8_t* __restrict__ pair_flag,
                                                 const int32_t* __restrict__ pair_i,
@@ -563,11 +582,14 @@ __device__ __forceinline__ void filter_bwd_body_h(const float* __restrict__ pair
                                                 float* __restrict__ partial_b1, float* __restrict__ partial_w2,
                                                 float* __restrict__ partial_b2, int Pstride,
                                                 const u32x4* __restrict__ img) {
-  constexpr int F = 32 * NW, NT = 128 * NW, KC = F / 16, CB = F / 32, AS = BwdLdsH<F>::AS, Q = F / 4;
-  static_assert(TR * (F / 8) == NT, "one dOr fragment lane per thread");
-  static_assert(TR == RBF_TILE_ROWS && RBF_TILE_ITEMS % (64 * NW) == 0, "whole items per role-B lane");
+  using Lds = BwdLdsH<32 * NW, TR>;
+  constexpr int F = 32 * NW, NT = 128 * NW, KC = F / 16, CB = F / 32, AS = Lds::AS, Q = F / 4, SUB = Lds::SUB, CAP = Lds::CAP;
+  static_assert(TR == 32 || TR == 64, "one or two 32-row M blocks per tile");
+  static_assert(Lds::bytes() <= 160 * 1024, "fragments of all M blocks + one atom window in the LDS of a CU");
+  static_assert(32 * (F / 8) == NT, "one dOr fragment lane per thread and M block");
+  static_assert(RBF_TILE_ROWS == 32 && RBF_TILE_ITEMS % (64 * NW) == 0, "whole items per role-B lane, one image tile per M block");
   extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
-  const BwdLdsH<F> L(smem_raw);
+  const Lds L(smem_raw);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, kh = lane >> 5;
   constexpr bool roleA = ROLE_A;
   const int hs = roleA ? wave : wave - NW;  // hidden-unit slice [32 hs, 32 hs + 32)
@@ -671,44 +693,42 @@ __device__ __forceinline__ void filter_bwd_body_h(const float* __restrict__ pair
   // the saved activations by every wave for its own hidden unit.  `alo` = first atom of a tile's window
   // (= pair_i[r0]: pair slots are lexicographic inside a molecule) is fetched two tiles ahead.
   constexpr int NTB = 64 * NW;                              // staging threads (role B)
-  constexpr int NPRE = (ATOM_CAP * Q + NTB - 1) / NTB;      // float4 per staging thread and array
+  constexpr int NPRE = (CAP * Q + NTB - 1) / NTB;           // float4 per staging thread and array
   const int stid = tid - NTB;                               // role B: 0 .. NTB-1
   f32x4 px[roleA ? 1 : NPRE], pdg[roleA ? 1 : NPRE];
   int ai = 0, aj = 0;
   float cval = 0.0f, dd = 0.0f;
   unsigned fl_raw = 0u;
-  float tc[16];
+  float tc[SUB][16];
   // The staged window is STICKY: it stays as long as the next tile's atoms still fall inside it (pair slots are
   // lexicographic, so a window that starts at some atom of a molecule serves the rest of that molecule and the next one) -
   // about nine tiles in ten of 18-atom molecules neither fetch nor store a window.  Every wave takes the decision itself
-  // from the same values: the second atoms of the tile's rows (ajn, fetched one tile before the decision) and the state
-  // wab = buffer holding the window, walo = its first atom.  The decision of a tile is taken when its requests are
-  // issued and kept (dec_*) until the tile is published one iteration later.
+  // from the same values: the second atoms of the tile's rows (ajn, fetched one tile before the decision; a lane per row of
+  // a 64-row tile, a lane pair per row of a 32-row one) and the state walo = the window's first atom.  The decision of a
+  // tile is taken when its requests are issued and kept (dec_*) until the tile is published one iteration later.
   int ajn = 0;
-  int wab = 0, walo = 0;
+  int walo = 0;
   bool whave = false;
   bool dec_staged = false, dec_fresh = false;
-  int dec_alo = 0, dec_wab = 0;
+  int dec_alo = 0;
   auto decide = [&](int alo_t) {
     const int amax = wave_max_i32(ajn + 1);
-    const bool fits = whave && alo_t >= walo && amax - walo <= ATOM_CAP;
-    dec_fresh = !fits && amax - alo_t <= ATOM_CAP;
+    const bool fits = whave && alo_t >= walo && amax - walo <= CAP;
+    dec_fresh = !fits && amax - alo_t <= CAP;
     if (dec_fresh) {
-      wab ^= 1;
       walo = alo_t;
       whave = true;
     }
     dec_staged = fits || dec_fresh;
     dec_alo = walo;
-    dec_wab = wab;
   };
-  auto request_rows = [&](int tt) { ajn = pair_j[min(tt * TR + j, P - 1)]; };
+  auto request_rows = [&](int tt) { ajn = pair_j[min(tt * TR + (lane & (TR - 1)), P - 1)]; };
   auto request_atoms = [&](int tt, int alo_t) {  // role B: window of x / dagg rows of tile tt (if it gets a new one); role A: its row descriptors
     if constexpr (!roleA) {
       if (!dec_fresh) return;
       // clamped addresses, no predication (a predicated load compiles to a branch with a full wait per element);
       // slots past the window are never read back
-      const int nwin = min(ATOM_CAP, N - alo_t);
+      const int nwin = min(CAP, N - alo_t);
       const f32x4* x4 = reinterpret_cast<const f32x4*>(x + (size_t)alo_t * F);
       const f32x4* d4 = reinterpret_cast<const f32x4*>(dagg + (size_t)alo_t * F);
 #pragma unroll
@@ -730,31 +750,34 @@ __device__ __forceinline__ void filter_bwd_body_h(const float* __restrict__ pair
   };
   // saved hidden activation of this lane's hidden unit: role A in C layout (register r <-> row c_row(r)), role B in
   // B-fragment layout (k-step s, element e <-> row 16s + 8kh + e); rows past P are clamped (their dO is 0)
-  float dreq = 0.0f;  // RECOMP: distance of this lane's pair row of the tile whose hidden rows are rebuilt next
-  auto request_t = [&](int tt) {
+  float dreq[SUB];  // RECOMP: distance of this lane's pair row of the tile whose hidden rows are rebuilt next, per M block
+#pragma unroll
+  for (int sb = 0; sb < SUB; ++sb) dreq[sb] = 0.0f;
+  auto request_t = [&](int tt, int sb) {  // M block sb of tile tt
     if constexpr (roleA && !RECOMP) {
-      const int rr0 = tt * TR;
-      if (rr0 + TR <= P) {
-        // a whole tile: row c_row(r) = (r & 3) + 8 (r >> 2) + 4 kh - register r is a constant number of rows behind the
+      const int rr0 = tt * TR + 32 * sb;
+      if (rr0 + 32 <= P) {
+        // a whole M block: row c_row(r) = (r & 3) + 8 (r >> 2) + 4 kh - register r is a constant number of rows behind the
         // lane's first row, so the sixteen requests share four bases and carry their offsets as immediates (as sixteen
         // clamped per-lane addresses they were ~50 vector instructions of a role-A wave's ~400 per tile)
         const float* tb = Tl + (size_t)(rr0 + 4 * kh) * F + tcol;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) tc[r] = tb[((r & 3) + 8 * (r >> 2)) * F];
+        for (int r = 0; r < 16; ++r) tc[sb][r] = tb[((r & 3) + 8 * (r >> 2)) * F];
       } else {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) tc[r] = Tl[(uint32_t)min(rr0 + c_row(r, lane), P - 1) * (uint32_t)F + tcol];
+        for (int r = 0; r < 16; ++r) tc[sb][r] = Tl[(uint32_t)min(rr0 + c_row(r, lane), P - 1) * (uint32_t)F + tcol];
       }
     }
-    if constexpr (roleA && RECOMP) dreq = pair_d[min(tt * TR + j, P - 1)];
+    if constexpr (roleA && RECOMP) dreq[sb] = pair_d[min(tt * TR + 32 * sb + j, P - 1)];
   };
   // RECOMP: the hidden rows of a tile for this wave's units, u = rbf(d) W1^T + b1, t = ssp(u) (schnet.py:141-145,205-207),
   // into tc.  A operand = the Gaussians of row j (8 per k-step and half) built in registers - every role-A wave its own
   // copy, one per SIMD.  Runs at the END of the wave's MFMA phase for the NEXT tile: role A finishes that phase first
   // and would wait at the barrier (in-kernel marks: 2 k of a tile's 8.7 k cycles); inside the build phase, where the
   // hidden rows are consumed, it sat on the tile's critical path (0.85 -> 0.99 ms per launch).
-  auto rebuild_t = [&](float dj) {
+  auto rebuild_t = [&](int sb) {
     if constexpr (roleA && RECOMP) {
+      const float dj = dreq[sb];
       f32x16 au;
 #pragma unroll
       for (int r = 0; r < 16; ++r) au[r] = 0.0f;
@@ -775,25 +798,33 @@ __device__ __forceinline__ void filter_bwd_body_h(const float* __restrict__ pair
         au = mfma_f16(a.h, bw1[ks].h, au);
       }
 #pragma unroll
-      for (int r = 0; r < 16; ++r) tc[r] = ssp(fmaf(au[r], inv1, b1v));
+      for (int r = 0; r < 16; ++r) tc[sb][r] = ssp(fmaf(au[r], inv1, b1v));
     }
   };
-  // IMG, role B: the words of this lane's items of tile tt's Gaussian fragments, from the image
+  // IMG, role B: the words of this lane's items of tile tt's Gaussian fragments, from the image.  The image keeps its
+  // 32-row tiles: M block sb of tile tt is image tile SUB tt + sb; the last image tile stands in for an M block that
+  // lies past the capacity altogether (all its rows are past P: dO exactly zero, the words only have to be finite).
   constexpr bool IMG = !RECOMP;  // (the form that rebuilds the hidden rows keeps its own Gaussians)
   const bool use_img = IMG && img != nullptr;
   constexpr int NIT = (IMG && !ROLE_A) ? RBF_TILE_ITEMS / (64 * NW) : 1;
-  u32x4 gfh[NIT], gfl[NIT];
+  const int nimg = (Pstride + RBF_TILE_ROWS - 1) / RBF_TILE_ROWS;
+  u32x4 gfh[SUB][NIT], gfl[SUB][NIT];
 #pragma unroll
-  for (int u = 0; u < NIT; ++u) gfh[u] = gfl[u] = u32x4{0u, 0u, 0u, 0u};
+  for (int sb = 0; sb < SUB; ++sb)
+#pragma unroll
+    for (int u = 0; u < NIT; ++u) gfh[sb][u] = gfl[sb][u] = u32x4{0u, 0u, 0u, 0u};
   auto request_rbf = [&](int tt) {
     if constexpr (IMG && !roleA) {
       if (!use_img) return;
-      const u32x4* __restrict__ src = img + (size_t)tt * RBF_TILE_WORDS;  // (uniform base, 32-bit lane offsets)
 #pragma unroll
-      for (int u = 0; u < NIT; ++u) {
-        const int w = rbf_item_word(64 * hs + lane + 64 * NW * u);
-        gfh[u] = src[w];
-        gfl[u] = src[w + 64];
+      for (int sb = 0; sb < SUB; ++sb) {
+        const u32x4* __restrict__ src = img + (size_t)min(SUB * tt + sb, nimg - 1) * RBF_TILE_WORDS;  // (uniform base, 32-bit lane offsets)
+#pragma unroll
+        for (int u = 0; u < NIT; ++u) {
+          const int w = rbf_item_word(64 * hs + lane + 64 * NW * u);
+          gfh[sb][u] = src[w];
+          gfl[sb][u] = src[w + 64];
+        }
       }
     }
   };
@@ -814,17 +845,17 @@ __device__ __forceinline__ void filter_bwd_body_h(const float* __restrict__ pair
         }
         if (lane == 0) {
           L.flag(bsel)[0] = staged0 ? 1 : 0;
-          L.flag(bsel)[1] = dec_wab;
           L.et[CB] = 0;
         }
       }
     } else if (fresh) {
-      const int bsel = dec_wab;
-      const int nwin = min(ATOM_CAP, N - alo_t);
+      // (the one window buffer: this runs behind the barrier that ended the build of the previous tile, the last reader
+      // of the window it overwrites, and in front of the barrier that opens the build of tile tt)
+      const int nwin = min(CAP, N - alo_t);
       FB3(0);
       FB3(1);
-      float* xs = L.xs(bsel);
-      float* ds = L.ds(bsel);
+      float* xs = L.xs;
+      float* ds = L.ds;
       float mx = 0.0f, md = 0.0f;  // largest |x|, |dagg| of the window (clamped duplicates are window values too)
 #pragma unroll
       for (int u = 0; u < NPRE; ++u) {
@@ -841,8 +872,8 @@ __device__ __forceinline__ void filter_bwd_body_h(const float* __restrict__ pair
       mx = wave_max(mx);
       md = wave_max(md);
       if (lane == 0) {
-        L.wmax(bsel)[2 * (wave - NW)] = mx;
-        L.wmax(bsel)[2 * (wave - NW) + 1] = md;
+        L.wmax[2 * (wave - NW)] = mx;
+        L.wmax[2 * (wave - NW) + 1] = md;
       }
       FB3(3);
     }
@@ -865,10 +896,12 @@ __device__ __forceinline__ void filter_bwd_body_h(const float* __restrict__ pair
     decide(alo_a);
     request_rbf(t_begin);
     request_atoms(t_begin, alo_a);
-    request_t(t_begin);
+#pragma unroll
+    for (int sb = 0; sb < SUB; ++sb) request_t(t_begin, sb);
     if constexpr (RECOMP) {
       lds_barrier();  // the Gaussian centres in LDS (block-uniform branch: every wave of the block takes it)
-      rebuild_t(dreq);
+#pragma unroll
+      for (int sb = 0; sb < SUB; ++sb) rebuild_t(sb);
     }
     publish(t_begin);
     if (t_begin + 1 < t_end) {
@@ -893,12 +926,12 @@ __device__ __forceinline__ void filter_bwd_body_h(const float* __restrict__ pair
                     // tiles ahead stay in flight; measured neutral against __syncthreads here)
     FBH_MARK(1);
     const bool staged = L.flag(bsel)[0] != 0;
-    const int wsel = L.flag(bsel)[1];  // staging buffer that holds this tile's atom window
-    // ---- tile build: every thread one dOr fragment lane; role A publishes its tf lanes, role B its rbf lanes
-    float v[8];
+    // ---- tile build: every thread one dOr fragment lane per M block; role A publishes its tf lanes, role B its rbf lanes
+    float v[SUB][8];
     auto build = [&](const float* xb, const float* db, int stride) {
-      {  // dOr: A[m = row][k = c = 16 r_ks + 8 r_kh + e]
-        const int4 q = L.desc(bsel)[r_row];
+#pragma unroll
+      for (int sb = 0; sb < SUB; ++sb) {  // dOr: A[m = row][k = c = 16 r_ks + 8 r_kh + e]
+        const int4 q = L.desc(bsel)[32 * sb + r_row];
         const float qm0 = __int_as_float(q.z), qm1 = __int_as_float(q.w);
         const int c0 = 16 * r_ks + 8 * r_kh;
         const float* di = db + (size_t)q.x * stride + c0;
@@ -909,34 +942,36 @@ __device__ __forceinline__ void filter_bwd_body_h(const float* __restrict__ pair
         for (int h4 = 0; h4 < 2; ++h4) {
           const float4 a = *reinterpret_cast<const float4*>(di + 4 * h4), b = *reinterpret_cast<const float4*>(xj + 4 * h4);
           const float4 c = *reinterpret_cast<const float4*>(dj + 4 * h4), d = *reinterpret_cast<const float4*>(xi + 4 * h4);
-          v[4 * h4 + 0] = qm0 * (a.x * b.x) + qm1 * (c.x * d.x);
-          v[4 * h4 + 1] = qm0 * (a.y * b.y) + qm1 * (c.y * d.y);
-          v[4 * h4 + 2] = qm0 * (a.z * b.z) + qm1 * (c.z * d.z);
-          v[4 * h4 + 3] = qm0 * (a.w * b.w) + qm1 * (c.w * d.w);
+          v[sb][4 * h4 + 0] = qm0 * (a.x * b.x) + qm1 * (c.x * d.x);
+          v[sb][4 * h4 + 1] = qm0 * (a.y * b.y) + qm1 * (c.y * d.y);
+          v[sb][4 * h4 + 2] = qm0 * (a.z * b.z) + qm1 * (c.z * d.z);
+          v[sb][4 * h4 + 3] = qm0 * (a.w * b.w) + qm1 * (c.w * d.w);
         }
       }
     };
     float bound;
     if (staged) {
-      build(L.xs(wsel), L.ds(wsel), 1);  // descriptors hold LDS float offsets
+      build(L.xs, L.ds, 1);  // descriptors hold LDS float offsets
       float mx = 0.0f, md = 0.0f;
 #pragma unroll
       for (int i = 0; i < NW; ++i) {
-        mx = fmaxf(mx, L.wmax(wsel)[2 * i]);
-        md = fmaxf(md, L.wmax(wsel)[2 * i + 1]);
+        mx = fmaxf(mx, L.wmax[2 * i]);
+        md = fmaxf(md, L.wmax[2 * i + 1]);
       }
       bound = 2.0f * mx * md;  // |dO| <= C (|dagg_i x_j| + |dagg_j x_i|), C <= 1
     } else {
       build(x, dagg, F);  // a run of tiny molecules: operands straight from global memory, exact largest magnitude
       float m = 0.0f;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf(v[e]));
+      for (int sb = 0; sb < SUB; ++sb)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf(v[sb][e]));
       m = wave_max(m);
       if (lane == 0) atomicMax(reinterpret_cast<unsigned*>(L.et + CB), __float_as_uint(m));  // zeroed by publish()
       lds_barrier();
       bound = __uint_as_float(*reinterpret_cast<volatile unsigned*>(L.et + CB));
     }
-    {
+    {  // the block scale of dO: taken once per tile, for all its M blocks
       const int e_t = __builtin_amdgcn_readfirstlane(mag_exponent(bound));
       if (e_t > EO) {
         const float f = __builtin_amdgcn_ldexpf(1.0f, EO - e_t);
@@ -954,31 +989,38 @@ __device__ __forceinline__ void filter_bwd_body_h(const float* __restrict__ pair
         EO = e_t;
       }
       const float sO = __builtin_amdgcn_ldexpf(1.0f, 14 - EO);
-      const Frag2 f = split8h_scaled(v, sO);
-      u32x4* dst = L.dOr + (size_t)(r_ks * 2) * 64 + (r_row + 32 * r_kh);
-      dst[0] = f.h;
-      dst[64] = f.l;
+#pragma unroll
+      for (int sb = 0; sb < SUB; ++sb) {
+        const Frag2 f = split8h_scaled(v[sb], sO);
+        u32x4* dst = L.dOr + sb * Lds::DOR_WORDS + (size_t)(r_ks * 2) * 64 + (r_row + 32 * r_kh);
+        dst[0] = f.h;
+        dst[64] = f.l;
+      }
     }
     if constexpr (roleA) {
       // t slice of this wave's hidden units as B fragments of dW2's contraction over pair rows: the C layout held in
       // tc (lane = h, register r <-> row c_row(r)) is the fragment layout with k-step s <-> registers 8s..8s+7
       float tm = 0.0f;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) tm = fmaxf(tm, fabsf(tc[r]));
+      for (int sb = 0; sb < SUB; ++sb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) tm = fmaxf(tm, fabsf(tc[sb][r]));
       tm = wave_max(tm);
       ET = max(ET, __builtin_amdgcn_readfirstlane(mag_exponent(tm)));
       const float sT = __builtin_amdgcn_ldexpf(1.0f, 14 - ET);
       if (lane == 0) L.et[hs] = ET;
 #pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        float u8[8];
+      for (int sb = 0; sb < SUB; ++sb)
 #pragma unroll
-        for (int e = 0; e < 8; ++e) u8[e] = tc[8 * s2 + e];
-        const Frag2 f = split8h_scaled(u8, sT);
-        u32x4* dst = L.tf + (size_t)((hs * 2 + s2) * 2) * 64 + lane;
-        dst[0] = f.h;
-        dst[64] = f.l;
-      }
+        for (int s2 = 0; s2 < 2; ++s2) {
+          float u8[8];
+#pragma unroll
+          for (int e = 0; e < 8; ++e) u8[e] = tc[sb][8 * s2 + e];
+          const Frag2 f = split8h_scaled(u8, sT);
+          u32x4* dst = L.tf + sb * Lds::TF_WORDS + (size_t)((hs * 2 + s2) * 2) * 64 + lane;
+          dst[0] = f.h;
+          dst[64] = f.l;
+        }
     }
     // Gaussian fragments: by the role-B waves (role A also splits its saved activations in this phase; with the sticky
     // window role B has the shorter build)
@@ -987,30 +1029,39 @@ __device__ __forceinline__ void filter_bwd_body_h(const float* __restrict__ pair
     if (use_img) {
       if constexpr (IMG && !roleA) {  // this tile's words were requested one MFMA phase ago
 #pragma unroll
-        for (int u = 0; u < NIT; ++u) {
-          u32x4* dst = L.rbf + rbf_item_word(64 * hs + lane + 64 * NW * u);
-          dst[0] = gfh[u];
-          dst[64] = gfl[u];
-        }
+        for (int sb = 0; sb < SUB; ++sb)
+#pragma unroll
+          for (int u = 0; u < NIT; ++u) {
+            u32x4* dst = L.rbf + sb * Lds::RBF_WORDS + rbf_item_word(64 * hs + lane + 64 * NW * u);
+            dst[0] = gfh[sb][u];
+            dst[64] = gfl[sb][u];
+          }
       }
     } else {
 #ifndef FBH_RBF_BY_A
     if (!roleA) {
-      for (int it = 64 * hs + lane; it < RBF_TILE_ITEMS; it += 64 * NW) {
+      for (int it = 64 * hs + lane; it < SUB * RBF_TILE_ITEMS; it += 64 * NW) {
 #else
     if (NW == 1 ? roleA : (roleA ? hs < NW / 2 : hs >= NW / 2)) {
-      for (int it = 64 * hs + lane; it < RBF_TILE_ITEMS; it += 64 * (NW == 1 ? 1 : NW)) {
+      for (int it = 64 * hs + lane; it < SUB * RBF_TILE_ITEMS; it += 64 * (NW == 1 ? 1 : NW)) {
 #endif
-        const Frag2 f = rbf_fragment_item(it, [&](int r) { return L.tdd(bsel)[r]; }, offset, coeff, G);
-        u32x4* dst = L.rbf + rbf_item_word(it);
+        const int sb = it / RBF_TILE_ITEMS, ib = it % RBF_TILE_ITEMS;  // M block, item inside its 32-row tile
+        const Frag2 f = rbf_fragment_item(ib, [&](int r) { return L.tdd(bsel)[32 * sb + r]; }, offset, coeff, G);
+        u32x4* dst = L.rbf + sb * Lds::RBF_WORDS + rbf_item_word(ib);
         dst[0] = f.h;
         dst[64] = f.l;
       }
     }
     }
-    float tcur[16];
+    // The activations of the NEXT tile are requested into tc while this tile's are still needed for ssp': a 32-row tile
+    // keeps a copy and requests at the start of the MFMA phase; a 64-row tile has no registers for two copies - its role-A
+    // wave requests M block sb of the next tile as soon as dU of M block sb is formed (LATE_T).
+    constexpr bool LATE_T = SUB > 1;
+    float tcur[LATE_T ? 1 : 16];
+    if constexpr (!LATE_T) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) tcur[r] = tc[r];
+      for (int r = 0; r < 16; ++r) tcur[r] = tc[0][r];
+    }
     FBH_MARK(2);
 #ifdef FBH_HALF_BARRIERS
     if (!(t & 1))
@@ -1037,105 +1088,85 @@ __device__ __forceinline__ void filter_bwd_body_h(const float* __restrict__ pair
           request_rows(t + 3);
         }
       }
-      request_t(t + 1);
+      if constexpr (!LATE_T || RECOMP) {  // (RECOMP: only the distances; the hidden rows are rebuilt at the end of the phase)
+#pragma unroll
+        for (int sb = 0; sb < SUB; ++sb) request_t(t + 1, sb);
+      }
     }
     FBH_MARK(4);
     if constexpr (roleA) {
-      // dt = dO W2 for this wave's hidden units (back-to-back MFMAs on one accumulator forward SrcC without a stall)
-      f32x16 acc0, acc1;  // small-weight and large-weight piece products apart: better conditioned, and two
-                          // independent MFMA chains
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc0[r] = acc1[r] = 0.0f;
-      {
-        Frag2 a0, an;  // fragments of the next k-step are requested before this step's MFMAs issue
-        {
-          const u32x4* s0 = L.dOr + lane;
-          a0.h = s0[0]; a0.l = s0[64];
-        }
-#pragma unroll
-        for (int ks = 0; ks < KC; ++ks) {
-          if (ks + 1 < KC) {
-            const u32x4* s0 = L.dOr + (size_t)((ks + 1) * 2) * 64 + lane;
-            an.h = s0[0]; an.l = s0[64];
-          }
-          __builtin_amdgcn_sched_barrier(0);
-          acc1 = mfma_f16(a0.l, bw2[ks].h, acc1);
-          acc0 = mfma_f16(a0.h, bw2[ks].h, acc0);
-          acc1 = mfma_f16(a0.h, bw2[ks].l, acc1);
-          __builtin_amdgcn_sched_barrier(0);
-          if (ks + 1 < KC) a0 = an;
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc0[r] += acc1[r];
-      // dU = dt * ssp'(pre) (C layout: lane = hidden unit, register = pair row); registers 0..7 / 8..15 are the
-      // elements of k-steps 0 / 1 of the contraction over pair rows
       // acc holds (2^(14-EO) dO)(2^(14-e2) W2); |dt| <= 2^EO * (largest column L1 norm of the W2 slice) < 2^(EO+eL)
       // dU = acc kdt ssp'(.) with kdt = 2^(EO + e2 - 28); the split wants dU 2^(14 - EO - eL): both powers of two, folded
       // into ONE scale 2^(e2 - eL - 14) of the split (exact), so the product with kdt is never formed
       const float kdt = __builtin_amdgcn_ldexpf(1.0f, EO + e2 - 28), sUk = __builtin_amdgcn_ldexpf(1.0f, e2 - eL - 14);
-      Frag2 du[2];
+      // the M blocks of the tile one after the other: one set of dt accumulators and dU fragments at a time, the W2
+      // fragments and the dW1 accumulators shared
 #pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        float u8[8];
+      for (int sb = 0; sb < SUB; ++sb) {
+        __builtin_amdgcn_sched_barrier(0);  // (nothing of the next M block hoisted into this one: registers)
+        // dt = dO W2 for this wave's hidden units (back-to-back MFMAs on one accumulator forward SrcC without a stall)
+        f32x16 acc0, acc1;  // small-weight and large-weight piece products apart: better conditioned, and two
+                            // independent MFMA chains
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          u8[e] = acc0[8 * s + e] * dssp_from_out(tcur[8 * s + e]);
-          if (G >= 64) bsum1 = fmaf(u8[e], kdt, bsum1);  // (no free column for the ones: the bias sum on the vector unit)
+        for (int r = 0; r < 16; ++r) acc0[r] = acc1[r] = 0.0f;
+        {
+          const u32x4* dOs = L.dOr + sb * Lds::DOR_WORDS + lane;
+          Frag2 a0, an;  // fragments of the next k-step are requested before this step's MFMAs issue
+          a0.h = dOs[0]; a0.l = dOs[64];
+#pragma unroll
+          for (int ks = 0; ks < KC; ++ks) {
+            if (ks + 1 < KC) {
+              const u32x4* s0 = dOs + (size_t)((ks + 1) * 2) * 64;
+              an.h = s0[0]; an.l = s0[64];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            acc1 = mfma_f16(a0.l, bw2[ks].h, acc1);
+            acc0 = mfma_f16(a0.h, bw2[ks].h, acc0);
+            acc1 = mfma_f16(a0.h, bw2[ks].l, acc1);
+            __builtin_amdgcn_sched_barrier(0);
+            if (ks + 1 < KC) a0 = an;
+          }
         }
-        du[s] = split8h_scaled(u8, sUk);
-      }
-      FBH_MARK(6);
-      // dW1[h][g] += sum_rows dU[row][h] * rbf(d_row)[g]
 #pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        Frag2 b0, b1;
-        const u32x4* s0 = L.rbf + (size_t)(s * 2) * 64 + lane;
-        b0.h = s0[0]; b0.l = s0[64];
-        b1.h = s0[256]; b1.l = s0[320];
-        accw1[0] = mfma_f16(du[s].l, b0.h, accw1[0]);
-        accw1[1] = mfma_f16(du[s].l, b1.h, accw1[1]);
-        accw1[0] = mfma_f16(du[s].h, b0.l, accw1[0]);
-        accw1[1] = mfma_f16(du[s].h, b1.l, accw1[1]);
-        accw1[0] = mfma_f16(du[s].h, b0.h, accw1[0]);
-        accw1[1] = mfma_f16(du[s].h, b1.h, accw1[1]);
+        for (int r = 0; r < 16; ++r) acc0[r] += acc1[r];
+        // dU = dt * ssp'(pre) (C layout: lane = hidden unit, register = pair row); registers 0..7 / 8..15 are the
+        // elements of k-steps 0 / 1 of the contraction over pair rows
+        Frag2 du[2];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          float u8[8];
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            u8[e] = acc0[8 * s + e] * dssp_from_out(LATE_T ? tc[sb][8 * s + e] : tcur[8 * s + e]);
+            if (G >= 64) bsum1 = fmaf(u8[e], kdt, bsum1);  // (no free column for the ones: the bias sum on the vector unit)
+          }
+          du[s] = split8h_scaled(u8, sUk);
+        }
+        if constexpr (LATE_T && !RECOMP) {
+          if (t + 1 < t_end) request_t(t + 1, sb);
+        }
+        if (sb == SUB - 1) FBH_MARK(6);
+        // dW1[h][g] += sum_rows dU[row][h] * rbf(d_row)[g]
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          Frag2 b0, b1;
+          const u32x4* s0 = L.rbf + sb * Lds::RBF_WORDS + (size_t)(s * 2) * 64 + lane;
+          b0.h = s0[0]; b0.l = s0[64];
+          b1.h = s0[256]; b1.l = s0[320];
+          accw1[0] = mfma_f16(du[s].l, b0.h, accw1[0]);
+          accw1[1] = mfma_f16(du[s].l, b1.h, accw1[1]);
+          accw1[0] = mfma_f16(du[s].h, b0.l, accw1[0]);
+          accw1[1] = mfma_f16(du[s].h, b1.l, accw1[1]);
+          accw1[0] = mfma_f16(du[s].h, b0.h, accw1[0]);
+          accw1[1] = mfma_f16(du[s].h, b1.h, accw1[1]);
+        }
       }
-      if (t + 1 < t_end) rebuild_t(dreq);  // the next tile's hidden rows (its distances were requested above)
+      if (t + 1 < t_end) {  // the next tile's hidden rows (its distances were requested above)
+#pragma unroll
+        for (int sb = 0; sb < SUB; ++sb) rebuild_t(sb);
+      }
     } else {
-      // Role B wave w owns filter output channels c in [32w, 32w+32).  Its dO^T fragments (lane = c, 8 pair rows) come
-      // from the dOr fragments through the matrix pipe: D = dOr_piece * I (I = 16 x 32 selection of the channel block)
-      // lands in C layout - lane = c, register = pair row in kperm order - i.e. in fragment order, and every value is
-      // an exact bf16 number (one piece times 1), so packing is exact.  No second evaluation of dO in the other
-      // orientation, no LDS traffic for it.
-      f32x16 tp[2];
-#pragma unroll
-      for (int pc = 0; pc < 2; ++pc)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) tp[pc][r] = 0.0f;
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const u32x4* s0 = L.dOr + (size_t)((2 * hs + q) * 2) * 64 + lane;
-        tp[0] = mfma_f16(s0[0], ident[q], tp[0]);
-        tp[1] = mfma_f16(s0[64], ident[q], tp[1]);
-      }
-      FBH_MARK(6);
-      Frag2 da[2];  // A fragments of dW2 = dO^T t: k-step s <-> registers 8s..8s+7 (every value is an fp16 number)
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const f16x2 ph = {(_Float16)tp[0][8 * s2 + 2 * q], (_Float16)tp[0][8 * s2 + 2 * q + 1]};
-          const f16x2 pl = {(_Float16)tp[1][8 * s2 + 2 * q], (_Float16)tp[1][8 * s2 + 2 * q + 1]};
-          da[s2].h[q] = __builtin_bit_cast(uint32_t, ph);
-          da[s2].l[q] = __builtin_bit_cast(uint32_t, pl);
-        }
-      {
-        float rs = 0.0f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) rs += tp[0][r] + tp[1][r];
-        bsum2 += rs * __builtin_amdgcn_ldexpf(1.0f, EO - 14);  // db2: rows of this half-wave
-      }
-      // follow the activation scales of the role-A waves
+      // follow the activation scales of the role-A waves (once per tile)
 #pragma unroll
       for (int hb = 0; hb < CB; ++hb) {
         const int et = __builtin_amdgcn_readfirstlane(L.et[hb]);
@@ -1146,24 +1177,61 @@ __device__ __forceinline__ void filter_bwd_body_h(const float* __restrict__ pair
           ETs[hb] = et;
         }
       }
-      // dW2[c][h] += sum_rows dO[row][c] * t[row][h], all four 32-wide blocks of h (t fragments published by role A)
-      constexpr int CP = CB >= 2 ? 2 : 1;
+      // Role B wave w owns filter output channels c in [32w, 32w+32).  Its dO^T fragments (lane = c, 8 pair rows) come
+      // from the dOr fragments through the matrix pipe: D = dOr_piece * I (I = 16 x 32 selection of the channel block)
+      // lands in C layout - lane = c, register = pair row in kperm order - i.e. in fragment order, and every value is
+      // an exact bf16 number (one piece times 1), so packing is exact.  No second evaluation of dO in the other
+      // orientation, no LDS traffic for it.
 #pragma unroll
-      for (int hb = 0; hb < CB; hb += CP) {
+      for (int sb = 0; sb < SUB; ++sb) {
+        __builtin_amdgcn_sched_barrier(0);  // (nothing of the next M block hoisted into this one: registers)
+        f32x16 tp[2];
 #pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          Frag2 tb[CP];
+        for (int pc = 0; pc < 2; ++pc)
 #pragma unroll
-          for (int u = 0; u < CP; ++u) {
-            const u32x4* s0 = L.tf + (size_t)(((hb + u) * 2 + s2) * 2) * 64 + lane;
-            tb[u].h = s0[0]; tb[u].l = s0[64];
+          for (int r = 0; r < 16; ++r) tp[pc][r] = 0.0f;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          const u32x4* s0 = L.dOr + sb * Lds::DOR_WORDS + (size_t)((2 * hs + q) * 2) * 64 + lane;
+          tp[0] = mfma_f16(s0[0], ident[q], tp[0]);
+          tp[1] = mfma_f16(s0[64], ident[q], tp[1]);
+        }
+        if (sb == SUB - 1) FBH_MARK(6);
+        Frag2 da[2];  // A fragments of dW2 = dO^T t: k-step s <-> registers 8s..8s+7 (every value is an fp16 number)
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const f16x2 ph = {(_Float16)tp[0][8 * s2 + 2 * q], (_Float16)tp[0][8 * s2 + 2 * q + 1]};
+            const f16x2 pl = {(_Float16)tp[1][8 * s2 + 2 * q], (_Float16)tp[1][8 * s2 + 2 * q + 1]};
+            da[s2].h[q] = __builtin_bit_cast(uint32_t, ph);
+            da[s2].l[q] = __builtin_bit_cast(uint32_t, pl);
           }
+        {
+          float rs = 0.0f;
 #pragma unroll
-          for (int u = 0; u < CP; ++u) accw2[hb + u] = mfma_f16(da[s2].l, tb[u].h, accw2[hb + u]);
+          for (int r = 0; r < 16; ++r) rs += tp[0][r] + tp[1][r];
+          bsum2 += rs * __builtin_amdgcn_ldexpf(1.0f, EO - 14);  // db2: rows of this half-wave
+        }
+        // dW2[c][h] += sum_rows dO[row][c] * t[row][h], all four 32-wide blocks of h (t fragments published by role A)
+        constexpr int CP = CB >= 2 ? 2 : 1;
 #pragma unroll
-          for (int u = 0; u < CP; ++u) accw2[hb + u] = mfma_f16(da[s2].h, tb[u].l, accw2[hb + u]);
+        for (int hb = 0; hb < CB; hb += CP) {
 #pragma unroll
-          for (int u = 0; u < CP; ++u) accw2[hb + u] = mfma_f16(da[s2].h, tb[u].h, accw2[hb + u]);
+          for (int s2 = 0; s2 < 2; ++s2) {
+            Frag2 tb[CP];
+#pragma unroll
+            for (int u = 0; u < CP; ++u) {
+              const u32x4* s0 = L.tf + sb * Lds::TF_WORDS + (size_t)(((hb + u) * 2 + s2) * 2) * 64 + lane;
+              tb[u].h = s0[0]; tb[u].l = s0[64];
+            }
+#pragma unroll
+            for (int u = 0; u < CP; ++u) accw2[hb + u] = mfma_f16(da[s2].l, tb[u].h, accw2[hb + u]);
+#pragma unroll
+            for (int u = 0; u < CP; ++u) accw2[hb + u] = mfma_f16(da[s2].h, tb[u].l, accw2[hb + u]);
+#pragma unroll
+            for (int u = 0; u < CP; ++u) accw2[hb + u] = mfma_f16(da[s2].h, tb[u].h, accw2[hb + u]);
+          }
         }
       }
     }
@@ -1208,31 +1276,29 @@ __device__ __forceinline__ void filter_bwd_body_h(const float* __restrict__ pair
 
 // The two roles run separate instantiations of the body (their register sets differ: W2 fragments + dW1
 // accumulators against dW2 accumulators); the branch is wave-uniform and both sides execute the same barriers.
+// tile_rows (uniform over the launch): 64, or 32 for the 32-row form of the same kernel (GEOSSL_FILTER_BWD_TILE32); the
+// form that rebuilds the hidden rows has the 32-row body only (see filter_bwd_launch).
 template <int NW, bool RECOMP>
-__global__ __launch_bounds__(128 * NW) void k_filter_bwd_h(const float* __restrict__ pair_d,
-                                                         const float* __restrict__ pair_c,
-                                                         const uint8_t* __restrict__ pair_flag,
-                                                         const int32_t* __restrict__ pair_i,
-                                                         const int32_t* __restrict__ pair_j, int P, int N,
-                                                         GeosslFilterWeights w, GeosslFilterGradIn g, int G,
-                                                         const float* __restrict__ offset, float coeff,
-                                                         const float* __restrict__ T,
-                                                         float* __restrict__ partial_w1,
-                                                         float* __restrict__ partial_b1,
-                                                         float* __restrict__ partial_w2,
-                                                         float* __restrict__ partial_b2,
-                                                         const int32_t* __restrict__ dyn_P,
-                                                         const int32_t* __restrict__ dyn_N,
-                                                         const u32x4* __restrict__ img) {
+__global__ __launch_bounds__(128 * NW) __attribute__((amdgpu_waves_per_eu(2))) void k_filter_bwd_h(
+    const float* __restrict__ pair_d, const float* __restrict__ pair_c, const uint8_t* __restrict__ pair_flag,
+    const int32_t* __restrict__ pair_i, const int32_t* __restrict__ pair_j, int P, int N, GeosslFilterWeights w,
+    GeosslFilterGradIn g, int G, const float* __restrict__ offset, float coeff, const float* __restrict__ T,
+    float* __restrict__ partial_w1, float* __restrict__ partial_b1, float* __restrict__ partial_w2,
+    float* __restrict__ partial_b2, const int32_t* __restrict__ dyn_P, const int32_t* __restrict__ dyn_N,
+    const u32x4* __restrict__ img, int tile_rows) {
   const int Pstride = P;
   P = dyn_count(P, dyn_P);
   N = dyn_count(N, dyn_N);
-  if ((int)(threadIdx.x >> 6) < NW)
-    filter_bwd_body_h<NW, true, RECOMP>(pair_d, pair_c, pair_flag, pair_i, pair_j, P, N, w, g, G, offset, coeff, T,
-                                             partial_w1, partial_b1, partial_w2, partial_b2, Pstride, img);
-  else
-    filter_bwd_body_h<NW, false, RECOMP>(pair_d, pair_c, pair_flag, pair_i, pair_j, P, N, w, g, G, offset, coeff, T,
-                                              partial_w1, partial_b1, partial_w2, partial_b2, Pstride, img);
+  const bool roleA = (int)(threadIdx.x >> 6) < NW;
+#define FB_BODY(ROLE_A, TRH)                                                                                           \
+  filter_bwd_body_h<NW, ROLE_A, RECOMP, TRH>(pair_d, pair_c, pair_flag, pair_i, pair_j, P, N, w, g, G, offset, coeff, T, \
+                                             partial_w1, partial_b1, partial_w2, partial_b2, Pstride, img)
+  if (RECOMP || tile_rows == 32) {
+    if (roleA) FB_BODY(true, 32); else FB_BODY(false, 32);
+  } else if constexpr (!RECOMP) {
+    if (roleA) FB_BODY(true, 64); else FB_BODY(false, 64);
+  }
+#undef FB_BODY
 }
 
 // The per-step image of the Gaussian fragments (rbf_frag.h): one block per 32-row tile of the CAPACITY P, one item per
@@ -1304,7 +1370,15 @@ int filter_bwd_launch(const float* pair_d, const float* pair_c, const uint8_t* p
   if (P <= 0 || L <= 0) return 0;
   // (G < 1: the kernels clamp the padded Gaussian index to G - 1, which would read in front of w1 and offset)
   if (L > GEOSSL_MAX_L || (F != 32 && F != 64 && F != 128) || G > 64 || G < 1) return (int)hipErrorInvalidValue;
-  const int ntiles = (int)((P + TR - 1) / TR);
+  // (read per call: an A/B run times both forms in one process)
+  const bool bf16x3 = getenv("GEOSSL_FILTER_BWD_BF16X3") != nullptr || getenv("GEOSSL_ARITH_24BIT") != nullptr;
+  // the two-piece kernel works on 64-row tiles; GEOSSL_FILTER_BWD_TILE32 selects its 32-row form (the three-piece kernel
+  // has that one only).  The workspace is sized for 32-row tiles, which never gives fewer blocks.
+  // The form that rebuilds the hidden rows (T == NULL) keeps 32 rows as well: its role-A wave holds the W1 fragments next
+  // to the W2 fragments, and a second set of hidden rows beside them does not fit 256 registers (63 spilled at F = 128).
+  const bool tile32 = getenv("GEOSSL_FILTER_BWD_TILE32") != nullptr || T == nullptr;
+  const int rows = (bf16x3 || tile32) ? TR : 64;
+  const int ntiles = (int)((P + rows - 1) / rows);
   const int nb = blocks_per_layer(L, ntiles);
   dim3 grid(nb, L);
   float* pw1 = workspace;                          // [L][nb][F][G]
@@ -1320,22 +1394,21 @@ int filter_bwd_launch(const float* pair_d, const float* pair_c, const uint8_t* p
   } while (0)
 #define LAUNCH_H(NW)                                                                                               \
   do {                                                                                                             \
-    const size_t lds = BwdLdsH<32 * NW>::bytes();                                                                  \
+    const size_t lds = tile32 ? BwdLdsH<32 * NW, 32>::bytes() : BwdLdsH<32 * NW, 64>::bytes();                     \
     if (T == nullptr) {                                                                                            \
       allow_big_lds(&k_filter_bwd_h<NW, true>);                                                                    \
       hipLaunchKernelGGL((k_filter_bwd_h<NW, true>), grid, dim3(128 * NW), lds, stream, pair_d, pair_c, pair_flag, \
                          pair_i, pair_j, (int)P, (int)N, *w, *g, G, offset, coeff, T, pw1, pb1, pw2, pb2, dyn_P,   \
-                         dyn_N, nullptr);                                                                          \
+                         dyn_N, nullptr, rows);                                                                    \
     } else {                                                                                                       \
       allow_big_lds(&k_filter_bwd_h<NW, false>);                                                                   \
       hipLaunchKernelGGL((k_filter_bwd_h<NW, false>), grid, dim3(128 * NW), lds, stream, pair_d, pair_c, pair_flag,\
                          pair_i, pair_j, (int)P, (int)N, *w, *g, G, offset, coeff, T, pw1, pb1, pw2, pb2, dyn_P,   \
-                         dyn_N, img);                                                                              \
+                         dyn_N, img, rows);                                                                        \
     }                                                                                                              \
   } while (0)
   // (the three-piece form and the form that rebuilds the hidden rows keep the in-kernel Gaussians: an image is ignored)
   const u32x4* img = static_cast<const u32x4*>(image);
-  const bool bf16x3 = getenv("GEOSSL_FILTER_BWD_BF16X3") != nullptr || getenv("GEOSSL_ARITH_24BIT") != nullptr;  // (read per call: bench.py times both forms in one process)
   if (bf16x3 && T == nullptr) return (int)hipErrorInvalidValue;  // (the three-piece form reads the saved hidden rows)
   if (!bf16x3) {
     if (F == 128) LAUNCH_H(4); else if (F == 64) LAUNCH_H(2); else LAUNCH_H(1);
