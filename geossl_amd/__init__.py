@@ -7,6 +7,7 @@ denoising-distance-matching (DDM) step, behind the reference's own Python interf
     from geossl_amd.finetune_md17 import do_MD17, predict_MD17, eval_MD17, MD17Trainer
     from geossl_amd.md import Simulator          # molecular dynamics on a fine-tuned force field
     from geossl_amd.relax import Minimizer       # structure relaxation (FIRE) on the same force field
+    from geossl_amd.vibrations import NormalModeAnalysis   # Hessian, harmonic frequencies and normal modes there
     from geossl_amd.pretrain_Supervised import do_Supervised, eval_Supervised, SupervisedTrainer
     from geossl_amd.evaluate import Evaluator
 

@@ -350,6 +350,12 @@ PROTOTYPES = {
     # structure relaxation: FIRE around the force pass (csrc/relax.hip)
     "geossl_fire_step": (i32, [vp] * 8 + [i64, i64] + [vp] * 5 + [i32, i64] + [vp] * 8 + [vp]),
     "geossl_fire_active": (i32, [vp, i64, vp, vp]),
+    # normal-mode analysis: central-difference Hessian, finishing pass, batched Jacobi (csrc/vibrations.hip)
+    "geossl_hessian_displace": (i32, [vp, vp, vp, vp, i64, i64, i64, vp, vp]),
+    "geossl_hessian_collect": (i32, [vp] * 5 + [i64] * 5 + [vp, vp, vp, vp]),
+    "geossl_hessian_finish_workspace": (i64, [i64, i64]),
+    "geossl_hessian_finish": (i32, [vp] * 4 + [i64, i64, i64, i32] + [vp] * 5),
+    "geossl_sym_eig_jacobi": (i32, [vp, vp, i64, i64, i32, vp, vp, vp, vp, vp]),
 }
 
 _lib = None

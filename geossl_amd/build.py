@@ -34,13 +34,16 @@ def _sources():
 # painn_tile.hip: painn_mma.hip's message arithmetic on atom tiles - the same flag for the same reason.
 # md_integrate.hip: likewise (per-atom fp32 fma chains over the three coordinates whose rounding the tests state).
 # relax.hip: likewise (the FIRE step's per-atom fp32 chain, stated in its header comment and checked by the tests).
+# vibrations.hip: likewise (the displaced coordinate is ONE fp32 addition the tests check bit for bit; the rest is fp64
+# in a stated order, which packed fp32 cannot speed up).
 SOURCE_FLAGS = {"painn_mma.hip": ["-fno-slp-vectorize"], "painn_tile.hip": ["-fno-slp-vectorize"],
                 "distance_head.hip": ["-fno-slp-vectorize"],
                 "charge_head.hip": ["-fno-slp-vectorize"], "infograph_head.hip": ["-fno-slp-vectorize"],
                 "property_head.hip": ["-fno-slp-vectorize"], "torsion_head.hip": ["-fno-slp-vectorize"],
                 "pair_head.hip": ["-fno-slp-vectorize"], "force_head.hip": ["-fno-slp-vectorize"],
                 "eval_collect.hip": ["-fno-slp-vectorize"], "rr_head.hip": ["-fno-slp-vectorize"],
-                "md_integrate.hip": ["-fno-slp-vectorize"], "relax.hip": ["-fno-slp-vectorize"]}
+                "md_integrate.hip": ["-fno-slp-vectorize"], "relax.hip": ["-fno-slp-vectorize"],
+                "vibrations.hip": ["-fno-slp-vectorize"]}
 
 
 def _headers():

@@ -1854,3 +1854,95 @@ def fire_active(mol_state, active):
     _md_dense(mol_state, torch.int32, (B, FIRE_MOL_WORDS), "mol_state")
     _md_dense(active, torch.int32, (1,), "active")
     call("geossl_fire_active", ptr(mol_state), B, ptr(active), stream())
+
+
+# ---- normal-mode analysis: Hessian rounds, finishing pass, batched Jacobi (csrc/vibrations.hip) ------------------------
+HESSIAN_STATE_WORDS = 4   # int64: round, round in flight, 2 unused
+HESSIAN_ROUND, HESSIAN_IN_FLIGHT = range(2)
+HESSIAN_PROJECT = {None: 0, "t": 1, "tr": 2}
+JACOBI_MAX_DIM = 99       # A and V of one matrix in the LDS of a CU
+HESSIAN_MAX_DIM = 3 * 255
+
+
+def _hessian_shapes(x0, mol_ptr, C):
+    N = x0.size(0) if torch.is_tensor(x0) and x0.dim() == 2 else -1
+    B = mol_ptr.numel() - 1 if torch.is_tensor(mol_ptr) else -1
+    C = int(C)
+    if C < 1 or B < 1:
+        raise ValueError("md: coords_per_pass and the number of molecules are at least 1")
+    _md_dense(x0, torch.float32, (N, 3), "x0")
+    _md_dense(mol_ptr, torch.int32, (B + 1,), "mol_ptr")
+    return N, B, C
+
+
+def hessian_displace(x0, mol_ptr, delta, state, C, img):
+    """The image positions of round state[0] (include/geossl_hip.h): img [2 C, N, 3] = x0 with local coordinate k =
+    round C + c of every molecule moved by +delta (image 2 c) and -delta (image 2 c + 1); delta fp32 [1] and state int64
+    [4] are device data."""
+    N, B, C = _hessian_shapes(x0, mol_ptr, C)
+    _md_dense(delta, torch.float32, (1,), "delta")
+    _md_dense(state, torch.int64, (HESSIAN_STATE_WORDS,), "state")
+    _md_dense(img, torch.float32, (2 * C, N, 3), "img")
+    call("geossl_hessian_displace", ptr(x0), ptr(mol_ptr), ptr(delta), ptr(state), B, N, C, ptr(img), stream())
+
+
+def hessian_collect(x0, img, grad, energy_img, mol_ptr, state, C, R, hessian, energy, fmax):
+    """The rows of round state[1] into hessian [B, M, M] fp64 from the image batch's gradients; at round R, energy and
+    fmax [B] fp64 of image 0 instead.  Advances state[0]."""
+    N, B, C = _hessian_shapes(x0, mol_ptr, C)
+    M = hessian.size(1) if torch.is_tensor(hessian) and hessian.dim() == 3 else -1
+    if not 1 <= M <= HESSIAN_MAX_DIM or int(R) < 0:
+        raise ValueError("md: hessian is [B, M, M] with 1 <= M <= %d and R >= 0" % HESSIAN_MAX_DIM)
+    _md_dense(img, torch.float32, (2 * C, N, 3), "img")
+    _md_dense(grad, torch.float32, (2 * C * N, 3), "grad")
+    _md_dense(energy_img, torch.float32, (2 * C * B,), "energy_img")
+    _md_dense(state, torch.int64, (HESSIAN_STATE_WORDS,), "state")
+    _md_dense(hessian, torch.float64, (B, M, M), "hessian")
+    _md_dense(energy, torch.float64, (B,), "energy")
+    _md_dense(fmax, torch.float64, (B,), "fmax")
+    call("geossl_hessian_collect", ptr(img), ptr(grad), ptr(energy_img), ptr(mol_ptr), ptr(state), B, N, C, int(R), M,
+         ptr(hessian), ptr(energy), ptr(fmax), stream())
+
+
+def hessian_finish(hessian, x0, masses, mol_ptr, project, D, asymmetry, n_projected, workspace=None):
+    """The finishing pass, in place on hessian [B, M, M] fp64 (symmetrised, zero outside each 3 n_b block): D [B, M, M] =
+    the mass-weighted, projected Hessian, asymmetry [B] fp64, n_projected [B] int32.  project: None, "t" or "tr"."""
+    N, B, _ = _hessian_shapes(x0, mol_ptr, 1)
+    M = hessian.size(1) if torch.is_tensor(hessian) and hessian.dim() == 3 else -1
+    if not 1 <= M <= HESSIAN_MAX_DIM or project not in HESSIAN_PROJECT:
+        raise ValueError("md: hessian is [B, M, M] with 1 <= M <= %d, project None, 't' or 'tr'" % HESSIAN_MAX_DIM)
+    _md_dense(hessian, torch.float64, (B, M, M), "hessian")
+    _md_dense(D, torch.float64, (B, M, M), "D")
+    _md_dense(masses, torch.float64, (N,), "masses")
+    _md_dense(asymmetry, torch.float64, (B,), "asymmetry")
+    _md_dense(n_projected, torch.int32, (B,), "n_projected")
+    words = int(_lib.load().geossl_hessian_finish_workspace(B, M))
+    if workspace is None:
+        workspace = torch.empty(words, dtype=torch.float64, device=hessian.device)
+    _md_dense(workspace, torch.float64, (words,), "workspace")
+    call("geossl_hessian_finish", ptr(hessian), ptr(x0), ptr(masses), ptr(mol_ptr), B, N, M, HESSIAN_PROJECT[project],
+         ptr(D), ptr(asymmetry), ptr(n_projected), ptr(workspace), stream())
+
+
+def sym_eig_jacobi(A, dims, max_sweeps, eigenvalues=None, modes=None, sweeps=None, converged=None):
+    """Batched symmetric eigendecomposition on the device -> (eigenvalues [B, M] ascending, NaN past dims; modes [B, M, M],
+    eigenvectors in columns; sweeps [B]; converged [B] int32).  A [B, M, M] fp64 with M <= 99, dims [B] int32."""
+    B = A.size(0) if torch.is_tensor(A) and A.dim() == 3 else -1
+    M = A.size(1) if B > 0 else -1
+    if not 1 <= M <= JACOBI_MAX_DIM or not 0 <= int(max_sweeps) <= 4096:
+        raise ValueError("md: the device eigensolver takes [B, M, M] with 1 <= M <= %d and 0 <= max_sweeps <= 4096"
+                         % JACOBI_MAX_DIM)
+    _md_dense(A, torch.float64, (B, M, M), "A")
+    _md_dense(dims, torch.int32, (B,), "dims")
+    dev = A.device
+    eigenvalues = torch.empty(B, M, dtype=torch.float64, device=dev) if eigenvalues is None else eigenvalues
+    modes = torch.empty(B, M, M, dtype=torch.float64, device=dev) if modes is None else modes
+    sweeps = torch.empty(B, dtype=torch.int32, device=dev) if sweeps is None else sweeps
+    converged = torch.empty(B, dtype=torch.int32, device=dev) if converged is None else converged
+    _md_dense(eigenvalues, torch.float64, (B, M), "eigenvalues")
+    _md_dense(modes, torch.float64, (B, M, M), "modes")
+    _md_dense(sweeps, torch.int32, (B,), "sweeps")
+    _md_dense(converged, torch.int32, (B,), "converged")
+    call("geossl_sym_eig_jacobi", ptr(A), ptr(dims), B, M, int(max_sweeps), ptr(eigenvalues), ptr(modes), ptr(sweeps),
+         ptr(converged), stream())
+    return eigenvalues, modes, sweeps, converged

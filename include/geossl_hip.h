@@ -1333,6 +1333,41 @@ int geossl_fire_step(float* pos, float* vel, const float* grad_new, const float*
                      float* traj_dt, float* traj_alpha, int32_t* traj_npos, int32_t* traj_done, hipStream_t stream);
 int geossl_fire_active(const int32_t* mol_state, int64_t B, int32_t* active, hipStream_t stream);
 
+/* ---- normal-mode analysis on a force field: central-difference Hessian, finishing pass, Jacobi (csrc/vibrations.hip) ---
+ * A round of B molecules (N atoms, mol_ptr [B + 1]) is geossl_hessian_displace, the force pass on the image batch,
+ * geossl_hessian_collect.  Device state: x0 [N][3] fp32, the reference geometry; img [2 C][N][3] fp32, the image batch
+ * (image 2 c is (c, +), image 2 c + 1 is (c, -)); grad [2 C][N][3] and energy_img [2 C][B] fp32, the pass's results;
+ * delta [1] fp32; state [4] int64 = (round, round in flight, unused, unused).  All of it is read from the device by every
+ * launch: a captured graph of these launches follows its changes.
+ * geossl_hessian_displace : with r = state[0] and k = r C + c, every image is x0 except local coordinate k of each
+ *   molecule with k < 3 n_b, which is fl32(x0_k + delta) in image (c, +) and fl32(x0_k - delta) in (c, -).  Writes
+ *   state[1] = r.
+ * geossl_hessian_collect : with r = state[1] and k = r C + c: for r < R and k < 3 n_b, hessian[b][k][t] = (g+[t] - g-[t]) /
+ *   (x+_k - x-_k) for t < 3 n_b, in fp64 from the fp32 gradients and the two fp32 coordinates the images hold; other rows
+ *   are not touched.  r == R: energy[b] = energy_img[0][b], fmax[b] = max_i |g_i| of image 0 (fp64).  Writes state[0] = r + 1.
+ *   hessian [B][M][M] fp64 with M >= 3 n_max (M <= 765).
+ * geossl_hessian_finish : per molecule, fp64, in a fixed order (no atomics): asymmetry = max |H - H^T|, H = (H + H^T) / 2,
+ *   D_ij = H_ij / sqrt(m_i m_j) (both zero outside the 3 n_b block); project 1: the three translations, 2: also the three
+ *   rotations about the centre of mass, mass-weighted, orthonormalised by modified Gram-Schmidt, a vector dropped when its
+ *   remaining norm is not above 1e-5 of its own; n_projected = the survivors; D = P D P, P = I - sum v v^T.  masses [N]
+ *   fp64; workspace: geossl_hessian_finish_workspace(B, M) doubles.
+ * geossl_sym_eig_jacobi : A [B][M][M] fp64 (the upper triangle of the leading dims[b] x dims[b] block is read), M <= 99.
+ *   One block per matrix: cyclic Jacobi in round-robin order, the disjoint rotations of a round computed first and then
+ *   applied; stop when max off-diagonal <= 2^-50 |A|_F (tested once per sweep) or after max_sweeps sweeps.  eigenvalues
+ *   [B][M] ascending (NaN past dims[b]), modes [B][M][M] with the eigenvectors in the columns (zero outside the block),
+ *   sweeps [B] and converged [B] int32.  The rotation formula and the skip rule are stated in csrc/vibrations.hip.       */
+int geossl_hessian_displace(const float* x0, const int32_t* mol_ptr, const float* delta, int64_t* state, int64_t B,
+                            int64_t N, int64_t C, float* img, hipStream_t stream);
+int geossl_hessian_collect(const float* img, const float* grad, const float* energy_img, const int32_t* mol_ptr,
+                           int64_t* state, int64_t B, int64_t N, int64_t C, int64_t R, int64_t M, double* hessian,
+                           double* energy, double* fmax, hipStream_t stream);
+int64_t geossl_hessian_finish_workspace(int64_t B, int64_t M);
+int geossl_hessian_finish(double* hessian, const float* x0, const double* masses, const int32_t* mol_ptr, int64_t B,
+                          int64_t N, int64_t M, int project, double* D, double* asymmetry, int32_t* n_projected,
+                          double* workspace, hipStream_t stream);
+int geossl_sym_eig_jacobi(const double* A, const int32_t* dims, int64_t B, int64_t M, int max_sweeps, double* eigenvalues,
+                          double* modes, int32_t* sweeps, int32_t* converged, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
